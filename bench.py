@@ -48,7 +48,13 @@ def parse():
                    'reference default 10 is reported as secondary.default_flags_vgg_on)')
     p.add_argument('--no_share_d_forward', action='store_true',
                    help='re-run the mask/image discriminator forwards in the D steps like the reference does')
-    return p.parse_args()
+    p.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed step computed (the step\'s outputs, its loss values '
+                        'and a fixed sample of the updated parameters) to DIR/<name>.npy, float32 / float64, at most 64 MB')
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def physical_cores():
@@ -209,6 +215,57 @@ def split_blocks(n_steps, want=5):
     nb = max(1, min(want, n_steps))
     base, extra = divmod(n_steps, nb)
     return [base + (1 if i < extra else 0) for i in range(nb)]
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20            # elements kept of an output / parameter buffer larger than this (fixed seeded positions)
+
+
+def dump_outputs(out_dir, model_out, trainer):
+    """What the caller of the timed path holds after its last step, as DIR/<name>.npy: the six outputs of Trainer.step
+    (imgs_pred, boxes_pred, masks_pred and the three layouts, densified here, after the timed region), every loss value of
+    the four loss managers (float64 scalars) and the four optimisers' updated parameter buffers.  A tensor of more than
+    DUMP_SAMPLE elements is written as a sample of DUMP_SAMPLE elements of its flattened form at the sorted positions
+    ``torch.randint(numel, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))``: the same for every build and run.
+    Returns {name: shape}."""
+    import numpy as np
+    from scene_generation_amd import ops
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def add(name, t):
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(n, (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+
+    names = ('imgs_pred', 'boxes_pred', 'masks_pred', 'layout', 'layout_pred', 'layout_wrong')
+    for name, t in zip(names, model_out):
+        if t is None:
+            continue
+        if name.startswith('layout'):
+            ops.ensure_dense(t)
+        add(name, t)
+    for tag, attr in (('G', 'generator_losses'), ('D_obj', 'd_obj_losses'), ('D_mask', 'd_mask_losses'),
+                      ('D_img', 'd_img_losses')):
+        L = getattr(trainer, attr, None)
+        if L is None:
+            continue
+        for k, v in L.items():
+            arrays['loss.%s.%s' % (tag, k)] = np.asarray(v, dtype=np.float64)
+    for tag, attr in (('G', 'optimizer'), ('D_img', 'optimizer_d_img'), ('D_obj', 'optimizer_d_obj'),
+                      ('D_mask', 'optimizer_d_mask')):
+        opt = getattr(trainer, attr, None)
+        if opt is not None:
+            add('params.' + tag, opt.fp.flat)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, 'output dump of %d bytes exceeds the %d byte budget' % (total, DUMP_BUDGET_BYTES)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+    return {name: list(v.shape) for name, v in arrays.items()}
 
 
 def cpu_baseline(image_size, n_images, n_steps):
@@ -415,9 +472,10 @@ def main():
     def one_step(trainer, i, batches=None):
         db = (batches or staged)[i % 2]
         trainer.model.objs_host, trainer.model.obj_to_img_host = db.objs_host, db.obj_to_img_host
-        trainer.step(db.batch, use_gt=trainer.draw_use_gt())      # train.py:195
+        return trainer.step(db.batch, use_gt=trainer.draw_use_gt())      # train.py:195
 
     issue = [0.0]
+    last_out = [None]
 
     blocks_ms = [None]
 
@@ -440,7 +498,7 @@ def main():
             evs[0].record()
         ie = 1
         for i in range(n_steps):
-            one_step(trainer, first + i, batches)
+            last_out[0] = one_step(trainer, first + i, batches)
             if evs and (i + 1) in bounds:
                 evs[ie].record()
                 ie += 1
@@ -477,6 +535,9 @@ def main():
     thr1 = cpu_throttle_count()
     clocks = sampler.stop(timed.t0, timed.t1)
     host_issue = issue[0]
+    # what the last timed step handed back, written before any further step can overwrite it (hipGraph output buffers)
+    dumped = dump_outputs(a.dump_outputs, last_out[0], tr) if a.dump_outputs and rank == 0 else None
+    last_out[0] = None
     # value = the MEDIAN block: the K steps run back to back exactly as the contract says, cut into >= 5
     # blocks by HIP events on the launch stream; the whole-region figure (host clock around barrier + synchronize) stays in
     # ``whole_region``.  Block rates are per-step rates, so blocks of unequal length compare directly.
@@ -572,6 +633,7 @@ def main():
         'repeat_spread': repeat['spread'], 'repeat': repeat,
         'whole_region': {'value': B * world * a.steps / dt, 'ms_per_step': 1e3 * dt / a.steps, 'seconds': dt},
         'clocks': clocks,
+        'dumped_outputs': dumped,
         # host side of the measurement: the cgroup's CPU quota (CPUs per period; None = unlimited) and how many scheduler periods
         # ended with the process frozen by it while the timed steps ran (0 = the host was never taken away from the launch thread)
         'host': {'cgroup_cpu_quota': cpu_quota(), 'cpu_throttled_periods_in_timed_region':

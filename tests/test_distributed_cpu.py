@@ -37,7 +37,16 @@ def _batch():
     return make_batch(N=4, min_objs=2, max_objs=3, size=16, mask_size=8, num_objs=12, num_preds=4, seed=3)
 
 
+def _host_only():
+    """Every rank of this file computes on the host.  On a machine with a GPU a rank must still not open it (torch's
+    is_available() initialises the HIP runtime, and eight gloo ranks would hold the device from nine processes with the test
+    runner): the ranks see no device, exactly as on a host without one."""
+    torch.cuda.is_available = lambda: False
+    torch.cuda.device_count = lambda: 0
+
+
 def _worker(rank, world, port, bucket_bytes, q):
+    _host_only()
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.set_num_threads(1)
     from scene_generation_amd.optim import FlatParams
@@ -114,6 +123,7 @@ def test_two_rank_gradient_mean_equals_sequential_shards(bucket_bytes):
 
 
 def _order_worker(rank, world, port, q):
+    _host_only()
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.set_num_threads(1)
     from scene_generation_amd.optim import FlatParams
@@ -176,6 +186,7 @@ def test_bucket_launch_order_is_rank_independent():
 
 
 def _ctrl_worker(rank, world, port, q):
+    _host_only()
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       SG_CTRL_GLOO='force')
     torch.set_num_threads(1)
@@ -236,6 +247,7 @@ class _OptStub(object):
 
 
 def _world8_worker(rank, world, port, shapes, q):
+    _host_only()
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.set_num_threads(1)
     from scene_generation_amd.optim import FlatParams
@@ -294,7 +306,7 @@ def _world8_worker(rank, world, port, shapes, q):
         v = fp.grad_view(i)
         bad += int(not bool((v == float(want)).all()))
     sizes = [(e - s) * 4 for s, e, _ in red.buckets]
-    q.put((rank, bad, len(red.buckets), min(sizes[:-1]), sum(sizes)))
+    q.put((rank, bad, len(red.buckets), min(sizes[:-1]), sum(sizes), torch.cuda.is_initialized()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -336,6 +348,7 @@ def test_world8_generator_buckets_and_config3_shards():
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
-    for rank, bad, nb, min_bucket, total in res:
+    for rank, bad, nb, min_bucket, total, gpu_init in res:
+        assert not gpu_init, 'rank %d initialised the GPU runtime' % rank
         assert bad == 0, 'rank %d: %d parameters hold a wrong sum' % (rank, bad)
         assert nb >= 10 and min_bucket >= (64 << 20) and total > 760e6

@@ -1,67 +1,82 @@
-"""The drop-in switch (scene_generation_amd.install_as) against the reference's own entry script, CPU only.
+"""The drop-in switch (scene_generation_amd.install_as) against what the reference's entry script asks of the package, CPU only.
 
-Container-only: needs the read-only reference checkout (it never travels to the GPU box, where this file skips).  A
-subprocess aliases the package as ``scene_generation``, executes the import block of the reference's train.py
-(train.py:9-13) with stand-ins for the third-party packages this image lacks (torchvision, pycocotools, skimage,
-tensorboardX), then builds the checkpoint dict and the Trainer the way train.py:119-188 does.
+tests/golden/dropin_train_py.npz (tools/make_golden.py::golden_dropin) holds the import statements of the reference's train.py
+(train.py:1-15, as module / names pairs) and the schema of the fresh checkpoint dict its get_checkpoint builds
+(train.py:128-163).  A subprocess lays out a stand-in host checkout in a temporary directory -- ``scene_generation/data``,
+``scene_generation/metrics.py`` and ``scripts/inception_score.py``, the parts of the reference this package does not replace --
+aliases the package as ``scene_generation``, executes those import statements, then builds the checkpoint dict and the Trainer
+the way train.py:119-188 does, saves with the reference's schema and restores.
 """
+import json
 import os
 import subprocess
 import sys
 import textwrap
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 
-SCRIPT = r'''
-import ast, os, sys, types, json
+# the stand-in host checkout: only names, no behaviour beyond what the script below calls
+HOST_FILES = {
+    'scene_generation/__init__.py': '',
+    'scene_generation/data/__init__.py': '',
+    'scene_generation/data/coco.py': 'class CocoSceneGraphDataset(object):\n    pass\n\n\ndef coco_collate_fn(batch):\n    return batch\n',
+    'scene_generation/data/coco_panoptic.py': ('class CocoPanopticSceneGraphDataset(object):\n    pass\n\n\n'
+                                               'def coco_panoptic_collate_fn(batch):\n    return batch\n'),
+    'scene_generation/metrics.py': 'def jaccard(boxes_pred, boxes):\n    return 0.0, 0, 0\n',
+    'scripts/__init__.py': '',
+    'scripts/inception_score.py': 'class InceptionScore(object):\n    pass\n',
+}
+
+SCRIPT = r"""
+import collections, importlib, json, os, sys
+host, spec = %(host)r, json.loads(open(%(spec)r).read())
 sys.path.insert(0, %(root)r)
-sys.path.insert(0, %(ref)r)
-import PIL.Image                      # data/utils.py touches PIL.Image after a bare ``import PIL``
-for n in ['torchvision', 'torchvision.transforms', 'torchvision.models', 'torchvision.utils', 'torchvision.datasets',
-          'torchvision.models.inception', 'pycocotools', 'pycocotools.mask', 'skimage', 'skimage.transform', 'tensorboardX']:
-    sys.modules[n] = types.ModuleType(n)
-tv = sys.modules['torchvision']
-tv.transforms, tv.models, tv.utils, tv.datasets = [sys.modules['torchvision.' + k] for k in
-                                                   ('transforms', 'models', 'utils', 'datasets')]
-sys.modules['torchvision.models.inception'].inception_v3 = lambda *a, **k: None
-sys.modules['skimage.transform'].resize = lambda *a, **k: None
-for n in ('Normalize', 'Compose', 'ToTensor', 'Resize'):
-    setattr(tv.transforms, n, type(n, (), {'__init__': lambda s, *a, **k: None}))
-
+sys.path.insert(0, host)
+os.chdir(host)
 import scene_generation_amd
 scene_generation_amd.install_as('scene_generation')
 
-# ---- train.py:9-15 executed verbatim from the reference file (the import statements only) ----
-src = open(os.path.join(%(ref)r, 'train.py')).read()
-tree = ast.parse(src)
-imports = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+# ---- train.py:1-15: every import statement of the reference's entry script ----
 ns = {}
-exec(compile(ast.Module(body=imports, type_ignores=[]), 'train.py', 'exec'), ns)
+for imp in spec['imports']:
+    if imp['module'] is None:
+        for n in imp['names']:
+            ns[n.split('.')[0]] = importlib.import_module(n)
+    else:
+        mod = importlib.import_module(imp['module'])
+        for n in imp['names']:
+            ns[n] = getattr(mod, n)
 assert ns['Trainer'].__module__ == 'scene_generation_amd.trainer', ns['Trainer'].__module__
 assert ns['get_args'].__module__ == 'scene_generation_amd.args'
 assert ns['CocoSceneGraphDataset'].__module__ == 'scene_generation.data.coco'
-assert os.path.realpath(sys.modules['scene_generation.data.coco'].__file__).startswith(os.path.realpath(%(ref)r))
-assert os.path.realpath(sys.modules['scene_generation.metrics'].__file__).startswith(os.path.realpath(%(ref)r))
+for m in ('scene_generation.data.coco', 'scene_generation.data.coco_panoptic', 'scene_generation.metrics'):
+    assert os.path.realpath(sys.modules[m].__file__).startswith(os.path.realpath(host)), m
 import torch
-iou = ns['jaccard'](torch.tensor([[0., 0., 1., 1.]]), torch.tensor([[0., 0., .5, 1.]]))
-assert abs(float(iou[0]) - 0.5) < 1e-6
 # the evaluation script's only import from the package (scripts/inception_score.py:12,30)
 from scene_generation.layers import Interpolate
 up = Interpolate(size=(9, 9), mode='bilinear')
 assert tuple(up(torch.zeros(1, 3, 4, 4)).shape) == (1, 3, 9, 9)
 
-# ---- train.py:119-163 (get_checkpoint) + :166-170 (Trainer construction), executed from the reference source ----
-fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == 'get_checkpoint'][0]
-exec(compile(ast.Module(body=[fn], type_ignores=[]), 'train.py', 'exec'), ns)
+
+# ---- train.py:119-163 (get_checkpoint) + :166-170 (Trainer construction) ----
+def get_checkpoint(args, vocab):
+    if args.restore_from_checkpoint:
+        checkpoint = torch.load(os.path.join(args.output_dir, '%%s_with_model.pt' %% args.checkpoint_name))
+        return checkpoint['counters']['t'], checkpoint['counters']['epoch'], checkpoint
+    kinds = {'args': lambda: args.__dict__, 'vocab': lambda: vocab, 'dict': dict, 'list': list,
+             'defaultdict(list)': lambda: collections.defaultdict(list)}
+    fresh = {k: (dict(v) if isinstance(v, dict) else kinds[v]() if isinstance(v, str) else v)
+             for k, v in spec['fresh_checkpoint'].items()}
+    return 0, 0, fresh
+
+
 from scene_generation_amd.synthetic import make_vocab
 args = ns['get_args'](['--output_dir', %(out)r, '--image_size', '32,32', '--n_downsample_global', '2', '--ndf', '8',
                        '--ndf_mask', '8', '--gconv_hidden_dim', '64'])
 os.makedirs(args.output_dir, exist_ok=True)
 vocab = make_vocab()
-t, epoch, checkpoint = ns['get_checkpoint'](args, vocab)
+t, epoch, checkpoint = get_checkpoint(args, vocab)
+assert (t, epoch) == (0, 0) and checkpoint['counters'] == {'t': None, 'epoch': None} and len(checkpoint) >= 30
 trainer = ns['Trainer'](args, vocab, checkpoint)
 for attr in ('model', 'netD', 'obj_discriminator', 'mask_discriminator', 'optimizer', 'optimizer_d_obj',
              'optimizer_d_mask', 'optimizer_d_img', 'num_obj', 'writer', 'criterionVGG', 'criterionGAN'):
@@ -85,19 +100,26 @@ assert torch.equal(trainer.model.box_net[0].weight, p0)
 _tl = torch.load                   # train.py:127 predates torch 2.6's weights_only=True default (the file holds dicts)
 torch.load = lambda *a, **k: _tl(*a, **dict(k, weights_only=False))
 args2 = ns['get_args'](['--output_dir', %(out)r, '--restore_from_checkpoint', '1', '--image_size', '32,32'])
-t2, epoch2, ck2 = ns['get_checkpoint'](args2, vocab)          # train.py:121-125 reads the file just written
+t2, epoch2, ck2 = get_checkpoint(args2, vocab)          # train.py:121-125 reads the file just written
 assert t2 == 7 and epoch2 == 1
 tr2 = ns['Trainer'](args2, vocab, ck2)
 tr2.restore_checkpoint(ck2)
 assert torch.equal(tr2.model.box_net[0].weight, p0)
 trainer.generator_losses = None
 print('DROPIN_OK')
-'''
+"""
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'scene_generation')), reason='reference checkout not present')
-def test_install_as_runs_reference_train_py_imports_and_trainer_construction(tmp_path):
-    code = SCRIPT % dict(root=ROOT, ref=REF, out=str(tmp_path / 'out'))
+def test_install_as_runs_reference_train_py_imports_and_trainer_construction(tmp_path, golden):
+    spec = json.loads(str(golden('dropin_train_py')['json']))
+    assert any(i['module'] == 'scene_generation.trainer' for i in spec['imports'])
+    host = tmp_path / 'host'
+    for rel, text in HOST_FILES.items():
+        f = host / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(text)
+    (tmp_path / 'spec.json').write_text(json.dumps(spec))
+    code = SCRIPT % dict(root=ROOT, host=str(host), spec=str(tmp_path / 'spec.json'), out=str(tmp_path / 'out'))
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, OMP_NUM_THREADS='4'))
     assert r.returncode == 0 and 'DROPIN_OK' in r.stdout, textwrap.shorten(r.stdout + r.stderr, 4000)

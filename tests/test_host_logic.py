@@ -708,3 +708,34 @@ def test_cpu_quota_parsing_and_thread_cap(tmp_path, monkeypatch):
         assert utils.respect_cpu_quota(verbose=False) == got          # once per process
     finally:
         torch.set_num_threads(n0)
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: the six step outputs, every loss value and the four parameter buffers land as float32 / float64
+    .npy files; a tensor above the sample size is written as a sample at seeded positions that repeat from run to run."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Opt:
+        def __init__(self, n):
+            self.fp = type('FP', (), {'flat': torch.arange(n, dtype=torch.float32)})()
+
+    L = LossManager()
+    L.add_loss(torch.tensor(0.25), 'bbox_pred', 10.0)
+    tr = type('T', (), {'generator_losses': L, 'd_obj_losses': None, 'optimizer': Opt(bench.DUMP_SAMPLE + 5),
+                        'optimizer_d_img': Opt(7), 'optimizer_d_obj': Opt(3), 'optimizer_d_mask': Opt(2)})()
+    big = torch.arange(2 * bench.DUMP_SAMPLE, dtype=torch.float32).view(2, -1)
+    out = (torch.ones(2, 3, 4, 4), torch.zeros(5, 4), torch.ones(5, 2, 2), big, big + 1, None)
+    shapes = [bench.dump_outputs(str(tmp_path / d), out, tr) for d in ('a', 'b')]
+    assert shapes[0] == shapes[1]
+    assert shapes[0]['imgs_pred'] == [2, 3, 4, 4] and shapes[0]['layout'] == [bench.DUMP_SAMPLE] and 'layout_wrong' not in shapes[0]
+    assert shapes[0]['params.G'] == [bench.DUMP_SAMPLE] and shapes[0]['params.D_mask'] == [2]
+    total = 0
+    for name in shapes[0]:
+        x, y = np.load(str(tmp_path / 'a' / (name + '.npy'))), np.load(str(tmp_path / 'b' / (name + '.npy')))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= bench.DUMP_BUDGET_BYTES
+    assert float(np.load(str(tmp_path / 'a' / 'loss.G.bbox_pred.npy'))) == 2.5
+    lay = np.load(str(tmp_path / 'a' / 'layout.npy'))
+    assert np.all(np.diff(lay) >= 0) and lay.min() >= 0 and lay.max() < big.numel()     # values = their sorted positions

@@ -647,9 +647,38 @@ def golden_args():
     npz('args_defaults', json=np.array(json.dumps({k: (list(v) if isinstance(v, tuple) else v) for k, v in d.items()})))
 
 
+
+def golden_dropin():
+    """what the reference's entry script asks of the package (train.py:1-15 import statements, as module / names pairs) and the
+    schema of the fresh checkpoint dict its get_checkpoint builds (train.py:128-163: key -> kind of empty value)"""
+    import ast
+    import json
+    tree = ast.parse(open(os.path.join(REF, 'train.py')).read())
+    imports = [{'module': n.module if isinstance(n, ast.ImportFrom) else None, 'names': [a.name for a in n.names]}
+               for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == 'get_checkpoint'][0]
+    fresh = [n for n in ast.walk(fn) if isinstance(n, ast.Dict)][0]
+    schema = {}
+    for k, v in zip(fresh.keys, fresh.values):
+        if isinstance(v, ast.Call):
+            kind = 'defaultdict(list)'
+        elif isinstance(v, ast.List):
+            kind = 'list'
+        elif isinstance(v, ast.Dict):
+            kind = {ast.literal_eval(kk): None for kk in v.keys} if v.keys else 'dict'
+        elif isinstance(v, ast.Attribute):
+            kind = 'args'
+        elif isinstance(v, ast.Name):
+            kind = 'vocab'
+        else:
+            kind = ast.literal_eval(v)
+        schema[ast.literal_eval(k)] = kind
+    npz('dropin_train_py', json=np.array(json.dumps({'imports': imports, 'fresh_checkpoint': schema})))
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     install_shims()
-    which = sys.argv[1:] or ['gconv', 'layout', 'crop', 'modules', 'losses', 'losses2', 'vgg', 'legacy', 'step', 'step_full', 'eval', 'testmode', 'args']
+    which = sys.argv[1:] or ['gconv', 'layout', 'crop', 'modules', 'losses', 'losses2', 'vgg', 'legacy', 'step', 'step_full', 'eval', 'testmode', 'args', 'dropin']
     for w in which:
         globals()['golden_' + w]()
