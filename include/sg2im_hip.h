@@ -161,6 +161,23 @@ int sg_conv2d_wino_fwd_instnorm(const sgConvDesc* d, const float* x, const float
 int sg_conv2d_wino_dgrad_instnorm(const sgConvDesc* d, const float* gout, const float* ypre, const float* mean, const float* rstd,
                                   int act, float slope, const float* w, float* gconv, float* gx, float* gb,
                                   const float* ut_saved, float* ytp_save, void* ws, size_t ws_bytes, sgStream stream);
+/* bf16-operand path of the same ResnetBlock convs (ReflectionPad2d(1) + Conv2d(C, C, 3), stride 1), the opt-in mixed-precision
+ * trunk of GlobalGenerator: every product of the forward / data-gradient / weight-gradient GEMMs takes its operands rounded to
+ * bf16 (round to nearest even), the sums are fp32 (v_mfma_f32_16x16x32_bf16); x, y, w, bias and all gradients stay fp32 NCHW.
+ * Supported (sg_conv3x3r_bf16_supported): C1 == Cout, C1 % 64 == 0 (64 .. 4096), C2 == 0, KS 3, stride 1, pad 1, pad_reflect,
+ * no upsample, H, W >= 2, OH == H, OW == W.  Other shapes return -1 ("unsupported shape").  ws: sg_conv3x3r_bf16_ws_bytes(d)
+ * (one size for all three calls).  Deterministic (split-K slices are reduced in a fixed order); no allocation, no host sync.
+ *   fwd  : y [N, Cout, H, W] = conv(reflectpad1(x), w) + bias (bias may be NULL)
+ *   dgrad: gx [N, C1, H, W], the reflection fold included
+ *   wgrad: gw [Cout, C1, 3, 3]; gb [Cout] = channel sum of gy (fp32, sg_channel_sum) when non-NULL */
+int sg_conv3x3r_bf16_supported(const sgConvDesc* d);
+size_t sg_conv3x3r_bf16_ws_bytes(const sgConvDesc* d);
+int sg_conv3x3r_bf16_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, void* ws,
+                         size_t ws_bytes, sgStream stream);
+int sg_conv3x3r_bf16_dgrad(const sgConvDesc* d, const float* gy, const float* w, float* gx, void* ws, size_t ws_bytes,
+                           sgStream stream);
+int sg_conv3x3r_bf16_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, float* gb, void* ws,
+                           size_t ws_bytes, sgStream stream);
 /* The GEMM stage of the Winograd convs on its own (the transforms of layers.py:251-270's convs aside):
  *   c[m][z*cols + j] = sum_k a[z][m][k] * b[z*cols + j][k],   z < nbatch   (both operands K-contiguous, fp32 MFMA)
  * tile: 0 = 128x128, 1 = 64x128, 2 = 64x64, 3 = 64x64 with 16-deep k-tiles; M, cols multiples of the tile, K of 32.  Exposed for

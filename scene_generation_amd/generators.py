@@ -105,6 +105,45 @@ class GlobalGenerator(nn.Module):
                                      clone_outputs=(b == len(mods)), name='GlobalGenerator[%d:%d]' % (a, b), modules=mods[a:b])
                       for a, b in zip(cuts[:-1], cuts[1:])]
 
+        self._trunk_precision = 'fp32'
+        for blk in self._trunk_blocks():
+            blk.conv_block.trunk_ran = []
+
+    def _trunk_blocks(self):
+        return [m for m in self.model if isinstance(m, ResnetBlock)]
+
+    @property
+    def trunk_precision(self):
+        """operand precision of the residual trunk's convs: 'fp32' (default) or 'bf16' (set_trunk_precision)"""
+        return self._trunk_precision
+
+    def set_trunk_precision(self, precision):
+        """'fp32': the trunk as the reference computes it.  'bf16': every product of the ResnetBlock convs' forward, data-
+        and weight-gradient GEMMs on bf16-rounded operands with fp32 sums (ops.conv3x3_reflect_bf16); weights, activations,
+        InstanceNorm and the residual adds stay fp32.  Nothing outside the trunk changes.  The graphed segments bake the path
+        in when they capture: changing the precision after that raises RuntimeError (build a new generator, or deepcopy
+        one that has not captured, instead)."""
+        from .ops import TRUNK_PRECISIONS
+        if precision not in TRUNK_PRECISIONS:
+            raise ValueError('trunk precision %r: expected one of %s' % (precision, ', '.join(TRUNK_PRECISIONS)))
+        if precision == self._trunk_precision:
+            return
+        if any(e for seg in self._tail for e in seg.entries.values()):
+            raise RuntimeError('GlobalGenerator.set_trunk_precision(%r): the graphed segments have already captured the %s '
+                               'trunk' % (precision, self._trunk_precision))
+        self._trunk_precision = precision
+        for blk in self._trunk_blocks():
+            blk.conv_block.trunk_bf16 = precision == 'bf16'
+
+    def trunk_paths(self):
+        """per ResnetBlock, the path its two convs took in the latest forward that ran them (a replayed graph: the capture):
+        'bf16', 'fp32' (fp32 trunk, or a shape the bf16 kernels do not support), or None before the first forward"""
+        out = []
+        for blk in self._trunk_blocks():
+            ran = blk.conv_block.trunk_ran
+            out.append(None if not ran else ('bf16' if all(r == 'bf16' for r in ran) else 'fp32'))
+        return out
+
     def _runner(self, a, b):
         return _RangeRunner(self.model, a, b)
 

@@ -207,9 +207,18 @@ class Flatten(nn.Module):
 # ---------------------------------------------------------------------------------------------
 
 class FusedSequential(nn.Sequential):
+    # set by GlobalGenerator.set_trunk_precision on the conv blocks of its ResnetBlocks: run pad + conv3x3 + InstanceNorm on the
+    # bf16-operand conv (ops.conv3x3_reflect_bf16) + the standalone InstanceNorm; ``trunk_ran`` (a list there) records, per
+    # forward, which path each of those convs took ('bf16', or 'fp32' for a shape the bf16 kernels do not support)
+    trunk_bf16 = False
+    trunk_ran = None
+
     def forward(self, x, skip=None, start=0, end=None):
         """``start`` / ``end``: run only modules [start, end) (the generator splits itself into a dynamic-shape stem and a
         static-shape remainder that is replayed as a hipGraph)"""
+        ran = self.trunk_ran
+        if ran is not None:
+            del ran[:]
         mods = list(self)[start:end]
         n = len(mods)
         i = 0
@@ -220,11 +229,26 @@ class FusedSequential(nn.Sequential):
                 nrm = mods[i + 2] if i + 2 < n else None
                 # (the fused operator IS plain InstanceNorm: an affine / running-statistics norm or a dilated conv -- both
                 #  rejected by the unfused modules' own forwards -- must reach those checks, not be computed as something else)
-                if (isinstance(nrm, InstanceNorm2d) and nxt.groups == 1
-                        and not getattr(nrm, 'affine', False) and not getattr(nrm, 'track_running_stats', False)
-                        and _pair_to_int(getattr(nxt, 'dilation', 1), 'dilation') == 1
-                        and ops.conv_instnorm_fusable(x, nxt.weight, int(m.padding),
-                                                      _pair_to_int(nxt.stride, 'stride'), _pair_to_int(nxt.padding, 'padding'))):
+                plain_in = (isinstance(nrm, InstanceNorm2d) and nxt.groups == 1
+                            and not getattr(nrm, 'affine', False) and not getattr(nrm, 'track_running_stats', False)
+                            and _pair_to_int(getattr(nxt, 'dilation', 1), 'dilation') == 1)
+                if (plain_in and self.trunk_bf16 and int(m.padding) == 1 and _pair_to_int(nxt.stride, 'stride') == 1
+                        and _pair_to_int(nxt.padding, 'padding') == 0 and ops.conv3x3_reflect_bf16_supported(x, nxt.weight)):
+                    # bf16 trunk: the bf16-operand conv, then InstanceNorm (+ act) (+ the block's residual) on its own
+                    act, slope, used = _peek_act(mods, i + 3, norm=True)
+                    sk = None
+                    if i + 3 + used == n and skip is not None:
+                        sk, skip = skip, None
+                    x = ops.conv3x3_reflect_bf16(x, nxt.weight, nxt.bias)
+                    x = ops.instance_norm(x, skip=sk, eps=nrm.eps, act=act, slope=slope)
+                    if ran is not None:
+                        ran.append('bf16')
+                    i += 3 + used
+                    continue
+                if ran is not None:
+                    ran.append('fp32')
+                if (plain_in and ops.conv_instnorm_fusable(x, nxt.weight, int(m.padding), _pair_to_int(nxt.stride, 'stride'),
+                                                           _pair_to_int(nxt.padding, 'padding'))):
                     # pad + conv + InstanceNorm (+ act) (+ the block's residual when this is its last norm): one fused operator
                     act, slope, used = _peek_act(mods, i + 3, norm=True)
                     sk = None

@@ -259,6 +259,20 @@ WINOGRAD24 = os.environ.get('SG_WINOGRAD24', '1') != '0'
 # convs over a masks_to_layout() layout computed from its factored form (SG_FACTORED_LAYOUT=0: channel-sparse path instead)
 FACTORED_LAYOUT = os.environ.get('SG_FACTORED_LAYOUT', '1') != '0'
 
+# operand precision of the generator's residual-trunk convs (GlobalGenerator.set_trunk_precision): 'fp32' (the default, the
+# reference's precision) or 'bf16' (operands rounded to bf16, fp32 sums: sg_conv3x3r_bf16_*).  SG_TRUNK_PRECISION is read when a
+# Trainer is built without an explicit trunk_precision (unset or empty: 'fp32'; anything else but the two names: ValueError).
+TRUNK_PRECISIONS = ('fp32', 'bf16')
+
+
+def trunk_precision_from_env(environ=None):
+    v = (os.environ if environ is None else environ).get('SG_TRUNK_PRECISION', '')
+    if v == '':
+        return 'fp32'
+    if v not in TRUNK_PRECISIONS:
+        raise ValueError('SG_TRUNK_PRECISION=%r: expected one of %s' % (v, ', '.join(TRUNK_PRECISIONS)))
+    return v
+
 _SKIP_PARAM_GRADS = set()
 
 

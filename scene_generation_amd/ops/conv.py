@@ -292,6 +292,74 @@ def conv2d_instnorm(x, weight, bias, skip=None, eps=1e-5, act=ACT_NONE, slope=0.
     return ConvInstNormFn.apply(x, weight, bias, skip, float(eps), act, float(slope))
 
 
+class Conv3x3ReflectBf16Fn(Function):
+    """conv2d(ReflectionPad2d(1)(x), weight) + bias of a ResnetBlock conv (layers.py:251-270) with every GEMM product on
+    bf16-rounded operands and fp32 sums (sg_conv3x3r_bf16_fwd / _dgrad / _wgrad): the opt-in bf16 trunk of GlobalGenerator.
+    x, y, weight, bias and every gradient stay fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = _f32(x, 'conv input')
+        weight = _f32(weight, 'conv weight')
+        N, C, H, W = x.shape
+        d = _conv_desc(N, C, 0, H, W, weight.size(0), 3, 1, 1, True, 1, H, W, 0, 0)
+        if not _q(d, 'sg_conv3x3r_bf16_supported'):
+            raise ValueError('bf16 trunk conv: unsupported shape x %s, weight %s' % (tuple(x.shape), tuple(weight.shape)))
+        y = torch.empty(N, d.Cout, H, W, dtype=torch.float32, device=x.device)
+        wsb = _q(d, 'sg_conv3x3r_bf16_ws_bytes')
+        _call('sg_conv3x3r_bf16_fwd', d._ref, _p(x), _p(weight), _p(bias), _p(y), _p(workspace(wsb, x.device)), wsb,
+              _stream())
+        ctx.desc = d
+        ctx.bias_ref = bias          # only its identity is used (gradient sink / skip list), never its values
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None:
+            return None, None, None
+        x, weight = ctx.saved_tensors
+        d = ctx.desc
+        gy = _f32(gy)
+        s = _stream()
+        dev = gy.device
+        wsb = _q(d, 'sg_conv3x3r_bf16_ws_bytes')
+        need_w = ctx.needs_input_grad[1] and _wants_grad(weight)
+        need_b = ctx.bias_ref is not None and ctx.needs_input_grad[2] and _wants_grad(ctx.bias_ref)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev)
+            _call('sg_conv3x3r_bf16_dgrad', d._ref, _p(gy), _p(weight), _p(gx), _p(workspace(wsb, dev)), wsb, s)
+        if need_w:
+            ow = GradOut(weight)
+            ob = GradOut(ctx.bias_ref) if need_b else None
+            _call('sg_conv3x3r_bf16_wgrad', d._ref, _p(gy), _p(x), _p(ow.buf), _p(ob.buf) if need_b else None,
+                  _p(workspace(wsb, dev)), wsb, s)
+            gw = ow.finish()
+            gb = ob.finish() if need_b else None
+        elif need_b:
+            ob = GradOut(ctx.bias_ref)
+            csb = _L().sg_channel_sum_ws_bytes(d.Cout)
+            _call('sg_channel_sum', _p(gy), _p(ob.buf), d.N, d.Cout, d.H * d.W, _p(workspace(csb, dev)), csb, s)
+            gb = ob.finish()
+        return gx, gw, gb
+
+
+def conv3x3_reflect_bf16_supported(x, weight):
+    """ReflectionPad2d(1) + Conv2d(3, stride 1) on x with weight, runnable on the bf16 trunk path?"""
+    if not (x.is_cuda and x.dim() == 4 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)
+            and weight.size(1) == x.size(1)):
+        return False
+    N, C, H, W = x.shape
+    d = _conv_desc(N, C, 0, H, W, weight.size(0), 3, 1, 1, True, 1, H, W, 0, 0)
+    return bool(_q(d, 'sg_conv3x3r_bf16_supported'))
+
+
+def conv3x3_reflect_bf16(x, weight, bias=None):
+    return Conv3x3ReflectBf16Fn.apply(x, weight, bias)
+
+
 class CondConv2dFn(Function):
     """act(conv2d([x1 || cond[:, :, None, None].expand(H, W)]) + bias) for a per-sample row ``cond`` [N, C2], zero padding: the
     constant channels never enter the gather.  With W = [W1 | W2] along the input channels,

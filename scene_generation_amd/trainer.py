@@ -83,7 +83,7 @@ def _frozen(*modules):
 
 
 class Trainer:
-    def __init__(self, args, vocab, checkpoint=None, device=None, distributed=False, model_extra=None):
+    def __init__(self, args, vocab, checkpoint=None, device=None, distributed=False, model_extra=None, trunk_precision=None):
         self.vocab = vocab
         self.args = args
         respect_cpu_quota()          # host threads <= the container's CPU quota: an OpenMP burst must not freeze the launch thread
@@ -98,6 +98,7 @@ class Trainer:
                                                                'd_mask_kwargs': {}, 'd_img_kwargs': {}}
         self.gan_g_loss, self.gan_d_loss = get_gan_losses(args.gan_loss_type)
         self._model_extra = model_extra or {}
+        self._trunk_precision = trunk_precision
         self.init_generator(args, checkpoint)
         self.init_image_discriminator(args, checkpoint)
         self.init_obj_discriminator(args, checkpoint)
@@ -174,6 +175,11 @@ class Trainer:
             model_kwargs.update(self._model_extra)
             checkpoint['model_kwargs'] = model_kwargs
         self.model = Model(**model_kwargs).to(self.device)
+        # operand precision of the generator's residual-trunk convs (GlobalGenerator.set_trunk_precision): None = the value of
+        # SG_TRUNK_PRECISION (unset: 'fp32').  A run-time choice, deliberately not a model kwarg or a flag: checkpoints and the
+        # flag surface stay the reference's
+        tp = getattr(self, '_trunk_precision', None)
+        self.model.layout_to_image.set_trunk_precision(ops.trunk_precision_from_env() if tp is None else tp)
         self.criterionVGG = None
         if args.vgg_features_weight > 0:             # trainer.py:57; ImageNet weights via --vgg_weights <state_dict path>
             vgg_weights = getattr(args, 'vgg_weights', None) or None
