@@ -439,6 +439,13 @@ int sg_cross_entropy_bwd(const float* logits, const int64_t* target, int rows, i
  * gradient buffer -- 8 B per parameter -- is folded into this kernel's read) */
 int sg_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                  float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, sgStream stream);
+/* sg_adam_step, then the parameter EMA on the updated value: e = e + ema_w * (p_new - e), as fmaf(ema_w, p_new - e, e); ema_w == 1
+ * writes e = p_new exactly.  p / m / v are bitwise those of sg_adam_step.  36 B per parameter (profile kind SG_K_ADAM).
+ * 0 <= ema_w <= 1; e has the layout of p. */
+int sg_adam_step_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, float lr, float beta1, float beta2,
+                     float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, float ema_w, sgStream stream);
+/* the same EMA expression alone, for parameter runs the Adam step skips: e = ema_w == 1 ? p : fmaf(ema_w, p - e, e) */
+int sg_ema_update(float* e, const float* p, int64_t n, float ema_w, sgStream stream);
 int sg_fill(float* p, float value, int64_t n, sgStream stream);
 int sg_scale(float* p, float alpha, int64_t n, sgStream stream);
 /* dst (device) <- src (PAGE-LOCKED host memory, read through its device mapping) by a kernel on ``stream``: how a collated host

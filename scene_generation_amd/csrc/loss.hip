@@ -1,7 +1,7 @@
 // Scalar losses (deterministic two-stage wave-shuffle reductions, no host sync), cross-entropy and the
 // fused flat-buffer Adam step.  Replaces nn.MSELoss / nn.L1Loss / bce_loss / F.cross_entropy reductions
 // (losses.py:26-44,135-175; trainer.py:215,331-340; discriminators.py:35) and torch.optim.Adam
-// (trainer.py:60,80,106,133).
+// (trainer.py:60,80,106,133), and the exponential moving average of the parameters fused into that step.
 #include "common.h"
 #include <algorithm>
 #include <stdint.h>
@@ -251,6 +251,31 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   m[i] = mi; v[i] = vi; p[i] = pi;
 }
 
+// e <- e + w * (p - e): one explicit fma, so -ffp-contract cannot re-associate it; w == 1 copies p (the lerp with weight 1 is not
+// exactly p in fp32).  Shared by the fused Adam + EMA kernel and the standalone EMA update, so both give the same bits.
+__device__ __forceinline__ float ema_one(float e, float p, float w) {
+  return w == 1.f ? p : __fmaf_rn(w, p - e, e);
+}
+
+// adam_kernel, then the EMA of the updated parameter while it is still in a register: 36 instead of 28 B per parameter, no second
+// pass over p.  p / m / v are bitwise those of adam_kernel (same adam_one, same stores).  One parameter per thread, as above.
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ e, size_t n, float gscale, float step_size, float beta1, float beta2, float eps,
+                                float bc2_sqrt, float ema_w) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float pi = p[i], mi = m[i], vi = v[i];
+  const float ei = e[i];
+  adam_one(pi, g[i], mi, vi, gscale, step_size, beta1, beta2, eps, bc2_sqrt);
+  m[i] = mi; v[i] = vi; p[i] = pi;
+  e[i] = ema_one(ei, pi, ema_w);
+}
+
+__global__ void ema_kernel(float* __restrict__ e, const float* __restrict__ p, size_t n, float ema_w) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) e[i] = ema_one(e[i], p[i], ema_w);
+}
+
 __global__ void fill_kernel(float* __restrict__ p, float value, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = value;
@@ -428,6 +453,26 @@ extern "C" int sg_adam_step(float* p, const float* g, float* m, float* v, int64_
   hipLaunchKernelGGL(adam_kernel, dim3(sg_cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, (size_t)n, grad_scale, lr / bias_corr1, beta1,
                      beta2, eps, bias_corr2_sqrt);
   SG_LAUNCH_CHECK("sg_adam_step");
+  return 0;
+}
+
+extern "C" int sg_adam_step_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, float lr, float beta1,
+                                float beta2, float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, float ema_w,
+                                sgStream stream) {
+  SG_ARG_CHECK(p && g && m && v && e && n > 0 && bias_corr1 > 0.f && bias_corr2_sqrt > 0.f && ema_w >= 0.f && ema_w <= 1.f,
+               "sg_adam_step_ema: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  SgProfScope prof(SG_K_ADAM, s, 0, 36.0 * (double)n);
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(sg_cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, e, (size_t)n, grad_scale,
+                     lr / bias_corr1, beta1, beta2, eps, bias_corr2_sqrt, ema_w);
+  SG_LAUNCH_CHECK("sg_adam_step_ema");
+  return 0;
+}
+
+extern "C" int sg_ema_update(float* e, const float* p, int64_t n, float ema_w, sgStream stream) {
+  SG_ARG_CHECK(e && p && n > 0 && ema_w >= 0.f && ema_w <= 1.f, "sg_ema_update: bad arguments");
+  hipLaunchKernelGGL(ema_kernel, dim3(sg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, e, p, (size_t)n, ema_w);
+  SG_LAUNCH_CHECK("sg_ema_update");
   return 0;
 }
 

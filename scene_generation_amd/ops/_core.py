@@ -378,6 +378,23 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
           _stream())
 
 
+def adam_step_ema(p, g, m, v, e, lr, beta1, beta2, eps, step, grad_scale=1.0, ema_w=1.0):
+    """adam_step, then e = e + ema_w * (p_new - e) on the updated parameter (ema_w == 1: e = p_new exactly).  p / m / v come out
+    bitwise as from adam_step (optim.ParamEMA)."""
+    assert e.numel() == p.numel()
+    bc1 = 1.0 - beta1 ** step
+    bc2_sqrt = (1.0 - beta2 ** step) ** 0.5
+    _call('sg_adam_step_ema', _p(p), _p(g), _p(m), _p(v), _p(e), p.numel(), lr, beta1, beta2, eps, bc1, bc2_sqrt,
+          float(grad_scale), float(ema_w), _stream())
+
+
+def ema_update(e, p, w):
+    """e = e + w * (p - e), the expression of adam_step_ema (w == 1: e = p exactly), for parameters the Adam step skips"""
+    assert e.numel() == p.numel()
+    _call('sg_ema_update', _p(e), _p(p), e.numel(), float(w), _stream())
+    return e
+
+
 def fill_(t, value):
     _call('sg_fill', _p(t), float(value), t.numel(), _stream())
     return t

@@ -8,6 +8,9 @@ their gradients and both Adam moments.  Consequences:
     (scene_generation_amd.parallel) instead of one small collective per tensor.
 ``state_dict()`` / ``load_state_dict()`` speak torch.optim.Adam's schema (trainer.py:138,186), so reference
 checkpoints round-trip.
+
+Optional: an exponential moving average of the parameters (``ParamEMA``, ``FusedAdam.attach_ema``) in a shadow buffer with the
+flat buffer's layout, updated inside the same launch (sg_adam_step_ema: 36 instead of 28 B/param, no second pass).
 """
 import os
 
@@ -58,6 +61,90 @@ class FlatParams:
                 p.grad = self.grad_view(i)
 
 
+def step_runs(touched, steps):
+    """The launches of one FusedAdam.step(): ``(i, j, active)`` for every maximal run of parameters i..j, in order, covering all of
+    them.  Active runs are touched parameters that share a step count (one Adam launch each); inactive runs are untouched
+    parameters, which Adam skips (one EMA launch each when an EMA is attached)."""
+    runs, i, n = [], 0, len(touched)
+    while i < n:
+        j = i
+        if touched[i]:
+            while j + 1 < n and touched[j + 1] and steps[j + 1] == steps[i]:
+                j += 1
+        else:
+            while j + 1 < n and not touched[j + 1]:
+                j += 1
+        runs.append((i, j, bool(touched[i])))
+        i = j + 1
+    return runs
+
+
+def ema_decay_from_env(environ=None):
+    """SG_G_EMA_DECAY: the decay of the generator's parameter EMA when a Trainer is built without ``ema_decay``.  Unset or empty:
+    None (no EMA); otherwise a float in (0, 1), anything else raises ValueError."""
+    v = (os.environ if environ is None else environ).get('SG_G_EMA_DECAY', '')
+    if v == '':
+        return None
+    return check_ema_decay(v, 'SG_G_EMA_DECAY=%r' % v)
+
+
+def check_ema_decay(value, what='ema_decay'):
+    try:
+        d = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s: expected a float in (0, 1)' % what)
+    if not 0.0 < d < 1.0:              # (also rejects nan)
+        raise ValueError('%s: expected a float in (0, 1), got %r' % (what, d))
+    return d
+
+
+class ParamEMA:
+    """Exponential moving average of the parameters of one ``FlatParams``: ``flat`` has the flat buffer's offsets and (zero)
+    alignment gaps and starts as a copy of it.  Update ``k`` (0-based) moves every parameter by
+
+        e = e + w_k * (p - e),   w_k = 1 if k < start (the average copies the weights) else 1 - decay
+
+    (sg_adam_step_ema / sg_ema_update: one fmaf; w = 1 is an exact copy).  Attached to a FusedAdam (``attach_ema``), every step()
+    is one update, fused into its Adam launches; ``update()`` is the standalone form for callers without Adam.
+    ``state_dict()`` holds the schedule ({'decay', 'start', 'updates'}); the averaged values are ``flat`` itself."""
+
+    def __init__(self, flat_params, decay, start=0):
+        self.fp = flat_params
+        self.decay = check_ema_decay(decay)
+        self.start = int(start)
+        if self.start < 0:
+            raise ValueError('ParamEMA: start must be >= 0, got %d' % self.start)
+        self.updates = 0
+        self.flat = flat_params.flat.detach().clone()
+
+    def weight(self, k=None):
+        """the lerp weight of update ``k`` (default: the next one)"""
+        k = self.updates if k is None else k
+        return 1.0 if k < self.start else 1.0 - self.decay
+
+    def update(self):
+        """one update of the whole buffer toward the current parameters, on the current stream"""
+        ops.ema_update(self.flat, self.fp.flat, self.weight())
+        self.updates += 1
+
+    def reset(self):
+        """the average becomes a copy of the current parameters (the schedule is kept)"""
+        with torch.no_grad():
+            self.flat.copy_(self.fp.flat)
+
+    def param_view(self, i):
+        p, o = self.fp.params[i], self.fp.offsets[i]
+        return self.flat[o:o + p.numel()].view(p.shape)
+
+    def state_dict(self):
+        return {'decay': self.decay, 'start': self.start, 'updates': self.updates}
+
+    def load_state_dict(self, sd):
+        self.decay = check_ema_decay(sd['decay'])
+        self.start = int(sd['start'])
+        self.updates = int(sd['updates'])
+
+
 class FusedAdam:
     """torch.optim.Adam(params, lr, betas, eps, weight_decay=0, amsgrad=False) semantics on flat buffers.
 
@@ -99,6 +186,7 @@ class FusedAdam:
         # side-stream groups (streams.py) whose kernels never write this optimiser's buffers: not waited for in zero_grad() /
         # step() (the Trainer's discriminator optimisers: ('front',) -- the generator's object front runs beside their steps)
         self.join_exclude = ()
+        self.ema = None                   # ParamEMA updated by every step() (attach_ema)
         self.pre_step_hooks = []          # e.g. GradReducer.wait
         self.zero_grad_hooks = []         # e.g. GradReducer.begin_step
         self.grad_listeners = []          # callables(i): parameter i just received (a contribution to) its gradient
@@ -204,6 +292,14 @@ class FusedAdam:
             self._spill_k = [0] * len(self.fp.params)
             self._spill_dirty = False
 
+    def attach_ema(self, ema):
+        """Update ``ema`` (a ParamEMA of this optimiser's parameters) in every step(): each Adam launch becomes the fused Adam + EMA
+        launch, and each run of parameters Adam skips gets one sg_ema_update, so every parameter moves once per step().  The Adam
+        results are bitwise unchanged."""
+        if ema is not None and (ema.fp is not self.fp or ema.flat.shape != self.fp.flat.shape):
+            raise ValueError('attach_ema: the EMA must be built over this optimiser\'s FlatParams')
+        self.ema = ema
+
     @property
     def step_count(self):
         return max(self.steps) if self.steps else 0
@@ -257,21 +353,25 @@ class FusedAdam:
             for h in self.pre_step_hooks:
                 h()
             self.fp.attach_grads()
-            fp = self.fp
-            i, n = 0, len(fp.params)
-            while i < n:
-                if not self._touched[i]:
-                    i += 1
-                    continue
-                j, st = i, self.steps[i]
-                while j + 1 < n and self._touched[j + 1] and self.steps[j + 1] == st:
-                    j += 1
+            fp, ema = self.fp, self.ema
+            w = ema.weight() if ema is not None else None
+            for i, j, active in step_runs(self._touched, self.steps):
                 lo, hi = fp.offsets[i], fp.offsets[j] + fp.params[j].numel()
-                ops.adam_step(fp.flat[lo:hi], fp.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr,
-                              self.betas[0], self.betas[1], self.eps, st + 1, self.grad_scale)
+                if not active:
+                    if ema is not None:        # skipped by Adam (no gradient), but the average still moves toward the weights
+                        ops.ema_update(ema.flat[lo:hi], fp.flat[lo:hi], w)
+                    continue
+                st = self.steps[i]
+                if ema is not None:
+                    ops.adam_step_ema(fp.flat[lo:hi], fp.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], ema.flat[lo:hi],
+                                      self.lr, self.betas[0], self.betas[1], self.eps, st + 1, self.grad_scale, w)
+                else:
+                    ops.adam_step(fp.flat[lo:hi], fp.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr,
+                                  self.betas[0], self.betas[1], self.eps, st + 1, self.grad_scale)
                 for q in range(i, j + 1):
                     self.steps[q] = st + 1
-                i = j + 1
+            if ema is not None:
+                ema.updates += 1
         finally:
             self.grad_scale = 1.0          # also when a hook or a launch raised: the scale never outlives its step
 

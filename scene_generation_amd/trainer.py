@@ -12,6 +12,8 @@ Same attributes and step functions as the reference Trainer; differences in HOW 
     factored layouts (_real_and_wrong_pass): the launches of the discriminators are occupancy-starved at N = 32
   * optional data parallelism: per-optimiser GradReducer (RCCL all-reduce of the flat gradient buffers)
   * optional host-side flow control (``max_lead_steps`` / SG_LEAD_STEPS, default off): see ``_lead_point``
+  * optional EMA of the generator's weights (``ema_decay`` / SG_G_EMA_DECAY, default off): fused into its Adam launch,
+    ``ema_model()`` for sampling, extra checkpoint keys next to the reference's
 TensorBoard / image logging of the reference (trainer.py:342-397) is glue outside the hot path: ``write_losses``
 prints; checkpoints keep the reference schema (trainer.py:136-203, train.py:132-162).
 """
@@ -83,7 +85,8 @@ def _frozen(*modules):
 
 
 class Trainer:
-    def __init__(self, args, vocab, checkpoint=None, device=None, distributed=False, model_extra=None, trunk_precision=None):
+    def __init__(self, args, vocab, checkpoint=None, device=None, distributed=False, model_extra=None, trunk_precision=None,
+                 ema_decay=None, ema_start=0):
         self.vocab = vocab
         self.args = args
         respect_cpu_quota()          # host threads <= the container's CPU quota: an OpenMP burst must not freeze the launch thread
@@ -99,6 +102,10 @@ class Trainer:
         self.gan_g_loss, self.gan_d_loss = get_gan_losses(args.gan_loss_type)
         self._model_extra = model_extra or {}
         self._trunk_precision = trunk_precision
+        # EMA of the generator's weights: None = the value of SG_G_EMA_DECAY (unset or empty: off).  Like the trunk precision, a
+        # run-time choice and not a flag: the flag surface stays the reference's
+        self._ema_decay = optim.ema_decay_from_env() if ema_decay is None else optim.check_ema_decay(ema_decay)
+        self._ema_start = int(ema_start)
         self.init_generator(args, checkpoint)
         self.init_image_discriminator(args, checkpoint)
         self.init_obj_discriminator(args, checkpoint)
@@ -131,6 +138,11 @@ class Trainer:
                     # the 1 / world of the mean is applied by the Adam kernel while it reads the gradient (no scaling pass)
                     opt.pre_step_hooks.append(r.wait_deferred_scale)
                     self.reducers.append(r)
+        # after the broadcast: every rank averages the same weights (each rank keeps its own EMA; no collective is added)
+        self.ema, self._ema_model = None, None
+        if self._ema_decay is not None:
+            self.ema = optim.ParamEMA(self.optimizer.fp, self._ema_decay, self._ema_start)
+            self.optimizer.attach_ema(self.ema)
 
     def _lead_point(self, k):
         """Host-side flow control (opt-in), called at fixed places of an iteration: wait until the GPU has passed THIS place of
@@ -174,6 +186,7 @@ class Trainer:
             }
             model_kwargs.update(self._model_extra)
             checkpoint['model_kwargs'] = model_kwargs
+        self._model_kwargs = model_kwargs
         self.model = Model(**model_kwargs).to(self.device)
         # operand precision of the generator's residual-trunk convs (GlobalGenerator.set_trunk_precision): None = the value of
         # SG_TRUNK_PRECISION (unset: 'fp32').  A run-time choice, deliberately not a model kwarg or a flag: checkpoints and the
@@ -246,6 +259,8 @@ class Trainer:
         k = (lambda name: name.replace('_state', '_best_state')) if best else (lambda name: name)
         self.model.load_state_dict(checkpoint[k('model_state')])
         self.optimizer.load_state_dict(checkpoint[k('optim_state')])
+        if self.ema is not None:
+            self._restore_ema(checkpoint, k('model_ema_state'))
         if self.obj_discriminator is not None:
             self.obj_discriminator.load_state_dict(checkpoint[k('d_obj_state')])
             self.optimizer_d_obj.load_state_dict(checkpoint[k('d_obj_optim_state')])
@@ -255,6 +270,58 @@ class Trainer:
         if self.netD is not None:
             self.netD.load_state_dict(checkpoint[k('d_img_state')])
             self.optimizer_d_img.load_state_dict(checkpoint[k('d_img_optim_state')])
+
+    def _restore_ema(self, checkpoint, key):
+        """EMA on: the averaged weights of ``checkpoint[key]`` (a Model state_dict) and the schedule of ``ema_state``; a checkpoint
+        without them (EMA off when it was written, or a reference checkpoint) starts the average as a copy of the weights."""
+        sd = checkpoint.get(key)
+        if sd is None:
+            self.ema.reset()
+            return
+        names = [n for n, _ in self.model.named_parameters()]
+        missing = [n for n in names if n not in sd]
+        if missing:
+            raise KeyError('%s lacks parameters %s' % (key, missing[:4]))
+        with torch.no_grad():
+            for i, n in enumerate(names):
+                self.ema.param_view(i).copy_(sd[n].reshape(self.ema.fp.params[i].shape))
+        if 'ema_state' in checkpoint:
+            self.ema.load_state_dict(checkpoint['ema_state'])
+
+    def ema_model(self):
+        """The generator with the EMA weights, for sampling, evaluation (evaluate.check_model) and ``test_mode=True`` forwards: a
+        ``Model`` of the same kwargs and trunk precision, in eval mode, without gradients, whose parameters are VIEWS into
+        ``self.ema.flat`` (no copy: it follows the average as training goes on).  Built once, on the meta device (no random init,
+        no allocation but the buffers).  Buffers are not averaged: every call copies the live model's (BatchNorm running statistics
+        of mask_net and the appearance encoder).  Read it after Trainer.step returns: the average is written on the step's Adam
+        side stream, which the step joins before it returns."""
+        if self.ema is None:
+            raise RuntimeError('Trainer.ema_model: no EMA (pass ema_decay= or set SG_G_EMA_DECAY)')
+        m = self._ema_model
+        if m is None:
+            with torch.device('meta'):
+                m = Model(**self._model_kwargs)
+            index = {id(p): i for i, p in enumerate(m.parameters())}
+            assert len(index) == len(self.ema.fp.params), 'EMA model and live model disagree on the parameters'
+            views = {}
+            for mod in m.modules():
+                for name, p in list(mod._parameters.items()):
+                    if p is not None:
+                        i = index[id(p)]
+                        if i not in views:
+                            views[i] = torch.nn.Parameter(self.ema.param_view(i), requires_grad=False)
+                        mod._parameters[name] = views[i]
+                for name, b in list(mod._buffers.items()):
+                    if b is not None:
+                        mod._buffers[name] = torch.empty(b.shape, dtype=b.dtype, device=self.ema.flat.device)
+            m.layout_to_image.set_trunk_precision(self.model.layout_to_image.trunk_precision)
+            m.eval()
+            self._ema_model = m
+        live = dict(self.model.named_buffers())
+        with torch.no_grad():
+            for name, b in m.named_buffers():
+                b.copy_(live[name])
+        return m
 
     def save_checkpoint(self, checkpoint, t, args, epoch, train_results=None, val_results=None):
         """trainer.py:152-203: same keys, same "best" bookkeeping (best = highest validation inception mean)."""
@@ -283,6 +350,9 @@ class Trainer:
             checkpoint['d_img_optim_state'] = self.optimizer_d_img.state_dict()
         checkpoint['model_state'] = self.model.state_dict()
         checkpoint['optim_state'] = self.optimizer.state_dict()
+        if self.ema is not None:              # EMA on only: the reference's keys above are unchanged
+            checkpoint['model_ema_state'] = self.ema_model().state_dict()
+            checkpoint['ema_state'] = self.ema.state_dict()
         if val_inception_mean is not None:
             history = checkpoint.setdefault('val_inception', [])
             history.append(val_inception_mean)
@@ -295,6 +365,8 @@ class Trainer:
                     checkpoint[name + '_optim_best_state'] = checkpoint.get(name + '_optim_state')
                 checkpoint['model_best_state'] = checkpoint['model_state']
                 checkpoint['optim_best_state'] = checkpoint['optim_state']
+                if self.ema is not None:
+                    checkpoint['model_ema_best_state'] = checkpoint['model_ema_state']
         checkpoint.setdefault('counters', {})['t'] = t
         checkpoint['counters']['epoch'] = epoch
         path = os.path.join(args.output_dir, '%s_with_model.pt' % args.checkpoint_name)
