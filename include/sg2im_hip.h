@@ -237,6 +237,9 @@ int sg_pad_upsample_bwd(const float* gp, float* gx, int NC, int H, int W, int pa
 /* per-channel sum over (N, HW): bias gradients.  ws (optional, sg_channel_sum_ws_bytes) enables the two-stage form */
 size_t sg_channel_sum_ws_bytes(int C);
 int sg_channel_sum(const float* g, float* out, int N, int C, int HW, void* ws, size_t ws_bytes, sgStream stream);
+/* host-only query of sg_channel_sum's launch plan (what it launches, from the same function): *S = slices of the two-stage
+ * form, 1 = the single-stage kernel.  ws_bytes = 0 stands for "no workspace". */
+int sg_channel_sum_plan(int N, int C, int HW, size_t ws_bytes, int* S);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense layers (nn.Linear inside build_mlp layers.py:215-231, generators.py:45, discriminators.py:23-27)
@@ -299,6 +302,11 @@ int sg_instnorm_fwd(const float* x, const float* skip, float* y, float* mean, fl
                     int act, float slope, sgStream stream);
 int sg_instnorm_bwd(const float* x, const float* gy, const float* mean, const float* rstd, float* gx, int NC, int HW,
                     int act, float slope, sgStream stream);
+/* host-only query of the InstanceNorm launch plan (sg_instnorm_fwd / _bwd launch from the same function, under the current
+ * option instnorm_reg): *kind one of SG_IN_*, *G / *E the kernel's template arguments -- threads per plane and values (reg) or
+ * float4s (vec) per thread; three-pass / big: threads per plane and 0.  aligned16: every operand pointer 16-byte aligned. */
+enum { SG_IN_THREE_PASS_WAVE = 0, SG_IN_THREE_PASS_BLOCK = 1, SG_IN_REG = 2, SG_IN_VEC = 3, SG_IN_BIG = 4 };
+int sg_instnorm_plan(int bwd, int HW, int aligned16, int* kind, int* G, int* E);
 /* training: batch stats (biased var) + running-stat update (unbiased var, momentum) + num_batches_tracked++;
    ws (sg_batchnorm_ws_bytes) holds the per-slice partial statistics of the multi-workgroup reduction */
 size_t sg_batchnorm_ws_bytes(int N, int C, int HW);
@@ -310,6 +318,10 @@ int sg_batchnorm_fwd(const float* x, const float* gamma, const float* beta, floa
 int sg_batchnorm_bwd(const float* x, const float* gy, const float* gamma, const float* beta, const float* save_mean,
                      const float* save_rstd, float* gx, float* ggamma, float* gbeta, int N, int C, int HW, int training,
                      int act, float slope, void* ws, size_t ws_bytes, sgStream stream);
+/* host-only query of the BatchNorm launch plan (sg_batchnorm_fwd / _bwd launch from the same functions): *S statistics slices
+ * per channel, *apply_form 1 = per-plane apply kernels, 0 = one thread per element, *stats_two_pass 1 = the statistics kernel
+ * reads its (longest) slices twice instead of holding them in registers */
+int sg_batchnorm_plan(int N, int C, int HW, int* S, int* apply_form, int* stats_two_pass);
 int sg_avgpool3s2_fwd(const float* x, float* y, int NC, int H, int W, int OH, int OW, sgStream stream);
 int sg_avgpool3s2_bwd(const float* gy, float* gx, int NC, int H, int W, int OH, int OW, sgStream stream);
 /* nn.MaxPool2d(2, 2) of the VGG19 feature extractor behind VGGLoss (losses.py:179-224; torchvision vgg19.features[4,9,18,27]):

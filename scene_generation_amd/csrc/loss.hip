@@ -30,15 +30,14 @@ __device__ __forceinline__ float loss_grad(int kind, float a, float b, float t) 
     case SG_LOSS_L1: { const float d = a - b; return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
     case SG_LOSS_MEAN: return 1.f;
     case SG_LOSS_MSE_SIGMOID_CONST: { const float sg = 1.f / (1.f + expf(-a)); return 2.f * (sg - t) * sg * (1.f - sg); }
-    case SG_LOSS_BCE_PROB_CONST: {
-      const float g1 = logf(a) > -100.f ? 1.f / a : 0.f, g0 = logf(1.f - a) > -100.f ? 1.f / (1.f - a) : 0.f;
-      return -(t * g1 - (1.f - t) * g0);
-    }
+    case SG_LOSS_BCE_PROB_CONST:      // torch's BCELoss backward: the denominator clamped at 1e-12 (not the clamped logs' derivative)
+      return (a - t) / fmaxf(a * (1.f - a), 1e-12f);
     default: {
-      // d/da [max(a,0) - a t + log(1+exp(-|a|))]
+      // d/da [max(a,0) - a t + log(1+exp(-|a|))], with the oracle's one-sided derivatives at a = 0 (clamp(min=0): 1, |a|: 0),
+      // i.e. 1 - t there; the derivative of the function itself is 0.5 - t at a = 0
       const float e = expf(-fabsf(a));
       const float sgn = a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f);
-      return (a > 0.f ? 1.f : 0.f) - t - sgn * e / (1.f + e);
+      return (a >= 0.f ? 1.f : 0.f) - t - sgn * e / (1.f + e);
     }
   }
 }

@@ -391,11 +391,6 @@ __global__ void __launch_bounds__(1024) instnorm_bwd_big_kernel(const float* __r
     }
   }
 }
-inline bool instnorm_big_ok(int HW, const void* a, const void* b, const void* c, const void* d) {
-  const uintptr_t u = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                      reinterpret_cast<uintptr_t>(d);
-  return HW % 4 == 0 && HW >= 4096 && (u & 15) == 0;
-}
 
 // (G, E) for a plane of HW elements, or G = 0 when it does not fit 64 registers per thread
 inline void instnorm_shape(int HW, int maxE, int& G, int& E) {
@@ -444,6 +439,26 @@ inline void instnorm_shape_vec(int HW, int max4, int& G, int& E4) {
   const int e = (HW4 + G - 1) / G;
   E4 = e <= 1 ? 1 : (e <= 2 ? 2 : (e <= 4 ? 4 : (e <= 8 ? 8 : 16)));
 }
+
+// THE InstanceNorm launch plan (sg_instnorm_fwd / _bwd launch exactly this; sg_instnorm_plan reports it): kind SG_IN_* and the
+// kernel's template arguments -- (G, E) of the reg kernels, (G, E4) of the vec kernels, (threads per plane, 0) otherwise.
+// ``aligned16``: every operand pointer (x, y, skip forward; x, gy, gx backward) is 16-byte aligned.
+inline void instnorm_plan(int bwd, int HW, bool aligned16, int reg, int& kind, int& G, int& E) {
+  const int maxE = bwd ? 32 : 64, max4 = bwd ? 8 : 16;             // (backward: two register arrays per thread)
+  if (reg >= 2 && aligned16 && HW % 4 == 0) {
+    instnorm_shape_vec(HW, max4, G, E);
+    if (G > 0) { kind = SG_IN_VEC; return; }
+  }
+  instnorm_shape(HW, maxE, G, E);
+  if (reg && G > 0) { kind = SG_IN_REG; return; }
+  if (reg && aligned16 && HW % 4 == 0 && HW >= 4096) { kind = SG_IN_BIG; G = 1024; E = 0; return; }
+  kind = HW <= 1024 ? SG_IN_THREE_PASS_WAVE : SG_IN_THREE_PASS_BLOCK;
+  G = HW <= 1024 ? 64 : 256;
+  E = 0;
+}
+inline bool sg_aligned16(const void* a, const void* b, const void* c) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
 #define SG_INV_CASE(KERNEL, Gv, Ev, ...)                                                                              \
   hipLaunchKernelGGL((KERNEL<Gv, Ev>), dim3(sg_cdiv(NC, Gv >= 256 ? 1 : 256 / Gv)), dim3(Gv > 256 ? Gv : 256), 0, s, __VA_ARGS__)
 // every (G, E4) pair instnorm_shape_vec can return for the given max4 -- and no other instantiation (a 1024-thread group has 128
@@ -454,11 +469,6 @@ inline void instnorm_shape_vec(int HW, int max4, int& G, int& E4) {
     case 2: SG_INV_CASE(KERNEL, Gv, 2, __VA_ARGS__); break;                \
     default: SG_INV_CASE(KERNEL, Gv, 4, __VA_ARGS__); break;               \
   }
-inline bool instnorm_vec_ok(int HW, const void* a, const void* b, const void* c, const void* d) {
-  const uintptr_t u = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                      reinterpret_cast<uintptr_t>(d);
-  return HW % 4 == 0 && (u & 15) == 0;
-}
 
 // ---------------- BatchNorm2d: one block per channel ---------------------------------------------
 // ---- BatchNorm2d (+ fused activation), three stages so that a 64..256-channel layer fills the chip ---------------------
@@ -763,6 +773,30 @@ inline int bn_slices(int N, int C, int HW) {
   // its two-pass loop of dependent loads: 85 us per launch at 3 TB/s (round 6)
   const long need = (cnt + (long)BN_REG * 256 - 1) / ((long)BN_REG * 256);
   if (S < need && need <= 512) S = (int)need;
+  return S < 1 ? 1 : S;
+}
+// apply kernels: per-plane (bn_apply_kernel / bn_bwd_apply_kernel, grid (ceil(HW / 1024), N C)) from 256-element planes on,
+// one thread per element below
+inline bool bn_apply_per_plane(int HW) { return HW >= 256; }
+// bn_stats_kernel runs its two-pass loop (x read twice) in the slices longer than its register-resident form holds; the first
+// slice is the longest
+inline bool bn_stats_two_pass(int N, int HW, int S) {
+  const long cnt = (long)N * HW;
+  return (cnt + S - 1) / S > (long)BN_REG * 256;
+}
+
+// slices of the two-stage channel sum (sg_channel_sum); 1 = the single-stage channel_sum_kernel.  ws_bytes = 0: no workspace
+inline int channel_sum_slices(int N, int C, int HW, size_t ws_bytes) {
+  const long cnt = (long)N * HW;
+  // small reductions: one block per channel; large ones: split so that ~1024 workgroups stream the tensor
+  int S = (int)(cnt / 4096);
+  const int want = (1024 + C - 1) / C;
+  if (S > want) S = want;
+  if (S > 64) S = 64;
+  if (S > 1 && ws_bytes < (size_t)C * S * sizeof(float)) S = 1;      // no scratch: single-stage fallback
+  // >= 256 channels already give one workgroup per CU: up to 64 elements per thread the single launch (6-8 us) beats the
+  // two-stage pair (14 + 5 us measured at 512 x 8192)
+  if (C >= 256 && cnt <= 16384) S = 1;
   return S < 1 ? 1 : S;
 }
 
@@ -1232,27 +1266,25 @@ extern "C" int sg_instnorm_fwd(const float* x, const float* skip, float* y, floa
   SG_ARG_CHECK(x && y && mean && rstd && NC > 0 && HW > 0, "sg_instnorm_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   SgProfScope prof(SG_K_INSTNORM, s, 0, (double)NC * HW * 4.0 * (skip ? 3 : 2));      // algorithmic: x (+ skip) in, y out
-  const int reg = sg_opt(SG_OPT_INSTNORM_REG);      // 0: the three-pass kernels
-  int G = 0, E = 0;
-  instnorm_shape(HW, 64, G, E);
-  int G4 = 0, E4 = 0;
-  if (reg >= 2 && instnorm_vec_ok(HW, x, y, skip, nullptr)) instnorm_shape_vec(HW, 16, G4, E4);
-  if (G4 > 0) {
+  int kind = 0, G = 0, E = 0;
+  instnorm_plan(0, HW, sg_aligned16(x, y, skip), sg_opt(SG_OPT_INSTNORM_REG), kind, G, E);
+  if (kind == SG_IN_VEC) {
     // forward: up to 16 float4s (64 values) per thread in groups of <= 256 threads, 8 in groups of 1024
+    const int E4 = E;
 #define SG_INV_FWD(Gv, Ev) SG_INV_CASE(instnorm_fwd_vec_kernel, Gv, Ev, x, skip, y, mean, rstd, NC, HW, eps, act, slope)
-    if (G4 == 16) { SG_INV_FWD(16, 1); }
-    else if (G4 == 64) { SG_INV_ROW(instnorm_fwd_vec_kernel, 64, x, skip, y, mean, rstd, NC, HW, eps, act, slope) }
-    else if (G4 == 256 && E4 == 16) { SG_INV_FWD(256, 16); }
-    else if (G4 == 256 && E4 == 8) { SG_INV_FWD(256, 8); }
-    else if (G4 == 256) { SG_INV_ROW(instnorm_fwd_vec_kernel, 256, x, skip, y, mean, rstd, NC, HW, eps, act, slope) }
+    if (G == 16) { SG_INV_FWD(16, 1); }
+    else if (G == 64) { SG_INV_ROW(instnorm_fwd_vec_kernel, 64, x, skip, y, mean, rstd, NC, HW, eps, act, slope) }
+    else if (G == 256 && E4 == 16) { SG_INV_FWD(256, 16); }
+    else if (G == 256 && E4 == 8) { SG_INV_FWD(256, 8); }
+    else if (G == 256) { SG_INV_ROW(instnorm_fwd_vec_kernel, 256, x, skip, y, mean, rstd, NC, HW, eps, act, slope) }
     else if (E4 == 8) { SG_INV_FWD(1024, 8); }
     else { SG_INV_ROW(instnorm_fwd_vec_kernel, 1024, x, skip, y, mean, rstd, NC, HW, eps, act, slope) }
 #undef SG_INV_FWD
-  } else if (reg && G > 0) {
+  } else if (kind == SG_IN_REG) {
     SG_IN_DISPATCH(instnorm_fwd_reg_kernel, 32, x, skip, y, mean, rstd, NC, HW, eps, act, slope)
-  } else if (reg && instnorm_big_ok(HW, x, y, skip, nullptr)) {
+  } else if (kind == SG_IN_BIG) {
     hipLaunchKernelGGL(instnorm_fwd_big_kernel, dim3(NC), dim3(1024), 0, s, x, skip, y, mean, rstd, HW, eps, act, slope);
-  } else if (HW <= 1024) hipLaunchKernelGGL(instnorm_fwd_kernel<true>, dim3(sg_cdiv(NC, 4)), dim3(256), 0, s, x, skip, y, mean, rstd, NC, HW, eps, act, slope);
+  } else if (kind == SG_IN_THREE_PASS_WAVE) hipLaunchKernelGGL(instnorm_fwd_kernel<true>, dim3(sg_cdiv(NC, 4)), dim3(256), 0, s, x, skip, y, mean, rstd, NC, HW, eps, act, slope);
   else hipLaunchKernelGGL(instnorm_fwd_kernel<false>, dim3(NC), dim3(256), 0, s, x, skip, y, mean, rstd, NC, HW, eps, act, slope);
   SG_LAUNCH_CHECK("sg_instnorm_fwd");
   return 0;
@@ -1263,27 +1295,45 @@ extern "C" int sg_instnorm_bwd(const float* x, const float* gy, const float* mea
   SG_ARG_CHECK(x && gy && mean && rstd && gx && NC > 0 && HW > 0, "sg_instnorm_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   SgProfScope prof(SG_K_INSTNORM_BWD, s, 0, (double)NC * HW * 4.0 * 3);      // algorithmic: x, gy in, gx out
-  const int reg = sg_opt(SG_OPT_INSTNORM_REG);
-  int G = 0, E = 0;
-  instnorm_shape(HW, 32, G, E);                        // (two register arrays: 2 x 32 values per thread at most)
-  int G4 = 0, E4 = 0;
-  if (reg >= 2 && instnorm_vec_ok(HW, x, gy, gx, nullptr)) instnorm_shape_vec(HW, 8, G4, E4);
-  if (G4 > 0) {
+  int kind = 0, G = 0, E = 0;
+  instnorm_plan(1, HW, sg_aligned16(x, gy, gx), sg_opt(SG_OPT_INSTNORM_REG), kind, G, E);
+  if (kind == SG_IN_VEC) {
     // backward (two register arrays): up to 8 float4s per array and thread in groups of <= 256 threads, 4 in groups of 1024
+    const int E4 = E;
 #define SG_INV_BWD(Gv, Ev) SG_INV_CASE(instnorm_bwd_vec_kernel, Gv, Ev, x, gy, mean, rstd, gx, NC, HW, act, slope)
-    if (G4 == 16) { SG_INV_BWD(16, 1); }
-    else if (G4 == 64) { SG_INV_ROW(instnorm_bwd_vec_kernel, 64, x, gy, mean, rstd, gx, NC, HW, act, slope) }
-    else if (G4 == 256 && E4 == 8) { SG_INV_BWD(256, 8); }
-    else if (G4 == 256) { SG_INV_ROW(instnorm_bwd_vec_kernel, 256, x, gy, mean, rstd, gx, NC, HW, act, slope) }
+    if (G == 16) { SG_INV_BWD(16, 1); }
+    else if (G == 64) { SG_INV_ROW(instnorm_bwd_vec_kernel, 64, x, gy, mean, rstd, gx, NC, HW, act, slope) }
+    else if (G == 256 && E4 == 8) { SG_INV_BWD(256, 8); }
+    else if (G == 256) { SG_INV_ROW(instnorm_bwd_vec_kernel, 256, x, gy, mean, rstd, gx, NC, HW, act, slope) }
     else { SG_INV_ROW(instnorm_bwd_vec_kernel, 1024, x, gy, mean, rstd, gx, NC, HW, act, slope) }
 #undef SG_INV_BWD
-  } else if (reg && G > 0) {
+  } else if (kind == SG_IN_REG) {
     SG_IN_DISPATCH(instnorm_bwd_reg_kernel, 16, x, gy, mean, rstd, gx, NC, HW, act, slope)
-  } else if (reg && instnorm_big_ok(HW, x, gy, gx, nullptr)) {
+  } else if (kind == SG_IN_BIG) {
     hipLaunchKernelGGL(instnorm_bwd_big_kernel, dim3(NC), dim3(1024), 0, s, x, gy, mean, rstd, gx, HW, act, slope);
-  } else if (HW <= 1024) hipLaunchKernelGGL(instnorm_bwd_kernel<true>, dim3(sg_cdiv(NC, 4)), dim3(256), 0, s, x, gy, mean, rstd, gx, NC, HW, act, slope);
+  } else if (kind == SG_IN_THREE_PASS_WAVE) hipLaunchKernelGGL(instnorm_bwd_kernel<true>, dim3(sg_cdiv(NC, 4)), dim3(256), 0, s, x, gy, mean, rstd, gx, NC, HW, act, slope);
   else hipLaunchKernelGGL(instnorm_bwd_kernel<false>, dim3(NC), dim3(256), 0, s, x, gy, mean, rstd, gx, NC, HW, act, slope);
   SG_LAUNCH_CHECK("sg_instnorm_bwd");
+  return 0;
+}
+
+extern "C" int sg_instnorm_plan(int bwd, int HW, int aligned16, int* kind, int* G, int* E) {
+  SG_ARG_CHECK(kind && G && E && HW > 0, "sg_instnorm_plan: bad arguments");
+  instnorm_plan(bwd ? 1 : 0, HW, aligned16 != 0, sg_opt(SG_OPT_INSTNORM_REG), *kind, *G, *E);
+  return 0;
+}
+
+extern "C" int sg_batchnorm_plan(int N, int C, int HW, int* S, int* apply_form, int* stats_two_pass) {
+  SG_ARG_CHECK(S && apply_form && stats_two_pass && N > 0 && C > 0 && HW > 0, "sg_batchnorm_plan: bad arguments");
+  *S = bn_slices(N, C, HW);
+  *apply_form = bn_apply_per_plane(HW) ? 1 : 0;
+  *stats_two_pass = bn_stats_two_pass(N, HW, *S) ? 1 : 0;
+  return 0;
+}
+
+extern "C" int sg_channel_sum_plan(int N, int C, int HW, size_t ws_bytes, int* S) {
+  SG_ARG_CHECK(S && N > 0 && C > 0 && HW > 0, "sg_channel_sum_plan: bad arguments");
+  *S = channel_sum_slices(N, C, HW, ws_bytes);
   return 0;
 }
 
@@ -1309,7 +1359,7 @@ extern "C" int sg_batchnorm_fwd(const float* x, const float* gamma, const float*
   if (!counter)
     hipLaunchKernelGGL(bn_final_kernel, dim3(sg_cdiv(C, 64)), dim3(64), 0, s, (const float*)part, save_mean, save_rstd,
                        running_mean, running_var, num_batches, C, S, eps, momentum, training);
-  if (HW >= 256)
+  if (bn_apply_per_plane(HW))
     hipLaunchKernelGGL(bn_apply_kernel, dim3(sg_cdiv(HW, 1024), N * C), dim3(256), 0, s, x, gamma, beta,
                        (const float*)save_mean, (const float*)save_rstd, y, C, HW, act, slope);
   else
@@ -1335,7 +1385,7 @@ extern "C" int sg_batchnorm_bwd(const float* x, const float* gy, const float* ga
                      HW, S, act, slope, counter, sums, ggamma, gbeta);
   if (!counter)
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(sg_cdiv(C, 64)), dim3(64), 0, s, (const float*)part, sums, ggamma, gbeta, C, S);
-  if (HW >= 256)
+  if (bn_apply_per_plane(HW))
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(sg_cdiv(HW, 1024), N * C), dim3(256), 0, s, x, gy, gamma, beta, save_mean,
                        save_rstd, (const float*)sums, gx, C, HW, 1.f / ((float)N * HW), training, act, slope);
   else
@@ -1351,16 +1401,7 @@ extern "C" int sg_channel_sum(const float* g, float* out, int N, int C, int HW, 
                               sgStream stream) {
   SG_ARG_CHECK(g && out && N > 0 && C > 0 && HW > 0, "sg_channel_sum: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const long cnt = (long)N * HW;
-  // small reductions: one block per channel; large ones: split so that ~1024 workgroups stream the tensor
-  int S = (int)(cnt / 4096);
-  const int want = (1024 + C - 1) / C;
-  if (S > want) S = want;
-  if (S > 64) S = 64;
-  if (S > 1 && (!ws || ws_bytes < (size_t)C * S * sizeof(float))) S = 1;      // no scratch: single-stage fallback
-  // >= 256 channels already give one workgroup per CU: up to 64 elements per thread the single launch (6-8 us) beats the
-  // two-stage pair (14 + 5 us measured at 512 x 8192)
-  if (C >= 256 && cnt <= 16384) S = 1;
+  const int S = channel_sum_slices(N, C, HW, ws ? ws_bytes : 0);
   if (S <= 1) {
     hipLaunchKernelGGL(channel_sum_kernel, dim3(C), dim3(256), 0, s, g, out, N, C, HW);
   } else {
