@@ -2,12 +2,18 @@
 """bench.py -- images/sec of one full G+D training step (train.py:190-215 semantics) on MI355X.
 
   python bench.py --gpus 1 --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus 1 --steps K --warmup W --full   (the same headline line plus everything else the bench measures)
 
 Workload (BASELINE.json configs[1]): COCO-Stuff-shaped synthetic scene graphs, 128x128, <=8 objects/image (+ the
 __image__ node), batch 32 PER GPU (weak scaling; configs[2] = 256 over 8 GPUs), reference default widths (183 M-param
 generator, 2-scale PatchGAN, object / mask discriminators), fp32, VGG loss off (needs pretrained weights).
 A step = Model.forward + train_generator + the three discriminator steps incl. four Adam updates and, for N>1, the
 RCCL gradient all-reduces.  Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, the K timed steps, --dump-outputs, the line.
+--full adds the passes that take runs of their own after the timed steps: the isolated host-issue steps, the per-launch
+roofline pass and its live rocprofv3 --pmc traffic, the secondary configurations, the c4 / c5 legs, the CPU baseline and, for
+N>1, the all-reduce observation steps.  The --no_* / --pmc / --cpu_baseline switches select among those under --full.
 """
 import argparse
 import json
@@ -33,6 +39,10 @@ def parse():
     p.add_argument('--warmup', type=int, default=4)
     p.add_argument('--batch_per_gpu', type=int, default=32)
     p.add_argument('--image_size', type=int, default=128)
+    p.add_argument('--full', action='store_true',
+                   help='after the headline pass, also run everything else the bench measures (isolated host-issue steps, '
+                        'roofline pass + live PMC traffic, secondary passes, legs, CPU baseline, all-reduce observation); the '
+                        'switches below apply under --full only')
     p.add_argument('--cpu_baseline', default='auto', choices=['auto', 'off'])
     p.add_argument('--cpu_images', type=int, default=32, help='images per CPU-baseline step (SURVEY 8d: config 2 at N = 32)')
     p.add_argument('--cpu_steps', type=int, default=3)
@@ -335,8 +345,8 @@ def measure_traffic(kind, timeout_s=150):
     for ctr in ('FETCH_SIZE', 'WRITE_SIZE'):
         d = tempfile.mkdtemp(prefix='sg_pmc_', dir='/tmp')
         cmd = [rp, '--pmc', ctr, '--kernel-trace', '--kernel-include-regex', '%s|adam_kernel' % rx, '-d', d, '-o', 'pmc', '--',
-               sys.executable, os.path.abspath(__file__), '--steps', '2', '--warmup', '3', '--no_legs', '--no_secondary',
-               '--no_prof', '--cpu_baseline', 'off', '--pmc', 'off']
+               sys.executable, os.path.abspath(__file__), '--steps', '2', '--warmup', '3', '--full', '--no_legs',
+               '--no_secondary', '--no_prof', '--cpu_baseline', 'off', '--pmc', 'off']
         env = dict(os.environ, TMPDIR='/tmp', SG_GRAPHS='0', SG_STREAM_GROUPS='')      # eager launches: every dispatch is visible to the counters
         try:
             # own process group: on a timeout the whole tree (rocprofv3 AND the python it started) is killed, nothing is left
@@ -548,19 +558,22 @@ def main():
               'ms_per_step_median': med_ms, 'ms_per_step_min': per_step[0], 'ms_per_step_max': per_step[-1],
               'spread': (per_step[-1] - per_step[0]) / med_ms}
     calls, replays = (ops.CALLS[0] - calls0) / a.steps, (graphs.REPLAYS[0] - replays0) / a.steps
+    # everything below that runs steps of its own is --full only; a plain run goes straight to the sanity check and the line
+    prof_on = a.full and not a.no_prof
     # host cost of ISSUING one step, measured with an idle GPU in front of it: once the step is GPU-bound the number above
     # mostly measures back-pressure of the full launch queue, not host work
     iso = []
     quick = os.environ.get('SG_BENCH_QUICK') == '1'      # test harnesses: one isolated / one observed step instead of three
-    for i in range(1 if quick else 3):
+    if a.full:
+        for i in range(1 if quick else 3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            one_step(tr, a.warmup + a.steps + i)
+            iso.append(time.perf_counter() - t0)
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        one_step(tr, a.warmup + a.steps + i)
-        iso.append(time.perf_counter() - t0)
-    torch.cuda.synchronize()
     # roofline pass: the SAME K steps again with a HIP event pair around every kernel launch on the launch stream
     dt_prof = None
-    if not a.no_prof:
+    if prof_on:
         # ... and with the side streams off (streams.py, group 'front'): a launch that shares the chip with another stream's
         # kernels is stretched by what they take, and the pass is there to price every kernel on its own.  The headline pass
         # above runs WITH them (`side_streams` in the JSON line); rocprofv3's durations of that pass are the stretched ones.
@@ -580,7 +593,7 @@ def main():
 
     # DP observability: isolated all-reduce time per bucket and how long the step was exposed to the collectives
     comm = None
-    if world > 1:
+    if world > 1 and a.full:
         comm = {'world': world}
         for r in tr.reducers:
             r.profile = True
@@ -620,8 +633,8 @@ def main():
                    'dense_layout_outputs': False, 'hip_graphs': graphs.ENABLED},
         # wall time the host needed to ISSUE the K steps (no sync): close to ms_per_step => launch-bound
         'host_issue_ms_per_step': 1e3 * host_issue / a.steps,
-        # the same for a single step issued into an idle GPU (no queue back-pressure): the host-side cost of a step
-        'host_issue_isolated_ms_per_step': 1e3 * sum(iso) / len(iso),
+        # the same for a single step issued into an idle GPU (no queue back-pressure): the host-side cost of a step (--full)
+        'host_issue_isolated_ms_per_step': 1e3 * sum(iso) / len(iso) if iso else None,
         # C-ABI calls (each launches 1..4 kernels) and hipGraph launches the host issues per step; the kernels inside a
         # replayed graph are dispatched by the GPU front-end without host involvement
         'host_calls_per_step': calls, 'graph_replays_per_step': replays,
@@ -643,9 +656,10 @@ def main():
     if world > 1:
         out['rccl_ranks'] = dist.get_world_size()
         out['dist_backend'] = backend
-        out['allreduce'] = comm
+        if comm is not None:
+            out['allreduce'] = comm
         out['rccl'] = rccl_info(backend)
-    if rank == 0 and not a.no_prof:
+    if rank == 0 and prof_on:
         prof = ops.prof_read()
         mm = {k: v for k, v in prof.items() if v['launches'] > 0 and v['flops'] > 0 and k not in ('linear', 'head_conv')}
         all_ms = sum(v['ms'] for v in prof.values())
@@ -734,7 +748,7 @@ def main():
                           'frac': round(gbs / HBM_PEAK_GBS, 3)}
         out['roofline_hbm'] = {'peak_GBps': HBM_PEAK_GBS, 'note': 'algorithmic bytes / HIP-event time per launch; a kernel that '
                                're-reads its input through L2 shows less than its real traffic rate', 'kernels': hbm}
-    if world == 1 and not a.no_secondary:
+    if world == 1 and a.full and not a.no_secondary:
         sec = {}
         n2 = max(2, min(a.steps, 6))
         # (1) the reference's DEFAULT flags: VGG19 perceptual loss on (args.py:73), random-init VGG weights
@@ -817,7 +831,7 @@ def main():
         finally:
             ops.WINOGRAD, ops.FACTORED_LAYOUT, ops.UPCONV, ops.HEADCONV = saved
         out['secondary'] = sec
-    if world == 1 and not a.no_legs:
+    if world == 1 and a.full and not a.no_legs:
         # the other BASELINE configs as secondary legs (parity-tested shapes; not the headline): c4 = configs[3] per-GPU shape
         # (256x256, <= 16 objects, 8 images per GPU), c5 = configs[4] (32 objects / 96 triples per image, 128x128, N = 32:
         # the GraphTripleConv scatter stress) with the graph kernels' own rates
@@ -858,7 +872,7 @@ def main():
             torch.cuda.empty_cache()
         out['legs'] = legs
     if rank == 0:
-        if world == 1 and a.cpu_baseline == 'auto':
+        if world == 1 and a.full and a.cpu_baseline == 'auto':
             try:
                 out['cpu_baseline'] = cpu_baseline(S, a.cpu_images, a.cpu_steps)
             except Exception as e:           # the baseline is a report, never a reason to lose the bench line

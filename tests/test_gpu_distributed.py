@@ -153,7 +153,8 @@ def test_bench_dp_leg_executes_two_ranks_on_one_gpu(world, per_gpu, steps):
     env = dict(os.environ, SG_DIST_BACKEND='gloo', SG_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr',
            '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps',
-           str(steps), '--warmup', '3', '--batch_per_gpu', str(per_gpu), '--no_secondary', '--no_legs', '--cpu_baseline', 'off']
+           str(steps), '--warmup', '3', '--batch_per_gpu', str(per_gpu), '--full', '--no_secondary', '--no_legs', '--cpu_baseline',
+           'off']
     if world == 2:
         cmd.append('--no_prof')
         env['SG_BENCH_QUICK'] = '1'

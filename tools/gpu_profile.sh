@@ -3,7 +3,7 @@
 # HBM-traffic summary (two separate --pmc passes, no other trace domain).  Databases stay under /tmp on the box; only the
 # summaries go to gpurun_out/.  usage: tools/gpu_profile.sh PREFIX
 R=$PWD; P=$R/gpurun_out/$1
-python bench.py --steps 20 --warmup 5 > ${P}_bench.json 2> ${P}_bench.err
+python bench.py --steps 20 --warmup 5 --full > ${P}_bench.json 2> ${P}_bench.err
 tail -c 600 ${P}_bench.err > ${P}_bench.err.tail; rm -f ${P}_bench.err
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --no_prof --no_secondary --no_legs --cpu_baseline off"

@@ -11,7 +11,7 @@ if [ -n "$extra" ]; then eval "$extra" > ${out}_extra.log 2>&1; fi
 i=0
 for v in "$@"; do
   echo "== variant $i: '$v'" >> ${out}_ab.log
-  env $v timeout 600 python bench.py --steps 20 --warmup 5 --no_secondary --no_legs --cpu_baseline off --pmc off 2>${out}_bench_err_$i.log | tail -1 > ${out}_bench_$i.json
+  env $v timeout 600 python bench.py --steps 20 --warmup 5 --full --no_secondary --no_legs --cpu_baseline off --pmc off 2>${out}_bench_err_$i.log | tail -1 > ${out}_bench_$i.json
   python - ${out}_bench_$i.json >> ${out}_ab.log 2>&1 <<'PY'
 import sys, json
 d = json.loads(open(sys.argv[1]).read())
