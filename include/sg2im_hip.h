@@ -377,6 +377,34 @@ size_t sg_masks_to_layout_test_ws_bytes(int O);
 int sg_masks_to_layout_test_fwd(const float* vecs, const float* boxes, const void* masks, int masks_i64,
                                 const int32_t* seg_off, float* out, void* ws, size_t ws_bytes, int N, int O, int D, int M,
                                 int H, int W, int avg, sgStream stream);
+/* The FACTORED form of the test-mode compositing: every pixel belongs to at most one object, so the layout is
+ * vecs[winner(p)] * value(p).  Same inputs, visiting order and arithmetic as sg_masks_to_layout_test_fwd (vecs are needed for the
+ * masses only); instead of the D channels it writes
+ *   Z [N, J, H, W]    Z[n, j, p] = value(p) if j == plane_idx[winner(p)] else 0   (EVERY element is written: no fill needed)
+ *   winner [N, H, W]  int32 global object index, -1 where no object's sampled mask exceeds 0.5
+ *   value [N, H, W]   the winner's sampled mask (divided by the image's object count under avg), 0 where nobody wins; may be null
+ * plane_idx [O]: the plane (0 <= plane < J) of every object inside its image.  vecs[winner] * value is bit-identical to the
+ * output of sg_masks_to_layout_test_fwd.  ws >= sg_masks_to_layout_test_planes_ws_bytes(O).  Inference only. */
+size_t sg_masks_to_layout_test_planes_ws_bytes(int O);
+int sg_masks_to_layout_test_planes(const float* vecs, const float* boxes, const void* masks, int masks_i64,
+                                   const int32_t* seg_off, const int64_t* plane_idx, float* Z, int32_t* winner, float* value,
+                                   void* ws, size_t ws_bytes, int N, int O, int D, int J, int M, int H, int W, int avg,
+                                   sgStream stream);
+/* imagenet_deprocess_batch (data/utils.py:17-51) on the device.  imgs (N, C, H, W) fp32 -> out_f32 (N, C, H, W) in [0, 255] and / or
+ * out_u8 (N, H, W, C) uint8 (either may be null, not both).  In IEEE fp32, in this order: y = x / 2 + 0.5; with rescale, per image
+ * over all channels lo = min y, hi = max y, y = (y - lo) / (hi - lo); v = clamp(y * 255, 0, 255); uint8 = (uint8)(v + 0.5f).
+ * A constant image under rescale (hi == lo) gives NaN in out_f32, as the reference does, and 0 in out_u8; so does a NaN input.
+ * ws >= sg_deprocess_images_ws_bytes(N, H, W) when rescale != 0 (per-(image, chunk) min / max partials); N <= 65535. */
+size_t sg_deprocess_images_ws_bytes(int N, int H, int W);
+int sg_deprocess_images(const float* imgs, float* out_f32, uint8_t* out_u8, void* ws, size_t ws_bytes, int N, int C, int H, int W,
+                        int rescale, sgStream stream);
+/* The label map of a test-mode layout as a picture (scripts/sample_images.py:156-160) without the dense layout:
+ * rgb[n, e, p] = colors[objs[winner[n, p]], e] * value[n, p] (0 where winner < 0), then the whole batch times 255 / (its maximum).
+ * winner / value as written by sg_masks_to_layout_test_planes, objs [O] int64 class ids, colors [num_colors, 3] fp32,
+ * rgb [N, 3, H, W] fp32.  An all-zero batch gives NaN, as the reference's 0 * (255 / 0) does.  ws >= sg_layout_rgb_ws_bytes. */
+size_t sg_layout_rgb_ws_bytes(int N, int H, int W);
+int sg_layout_rgb(const int32_t* winner, const float* value, const int64_t* objs, const float* colors, float* rgb, void* ws,
+                  size_t ws_bytes, int N, int O, int num_colors, int H, int W, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

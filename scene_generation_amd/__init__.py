@@ -16,7 +16,7 @@ os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
 
 __version__ = '0.1.0'
 _SUBMODULES = ('args', 'utils', 'layers', 'graph', 'layout', 'bilinear', 'generators', 'discriminators', 'losses',
-               'model', 'trainer', 'optim', 'parallel', 'synthetic', 'ops', 'pipeline')
+               'model', 'trainer', 'optim', 'parallel', 'synthetic', 'ops', 'pipeline', 'sample')
 
 
 def _find_host_package(name):

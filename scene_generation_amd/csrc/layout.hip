@@ -499,6 +499,68 @@ __global__ void __launch_bounds__(256) layout_test_fwd_kernel(const float* __res
   for (int d = 0; d < D; ++d) op[(size_t)d * HW] = win < 0 ? 0.f : vr[d] * sv;
 }
 
+// Factored form of the kernel above.  A pixel of the test-mode layout is vecs[winner(p)] * value(p): instead of the D channels
+// the kernel writes the J mask planes of the image (value(p) in the plane of the winner, 0 in the others: EVERY element of
+// Z [N, J, H, W] is written), the winner's global object index (-1: nobody) and, when asked, the value plane itself.
+// 4 * (J + 2) instead of 4 * D bytes per pixel.  Winner and value come from the same expressions as above (same visiting order,
+// same sampled mask, same division for 'avg'), so vecs[winner] * value reproduces the dense kernel's output bit for bit.
+// VEC = 4 needs W % 4 == 0 (a thread's pixels then share a row and every store is a 16-byte vector store).
+template <bool I64, int VEC>
+__global__ void __launch_bounds__(256) layout_test_planes_kernel(const float* __restrict__ boxes, const void* __restrict__ masks,
+                                                                const int32_t* __restrict__ seg, const int32_t* __restrict__ order,
+                                                                const int64_t* __restrict__ plane_idx, float* __restrict__ Z,
+                                                                int32_t* __restrict__ winner, float* __restrict__ value, int J,
+                                                                int M, int H, int W, int avg, int ac) {
+  const int n = blockIdx.y;
+  const int beg = seg[n], cnt = seg[n + 1] - beg;
+  const int HW = H * W;
+  const int px0 = (blockIdx.x * 256 + threadIdx.x) * VEC;
+  if (px0 >= HW) return;
+  const int h = px0 / W, w0 = px0 - h * W;
+  const float Y = lin01(h, H);
+  int win[VEC], pj[VEC];
+  float sv[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) { win[v] = -1; pj[v] = -1; sv[v] = 0.f; }
+  for (int r = 0; r < cnt; ++r) {
+    const size_t o = (size_t)(beg + order[beg + r]);
+    const float x0 = boxes[o * 4 + 0], x1 = boxes[o * 4 + 2];
+    const Tap ty = make_tap(box_coord(Y, boxes[o * 4 + 1], boxes[o * 4 + 3]), M, ac);
+    bool open = false;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      // sampled unconditionally and kept by a select: the arithmetic sits in the same straight-line form as in the dense kernel
+      const Tap tx = make_tap(box_coord(lin01(w0 + v, W), x0, x1), M, ac);
+      const float s = sample_mask<I64>(masks, o, M, ty, tx);
+      const bool take = win[v] < 0 && s > 0.5f;
+      win[v] = take ? (int)o : win[v];
+      sv[v] = take ? s : sv[v];
+      open = open || win[v] < 0;
+    }
+    if (!open) break;
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    if (avg) sv[v] /= (float)(cnt > 1 ? cnt : 1);
+    if (win[v] >= 0) pj[v] = (int)plane_idx[win[v]];
+  }
+  const size_t po = (size_t)n * HW + px0;
+  float* zp = Z + (size_t)n * J * HW + px0;
+  if (VEC == 4) {
+    typedef int nt_i4 __attribute__((ext_vector_type(4)));
+    const nt_i4 wv = {win[0], win[1], win[2], win[3]};
+    *reinterpret_cast<nt_i4*>(winner + po) = wv;
+    if (value) *reinterpret_cast<float4*>(value + po) = make_float4(sv[0], sv[1], sv[2], sv[3]);
+    for (int j = 0; j < J; ++j)
+      *reinterpret_cast<float4*>(zp + (size_t)j * HW) =
+          make_float4(pj[0] == j ? sv[0] : 0.f, pj[1] == j ? sv[1] : 0.f, pj[2] == j ? sv[2] : 0.f, pj[3] == j ? sv[3] : 0.f);
+  } else {
+    winner[po] = win[0];
+    if (value) value[po] = sv[0];
+    for (int j = 0; j < J; ++j) zp[(size_t)j * HW] = pj[0] == j ? sv[0] : 0.f;
+  }
+}
+
 }  // namespace
 
 // grid_sample geometry of every bilinear operator of this file: 0 = align_corners=False (what torch >= 1.3 executes for the
@@ -590,6 +652,35 @@ extern "C" int sg_masks_to_layout_test_fwd(const float* vecs, const float* boxes
                        (const int32_t*)order, out, D, M, H, W, avg, g_align_corners);
   }
   SG_LAUNCH_CHECK("sg_masks_to_layout_test_fwd");
+  return 0;
+}
+
+extern "C" size_t sg_masks_to_layout_test_planes_ws_bytes(int O) { return sg_masks_to_layout_test_ws_bytes(O); }
+
+extern "C" int sg_masks_to_layout_test_planes(const float* vecs, const float* boxes, const void* masks, int masks_i64,
+                                              const int32_t* seg_off, const int64_t* plane_idx, float* Z, int32_t* winner,
+                                              float* value, void* ws, size_t ws_bytes, int N, int O, int D, int J, int M, int H,
+                                              int W, int avg, sgStream stream) {
+  SG_ARG_CHECK(vecs && boxes && masks && seg_off && plane_idx && Z && winner && ws && N > 0 && O > 0 && D > 0 && J > 0 && M > 0 &&
+                   H > 0 && W > 0,
+               "sg_masks_to_layout_test_planes: bad arguments");
+  SG_ARG_CHECK(ws_bytes >= sg_masks_to_layout_test_planes_ws_bytes(O), "sg_masks_to_layout_test_planes: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  double* mass = reinterpret_cast<double*>(ws);
+  int32_t* order = reinterpret_cast<int32_t*>(mass + O);
+  const int ac = g_align_corners;
+  SgProfScope prof(SG_K_LAYOUT_TEST_PLANES, s, 0, 4.0 * N * (J + (value ? 2 : 1)) * (double)H * W);
+  // the visiting order of the dense form, from the same two kernels (the mass needs the full vectors)
+  if (masks_i64) hipLaunchKernelGGL((layout_mass_kernel<true>), dim3(O), dim3(256), 0, s, vecs, boxes, masks, mass, D, M, H, W, ac);
+  else hipLaunchKernelGGL((layout_mass_kernel<false>), dim3(O), dim3(256), 0, s, vecs, boxes, masks, mass, D, M, H, W, ac);
+  hipLaunchKernelGGL(layout_order_kernel, dim3(N), dim3(64), 0, s, (const double*)mass, seg_off, order);
+#define LAUNCH_PLANES(I64, VEC)                                                                                              \
+  hipLaunchKernelGGL((layout_test_planes_kernel<I64, VEC>), dim3(sg_cdiv(H * W, 256 * VEC), N), dim3(256), 0, s, boxes, masks, \
+                     seg_off, (const int32_t*)order, plane_idx, Z, winner, value, J, M, H, W, avg, ac)
+  if (W % 4 == 0) { if (masks_i64) LAUNCH_PLANES(true, 4); else LAUNCH_PLANES(false, 4); }
+  else { if (masks_i64) LAUNCH_PLANES(true, 1); else LAUNCH_PLANES(false, 1); }
+#undef LAUNCH_PLANES
+  SG_LAUNCH_CHECK("sg_masks_to_layout_test_planes");
   return 0;
 }
 

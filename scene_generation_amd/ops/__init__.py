@@ -11,6 +11,7 @@ One namespace, six modules (the single 1 741-line ops.py of rounds 1-3, split by
   nn       activations, residual add, dropout mask, Instance / BatchNorm, pooling, padding
   graph    CSR build, row gather, bit-exact triple pool, embeddings, concat
   layout   masks_to_layout (dense / deferred / test mode / factored), per-image-weight convs, bilinear crops, VectorPool
+           and the sampling tail (factored test-mode planes, deprocess_images, layout_rgb)
   losses   scalar losses, weighted sum, cross-entropy
 Everything is re-exported here, so ``ops.conv2d``, ``ops.GradOut``, ``ops._call`` ... keep working.  The path switches
 (``ops.WINOGRAD``, ``ops.FACTORED_LAYOUT``, ``ops.UPCONV``, ``ops.HEADCONV``, ``ops.WINOGRAD24``, ``ops.COND_FOLD``) are WRITABLE through this

@@ -301,12 +301,13 @@ def skip_state_key():
 # ---- layout hints -------------------------------------------------------------------------------------
 # What the model knows about a masks_to_layout() result -- which channels can be non-zero per image ('sparse',
 # 'sparse_cat'), that the one-hot block is a constant of the graph ('grad_from'), its factored form ('factored'), whether
-# the dense tensor has been written yet ('pending') -- lives in a side table keyed by the tensor's storage address, NOT in
+# the dense tensor has been written yet ('pending'), the (winner, value) planes of a factored test-mode layout ('test_planes')
+# -- lives in a side table keyed by the tensor's storage address, NOT in
 # Python attributes: the reference's training loop passes ``layout.detach()`` around (train.py:208-215) and a plain
 # ``.detach()`` keeps the storage but drops attributes.  An entry holds a strong reference to its tensor, so the address
 # cannot be recycled while the entry exists; Model.forward clears the table at the start of every iteration.
 _HINT_TABLE = {}
-_HINT_KEYS = ('sparse', 'sparse_cat', 'grad_from', 'factored', 'keep_grad', 'pending', 'wrong_twin')
+_HINT_KEYS = ('sparse', 'sparse_cat', 'grad_from', 'factored', 'keep_grad', 'pending', 'wrong_twin', 'test_planes')
 
 
 def clear_hints():

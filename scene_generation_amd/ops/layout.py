@@ -112,6 +112,81 @@ def masks_to_layout_test(vecs, boxes, masks, seg_off, N, H, W, avg):
     return out
 
 
+def _test_layout_operands(vecs, boxes, masks):
+    if torch.is_grad_enabled() and (vecs.requires_grad or masks.requires_grad or boxes.requires_grad):
+        raise NotImplementedError('masks_to_layout(test_mode=True) is inference-only (the reference composites through '
+                                  '.item()/numpy argsort, layout.py:161-162): run it under torch.no_grad()')
+    vecs, boxes = _f32(vecs.detach(), 'vecs'), _f32(boxes.detach(), 'boxes')
+    masks = _dev(masks.detach(), 'masks')
+    if masks.dtype not in (torch.int64, torch.float32):
+        raise TypeError('masks must be int64 or float32')
+    return vecs, boxes, masks if masks.is_contiguous() else masks.contiguous()
+
+
+def masks_to_layout_test_planes(vecs, boxes, masks, seg_off, plane_idx, N, J, H, W, avg, want_value=True):
+    """The factored form of masks_to_layout_test: in test mode every pixel belongs to at most one object, so the layout is
+    ``vecs[winner] * value``.  -> (Z [N, J, H, W], winner [N, H, W] int32 (global object index, -1: nobody), value [N, H, W] or
+    None): Z holds ``value`` in the plane ``plane_idx[winner]`` and zeros elsewhere -- the planes an ops.FactoredLayout wants.
+    Inference only; ``vecs[winner] * value`` is bit-identical to the dense kernel's output."""
+    vecs, boxes, masks = _test_layout_operands(vecs, boxes, masks)
+    plane_idx = _i64(plane_idx, 'plane_idx')
+    O, D = vecs.shape
+    assert plane_idx.numel() == O and J > 0
+    dev = vecs.device
+    Z = torch.empty(N, J, H, W, dtype=torch.float32, device=dev)
+    winner = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+    value = torch.empty(N, H, W, dtype=torch.float32, device=dev) if want_value else None
+    wsb = _L().sg_masks_to_layout_test_planes_ws_bytes(O)
+    _call('sg_masks_to_layout_test_planes', _p(vecs), _p(boxes), _p(masks), 1 if masks.dtype == torch.int64 else 0, _p(seg_off),
+          _p(plane_idx), _p(Z), _p(winner), _p(value), _p(workspace(wsb, dev)), wsb, N, O, D, J, masks.size(1), H, W,
+          1 if avg else 0, _stream())
+    return Z, winner, value
+
+
+def masks_to_layout_test_deferred(vecs, boxes, masks, seg_off, N, H, W, avg):
+    """An (N, D, H, W) test-mode layout whose sg_masks_to_layout_test_fwd launch is deferred until ensure_dense (the test-mode
+    twin of masks_to_layout_deferred): UNINITIALISED memory until then."""
+    vecs, boxes, masks = _test_layout_operands(vecs, boxes, masks)
+    O, D = vecs.shape
+    out = torch.empty(N, D, H, W, dtype=torch.float32, device=vecs.device)
+
+    def fill():
+        wsb = _L().sg_masks_to_layout_test_ws_bytes(O)
+        _call('sg_masks_to_layout_test_fwd', _p(vecs), _p(boxes), _p(masks), 1 if masks.dtype == torch.int64 else 0, _p(seg_off),
+              _p(out), _p(workspace(wsb, vecs.device)), wsb, N, O, D, masks.size(1), H, W, 1 if avg else 0, _stream())
+    return set_hints(out, pending=fill)
+
+
+def deprocess_images(imgs, rescale=True, uint8=True, float32=False):
+    """imagenet_deprocess_batch (data/utils.py:17-51) on the device: imgs (N, C, H, W) fp32 -> the uint8 (N, H, W, C) image an
+    image writer wants (``uint8``) and / or the reference's fp32 (N, C, H, W) in [0, 255] (``float32``).  One of them: that tensor;
+    both: (float32, uint8).  A constant image under ``rescale`` is NaN in fp32 (as in the reference) and 0 in uint8."""
+    imgs = _f32(imgs.detach(), 'imgs')
+    assert imgs.dim() == 4 and (uint8 or float32)
+    N, C, H, W = imgs.shape
+    dev = imgs.device
+    of = torch.empty(N, C, H, W, dtype=torch.float32, device=dev) if float32 else None
+    ob = torch.empty(N, H, W, C, dtype=torch.uint8, device=dev) if uint8 else None
+    wsb = _L().sg_deprocess_images_ws_bytes(N, H, W)
+    _call('sg_deprocess_images', _p(imgs), _p(of), _p(ob), _p(workspace(wsb, dev)), wsb, N, C, H, W, 1 if rescale else 0, _stream())
+    return (of, ob) if (uint8 and float32) else (ob if uint8 else of)
+
+
+def layout_rgb(winner, value, objs, colors):
+    """The label map as a picture (scripts/sample_images.py:156-160) from the winner / value planes of
+    masks_to_layout_test_planes: rgb [N, 3, H, W] = colors[objs[winner]] * value, the batch scaled to a maximum of 255."""
+    value, colors, objs = _f32(value, 'value'), _f32(colors, 'colors'), _i64(objs, 'objs')
+    _dev(winner, 'winner')
+    assert winner.dtype == torch.int32 and winner.is_contiguous() and winner.shape == value.shape and winner.dim() == 3
+    assert colors.dim() == 2 and colors.size(1) == 3
+    N, H, W = winner.shape
+    rgb = torch.empty(N, 3, H, W, dtype=torch.float32, device=value.device)
+    wsb = _L().sg_layout_rgb_ws_bytes(N, H, W)
+    _call('sg_layout_rgb', _p(winner), _p(value), _p(objs), _p(colors), _p(rgb), _p(workspace(wsb, value.device)), wsb, N,
+          objs.numel(), colors.size(0), H, W, _stream())
+    return rgb
+
+
 # ------------------------------------------------------------------------------------------
 # factored layout convolutions
 # ------------------------------------------------------------------------------------------

@@ -1,0 +1,319 @@
+"""Scene graphs in, pictures out: the sampling path (surface of the reference's scripts/sample_images.py and the parts of
+scene_generation/data/utils.py it needs).
+
+    python -m scene_generation_amd.sample --checkpoint CKPT.pt --output_dir OUT [--weights ema] [--scene_graphs FILE.json]
+
+* ``Sampler``: one test-mode forward per collated batch (``sample_batch``, the flags of sample_images.py:203-221) or per list of
+  scene graphs written by a person (``sample_json`` -> Model.forward_json), then the device-side ``imagenet_deprocess_batch``
+  (sg_deprocess_images) straight to the uint8 (N, H, W, 3) array an image writer wants, and optionally the label-map picture
+  (sg_layout_rgb).  The only host synchronisation of a call is the one ``tolist()`` of the class ids that Model.forward needs
+  anyway (done here and handed to the model).  With ``factored`` the stem of the generator runs on the factored test-mode layout
+  (Model.factored_test_layout) and the dense (N, num_objs + rep_size, H, W) tensor is only written when a caller asks for it.
+* the box IoU bookkeeping of sample_images.py:241-255 as tensor operations (``iou_totals``), read once at the end.
+* ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
+  (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
+Not here: the accuracy network, scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
+checkout's under install_as)."""
+import argparse
+import json
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import ops
+from .evaluate import _area, intersection
+from .utils import bool_flag, int_tuple, to_device_async
+
+WEIGHT_KEYS = {'model': 'model_state', 'best': 'model_best_state', 'ema': 'model_ema_state', 'ema_best': 'model_ema_best_state'}
+
+
+def imagenet_deprocess_batch(imgs, rescale=True):
+    """data/utils.py:32-51 with the reference's contract -- a CPU float tensor (N, C, H, W) in [0, 255] -- computed on the device
+    (ops.deprocess_images); the copy to the host is the call's synchronisation, as ``imgs.cpu()`` is the reference's."""
+    return ops.deprocess_images(imgs, rescale=rescale, uint8=False, float32=True).cpu()
+
+
+def iou_totals(boxes_pred, boxes_gt, obj_to_img):
+    """sample_images.py:241-255 without the Python loop: an object is kept iff it is not the last of the batch and the next object
+    belongs to the same image (that drops every image's trailing __image__ object).  -> float tensor [4] on the boxes' device:
+    (sum of IoU, #IoU > 0.5, #IoU > 0.3, #kept) over the kept boxes (metrics.py:27-35).  No host synchronisation."""
+    O = obj_to_img.numel()
+    keep = torch.zeros(O, dtype=torch.bool, device=obj_to_img.device)
+    if O > 1:
+        keep[:-1] = obj_to_img[:-1] == obj_to_img[1:]
+    inter = intersection(boxes_pred, boxes_gt)
+    iou = inter / (_area(boxes_pred) + _area(boxes_gt) - inter)
+    zero = torch.zeros_like(iou)
+    iou = torch.where(keep, iou, zero)                      # a dropped box (possibly degenerate: NaN) counts for nothing
+    return torch.stack([iou.sum(), (iou > 0.5).sum().to(iou.dtype), (iou > 0.3).sum().to(iou.dtype), keep.sum().to(iou.dtype)])
+
+
+def iou_summary(totals):
+    """the ONE device-to-host read of the bookkeeping: {'avg_iou', 'r0.5', 'r0.3', 'total_boxes'}"""
+    s, r5, r3, n = [float(v) for v in totals.tolist()]
+    return {'avg_iou': s / n if n else float('nan'), 'r0.5': r5 / n if n else float('nan'),
+            'r0.3': r3 / n if n else float('nan'), 'total_boxes': int(n)}
+
+
+class SampleOut(object):
+    """images uint8 (N, H, W, 3); boxes_pred (O, 4); masks_pred (O, M, M); layout_rgb fp32 (N, 3, H, W) in [0, 255] or None;
+    layout: the dense test-mode layout or None; objs (sample_json)"""
+
+    def __init__(self, images, boxes_pred, masks_pred, layout_rgb=None, layout=None, objs=None):
+        self.images, self.boxes_pred, self.masks_pred = images, boxes_pred, masks_pred
+        self.layout_rgb, self.layout, self.objs = layout_rgb, layout, objs
+
+
+class Sampler(object):
+    """``features``: the appearance bank {class id: array [rows, rep_size]} that replaces the crops' encoding when a batch is
+    sampled without ground-truth textures (features_clustered_001.npy of the reference).  ``colors``: [num_objs, 3] table of the
+    label-map picture (default: torch.randint(0, 256), sample_images.py:197).  ``factored``: run the generator's stem on the
+    factored test-mode layout (Model.factored_test_layout).  ON by default: measured on MI355X at N = 32 / 128 x 128, 6.82 against
+    7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
+
+    def __init__(self, model, features=None, colors=None, factored=True):
+        self.model, self.features, self.factored = model, features, bool(factored)
+        self.device = next(model.parameters()).device
+        if colors is None:
+            colors = torch.randint(0, 256, [model.num_objs, 3]).float()
+        self.colors = to_device_async(torch.as_tensor(colors, dtype=torch.float32).contiguous(), self.device)
+        self.iou = None                      # running (sum IoU, > 0.5, > 0.3, boxes) of sample_batch, on the device
+
+    # -- the forward + what follows the network -------------------------------------------------------------------------------------
+    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs):
+        m = self.model
+        saved = (m.factored_test_layout, m.objs_host, m.obj_to_img_host)
+        m.factored_test_layout, m.objs_host, m.obj_to_img_host = self.factored, objs_h, o2i_h
+        try:
+            with torch.no_grad():
+                imgs_pred, boxes_pred, masks_pred, _, layout, _ = fn()
+                images = ops.deprocess_images(imgs_pred, rescale=True, uint8=True)
+                rgb = None
+                if want_layout_rgb:
+                    planes = ops.hint(layout, 'test_planes')
+                    if planes is not None:                  # factored: the winner / value planes the layout was built from
+                        rgb = ops.layout_rgb(planes[0], planes[1], objs, self.colors)
+                    else:   # dense baseline: a pixel's only non-zero one-hot channel is its winner's class and holds the value
+                        value, cls = layout[:, :m.num_objs].max(1)
+                        winner = torch.where(value > 0, cls, torch.full_like(cls, -1)).to(torch.int32)
+                        table = torch.arange(m.num_objs, dtype=torch.int64, device=layout.device)
+                        rgb = ops.layout_rgb(winner.contiguous(), value.contiguous(), table, self.colors)
+                if want_layout:
+                    ops.ensure_dense(layout)                # factored: the deferred dense kernel runs only here
+        finally:
+            m.factored_test_layout, m.objs_host, m.obj_to_img_host = saved
+        return SampleOut(images, boxes_pred, masks_pred, rgb, layout if want_layout else None, objs)
+
+    def sample_batch(self, batch, use_gt_boxes=False, use_gt_masks=False, use_gt_textures=False, use_gt_attr=False,
+                     want_layout_rgb=False, want_layout=False):
+        """One collated batch (imgs, objs, boxes, masks, triples, obj_to_img, triple_to_img, attributes), the flags of
+        sample_images.py:203-221.  Without ground-truth textures every object takes a random row of its class's bank, drawn with
+        ``random.randint`` in object order like the reference (``random.seed`` reproduces it)."""
+        imgs, objs, boxes, masks, triples, obj_to_img, _, attributes = [t.to(self.device) for t in batch]
+        objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()        # the call's one host synchronisation
+        features = None
+        if not use_gt_textures:
+            if self.features is None:
+                raise ValueError('No features file')                    # sample_images.py:174
+            rows = []
+            for c in objs_h:
+                bank = self.features[c]
+                rows.append(bank[random.randint(0, bank.shape[0] - 1), :])
+            features = list(to_device_async(torch.from_numpy(np.stack(rows).astype(np.float32)), self.device).unbind(0))
+        if not use_gt_attr:
+            attributes = torch.zeros_like(attributes)
+        m = self.model
+        out = self._forward(lambda: m(imgs, objs, triples, obj_to_img, boxes_gt=boxes, masks_gt=masks if use_gt_masks else None,
+                                      attributes=attributes, test_mode=True, use_gt_box=use_gt_boxes, features=features),
+                            objs_h, o2i_h, want_layout_rgb, want_layout, objs)
+        tot = iou_totals(out.boxes_pred, boxes, obj_to_img)
+        self.iou = tot if self.iou is None else self.iou + tot
+        return out
+
+    def sample_json(self, scene_graphs, want_layout_rgb=False, want_layout=False):
+        """Scene graphs as dictionaries (Model.encode_scene_graphs, which APPENDS to them) -> SampleOut with ``objs``."""
+        m = self.model
+        if isinstance(scene_graphs, dict):
+            scene_graphs = [scene_graphs]
+        objs, triples, obj_to_img, attributes, features = m.encode_scene_graphs(scene_graphs)
+        objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()
+        return self._forward(lambda: m(None, objs, triples, obj_to_img, attributes=attributes, test_mode=True, use_gt_box=False,
+                                       features=features), objs_h, o2i_h, want_layout_rgb, want_layout, objs)
+
+    def iou_summary(self):
+        return iou_summary(self.iou) if self.iou is not None else None
+
+
+# ---- checkpoint -> model ------------------------------------------------------------------------------------------------------
+def select_weights(checkpoint, which='model'):
+    """the state dict ``--weights`` names: model -> model_state, best -> model_best_state, ema -> model_ema_state,
+    ema_best -> model_ema_best_state"""
+    if which not in WEIGHT_KEYS:
+        raise ValueError('--weights %r: expected one of %s' % (which, ', '.join(sorted(WEIGHT_KEYS))))
+    key = WEIGHT_KEYS[which]
+    if checkpoint.get(key) is None:
+        if which.startswith('ema'):
+            raise ValueError('--weights %s: the checkpoint has no %s -- it was written without a generator EMA '
+                             '(train with Trainer(ema_decay=...) / SG_G_EMA_DECAY)' % (which, key))
+        raise ValueError('--weights %s: the checkpoint has no %s' % (which, key))
+    return checkpoint[key]
+
+
+def build_model(args, checkpoint, device='cuda'):
+    """sample_images.py:133-144 plus the choice of weights"""
+    from .model import Model
+    model = Model(**checkpoint['model_kwargs'])
+    model.load_state_dict(select_weights(checkpoint, getattr(args, 'weights', 'model')))
+    if getattr(args, 'model_mode', 'eval') == 'eval':
+        model.eval()
+    else:
+        model.train()
+    if getattr(args, 'image_size', None):
+        model.image_size = tuple(args.image_size)
+    return model.to(device)
+
+
+def synthetic_loader(model, batch_size, num_samples, mask_size=32, seed=0):
+    """collated batches of the synthetic generator (scene_generation_amd.synthetic) shaped for ``model``"""
+    from .synthetic import make_batch
+    done, k = 0, 0
+    while done < num_samples:
+        n = min(batch_size, num_samples - done)
+        yield make_batch(N=n, size=model.image_size[0], mask_size=mask_size, num_objs=model.num_objs, num_preds=model.num_preds,
+                         num_attributes=model.vocab.get('num_attributes', 35), seed=seed + k)
+        done, k = done + n, k + 1
+
+
+def write_image(path_stem, array):
+    """uint8 (H, W, 3) -> path_stem + '.png' through PIL, or '.npy' when PIL is absent; -> the path written"""
+    array = np.ascontiguousarray(array)
+    try:
+        from PIL import Image
+    except ImportError:
+        np.save(path_stem + '.npy', array)
+        return path_stem + '.npy'
+    Image.fromarray(array).save(path_stem + '.png')
+    return path_stem + '.png'
+
+
+def _float_picture(chw):
+    """fp32 (3, H, W) in [0, 255] -> uint8 (H, W, 3), the rounding of sg_deprocess_images"""
+    a = np.nan_to_num(np.asarray(chw, dtype=np.float32), nan=0.0).transpose(1, 2, 0)
+    return (np.clip(a, 0, 255) + 0.5).astype(np.uint8)
+
+
+def _makedir(base, name, flag=True):
+    if not flag:
+        return None
+    d = os.path.join(base, name)
+    os.makedirs(d, exist_ok=True)
+    return d
+
+
+def load_scene_graphs(path):
+    """a JSON file with one scene graph or a list of them; the keys encode_scene_graphs insists on get neutral defaults
+    (feature number -1 = the class's single-row bank, no size / location attributes)"""
+    with open(path) as f:
+        sgs = json.load(f)
+    sgs = [sgs] if isinstance(sgs, dict) else list(sgs)
+    for sg in sgs:
+        sg.setdefault('relationships', [])
+        sg.setdefault('features', [-1] * len(sg['objects']))
+        sg.setdefault('image_id', -1)
+        sg.setdefault('attributes', {})
+        sg['attributes'].setdefault('size', [])
+        sg['attributes'].setdefault('location', [])
+    return sgs
+
+
+def load_features(args):
+    """the appearance bank next to the checkpoint (sample_images.py:166-174) or ``--features``"""
+    path = getattr(args, 'features', None) or os.path.join(os.path.dirname(args.checkpoint or ''), 'features_clustered_001.npy')
+    if not os.path.isfile(path):
+        raise ValueError('No features file')
+    return np.load(path, allow_pickle=True).item()
+
+
+def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
+    """sample_images.py:163-295 without COCO: sample every batch of ``loader`` (any iterable of collated batches; the synthetic
+    generator when None) or the scene graphs of ``args.scene_graphs``, write one picture per image into output_dir/images
+    (+ images_gt, layouts), print and return the IoU summary and the paths written."""
+    model = build_model(args, checkpoint, device)
+    graphs = getattr(args, 'scene_graphs', None)
+    features = None
+    if not graphs and not args.use_gt_textures:
+        features = load_features(args)
+    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True))
+    img_dir = _makedir(output_dir, 'images')
+    gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs)
+    layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
+    paths, idx = [], 0
+
+    def save(out, imgs_gt):
+        nonlocal idx
+        images = out.images.cpu().numpy()
+        rgb = out.layout_rgb.cpu().numpy() if out.layout_rgb is not None else None
+        for i in range(images.shape[0]):
+            stem = '%04d' % idx
+            if gt_dir is not None and imgs_gt is not None:
+                write_image(os.path.join(gt_dir, stem), imgs_gt[i])
+            if layout_dir is not None:
+                write_image(os.path.join(layout_dir, stem), _float_picture(rgb[i]))
+            paths.append(write_image(os.path.join(img_dir, stem), images[i]))
+            idx += 1
+        print('Saved %d images' % idx)
+
+    if graphs:
+        if getattr(args, 'features', None):
+            bank = np.load(args.features, allow_pickle=True).item()
+            model.features = bank
+            model.features_one = bank
+        sgs = load_scene_graphs(graphs)
+        for a in range(0, len(sgs), args.batch_size):
+            save(sampler.sample_json(sgs[a:a + args.batch_size], want_layout_rgb=args.save_layout), None)
+    else:
+        if loader is None:
+            loader = synthetic_loader(model, args.batch_size, args.num_samples, checkpoint['model_kwargs'].get('mask_size', 32))
+        for batch in loader:
+            imgs_gt = None
+            if gt_dir is not None:
+                imgs_gt = ops.deprocess_images(batch[0].to(sampler.device), rescale=True, uint8=True).cpu().numpy()
+            save(sampler.sample_batch(batch, args.use_gt_boxes, args.use_gt_masks, args.use_gt_textures, args.use_gt_attr,
+                                      want_layout_rgb=args.save_layout), imgs_gt)
+    summary = sampler.iou_summary()
+    if summary is not None:
+        print('avg_iou {}'.format(summary['avg_iou']))
+        print('r0.5 {}'.format(summary['r0.5']))
+        print('r0.3 {}'.format(summary['r0.3']))
+    return {'paths': paths, 'iou': summary}
+
+
+def make_parser():
+    p = argparse.ArgumentParser(prog='python -m scene_generation_amd.sample', description=__doc__.split('\n')[0])
+    p.add_argument('--checkpoint', required=True)
+    p.add_argument('--output_dir', default='output')
+    p.add_argument('--weights', default='model', choices=sorted(WEIGHT_KEYS),
+                   help='model_state / model_best_state / model_ema_state / model_ema_best_state of the checkpoint')
+    p.add_argument('--model_mode', default='eval', choices=['train', 'eval'])
+    p.add_argument('--image_size', default=None, type=int_tuple, help='default: the size the checkpoint was trained at')
+    p.add_argument('--batch_size', default=24, type=int)
+    p.add_argument('--num_samples', default=24, type=int, help='images from the synthetic generator when no loader is given')
+    p.add_argument('--scene_graphs', default=None, help='JSON file with one scene graph or a list of them')
+    p.add_argument('--features', default=None, help='appearance bank (.npy); default: features_clustered_001.npy next to the checkpoint')
+    for flag in ('save_gt_imgs', 'use_gt_boxes', 'use_gt_masks', 'use_gt_attr', 'use_gt_textures', 'save_layout'):
+        p.add_argument('--' + flag, default=False, type=bool_flag)
+    p.add_argument('--factored', default=True, type=bool_flag, help='0: the dense test-mode layout (the baseline path)')
+    return p
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    checkpoint = torch.load(args.checkpoint, map_location='cpu', weights_only=False)
+    print('Loading model from ', args.checkpoint)
+    return run_model(args, checkpoint, args.output_dir)
+
+
+if __name__ == '__main__':
+    main()

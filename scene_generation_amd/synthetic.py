@@ -41,6 +41,19 @@ def make_vocab(num_objs=VOCAB_C, num_preds=VOCAB_P, num_attributes=VOCAB_A):
     }
 
 
+def make_sampling_vocab(num_objs=VOCAB_C, num_preds=VOCAB_P, num_attributes=VOCAB_A):
+    """make_vocab plus the keys Model.encode_scene_graphs reads (model.py:217,231), shaped like the COCO vocabulary: object name ->
+    dataset id (``object_name_to_idx``), str(dataset id) -> class (``object_to_idx``), relationship name -> index.  Class 0 is
+    '__image__' (dataset id 0); object k is called 'obj<k>' and has dataset id 100 + k."""
+    v = make_vocab(num_objs, num_preds, num_attributes)
+    names = ['__image__'] + ['obj%d' % k for k in range(1, num_objs)]
+    ids = [0] + [100 + k for k in range(1, num_objs)]
+    v['object_name_to_idx'] = dict(zip(names, ids))
+    v['object_to_idx'] = {str(i): k for k, i in enumerate(ids)}
+    v['pred_name_to_idx'] = {n: i for i, n in enumerate(v['pred_idx_to_name'])}
+    return v
+
+
 def make_batch(N=32, min_objs=3, max_objs=8, spatial_per_obj=1, size=128, mask_size=32,
                num_objs=VOCAB_C, num_preds=VOCAB_P, num_attributes=VOCAB_A, seed=0,
                zero_attributes=False):

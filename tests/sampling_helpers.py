@@ -1,0 +1,109 @@
+"""Shared by tests/test_sampling_cpu.py, tests/test_gpu_sampling.py and tools/make_golden_sampling.py: the inputs of the sampling
+fixtures (built from seeds, so that the fixtures only hold what the reference RETURNED) and plain-torch restatements of what
+the sampling kernels compute.  The restatements are pinned to the reference's recorded outputs by test_sampling_cpu.py."""
+import copy
+
+import numpy as np
+import torch
+
+from scene_generation_amd.synthetic import fill_deterministic, make_sampling_vocab
+
+C, P, A, REP = 12, 4, 35, 32
+BANK_SEED = 97
+
+
+def make_banks(seed=BANK_SEED, num_objs=C, rep=REP):
+    """({class: float64 [100, rep]}, {class: float64 [1, rep]}): the two appearance banks scripts/gui/model.py hangs on the model"""
+    rs = np.random.RandomState(seed)
+    many = {c: rs.rand(100, rep) for c in range(num_objs)}
+    one = {c: rs.rand(1, rep) for c in range(num_objs)}
+    return many, one
+
+
+def scene_graphs():
+    """Two graphs for ONE call: the second one's classes differ from the first one's, so the cumulative zip of
+    encode_scene_graphs (model.py:223) serves it from the banks of obj3, obj5, obj7; feature numbers -1, in range and > 99."""
+    return copy.deepcopy([
+        {'objects': ['obj3', 'obj5', 'obj7'],
+         'relationships': [[0, 'left of', 1], [1, 'above', 2]],
+         'attributes': {'size': [1, 4, 8], 'location': [0, 7, 24]},
+         'features': [5, -1, 140], 'image_id': 17},
+        {'objects': ['obj2', 'obj9'],
+         'relationships': [[1, 'right of', 0]],
+         'attributes': {'size': [2, 9], 'location': [3, 12]},
+         'features': [-1, 99], 'image_id': 250},
+    ])
+
+
+def small_model(cls, vocab=None):
+    """the small model of the model_test_mode golden (same widths, fill and box_net override), on the sampling vocabulary"""
+    m = cls(vocab or make_sampling_vocab(C, P, A), image_size=(32, 32), gconv_hidden_dim=64, gconv_num_layers=3, mask_size=8,
+            mlp_normalization='none', appearance_normalization='batch', activation='leakyrelu-0.2', n_downsample_global=2,
+            use_attributes=True, pool_size=2)
+    fill_deterministic(m)
+    with torch.no_grad():       # non-degenerate predicted boxes (see tools/make_golden.py: golden_testmode)
+        m.box_net[2].weight.mul_(0.05)
+        m.box_net[2].bias.copy_(torch.tensor([0.1, 0.15, 0.6, 0.7]))
+    m.eval()
+    m.features, m.features_one = make_banks()
+    return m
+
+
+def deprocess_inputs():
+    """{'a': (4, 3, 16, 20) with image 2 constant, 'b': (2, 3, 5, 6): a width the vector form cannot take}"""
+    g = torch.Generator().manual_seed(31)
+    a = torch.randn(4, 3, 16, 20, generator=g) * 0.7
+    a[2] = 0.25
+    a[3] = a[3].clamp(-1, 1)
+    b = torch.rand(2, 3, 5, 6, generator=g) * 2 - 1
+    return {'a': a, 'b': b}
+
+
+def deprocess_ref(imgs, rescale=True):
+    """imagenet_deprocess_batch (data/utils.py:17-51) as one expression per image; float (N, C, H, W) in [0, 255]"""
+    out = []
+    for x in imgs.detach().cpu().float():
+        y = x / 2 + 0.5
+        if rescale:
+            lo, hi = y.min(), y.max()
+            y = (y - lo) / (hi - lo)
+        out.append((y * 255).clamp(0, 255))
+    return torch.stack(out)
+
+
+def to_uint8_ref(v):
+    """what sg_deprocess_images stores for a [0, 255] float value v: (uint8)(v + 0.5), NaN -> 0; (N, C, H, W) -> (N, H, W, C)"""
+    return torch.nan_to_num(v + 0.5, nan=0.0).floor().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def layout_rgb_inputs():
+    """a two-image test-mode compositing problem whose vectors are [one_hot(class) | repr]: (vecs, boxes, masks, obj_to_img, objs,
+    colors, num_objs, H)"""
+    g = torch.Generator().manual_seed(23)
+    num_objs, rep, H = 6, 4, 16
+    objs = torch.tensor([2, 4, 1, 0, 5, 3, 0])
+    o2i = torch.tensor([0, 0, 0, 0, 1, 1, 1])
+    O = objs.numel()
+    vecs = torch.cat([torch.eye(num_objs)[objs], torch.rand(O, rep, generator=g)], 1)
+    x0, y0 = torch.rand(O, generator=g) * 0.5, torch.rand(O, generator=g) * 0.5
+    boxes = torch.stack([x0, y0, x0 + 0.2 + 0.3 * torch.rand(O, generator=g), y0 + 0.2 + 0.3 * torch.rand(O, generator=g)], 1)
+    boxes[3] = boxes[6] = torch.tensor([0., 0., 1., 1.])
+    masks = 0.3 + 0.7 * torch.rand(O, 8, 8, generator=g)
+    colors = torch.randint(0, 256, [num_objs, 3], generator=g).float()
+    return vecs, boxes, masks, o2i, objs, colors, num_objs, H
+
+
+def layout_rgb_ref(layout, colors, num_objs):
+    """one_hot_to_rgb (scripts/sample_images.py:156-160)"""
+    rgb = torch.einsum('abcd,be->aecd', layout[:, :num_objs].cpu(), colors.cpu())
+    return rgb * (255.0 / rgb.max())
+
+
+def iou_inputs():
+    g = torch.Generator().manual_seed(41)
+    o2i = torch.tensor([0, 0, 0, 1, 1, 2, 3, 3, 3, 3, 4, 4])
+    O = o2i.numel()
+    a = torch.rand(O, 2, generator=g) * 0.5
+    gt = torch.cat([a, a + 0.1 + 0.4 * torch.rand(O, 2, generator=g)], 1)
+    pred = (gt + 0.12 * torch.randn(O, 4, generator=g)).clamp(0, 1)
+    return pred, gt, o2i
