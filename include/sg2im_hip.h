@@ -405,6 +405,46 @@ int sg_deprocess_images(const float* imgs, float* out_f32, uint8_t* out_u8, void
 size_t sg_layout_rgb_ws_bytes(int N, int H, int W);
 int sg_layout_rgb(const int32_t* winner, const float* value, const int64_t* objs, const float* colors, float* rgb, void* ws,
                   size_t ws_bytes, int N, int O, int num_colors, int H, int W, sgStream stream);
+/* ---- segmented k-means for the appearance bank (kmeans.hip; scene_generation_amd/bank.py) -----------------------------------
+ * Many independent k-means problems in one launch.  x [P, D] fp32 with every class's rows contiguous, offsets [C + 1] int32 (CSR).
+ * Every per-problem array has a leading restart dimension R (R = 1: none): centers [R, C, K, D], labels / mind2 [R, P], the
+ * per-class arrays [R, C].  Class c uses the first k_c = min(n_c, K) rows of its block of centers; a class without rows does no
+ * work.  Supported: 1 <= D <= SG_KMEANS_MAX_D, 1 <= K <= SG_KMEANS_MAX_K, R <= 65535, P * R < 2^31 (checked, rc -1).
+ * tiles [T, 2] int32 = (class, first row relative to the class's start) cuts every class into pieces of at most SG_KMEANS_TILE rows,
+ * ascending per class; tile_off [C + 1] = CSR of the tiles per class.  Results of a class depend on the class's own rows only and
+ * are bit-identical from run to run (no floating-point atomics).
+ * state [R, C] (may be null: every class runs): 0 running, 1 finished, 2 converged, final pass outstanding.  With final_pass = 0
+ * the classes with state != 0 are skipped; with final_pass = 1 those with state == 1 are. */
+#define SG_KMEANS_MAX_D 128
+#define SG_KMEANS_MAX_K 256
+#define SG_KMEANS_TILE 1024
+/* labels[i] = argmin_j |x_i - c_j|^2 over the class's k_c centres (a tie: the lowest j), mind2[i] = that distance (direct form, fp32).
+ * ADDS to changed [R, C] the number of rows whose label differs from the one found in labels, and to acount [R, C, K] the rows per
+ * centre (integer atomics); sg_kmeans_update clears both. */
+int sg_kmeans_assign(const float* x, const int32_t* offsets, const int32_t* tiles, const float* centers, const int32_t* state,
+                     int32_t* labels, float* mind2, int32_t* changed, int32_t* acount, int P, int C, int K, int D, int R, int T,
+                     int final_pass, sgStream stream);
+/* centers[c, j] = mean of the class's rows labelled j (a centre without rows keeps its value), counts [R, C, K], inertia [R, C] =
+ * sum of mind2, shift [R, C] = sum of squared centre movement; n_iter [R, C] += 1; state: 1 if changed == 0, else 2 if k_c == 1 or
+ * shift <= tolvar[c] (tolvar [C], may be null), else 0; changed and acount (either may be null) are cleared.  final_pass = 1:
+ * counts and inertia only, state = 1.  ws >= sg_kmeans_update_ws_bytes(T, K, D, R). */
+size_t sg_kmeans_update_ws_bytes(int T, int K, int D, int R);
+int sg_kmeans_update(const float* x, const int32_t* offsets, const int32_t* tiles, const int32_t* tile_off, const int32_t* labels,
+                     const float* mind2, float* centers, int32_t* counts, float* inertia, float* shift, const float* tolvar,
+                     int32_t* state, int32_t* n_iter, int32_t* changed, int32_t* acount, void* ws, size_t ws_bytes, int P, int C,
+                     int K, int D, int R, int T, int final_pass, sgStream stream);
+/* Empty clusters, between assign and update: per centre of a running class with acount == 0 (ascending), the class's row with the
+ * largest mind2 (a tie: the lowest row) among the rows whose centre holds more than one row takes that centre's label. */
+int sg_kmeans_relocate(const int32_t* offsets, const int32_t* state, int32_t* labels, const float* mind2, const int32_t* acount,
+                       int P, int C, int K, int R, sgStream stream);
+/* Round ``round`` of k-means++ seeding (one trial per round) for every class with round < k_c: round 0 picks row floor(u * n_c);
+ * round t updates mind2 with the centre of round t - 1 and picks the first row whose running sum of mind2 exceeds u * total (a row
+ * at distance zero from a chosen centre is never picked).  u [R, C, K] fp32 in [0, 1); the picked row goes to centers[c, round]
+ * and its class-relative index to picks [R, C, K].  ws >= sg_kmeans_pp_step_ws_bytes(T, R) (the tiles' sums). */
+size_t sg_kmeans_pp_step_ws_bytes(int T, int R);
+int sg_kmeans_pp_step(const float* x, const int32_t* offsets, const int32_t* tiles, const int32_t* tile_off, const float* u,
+                      float* centers, float* mind2, int32_t* picks, void* ws, size_t ws_bytes, int P, int C, int K, int D, int R,
+                      int T, int round, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

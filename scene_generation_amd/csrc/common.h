@@ -108,6 +108,8 @@ enum {
   SG_K_LAYOUT_TEST_PLANES,  // factored test-mode compositing: mass + order + planes (layout.hip)
   SG_K_DEPROCESS,           // sg_deprocess_images (sample.hip)
   SG_K_LAYOUT_RGB,          // sg_layout_rgb (sample.hip)
+  // the appearance bank's segmented k-means (kmeans.hip)
+  SG_K_KMEANS_ASSIGN, SG_K_KMEANS_UPDATE, SG_K_KMEANS_RELOCATE, SG_K_KMEANS_PP,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -4,7 +4,7 @@ PyTorch-ROCm is used here as plumbing only: device allocation (torch.empty), the
 Every forward / backward is one or a few hand-written gfx950 kernel launches through ctypes; there is no eager / CPU fallback --
 a CPU tensor raises.
 
-One namespace, six modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
+One namespace, seven modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
   _core    ctypes call helpers, stream handle, workspace, parameter-gradient sinks (GradOut), path switches, layout hints,
            flat-buffer updates (Adam, fill, fold), profiler front end
   conv     Conv2d / ConvTranspose2d / sub-pixel up-conv / Linear (implicit GEMM, Winograd, head, skinny kernels)
@@ -13,6 +13,7 @@ One namespace, six modules (the single 1 741-line ops.py of rounds 1-3, split by
   layout   masks_to_layout (dense / deferred / test mode / factored), per-image-weight convs, bilinear crops, VectorPool
            and the sampling tail (factored test-mode planes, deprocess_images, layout_rgb)
   losses   scalar losses, weighted sum, cross-entropy
+  kmeans   segmented k-means of the appearance bank (assign / update / relocate / k-means++ round)
 Everything is re-exported here, so ``ops.conv2d``, ``ops.GradOut``, ``ops._call`` ... keep working.  The path switches
 (``ops.WINOGRAD``, ``ops.FACTORED_LAYOUT``, ``ops.UPCONV``, ``ops.HEADCONV``, ``ops.WINOGRAD24``, ``ops.COND_FOLD``) are WRITABLE through this
 namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator modules read (``_core.WINOGRAD``).
@@ -20,9 +21,9 @@ namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator mod
 import sys
 import types
 
-from . import _core, graph, losses, layout, conv, nn
+from . import _core, graph, losses, layout, conv, nn, kmeans
 
-_MODULES = (_core, graph, losses, layout, conv, nn)
+_MODULES = (_core, graph, losses, layout, conv, nn, kmeans)
 _FLAGS = ('HEADCONV', 'WINOGRAD', 'WINOGRAD24', 'FACTORED_LAYOUT', 'UPCONV', 'COND_FOLD')
 
 for _m in _MODULES:

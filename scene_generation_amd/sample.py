@@ -1,7 +1,7 @@
 """Scene graphs in, pictures out: the sampling path (surface of the reference's scripts/sample_images.py and the parts of
 scene_generation/data/utils.py it needs).
 
-    python -m scene_generation_amd.sample --checkpoint CKPT.pt --output_dir OUT [--weights ema] [--scene_graphs FILE.json]
+    python -m scene_generation_amd.sample --checkpoint CKPT.pt --output_dir OUT [--weights ema] [--scene_graphs FILE.json [--bank DIR]]
 
 * ``Sampler``: one test-mode forward per collated batch (``sample_batch``, the flags of sample_images.py:203-221) or per list of
   scene graphs written by a person (``sample_json`` -> Model.forward_json), then the device-side ``imagenet_deprocess_batch``
@@ -236,6 +236,18 @@ def load_features(args):
     return np.load(path, allow_pickle=True).item()
 
 
+def load_bank(directory):
+    """(features_clustered_100.npy, features_clustered_001.npy) of ``directory``: the two banks scripts/gui/model.py:47-55 hangs on
+    the model (``Model.features`` / ``Model.features_one``), as python -m scene_generation_amd.bank writes them"""
+    banks = []
+    for name in ('features_clustered_100.npy', 'features_clustered_001.npy'):
+        path = os.path.join(directory, name)
+        if not os.path.isfile(path):
+            raise ValueError('No features file: %s' % path)
+        banks.append(np.load(path, allow_pickle=True).item())
+    return tuple(banks)
+
+
 def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     """sample_images.py:163-295 without COCO: sample every batch of ``loader`` (any iterable of collated batches; the synthetic
     generator when None) or the scene graphs of ``args.scene_graphs``, write one picture per image into output_dir/images
@@ -270,6 +282,8 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
             bank = np.load(args.features, allow_pickle=True).item()
             model.features = bank
             model.features_one = bank
+        if getattr(args, 'bank', None):
+            model.features, model.features_one = load_bank(args.bank)
         sgs = load_scene_graphs(graphs)
         for a in range(0, len(sgs), args.batch_size):
             save(sampler.sample_json(sgs[a:a + args.batch_size], want_layout_rgb=args.save_layout), None)
@@ -302,6 +316,8 @@ def make_parser():
     p.add_argument('--num_samples', default=24, type=int, help='images from the synthetic generator when no loader is given')
     p.add_argument('--scene_graphs', default=None, help='JSON file with one scene graph or a list of them')
     p.add_argument('--features', default=None, help='appearance bank (.npy); default: features_clustered_001.npy next to the checkpoint')
+    p.add_argument('--bank', default=None, help='with --scene_graphs: directory of features_clustered_100.npy (feature numbers '
+                   '>= 0) and features_clustered_001.npy (feature number -1), as python -m scene_generation_amd.bank writes them')
     for flag in ('save_gt_imgs', 'use_gt_boxes', 'use_gt_masks', 'use_gt_attr', 'use_gt_textures', 'save_layout'):
         p.add_argument('--' + flag, default=False, type=bool_flag)
     p.add_argument('--factored', default=True, type=bool_flag, help='0: the dense test-mode layout (the baseline path)')
