@@ -258,7 +258,11 @@ int sg_act_fwd(const float* x, float* y, int64_t n, int act, float slope, sgStre
  * ------------------------------------------------------------------------------------------- */
 /* destination-major CSR of the 2T (pass, t) entries: pass 0 = subject column, pass 1 = object column,
  * entries of a row ordered (pass, t ascending) == the order CPU scatter_add applies them (graph.py:98-101).
- * csr_off[O+1], csr_ent[2T] (t | pass<<30). */
+ * csr_off[O+1], csr_ent[2T] (t | pass<<30).
+ * Zero-length calls (here and below: T = 0 triples, n = 0 indices, rows = 0, B = 0 boxes) are valid: the operands that are
+ * indexed by the empty dimension may be null (a tensor without elements has no storage) and the other outputs are still
+ * written -- csr_off all zero, sg_embedding_bwd's g_table and sg_crop_bbox_bwd's g_feats zero-filled.  sg_segment_sum takes
+ * no count: its src must be valid whenever the CSR holds an entry. */
 int sg_build_csr(const int64_t* edges /*T,2*/, int T, int O, int32_t* csr_off, int32_t* csr_ent, sgStream stream);
 /* Range check of an index operand on the device: 0 if lo <= idx[i] < hi for every i < n, else SG_ERR_INDEX with the first
  * offending position and value in sg_last_error_string() -- what the reference's indexing raises as IndexError
@@ -458,8 +462,8 @@ int sg_masks_to_layout_bwd_geom(const float* gout, const float* vecs, const floa
                                 size_t ws_bytes, int N, int O, int D, int M, int H, int W, int avg, sgStream stream);
 int sg_crop_bbox_fwd(const float* feats, const float* boxes, const int64_t* box_to_feat, float* out, int N, int C, int H,
                      int W, int B, int HH, int WW, sgStream stream);
-/* g_feats [N, C, H, W] is written completely (no zero fill needed): a gather over the crop pixels whose bilinear
- * footprint covers each image pixel, summed in (box, crop row, crop column) order => bit-reproducible */
+/* g_feats [N, C, H, W] is written completely (no zero fill needed; all zero for B = 0): a gather over the crop pixels whose
+ * bilinear footprint covers each image pixel, summed in (box, crop row, crop column) order => bit-reproducible */
 int sg_crop_bbox_bwd(const float* gout, const float* boxes, const int64_t* box_to_feat, float* g_feats, int N, int C,
                      int H, int W, int B, int HH, int WW, sgStream stream);
 /* crop_bbox(feats, bbox, HH, WW, backend='jj') (bilinear.py:101-130 with bilinear_sample, bilinear.py:188-243): one box per

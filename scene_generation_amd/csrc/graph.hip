@@ -335,7 +335,8 @@ int sg_check_indices_if_enabled(const int64_t* idx, int64_t n, int64_t lo, int64
 }
 
 extern "C" int sg_build_csr(const int64_t* edges, int T, int O, int32_t* csr_off, int32_t* csr_ent, sgStream stream) {
-  SG_ARG_CHECK(edges && csr_off && csr_ent && T >= 0 && O > 0, "sg_build_csr: bad arguments");
+  // (a tensor without elements has no storage: the per-row operands of every entry point below may be null when the row count is 0)
+  SG_ARG_CHECK((edges || T == 0) && csr_off && csr_ent && T >= 0 && O > 0, "sg_build_csr: bad arguments");
   SG_ARG_CHECK(T < (1 << PASS_SHIFT), "sg_build_csr: too many triples");
   hipStream_t s = (hipStream_t)stream;
   // the (s, o) columns index LDS counters / object rows unchecked in every kernel that follows (graph.py:79-80 raises there)
@@ -354,7 +355,7 @@ extern "C" int sg_build_csr(const int64_t* edges, int T, int O, int32_t* csr_off
 
 extern "C" int sg_gather_concat_fwd(const float* obj, const float* pred, const int64_t* edges, float* out, int T, int Do,
                                     int Dp, sgStream stream) {
-  SG_ARG_CHECK(obj && pred && edges && out && T >= 0 && Do > 0 && Dp > 0, "sg_gather_concat_fwd: bad arguments");
+  SG_ARG_CHECK(T >= 0 && Do > 0 && Dp > 0 && (T == 0 || (obj && pred && edges && out)), "sg_gather_concat_fwd: bad arguments");
   if (T == 0) return 0;
   hipLaunchKernelGGL(gather_concat_kernel, dim3(T), dim3(row_threads(2 * Do + Dp)), 0, (hipStream_t)stream, obj, pred,
                      edges, out, T, Do, Dp);
@@ -375,7 +376,8 @@ extern "C" size_t sg_gconv_gather_linear_ws_bytes(int T, int Do, int Dp, int out
 extern "C" int sg_gconv_gather_linear_fwd(const float* obj, const float* pred, const int64_t* edges, const float* w, const float* b,
                                           float* y, int T, int Do, int Dp, int out_f, int act, float slope, void* ws,
                                           size_t ws_bytes, sgStream stream) {
-  SG_ARG_CHECK(obj && pred && edges && w && y && T >= 0 && Do > 0 && Dp > 0 && out_f > 0, "sg_gconv_gather_linear_fwd: bad arguments");
+  SG_ARG_CHECK(T >= 0 && Do > 0 && Dp > 0 && out_f > 0 && (T == 0 || (obj && pred && edges && w && y)),
+               "sg_gconv_gather_linear_fwd: bad arguments");
   if (T == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int K = 2 * Do + Dp;
@@ -410,7 +412,7 @@ extern "C" int sg_segment_sum(const float* src, int src_ld, int col_off0, int co
 
 extern "C" int sg_pool_bwd(const float* g_pooled, const float* g_new_p, const int64_t* edges, const int32_t* csr_off,
                            float* g_new_t, int T, int H, int Dout, int avg, sgStream stream) {
-  SG_ARG_CHECK(g_pooled && edges && csr_off && g_new_t && T >= 0, "sg_pool_bwd: bad arguments");
+  SG_ARG_CHECK(T >= 0 && (T == 0 || (g_pooled && edges && csr_off && g_new_t)), "sg_pool_bwd: bad arguments");
   if (T == 0) return 0;
   hipLaunchKernelGGL(pool_bwd_kernel, dim3(T), dim3(row_threads(2 * H + Dout)), 0, (hipStream_t)stream, g_pooled, g_new_p,
                      edges, csr_off, g_new_t, H, Dout, avg);
@@ -419,7 +421,7 @@ extern "C" int sg_pool_bwd(const float* g_pooled, const float* g_new_p, const in
 }
 
 extern "C" int sg_embedding_fwd(const float* table, const int64_t* idx, float* out, int n, int dim, sgStream stream) {
-  SG_ARG_CHECK(table && idx && out && n >= 0 && dim > 0, "sg_embedding_fwd: bad arguments");
+  SG_ARG_CHECK(table && n >= 0 && dim > 0 && (n == 0 || (idx && out)), "sg_embedding_fwd: bad arguments");
   if (n == 0) return 0;
   hipLaunchKernelGGL(embedding_fwd_kernel, dim3(n), dim3(row_threads(dim)), 0, (hipStream_t)stream, table, idx, out, dim);
   SG_LAUNCH_CHECK("sg_embedding_fwd");
@@ -428,7 +430,8 @@ extern "C" int sg_embedding_fwd(const float* table, const int64_t* idx, float* o
 
 extern "C" int sg_embedding_bwd(const float* g, const int64_t* idx, float* g_table, int n, int num_rows, int dim,
                                 sgStream stream) {
-  SG_ARG_CHECK(g && idx && g_table && num_rows > 0 && dim > 0, "sg_embedding_bwd: bad arguments");
+  // n == 0: the kernel zero-fills g_table and reads neither g nor idx
+  SG_ARG_CHECK(g_table && n >= 0 && num_rows > 0 && dim > 0 && (n == 0 || (g && idx)), "sg_embedding_bwd: bad arguments");
   // column chunks so that ~1024 workgroups are in flight (at least 256 columns each)
   int ysplit = (1024 + num_rows - 1) / num_rows;
   const int maxy = dim / 256 > 0 ? dim / 256 : 1;
@@ -441,7 +444,7 @@ extern "C" int sg_embedding_bwd(const float* g, const int64_t* idx, float* g_tab
 
 extern "C" int sg_copy_cols(const float* src, int src_ld, int src_off, float* dst, int dst_ld, int dst_off, int rows,
                             int width, sgStream stream) {
-  SG_ARG_CHECK(src && dst && rows >= 0 && width > 0, "sg_copy_cols: bad arguments");
+  SG_ARG_CHECK(rows >= 0 && width > 0 && (rows == 0 || (src && dst)), "sg_copy_cols: bad arguments");
   if (rows == 0) return 0;
   hipLaunchKernelGGL(copy_cols_kernel, dim3(sg_cdiv((size_t)rows * width, 256)), dim3(256), 0, (hipStream_t)stream, src,
                      src_ld, src_off, dst, dst_ld, dst_off, rows, width);

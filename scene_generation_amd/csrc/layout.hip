@@ -703,7 +703,8 @@ extern "C" int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes
 
 extern "C" int sg_crop_bbox_fwd(const float* feats, const float* boxes, const int64_t* box_to_feat, float* out, int N, int C,
                                 int H, int W, int B, int HH, int WW, sgStream stream) {
-  SG_ARG_CHECK(feats && boxes && box_to_feat && out && N > 0 && C > 0 && B >= 0 && HH > 0 && WW > 0,
+  // (no boxes: boxes, box_to_feat and out are tensors without elements, i.e. without storage)
+  SG_ARG_CHECK(feats && N > 0 && C > 0 && B >= 0 && HH > 0 && WW > 0 && (B == 0 || (boxes && box_to_feat && out)),
                "sg_crop_bbox_fwd: bad arguments");
   if (B == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -716,9 +717,16 @@ extern "C" int sg_crop_bbox_fwd(const float* feats, const float* boxes, const in
 
 extern "C" int sg_crop_bbox_bwd(const float* gout, const float* boxes, const int64_t* box_to_feat, float* g_feats, int N, int C,
                                 int H, int W, int B, int HH, int WW, sgStream stream) {
-  SG_ARG_CHECK(gout && boxes && box_to_feat && g_feats && N > 0 && C > 0 && B >= 0, "sg_crop_bbox_bwd: bad arguments");
-  if (B == 0) return 0;
+  SG_ARG_CHECK(g_feats && N > 0 && C > 0 && H > 0 && W > 0 && B >= 0 && (B == 0 || (gout && boxes && box_to_feat)),
+               "sg_crop_bbox_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
+  if (B == 0) {                                         // no boxes: the gradient is all zero (the caller's buffer is not)
+    if (hipMemsetAsync(g_feats, 0, (size_t)N * C * H * W * sizeof(float), s) != hipSuccess) {
+      sg_set_error("sg_crop_bbox_bwd: hipMemsetAsync failed");
+      return -1;
+    }
+    return 0;
+  }
   SgProfScope prof(SG_K_CROP, s, 0, 4.0 * B * C * (double)HH * WW + 4.0 * N * C * (double)H * W);
   // writes EVERY element of g_feats (no zero fill needed), additions in a fixed order
   if (C <= 1)

@@ -51,8 +51,11 @@ class GatherConcatFn(Function):
         s = _stream()
         g_obj = g_pred = None
         if ctx.needs_input_grad[0]:
-            g_obj = torch.empty(O, Do, dtype=torch.float32, device=g.device)
-            _call('sg_segment_sum', _p(g), 2 * Do + Dp, 0, Do + Dp, Do, _p(off), _p(ent), _p(g_obj), O, 0, s)
+            if T == 0:                       # no triples: g has no rows (and no storage) to sum
+                g_obj = torch.zeros(O, Do, dtype=torch.float32, device=g.device)
+            else:
+                g_obj = torch.empty(O, Do, dtype=torch.float32, device=g.device)
+                _call('sg_segment_sum', _p(g), 2 * Do + Dp, 0, Do + Dp, Do, _p(off), _p(ent), _p(g_obj), O, 0, s)
         if ctx.needs_input_grad[1]:
             g_pred = torch.empty(T, Dp, dtype=torch.float32, device=g.device)
             _call('sg_copy_cols', _p(g), 2 * Do + Dp, Do, _p(g_pred), Dp, 0, T, Dp, s)
@@ -139,10 +142,13 @@ class TriplePoolFn(Function):
         new_t = _f32(new_t)
         T = new_t.size(0)
         ld = 2 * H + Dout
-        pooled = torch.empty(O, H, dtype=torch.float32, device=new_t.device)
         new_p = torch.empty(T, Dout, dtype=torch.float32, device=new_t.device)
         s = _stream()
-        _call('sg_segment_sum', _p(new_t), ld, 0, H + Dout, H, _p(off), _p(ent), _p(pooled), O, 1 if avg else 0, s)
+        if T == 0:                           # no triples: every node pools nothing (new_t has no storage to read)
+            pooled = torch.zeros(O, H, dtype=torch.float32, device=new_t.device)
+        else:
+            pooled = torch.empty(O, H, dtype=torch.float32, device=new_t.device)
+            _call('sg_segment_sum', _p(new_t), ld, 0, H + Dout, H, _p(off), _p(ent), _p(pooled), O, 1 if avg else 0, s)
         _call('sg_copy_cols', _p(new_t), ld, H, _p(new_p), Dout, 0, T, Dout, s)
         ctx.dims = (T, O, H, Dout, avg)
         ctx.save_for_backward(edges, off)

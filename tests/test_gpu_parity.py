@@ -846,7 +846,7 @@ def test_masks_to_layout_validation(hip):
 
 
 @pytest.mark.parametrize('cfg', [dict(N=3, min_objs=2, max_objs=5, size=32, mask_size=8, seed=1),
-                                 dict(N=2, min_objs=14, max_objs=20, size=36, mask_size=16, seed=2),     # > LDS hint: chunked
+                                 dict(N=2, min_objs=14, max_objs=20, size=36, mask_size=16, seed=2),     # > 12 per image: two passes
                                  dict(N=4, min_objs=3, max_objs=8, size=128, mask_size=32, seed=3)])
 def test_masks_to_layout_vs_oracle(hip, cfg):
     from scene_generation_amd.layout import masks_to_layout
