@@ -449,6 +449,53 @@ size_t sg_kmeans_pp_step_ws_bytes(int T, int R);
 int sg_kmeans_pp_step(const float* x, const int32_t* offsets, const int32_t* tiles, const int32_t* tile_off, const float* u,
                       float* centers, float* mind2, int32_t* picks, void* ws, size_t ws_bytes, int P, int C, int K, int D, int R,
                       int T, int round, sgStream stream);
+/* ---- scene graphs from layouts (scenegraph.hip; scene_generation_amd/scenegraph.py) ------------------------------------------
+ * What CocoSceneGraphDataset.__getitem__ derives from a layout in Python loops (data/coco.py:323-416), as launches over the
+ * collated batch: boxes [O, 4] fp32 (x0, y0, x1, y1), masks [O, M, M] int64 (masks_i64 = 1; an element is set when == 1) or
+ * fp32 (set when > 0.5f), centers [O, 2] fp32.  Every decision is an exact function of fp32 inputs; the only sums are integer
+ * sums, so results do not depend on any order and are bit-identical from run to run.  Predicates in the vocabulary order of
+ * coco.py:18,206: 0 __in_image__, 1 left of, 2 right of, 3 above, 4 below, 5 inside, 6 surrounding. */
+#define SG_SCENEGRAPH_MAX_M 256
+#define SG_SCENEGRAPH_MAX_P 64
+/* coco.py:326-341: the mean of the box's linspace coordinates over the set mask elements.  count[o] = number of set elements;
+ * with Sx / Sy the sums of the set elements' column / row indices, in fp64 from the fp32 box and rounded to fp32 once:
+ *   cx = x0 + (x1 - x0) * Sx / (count * (M - 1)),  cy likewise;  count == 0: the fp32 box centre 0.5f * (x0 + x1)
+ *   (coco.py:335-337);  M == 1: (x0, y0), the start of a one-step torch.linspace.  1 <= M <= SG_SCENEGRAPH_MAX_M. */
+int sg_object_centers(const float* boxes, const void* masks, int masks_i64, float* centers, int32_t* count, int O, int M,
+                      sgStream stream);
+/* coco.py:296-297,347-348 (and the __image__ row of coco.py:315, model.py:246-249, which needs no special case), in fp64 with
+ * round-half-to-even like Python's round():
+ *   size_idx = clamp(rint((S - 1) * double(x1 - x0) * double(y1 - y0)), 0, S - 1)   (the differences taken in fp32)
+ *   loc_idx  = clamp(rint(double(cx) * (g - 1)), 0, g - 1) + g * clamp(rint(double(cy) * (g - 1)), 0, g - 1)
+ * onehot [O, S + g * g] fp32 (may be null): every element is written. */
+int sg_object_attributes(const float* boxes, const float* centers, int32_t* size_idx, int32_t* loc_idx, float* onehot, int O,
+                         int S, int g, sgStream stream);
+/* coco.py:368-385 for T (subject, object) pairs of global object ids: surrounding, else inside (strict comparisons of the boxes),
+ * else the angle class of the centre difference (dx, dy) in fp32 -- as comparisons that equal the reference's math.atan2
+ * thresholds: dx < 0 && |dy| <= |dx| left of, else dy < 0 && |dy| > |dx| above, else dy > 0 && |dy| >= |dx| below, else right
+ * of.  Element t of s / o is read at s[t * idx_stride], p is written at p[t * p_stride] (1, 1: plain arrays; 3, 3 with
+ * s = triples, o = triples + 2, p = triples + 1: the columns of a [T, 3] array).  An id outside [0, O) gives p = -1. */
+int sg_pair_predicates(const float* boxes, const float* centers, const int64_t* s, const int64_t* o, int idx_stride, int64_t* p,
+                       int p_stride, int T, int O, sgStream stream);
+/* The random partner draw of coco.py:358-366 and the collate order of coco.py:406-413,501-547, driven by a table of uniforms.
+ * Image n owns the objects seg_off[n] .. seg_off[n + 1] - 1, the last of which is its __image__ object, and the triples
+ * tri_off[n] .. tri_off[n + 1] - 1.  With k = its number of real objects, every real object i (ascending) draws r partners,
+ *   j = min(int(double(u[o, q, 0]) * (k - 1)), k - 2), j += (j >= i);  subject = i if u[o, q, 1] > 0.5f else j   (o = seg_off[n] + i)
+ * with the derived predicate (sg_pair_predicates); then the k triples (i, 0, last).  k < 2: only those (coco.py:359-361), so
+ * tri_off[n + 1] - tri_off[n] must be k + (k >= 2 ? k * r : 0) (an image whose count differs is left unwritten).  u [O, r, 2]
+ * fp32 in [0, 1), triples [T, 3] / triple_to_img [T] int64 with T = tri_off[N]. */
+int sg_draw_pairs(const int32_t* seg_off, const int32_t* tri_off, const float* u, const float* boxes, const float* centers,
+                  int64_t* triples, int64_t* triple_to_img, int N, int O, int T, int r, sgStream stream);
+/* How many triples a layout honours: ADDS to counts [P, 2] int64 (the caller zeroes it once; integer atomics), for every triple
+ * with 1 <= p < P, counts[p, 0] += 1 and counts[p, 1] += (the predicate derived as in sg_pair_predicates == p).  Row 0 and
+ * triples with ids outside [0, O) are left alone.  P <= SG_SCENEGRAPH_MAX_P. */
+int sg_triple_agreement(const int64_t* triples, const float* boxes, const float* centers, int64_t* counts, int T, int O, int P,
+                        sgStream stream);
+/* The same for the attribute block attrs [O, S + g * g] fp32 (a bit is set when > 0.5f): ADDS to counts [2, 2] int64
+ * counts[0, 0] += objects whose size block has exactly one bit set, counts[0, 1] += those whose bit is size_idx[o];
+ * counts[1, :] likewise for the location block and loc_idx.  Rows without a set bit count for nothing. */
+int sg_attribute_agreement(const float* attrs, const int32_t* size_idx, const int32_t* loc_idx, int64_t* counts, int O, int S,
+                           int g, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

@@ -110,6 +110,9 @@ enum {
   SG_K_LAYOUT_RGB,          // sg_layout_rgb (sample.hip)
   // the appearance bank's segmented k-means (kmeans.hip)
   SG_K_KMEANS_ASSIGN, SG_K_KMEANS_UPDATE, SG_K_KMEANS_RELOCATE, SG_K_KMEANS_PP,
+  // scene graphs from layouts (scenegraph.hip): the mask centroids (the streaming read), the derived attributes / predicates /
+  // partner draw, the agreement counters
+  SG_K_SCENEGRAPH_CENTERS, SG_K_SCENEGRAPH_DERIVE, SG_K_SCENEGRAPH_AGREE,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

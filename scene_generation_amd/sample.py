@@ -2,6 +2,7 @@
 scene_generation/data/utils.py it needs).
 
     python -m scene_generation_amd.sample --checkpoint CKPT.pt --output_dir OUT [--weights ema] [--scene_graphs FILE.json [--bank DIR]]
+                                          [--layouts FILE.json] [--consistent_graphs 1] [--graph_metrics 1]
 
 * ``Sampler``: one test-mode forward per collated batch (``sample_batch``, the flags of sample_images.py:203-221) or per list of
   scene graphs written by a person (``sample_json`` -> Model.forward_json), then the device-side ``imagenet_deprocess_batch``
@@ -10,6 +11,8 @@ scene_generation/data/utils.py it needs).
   anyway (done here and handed to the model).  With ``factored`` the stem of the generator runs on the factored test-mode layout
   (Model.factored_test_layout) and the dense (N, num_objs + rep_size, H, W) tensor is only written when a caller asks for it.
 * the box IoU bookkeeping of sample_images.py:241-255 as tensor operations (``iou_totals``), read once at the end.
+* ``graph_metrics`` (off by default): how many of the call's triples and attribute bits the predicted boxes and masks honour
+  (scene_generation_amd.scenegraph), accumulated on the device next to the IoU totals and read once by ``graph_summary``.
 * ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
   (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
 Not here: the accuracy network, scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
@@ -73,8 +76,10 @@ class Sampler(object):
     factored test-mode layout (Model.factored_test_layout).  ON by default: measured on MI355X at N = 32 / 128 x 128, 6.82 against
     7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
 
-    def __init__(self, model, features=None, colors=None, factored=True):
+    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False):
         self.model, self.features, self.factored = model, features, bool(factored)
+        self.graph_metrics = bool(graph_metrics)
+        self.graph_counts = None             # running agreement counters (scenegraph.new_counts), on the device
         self.device = next(model.parameters()).device
         if colors is None:
             colors = torch.randint(0, 256, [model.num_objs, 3]).float()
@@ -122,6 +127,7 @@ class Sampler(object):
                 bank = self.features[c]
                 rows.append(bank[random.randint(0, bank.shape[0] - 1), :])
             features = list(to_device_async(torch.from_numpy(np.stack(rows).astype(np.float32)), self.device).unbind(0))
+        given_attributes = attributes        # what the batch specified: the graph metrics score these
         if not use_gt_attr:
             attributes = torch.zeros_like(attributes)
         m = self.model
@@ -130,6 +136,7 @@ class Sampler(object):
                             objs_h, o2i_h, want_layout_rgb, want_layout, objs)
         tot = iou_totals(out.boxes_pred, boxes, obj_to_img)
         self.iou = tot if self.iou is None else self.iou + tot
+        self._graph_metrics(out, triples, given_attributes)
         return out
 
     def sample_json(self, scene_graphs, want_layout_rgb=False, want_layout=False):
@@ -139,11 +146,33 @@ class Sampler(object):
             scene_graphs = [scene_graphs]
         objs, triples, obj_to_img, attributes, features = m.encode_scene_graphs(scene_graphs)
         objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()
-        return self._forward(lambda: m(None, objs, triples, obj_to_img, attributes=attributes, test_mode=True, use_gt_box=False,
-                                       features=features), objs_h, o2i_h, want_layout_rgb, want_layout, objs)
+        out = self._forward(lambda: m(None, objs, triples, obj_to_img, attributes=attributes, test_mode=True, use_gt_box=False,
+                                      features=features), objs_h, o2i_h, want_layout_rgb, want_layout, objs)
+        self._graph_metrics(out, triples, attributes)
+        return out
+
+    def _graph_metrics(self, out, triples, attributes):
+        """with ``graph_metrics``: four launches that add to the counters (centroids of the predicted masks, triple agreement, the
+        derived size / location indices, attribute agreement); no host synchronisation.  Off: nothing is launched."""
+        if not self.graph_metrics:
+            return
+        from . import scenegraph
+        if self.graph_counts is None:
+            self.graph_counts = scenegraph.new_counts(self.model.num_preds, self.device)
+        centers = scenegraph.object_centers(out.boxes_pred, out.masks_pred)
+        scenegraph.triple_agreement(triples, out.boxes_pred, centers=centers, counts=self.graph_counts)
+        if attributes is not None and attributes.dim() == 2 and attributes.size(1) == scenegraph.SIZE_LEN + scenegraph.GRID ** 2:
+            scenegraph.attribute_agreement(attributes, out.boxes_pred, centers=centers, counts=self.graph_counts)
 
     def iou_summary(self):
         return iou_summary(self.iou) if self.iou is not None else None
+
+    def graph_summary(self):
+        """the ONE device-to-host read of the graph metrics (scenegraph.summary); None when they are off or nothing was sampled"""
+        if self.graph_counts is None:
+            return None
+        from . import scenegraph
+        return scenegraph.summary(self.graph_counts, self.model.vocab)
 
 
 # ---- checkpoint -> model ------------------------------------------------------------------------------------------------------
@@ -228,6 +257,13 @@ def load_scene_graphs(path):
     return sgs
 
 
+def load_layouts(path):
+    """a JSON file with one layout of a drawing front end or a list of them (scenegraph.layout_json_to_scene_graphs) -> scene graphs"""
+    from .scenegraph import layout_json_to_scene_graphs
+    with open(path) as f:
+        return layout_json_to_scene_graphs(json.load(f))
+
+
 def load_features(args):
     """the appearance bank next to the checkpoint (sample_images.py:166-174) or ``--features``"""
     path = getattr(args, 'features', None) or os.path.join(os.path.dirname(args.checkpoint or ''), 'features_clustered_001.npy')
@@ -254,12 +290,18 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     (+ images_gt, layouts), print and return the IoU summary and the paths written."""
     model = build_model(args, checkpoint, device)
     graphs = getattr(args, 'scene_graphs', None)
+    layouts = getattr(args, 'layouts', None)
+    if graphs and layouts:
+        raise ValueError('--scene_graphs and --layouts: give one of them')
+    metrics = bool(getattr(args, 'graph_metrics', False))
+    if getattr(args, 'consistent_graphs', False) and model.num_preds < 7:
+        raise ValueError('--consistent_graphs derives the six geometric predicates; the checkpoint knows %d' % model.num_preds)
     features = None
-    if not graphs and not args.use_gt_textures:
+    if not graphs and not layouts and not args.use_gt_textures:
         features = load_features(args)
-    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True))
+    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics)
     img_dir = _makedir(output_dir, 'images')
-    gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs)
+    gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
     paths, idx = [], 0
 
@@ -277,19 +319,22 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
             idx += 1
         print('Saved %d images' % idx)
 
-    if graphs:
+    if graphs or layouts:
         if getattr(args, 'features', None):
             bank = np.load(args.features, allow_pickle=True).item()
             model.features = bank
             model.features_one = bank
         if getattr(args, 'bank', None):
             model.features, model.features_one = load_bank(args.bank)
-        sgs = load_scene_graphs(graphs)
+        sgs = load_scene_graphs(graphs) if graphs else load_layouts(layouts)
         for a in range(0, len(sgs), args.batch_size):
             save(sampler.sample_json(sgs[a:a + args.batch_size], want_layout_rgb=args.save_layout), None)
     else:
         if loader is None:
             loader = synthetic_loader(model, args.batch_size, args.num_samples, checkpoint['model_kwargs'].get('mask_size', 32))
+            if getattr(args, 'consistent_graphs', False):   # every batch's graph re-derived from its own boxes and masks
+                from .scenegraph import regraph
+                loader = (regraph(batch, seed=k) for k, batch in enumerate(loader))
         for batch in loader:
             imgs_gt = None
             if gt_dir is not None:
@@ -301,7 +346,16 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         print('avg_iou {}'.format(summary['avg_iou']))
         print('r0.5 {}'.format(summary['r0.5']))
         print('r0.3 {}'.format(summary['r0.3']))
-    return {'paths': paths, 'iou': summary}
+    result = {'paths': paths, 'iou': summary}
+    if metrics:
+        graph = result['graph'] = sampler.graph_summary()
+        if graph is not None:
+            print('rel_acc {}'.format(graph['rel_acc']))
+            for name, (agree, seen) in graph['rel_acc_by_pred'].items():
+                print('  {}: {} / {}'.format(name, agree, seen))
+            print('size_acc {}'.format(graph['size_acc']))
+            print('loc_acc {}'.format(graph['loc_acc']))
+    return result
 
 
 def make_parser():
@@ -321,6 +375,12 @@ def make_parser():
     for flag in ('save_gt_imgs', 'use_gt_boxes', 'use_gt_masks', 'use_gt_attr', 'use_gt_textures', 'save_layout'):
         p.add_argument('--' + flag, default=False, type=bool_flag)
     p.add_argument('--factored', default=True, type=bool_flag, help='0: the dense test-mode layout (the baseline path)')
+    p.add_argument('--layouts', default=None, help='JSON file with one layout or a list of them (objects with text / left / top / '
+                   'width / height / size / location / feature): converted to scene graphs, then as --scene_graphs')
+    p.add_argument('--consistent_graphs', default=False, type=bool_flag, help='synthetic batches: triples and attributes derived '
+                   'from the batch\'s own boxes and masks instead of drawn at random')
+    p.add_argument('--graph_metrics', default=False, type=bool_flag, help='report how many of the requested relations and size / '
+                   'location attributes the predicted layout honours')
     return p
 
 
