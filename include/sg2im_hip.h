@@ -249,6 +249,20 @@ int sg_linear_fwd(const float* x, const float* w, const float* b, float* y, int 
 int sg_linear_bwd_data(const float* gy, const float* w, float* gx, int rows, int in_f, int out_f, sgStream stream);
 int sg_linear_bwd_weight(const float* gy, const float* x, float* gw, float* gb, int rows, int in_f, int out_f,
                          sgStream stream);
+/* host-only query of a dense layer's launch plan (the three entry points above launch from the same function, under the
+ * current options linear_skinny / linear_nsub).  entry: SG_LINEAR_*.  The GEMM is C[M][N] = sum_k A(m, k) B(n, k) with
+ *   fwd: A = x, B = w, K = in_f;   bwd_data: A = gy, B = w, K = out_f;   bwd_weight: A = gy, B = x, K = rows
+ * a_align / b_align: alignment in bytes (16, 8 or 4) of the address of A / B.
+ *   *kind   SG_LIN_SKINNY: skinny_gemm_kernel<AV, BV> on 32x32 tiles with (AV, BV) = (*a_form, *b_form), *bm = *bn = 32, *nsub = 1
+ *           SG_LIN_TILED : the LDS-tiled kernel on *bm x *bn tiles (64x64, or 32x128 when M <= 32), k-tiles 16 * *nsub deep
+ *   *a_form / *b_form  how the operand is read: SG_LIN_ROWMAJOR = elem(x, k) = p[k*ld + x] (w of bwd_data, both operands of
+ *           bwd_weight); otherwise rows of k -- skinny: 4 / 2 / 1 floats per load; tiled: SG_LIN_KVEC (float4 loads with a masked
+ *           tail; needs K % 4 == 0 and 16-byte alignment of every K-contiguous operand) or SG_LIN_KSCALAR */
+enum { SG_LINEAR_FWD = 0, SG_LINEAR_BWD_DATA = 1, SG_LINEAR_BWD_WEIGHT = 2 };
+enum { SG_LIN_SKINNY = 0, SG_LIN_TILED = 1 };
+enum { SG_LIN_ROWMAJOR = 0, SG_LIN_KSCALAR = 1, SG_LIN_KVEC = 4 };
+int sg_linear_plan(int entry, int rows, int in_f, int out_f, int a_align, int b_align, int* kind, int* a_form, int* b_form,
+                   int* bm, int* bn, int* nsub);
 /* gx = gy * act'(.) evaluated from the activation OUTPUT y (relu / leaky / tanh / sigmoid) */
 int sg_act_bwd(const float* y, const float* gy, float* gx, int64_t n, int act, float slope, sgStream stream);
 int sg_act_fwd(const float* x, float* y, int64_t n, int act, float slope, sgStream stream);

@@ -2377,20 +2377,67 @@ namespace {
 inline bool dense_sizes_ok(int rows, int in_f, int out_f) {
   return (double)rows * in_f <= SG_MAX_ELEMS && (double)rows * out_f <= SG_MAX_ELEMS && (double)in_f * out_f <= SG_MAX_ELEMS;
 }
-template <class A64, class B64, class A32, class B128>
-int run_dense(const A64& a64, const B64& b64, const A32& a32, const B128& b128, const EpRowMajor& ep, int M, int N,
-              int K, hipStream_t s) {
+inline int align_of(const void* p) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  return a % 16 == 0 ? 16 : (a % 8 == 0 ? 8 : 4);
+}
+// THE launch plan of a dense layer (sg_linear_fwd / _bwd_data / _bwd_weight launch exactly this; sg_linear_plan reports it).
+// The GEMM of entry point e is C[M][N] = sum_k A(m, k) B(n, k):
+//   fwd        M = rows,  N = out_f, K = in_f,  A = x  (K-contiguous), B = w (K-contiguous)
+//   bwd_data   M = rows,  N = in_f,  K = out_f, A = gy (K-contiguous), B = w (row-index-major)
+//   bwd_weight M = out_f, N = in_f,  K = rows,  A = gy, B = x (both row-index-major)
+// a_form / b_form: SG_LIN_ROWMAJOR, or the width of the K-contiguous loads -- skinny kernel 4 / 2 / 1 floats (skinny_vec), tiled
+// kernel SG_LIN_KVEC (float4, masked tail) / SG_LIN_KSCALAR.  a_align / b_align: alignment in bytes of the A / B address.
+struct DensePlan { int kind, a_form, b_form, bm, bn, nsub, M, N, K; };
+DensePlan dense_plan(int entry, int rows, int in_f, int out_f, int a_align, int b_align) {
+  DensePlan p{};
+  const bool a_k = entry != SG_LINEAR_BWD_WEIGHT, b_k = entry == SG_LINEAR_FWD;
+  p.M = entry == SG_LINEAR_BWD_WEIGHT ? out_f : rows;
+  p.N = entry == SG_LINEAR_FWD ? out_f : in_f;
+  p.K = entry == SG_LINEAR_FWD ? in_f : (entry == SG_LINEAR_BWD_DATA ? out_f : rows);
+  const int lda = entry == SG_LINEAR_FWD ? in_f : out_f;          // row pitch of A; B's is in_f in all three
+  if (sgk::skinny_shape(p.M, p.N)) {           // small layer: latency-bound, register-streaming kernel (skinny.hip)
+    p.kind = SG_LIN_SKINNY;
+    p.a_form = a_k ? sgk::skinny_vec(a_align, lda, p.K) : SG_LIN_ROWMAJOR;
+    p.b_form = b_k ? sgk::skinny_vec(b_align, in_f, p.K) : SG_LIN_ROWMAJOR;
+    p.bm = p.bn = 32;
+    p.nsub = 1;
+    return p;
+  }
+  p.kind = SG_LIN_TILED;
+  // one switch for both K-contiguous operands: the vector loaders need K % 4 == 0 and 16-byte aligned rows
+  const bool vec = p.K % 4 == 0 && (!a_k || a_align % 16 == 0) && (!b_k || b_align % 16 == 0);
+  p.a_form = a_k ? (vec ? SG_LIN_KVEC : SG_LIN_KSCALAR) : SG_LIN_ROWMAJOR;
+  p.b_form = b_k ? (vec ? SG_LIN_KVEC : SG_LIN_KSCALAR) : SG_LIN_ROWMAJOR;
   // these GEMMs are a chain of K/16 dependent load -> LDS -> MFMA rounds on a grid that does not even fill the chip
   // (graph-conv MLPs: ~150 workgroups): 32-deep k-tiles halve the number of rounds.  SG_LINEAR_NSUB=1 restores depth 16.
-  const int deep = sg_opt(SG_OPT_LINEAR_NSUB);
-  if (deep == 2 && K >= 64) {
-    if (M <= 32) return launch_cfg<TileCfg<32, 128, 1, 2>>(a32, b128, ep, M, N, K, 1, s);
-    return launch_cfg<TileCfg<64, 64, 2, 2>>(a64, b64, ep, M, N, K, 1, s);
+  p.nsub = (sg_opt(SG_OPT_LINEAR_NSUB) == 2 && p.K >= 64) ? 2 : Cfg64::NSUB;
+  p.bm = p.M <= 32 ? 32 : 64;
+  p.bn = p.M <= 32 ? 128 : 64;
+  return p;
+}
+template <class A64, class B64, class A32, class B128>
+int run_dense(const DensePlan& p, const A64& a64, const B64& b64, const A32& a32, const B128& b128, const EpRowMajor& ep,
+              hipStream_t s) {
+  if (p.nsub == 2) {
+    if (p.bm == 32) return launch_cfg<TileCfg<32, 128, 1, 2>>(a32, b128, ep, p.M, p.N, p.K, 1, s);
+    return launch_cfg<TileCfg<64, 64, 2, 2>>(a64, b64, ep, p.M, p.N, p.K, 1, s);
   }
-  if (M <= 32) return launch_cfg<Cfg32>(a32, b128, ep, M, N, K, 1, s);
-  return launch_cfg<Cfg64>(a64, b64, ep, M, N, K, 1, s);
+  if (p.bm == 32) return launch_cfg<Cfg32>(a32, b128, ep, p.M, p.N, p.K, 1, s);
+  return launch_cfg<Cfg64>(a64, b64, ep, p.M, p.N, p.K, 1, s);
 }
 }  // namespace
+
+extern "C" int sg_linear_plan(int entry, int rows, int in_f, int out_f, int a_align, int b_align, int* kind, int* a_form,
+                              int* b_form, int* bm, int* bn, int* nsub) {
+  SG_ARG_CHECK(entry >= SG_LINEAR_FWD && entry <= SG_LINEAR_BWD_WEIGHT && rows > 0 && in_f > 0 && out_f > 0 && kind && a_form &&
+               b_form && bm && bn && nsub, "sg_linear_plan: bad arguments");
+  SG_ARG_CHECK((a_align == 16 || a_align == 8 || a_align == 4) && (b_align == 16 || b_align == 8 || b_align == 4),
+               "sg_linear_plan: alignments are 16, 8 or 4 bytes");
+  const DensePlan p = dense_plan(entry, rows, in_f, out_f, a_align, b_align);
+  *kind = p.kind; *a_form = p.a_form; *b_form = p.b_form; *bm = p.bm; *bn = p.bn; *nsub = p.nsub;
+  return 0;
+}
 
 extern "C" int sg_linear_fwd(const float* x, const float* w, const float* b, float* y, int rows, int in_f, int out_f,
                              int act, float slope, sgStream stream) {
@@ -2399,16 +2446,16 @@ extern "C" int sg_linear_fwd(const float* x, const float* w, const float* b, flo
   sgk::t_alg_bytes = 4.0 * ((double)rows * in_f + (double)in_f * out_f + (double)rows * out_f);
   hipStream_t s = (hipStream_t)stream;
   EpRowMajor ep{y, b, rows, out_f, out_f, act, slope, 0};
-  const bool vec = (in_f % 4 == 0) && aligned16(x) && aligned16(w);
+  const DensePlan p = dense_plan(SG_LINEAR_FWD, rows, in_f, out_f, align_of(x), align_of(w));
   SgProfScope prof(SG_K_LINEAR, s, 2.0 * rows * (double)in_f * out_f, 0);
-  if (sgk::skinny_shape(rows, out_f))          // small layer: latency-bound, register-streaming kernel (skinny.hip)
-    sgk::skinny_gemm(x, in_f, 1, w, in_f, 1, y, b, nullptr, rows, out_f, in_f, act, slope, s);
-  else if (vec)
-    run_dense(LoadKContig<64, true>{x, in_f, rows}, LoadKContig<64, true>{w, in_f, out_f},
-              LoadKContig<32, true>{x, in_f, rows}, LoadKContig<128, true>{w, in_f, out_f}, ep, rows, out_f, in_f, s);
+  if (p.kind == SG_LIN_SKINNY)
+    sgk::skinny_gemm(x, in_f, p.a_form, w, in_f, p.b_form, y, b, nullptr, rows, out_f, in_f, act, slope, s);
+  else if (p.a_form == SG_LIN_KVEC)
+    run_dense(p, LoadKContig<64, true>{x, in_f, rows}, LoadKContig<64, true>{w, in_f, out_f},
+              LoadKContig<32, true>{x, in_f, rows}, LoadKContig<128, true>{w, in_f, out_f}, ep, s);
   else
-    run_dense(LoadKContig<64, false>{x, in_f, rows}, LoadKContig<64, false>{w, in_f, out_f},
-              LoadKContig<32, false>{x, in_f, rows}, LoadKContig<128, false>{w, in_f, out_f}, ep, rows, out_f, in_f, s);
+    run_dense(p, LoadKContig<64, false>{x, in_f, rows}, LoadKContig<64, false>{w, in_f, out_f},
+              LoadKContig<32, false>{x, in_f, rows}, LoadKContig<128, false>{w, in_f, out_f}, ep, s);
   SG_LAUNCH_CHECK("sg_linear_fwd");
   return 0;
 }
@@ -2420,16 +2467,17 @@ extern "C" int sg_linear_bwd_data(const float* gy, const float* w, float* gx, in
   sgk::t_alg_bytes = 4.0 * ((double)rows * in_f + (double)in_f * out_f + (double)rows * out_f);
   hipStream_t s = (hipStream_t)stream;
   EpRowMajor ep{gx, nullptr, rows, in_f, in_f, SG_ACT_NONE, 0.f, 0};
-  const bool vec = (out_f % 4 == 0) && aligned16(gy);
+  // gx[rows][in_f] = sum_o gy[row][o] w[o][in_f]: B(n = i, k = o) = w[o*in_f + i]
+  const DensePlan p = dense_plan(SG_LINEAR_BWD_DATA, rows, in_f, out_f, align_of(gy), align_of(w));
   SgProfScope prof(SG_K_LINEAR, s, 2.0 * rows * (double)in_f * out_f, 0);
-  if (sgk::skinny_shape(rows, in_f))           // gx[rows][in_f] = sum_o gy[row][o] w[o][in_f]: B(n = i, k = o) = w[o*in_f + i]
-    sgk::skinny_gemm(gy, out_f, 1, w, in_f, 0, gx, nullptr, nullptr, rows, in_f, out_f, SG_ACT_NONE, 0.f, s);
-  else if (vec)
-    run_dense(LoadKContig<64, true>{gy, out_f, rows}, LoadXContig<64>{w, in_f, in_f}, LoadKContig<32, true>{gy, out_f, rows},
-              LoadXContig<128>{w, in_f, in_f}, ep, rows, in_f, out_f, s);
+  if (p.kind == SG_LIN_SKINNY)
+    sgk::skinny_gemm(gy, out_f, p.a_form, w, in_f, p.b_form, gx, nullptr, nullptr, rows, in_f, out_f, SG_ACT_NONE, 0.f, s);
+  else if (p.a_form == SG_LIN_KVEC)
+    run_dense(p, LoadKContig<64, true>{gy, out_f, rows}, LoadXContig<64>{w, in_f, in_f}, LoadKContig<32, true>{gy, out_f, rows},
+              LoadXContig<128>{w, in_f, in_f}, ep, s);
   else
-    run_dense(LoadKContig<64, false>{gy, out_f, rows}, LoadXContig<64>{w, in_f, in_f},
-              LoadKContig<32, false>{gy, out_f, rows}, LoadXContig<128>{w, in_f, in_f}, ep, rows, in_f, out_f, s);
+    run_dense(p, LoadKContig<64, false>{gy, out_f, rows}, LoadXContig<64>{w, in_f, in_f},
+              LoadKContig<32, false>{gy, out_f, rows}, LoadXContig<128>{w, in_f, in_f}, ep, s);
   SG_LAUNCH_CHECK("sg_linear_bwd_data");
   return 0;
 }
@@ -2442,14 +2490,16 @@ extern "C" int sg_linear_bwd_weight(const float* gy, const float* x, float* gw, 
   hipStream_t s = (hipStream_t)stream;
   EpRowMajor ep{gw, nullptr, out_f, in_f, in_f, SG_ACT_NONE, 0.f, 0};
   {
+    // gw[o][i] = sum_row gy[row][o] x[row][i]: both operands row-index-major
+    const DensePlan p = dense_plan(SG_LINEAR_BWD_WEIGHT, rows, in_f, out_f, align_of(gy), align_of(x));
     SgProfScope prof(SG_K_LINEAR, s, 2.0 * rows * (double)in_f * out_f, 0);
-    if (sgk::skinny_shape(out_f, in_f)) {      // gw[o][i] = sum_row gy[row][o] x[row][i]: both operands row-index-major;
+    if (p.kind == SG_LIN_SKINNY) {
       // the bias gradient (column sums of gy = row sums of the A operand) comes out of the same launch
-      sgk::skinny_gemm(gy, out_f, 0, x, in_f, 0, gw, nullptr, gb, out_f, in_f, rows, SG_ACT_NONE, 0.f, s);
+      sgk::skinny_gemm(gy, out_f, p.a_form, x, in_f, p.b_form, gw, nullptr, gb, out_f, in_f, rows, SG_ACT_NONE, 0.f, s);
       gb = nullptr;
     } else
-      run_dense(LoadXContig<64>{gy, out_f, out_f}, LoadXContig<64>{x, in_f, in_f}, LoadXContig<32>{gy, out_f, out_f},
-                LoadXContig<128>{x, in_f, in_f}, ep, out_f, in_f, rows, s);
+      run_dense(p, LoadXContig<64>{gy, out_f, out_f}, LoadXContig<64>{x, in_f, in_f}, LoadXContig<32>{gy, out_f, out_f},
+                LoadXContig<128>{x, in_f, in_f}, ep, s);
   }
   SG_LAUNCH_CHECK("sg_linear_bwd_weight");
   if (gb) return sg_channel_sum(gy, gb, rows, out_f, 1, nullptr, 0, stream);   // column sums of gy[rows][out_f]

@@ -61,9 +61,10 @@ int kn_parity_run(int KS, const float* W, int Rdim, int B, int m0, int M, const 
 int nk_run(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, float* out, void* ws, size_t ws_bytes,
            double flops, hipStream_t s, const Sparse* sp, float* gb = nullptr, bool* gb_done = nullptr);
 // register-streaming GEMM for small dense layers (skinny.hip): C[M][N] = act(sum_k A(m,k) B(n,k) + bias[n]);
-// *_kcontig: 1 = elem(x, k) = p[x*ld + k], 0 = elem(x, k) = p[k*ld + x]
+// av / bv: 4 / 2 / 1 = elem(x, k) = p[x*ld + k] read 16 / 8 / 4 bytes at a time (skinny_vec of the operand), 0 = elem(x, k) = p[k*ld + x]
 // rowsum (optional): [M] row sums of A over k, written by the workgroups of the first column tile
-int skinny_gemm(const float* a, int lda, int a_kcontig, const float* b, int ldb, int b_kcontig, float* c, const float* bias,
+int skinny_vec(int align, int ld, int K);
+int skinny_gemm(const float* a, int lda, int av, const float* b, int ldb, int bv, float* c, const float* bias,
                 float* rowsum, int M, int N, int K, int act, float slope, hipStream_t s);
 int skinny_gemm_gather(const float* obj, const float* pred, const int64_t* edges, int T, int Do, int Dp, const float* w, float* c,
                        const float* bias, int N, int act, float slope, hipStream_t s);

@@ -250,21 +250,26 @@ void launch_b(int bv, const SkOperand& A, const SkOperand& B, float* C, const fl
   }
 }
 
-// widest load a K-contiguous operand allows: every row start and every 8-value run must be aligned to it
-inline int vec_of(const float* p, int ld, int K) {
+inline int align_of(const float* p) {
   const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  if (a % 16 == 0 && ld % 4 == 0 && K % 4 == 0) return 4;
-  if (a % 8 == 0 && ld % 2 == 0 && K % 2 == 0) return 2;
-  return 1;
+  return a % 16 == 0 ? 16 : (a % 8 == 0 ? 8 : 4);
 }
 }  // namespace
 
 namespace sgk {
-// a_kcontig / b_kcontig: 1 = elem(x, k) = p[x*ld + k], 0 = elem(x, k) = p[k*ld + x]
-int skinny_gemm(const float* a, int lda, int a_kcontig, const float* b, int ldb, int b_kcontig, float* c, const float* bias,
+// widest load a K-contiguous operand allows: every row start and every 8-value run must be aligned to it.  align: the
+// alignment of the operand's address in bytes (16, 8 or 4).  The one place this is decided: the dense plan (igemm.hip:
+// dense_plan, what sg_linear_plan reports) and the gathered form below both call it.
+int skinny_vec(int align, int ld, int K) {
+  if (align % 16 == 0 && ld % 4 == 0 && K % 4 == 0) return 4;
+  if (align % 8 == 0 && ld % 2 == 0 && K % 2 == 0) return 2;
+  return 1;
+}
+// av / bv: the operand's loader as planned by the caller -- 4 / 2 / 1 = elem(x, k) = p[x*ld + k] fetched 16 / 8 / 4 bytes at a
+// time (skinny_vec), 0 = elem(x, k) = p[k*ld + x]
+int skinny_gemm(const float* a, int lda, int av, const float* b, int ldb, int bv, float* c, const float* bias,
                 float* rowsum, int M, int N, int K, int act, float slope, hipStream_t s) {
   const SkOperand A{a, lda, M}, B{b, ldb, N};
-  const int av = a_kcontig ? vec_of(a, lda, K) : 0, bv = b_kcontig ? vec_of(b, ldb, K) : 0;
   switch (av) {
     case 4: launch_b<4>(bv, A, B, c, bias, rowsum, M, N, K, act, slope, s); break;
     case 2: launch_b<2>(bv, A, B, c, bias, rowsum, M, N, K, act, slope, s); break;
@@ -281,7 +286,7 @@ int skinny_gemm_gather(const float* obj, const float* pred, const int64_t* edges
   const SkOperand A{nullptr, K, T}, B{w, K, N};
   const SkGather G{obj, pred, edges, Do, Dp, T};
   const bool v4 = Do % 4 == 0 && Dp % 4 == 0 && (reinterpret_cast<uintptr_t>(obj) % 16 == 0) && (reinterpret_cast<uintptr_t>(pred) % 16 == 0);
-  const int bv = vec_of(w, K, K);
+  const int bv = skinny_vec(align_of(w), K, K);
   if (v4) launch_b<5>(bv, A, B, c, bias, nullptr, T, N, K, act, slope, s, G);
   else launch_b<6>(bv, A, B, c, bias, nullptr, T, N, K, act, slope, s, G);
   return 0;
