@@ -510,6 +510,34 @@ int sg_triple_agreement(const int64_t* triples, const float* boxes, const float*
  * counts[1, :] likewise for the location block and loc_idx.  Rows without a set bit count for nothing. */
 int sg_attribute_agreement(const float* attrs, const int32_t* size_idx, const int32_t* loc_idx, int64_t* counts, int O, int S,
                            int g, sgStream stream);
+/* ---- the object-accuracy classifier (classifier.hip; scene_generation_amd/accuracy.py) ------------------------------------------
+ * What a torchvision ResNet (scripts/train_accuracy_net.py:62-101) needs beyond the entry points above.  No float atomics: every
+ * result is bit-identical from run to run.  Base pointers may be unaligned (16-byte loads are used only where they allow it).
+ *
+ * nn.MaxPool2d(3, stride=2, padding=1) on [NC, H, W] with OH = (H - 1) / 2 + 1, OW likewise.  Padding counts as -inf; a NaN in
+ * a window wins.  A window's winner is the element torch's scan keeps (rows, then columns, taking a value when it is greater than
+ * the running maximum or a NaN): the first maximum in scan order.  _bwd is a gather that recomputes the winners from x (no saved
+ * indices): gx[pixel] = sum of gy over the at most four windows the pixel won, in (oh, ow) order.  NC * H * W < 2^31. */
+int sg_maxpool3s2_fwd(const float* x, float* y, int NC, int H, int W, int OH, int OW, sgStream stream);
+int sg_maxpool3s2_bwd(const float* x, const float* gy, float* gx, int NC, int H, int W, int OH, int OW, sgStream stream);
+/* y = max(a + b, 0) (a NaN stays a NaN): the tail relu(bn(...) + identity) of a residual block.  Its backward is sg_act_bwd
+ * (SG_ACT_RELU) on y; the result is the gradient of both operands. */
+int sg_add_relu_fwd(const float* a, const float* b, float* y, int64_t n, sgStream stream);
+/* An eval-mode BatchNorm folded into the convolution before it: s = gamma / sqrt(var + eps), w_out[co, k] = w[co, k] * s[co]
+ * (w as [Cout, K], K = Cin * KS * KS), b_out[co] = beta[co] - mean[co] * s[co].  Cout <= 65535. */
+int sg_bn_fold(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* w_out,
+               float* b_out, int Cout, int K, sgStream stream);
+/* torch.optim.SGD(lr, momentum) without dampening, Nesterov or weight decay over one flat buffer; the gradient enters as
+ * g * grad_scale.  first != 0: buf = g (buf is not read); else buf = momentum * buf + g; then p = p - lr * buf.  Every product and
+ * every sum is rounded on its own (no fused multiply-add), like torch's sequence of separate operations. */
+int sg_sgd_momentum_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, int first, float grad_scale,
+                         sgStream stream);
+/* torch.max(logits, 1) per row of logits [rows, classes] -- the first index of the maximum, a NaN counting as the maximum -- written
+ * to preds [rows] int64 when non-null, and the record acc [3] int64 = {correct, counted, rows}, which the call ADDS to (integer
+ * atomics; the caller zeroes it once): a row counts when target[row] != ignore_label and is correct when it counts and its argmax
+ * equals its target (scripts/sample_images.py:233-239 with ignore_label = 0); ignore_label = -1 counts every row. */
+int sg_classify_stats(const float* logits, const int64_t* target, int rows, int classes, int64_t ignore_label, int64_t* preds,
+                      int64_t* acc, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

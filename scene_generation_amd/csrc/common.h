@@ -113,6 +113,9 @@ enum {
   // scene graphs from layouts (scenegraph.hip): the mask centroids (the streaming read), the derived attributes / predicates /
   // partner draw, the agreement counters
   SG_K_SCENEGRAPH_CENTERS, SG_K_SCENEGRAPH_DERIVE, SG_K_SCENEGRAPH_AGREE,
+  // the object-accuracy classifier (classifier.hip): padded max-pool (both directions), relu(a + b), BatchNorm fold, SGD step,
+  // argmax + accuracy record
+  SG_K_MAXPOOL3S2, SG_K_ADD_RELU, SG_K_BN_FOLD, SG_K_SGD, SG_K_CLASSIFY_STATS,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -171,6 +171,16 @@ class MaxPool2d(nn.Module):
         return 'kernel_size=%d, stride=%d' % (self.kernel_size, self.kernel_size)
 
 
+class MaxPool3s2(nn.Module):
+    """nn.MaxPool2d(kernel_size=3, stride=2, padding=1): the stem pool of a torchvision ResNet (scene_generation_amd.accuracy)."""
+
+    def forward(self, x):
+        return ops.maxpool3s2(x)
+
+    def extra_repr(self):
+        return 'kernel_size=3, stride=2, padding=1'
+
+
 class AvgPool2d(nn.Module):
     """nn.AvgPool2d(kernel_size=k, stride=k) (build_cnn 'P<k>' with pooling='avg', layers.py:185-186)."""
 

@@ -11,6 +11,8 @@ checkpoints round-trip.
 
 Optional: an exponential moving average of the parameters (``ParamEMA``, ``FusedAdam.attach_ema``) in a shadow buffer with the
 flat buffer's layout, updated inside the same launch (sg_adam_step_ema: 36 instead of 28 B/param, no second pass).
+
+``FusedSGD`` (at the end) is the same idea for torch.optim.SGD with momentum, the optimiser of the accuracy network.
 """
 import os
 
@@ -405,3 +407,98 @@ class FusedAdam:
                 self.exp_avg[o:o + n].copy_(st['exp_avg'].reshape(-1))
                 self.exp_avg_sq[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
                 self.steps[i] = int(float(st['step']))
+
+
+def _increment_version(p):
+    """mark ``p`` as written (its version counter moves): a kernel wrote it behind torch's back.  torch.autograd.graph's
+    increment_version where it exists; else an in-place no-op through torch, which bumps the counter like any write"""
+    inc = getattr(getattr(torch.autograd, 'graph', None), 'increment_version', None)
+    if inc is not None:
+        inc(p)
+    else:
+        with torch.no_grad():
+            p.add_(0)
+
+
+class FusedSGD:
+    """torch.optim.SGD(params, lr, momentum) semantics (no dampening, Nesterov or weight decay: scripts/train_accuracy_net.py:265)
+    on flat buffers: the parameters that require gradients, their gradients and the momentum buffer each live in ONE contiguous
+    fp32 buffer (FlatParams), so step() is one launch (sg_sgd_momentum_step, 20 B per parameter) and zero_grad() one fill.
+
+    ``param_groups[0]['lr']`` (and ``['momentum']``) are read by every step(), so a StepLR-style schedule that writes them works.
+    Unlike torch, a parameter that received no gradient since zero_grad() is stepped with a zero gradient (its momentum keeps
+    moving it); every trainable parameter of the accuracy network receives one in every step.  ``state_dict()`` /
+    ``load_state_dict()`` speak torch.optim.SGD's schema (``momentum_buffer``)."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, direct_grads=True):
+        params = [p for p in params if p.requires_grad]
+        self.fp = FlatParams(params)
+        self.momentum_buffer = torch.zeros_like(self.fp.flat)
+        self.param_groups = [dict(lr=float(lr), momentum=float(momentum), dampening=0, weight_decay=0, nesterov=False,
+                                  maximize=False, foreach=None, differentiable=False, fused=None, params=self.fp.params)]
+        self.steps = 0
+        self.grad_scale = 1.0             # the gradient enters the update as grad * grad_scale; reset to 1 by step()
+        n = len(self.fp.params)
+        self._touched = [False] * n
+        self.use_spill = False            # a second contribution to a parameter is added at once (ops.GradOut mode 1)
+        for i, p in enumerate(self.fp.params):
+            p.register_post_accumulate_grad_hook(self._make_hook(i))
+        if direct_grads and self.fp.flat.is_cuda:
+            ops.register_param_sinks(self)      # weight-gradient kernels write straight into the flat gradient buffer
+
+    def _make_hook(self, i):
+        def hook(param):
+            self._on_grad(i)
+        return hook
+
+    def _on_grad(self, i):
+        self._touched[i] = True
+
+    @property
+    def lr(self):
+        return float(self.param_groups[0]['lr'])
+
+    def zero_grad(self, set_to_none=False):
+        if set_to_none:
+            raise NotImplementedError('FusedSGD keeps every gradient in its flat buffer: zero_grad() fills it with zeros')
+        if self.fp.grad.is_cuda:
+            ops.fill_(self.fp.grad, 0.0)
+        else:
+            self.fp.grad.zero_()
+        self.fp.attach_grads()
+        self._touched = [False] * len(self.fp.params)
+        self.grad_scale = 1.0
+
+    def step(self):
+        try:
+            self.fp.attach_grads()
+            g = self.param_groups[0]
+            ops.sgd_momentum_step(self.fp.flat, self.fp.grad, self.momentum_buffer, g['lr'], g['momentum'], self.steps == 0,
+                                  self.grad_scale)
+            self.steps += 1
+            for p in self.fp.params:      # the kernel wrote the parameters behind torch's back: let version-keyed caches
+                _increment_version(p)     # (the accuracy network's folded BatchNorm weights) see the write
+        finally:
+            self.grad_scale = 1.0
+
+    def state_dict(self):
+        state = {}
+        if self.steps > 0:
+            for i, (p, o) in enumerate(zip(self.fp.params, self.fp.offsets)):
+                state[i] = {'momentum_buffer': self.momentum_buffer[o:o + p.numel()].view(p.shape).clone()}
+        group = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
+        group['params'] = list(range(len(self.fp.params)))
+        return {'state': state, 'param_groups': [group]}
+
+    def load_state_dict(self, sd):
+        g = sd['param_groups'][0]
+        self.param_groups[0]['lr'] = float(g['lr'])
+        self.param_groups[0]['momentum'] = float(g['momentum'])
+        have = [sd['state'].get(i) for i in range(len(self.fp.params))]
+        have = [None if st is None else st.get('momentum_buffer') for st in have]
+        with torch.no_grad():
+            self.momentum_buffer.zero_()
+            for (p, o), buf in zip(zip(self.fp.params, self.fp.offsets), have):
+                if buf is not None:
+                    self.momentum_buffer[o:o + p.numel()].copy_(buf.reshape(-1))
+        self.steps = 1 if any(b is not None for b in have) else 0

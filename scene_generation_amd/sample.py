@@ -13,9 +13,11 @@ scene_generation/data/utils.py it needs).
 * the box IoU bookkeeping of sample_images.py:241-255 as tensor operations (``iou_totals``), read once at the end.
 * ``graph_metrics`` (off by default): how many of the call's triples and attribute bits the predicted boxes and masks honour
   (scene_generation_amd.scenegraph), accumulated on the device next to the IoU totals and read once by ``graph_summary``.
+* ``accuracy`` (an ``accuracy.AccuracyMeter``, off by default): the object classifier's verdict on the crops of the generated images
+  (sample_images.py:224-239), accumulated on the device and read once; ``--accuracy_model_path`` on the command line.
 * ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
   (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
-Not here: the accuracy network, scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
+Not here: scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
 checkout's under install_as)."""
 import argparse
 import json
@@ -76,8 +78,9 @@ class Sampler(object):
     factored test-mode layout (Model.factored_test_layout).  ON by default: measured on MI355X at N = 32 / 128 x 128, 6.82 against
     7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
 
-    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False):
+    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None):
         self.model, self.features, self.factored = model, features, bool(factored)
+        self.accuracy = accuracy             # accuracy.AccuracyMeter fed by sample_batch, or None
         self.graph_metrics = bool(graph_metrics)
         self.graph_counts = None             # running agreement counters (scenegraph.new_counts), on the device
         self.device = next(model.parameters()).device
@@ -87,13 +90,15 @@ class Sampler(object):
         self.iou = None                      # running (sum IoU, > 0.5, > 0.3, boxes) of sample_batch, on the device
 
     # -- the forward + what follows the network -------------------------------------------------------------------------------------
-    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs):
+    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs, score=None):
         m = self.model
         saved = (m.factored_test_layout, m.objs_host, m.obj_to_img_host)
         m.factored_test_layout, m.objs_host, m.obj_to_img_host = self.factored, objs_h, o2i_h
         try:
             with torch.no_grad():
                 imgs_pred, boxes_pred, masks_pred, _, layout, _ = fn()
+                if score is not None:                       # the accuracy network reads the network's output, before deprocessing
+                    score(imgs_pred, boxes_pred)
                 images = ops.deprocess_images(imgs_pred, rescale=True, uint8=True)
                 rgb = None
                 if want_layout_rgb:
@@ -131,9 +136,13 @@ class Sampler(object):
         if not use_gt_attr:
             attributes = torch.zeros_like(attributes)
         m = self.model
+        score = None
+        if self.accuracy is not None:        # sample_images.py:224-239: crops at the ground-truth boxes when they drive the layout
+            def score(imgs_pred, boxes_pred):
+                self.accuracy.update(imgs_pred, boxes if use_gt_boxes else boxes_pred, obj_to_img, objs)
         out = self._forward(lambda: m(imgs, objs, triples, obj_to_img, boxes_gt=boxes, masks_gt=masks if use_gt_masks else None,
                                       attributes=attributes, test_mode=True, use_gt_box=use_gt_boxes, features=features),
-                            objs_h, o2i_h, want_layout_rgb, want_layout, objs)
+                            objs_h, o2i_h, want_layout_rgb, want_layout, objs, score)
         tot = iou_totals(out.boxes_pred, boxes, obj_to_img)
         self.iou = tot if self.iou is None else self.iou + tot
         self._graph_metrics(out, triples, given_attributes)
@@ -166,6 +175,10 @@ class Sampler(object):
 
     def iou_summary(self):
         return iou_summary(self.iou) if self.iou is not None else None
+
+    def accuracy_summary(self):
+        """the ONE device-to-host read of the accuracy record (AccuracyMeter.summary); None without a meter"""
+        return self.accuracy.summary() if self.accuracy is not None else None
 
     def graph_summary(self):
         """the ONE device-to-host read of the graph metrics (scenegraph.summary); None when they are off or nothing was sampled"""
@@ -299,7 +312,13 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     features = None
     if not graphs and not layouts and not args.use_gt_textures:
         features = load_features(args)
-    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics)
+    meter = None
+    acc_path = getattr(args, 'accuracy_model_path', None)
+    if acc_path is not None and os.path.isfile(acc_path):      # sample_images.py:181
+        from .accuracy import AccuracyMeter, load_model
+        meter = AccuracyMeter(load_model(acc_path, getattr(args, 'accuracy_model_name', 'resnet101'), n_class=None, device=device),
+                              input_shape=getattr(args, 'accuracy_input_shape', 224))
+    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter)
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -347,6 +366,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         print('r0.5 {}'.format(summary['r0.5']))
         print('r0.3 {}'.format(summary['r0.3']))
     result = {'paths': paths, 'iou': summary}
+    if meter is not None and meter.acc is not None:
+        result['accuracy'] = meter.summary()
+        print('Accuracy {}'.format(result['accuracy']['accuracy']))
     if metrics:
         graph = result['graph'] = sampler.graph_summary()
         if graph is not None:
@@ -381,6 +403,10 @@ def make_parser():
                    'from the batch\'s own boxes and masks instead of drawn at random')
     p.add_argument('--graph_metrics', default=False, type=bool_flag, help='report how many of the requested relations and size / '
                    'location attributes the predicted layout honours')
+    p.add_argument('--accuracy_model_path', default=None, help='the object classifier (python -m scene_generation_amd.accuracy '
+                   'train, or the reference\'s resnet101_172_classes.pth): prints the Accuracy line of sample_images.py')
+    p.add_argument('--accuracy_model_name', default='resnet101', help='its architecture: resnet18 / 34 / 50 / 101 / 152')
+    p.add_argument('--accuracy_input_shape', default=224, type=int, help='side of the crops the classifier sees')
     return p
 
 
