@@ -222,6 +222,29 @@ int sg_convT2d_dgrad(const sgConvDesc* d, const float* gy, const float* w, float
                      sgStream stream);
 int sg_convT2d_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, float* gb,
                      void* ws, size_t ws_bytes, sgStream stream);
+/* host-only query of the launch plan of a transposed gather (csrc/igemm_kn1.hip): what sg_convT2d_fwd, sg_conv2d_dgrad on the
+ * channel window [c_begin, c_end) or sg_conv2d_dgrad_folded launches for this desc, from the same functions the launchers use,
+ * under the current options (tile, splits, fixedtap, ...).  Never touches the device.  ws_mod16: the workspace address modulo 16
+ * (0, 4, 8 or 12); ws_bytes: its size, 0 = what the entry point's own *_ws_bytes query returns (a smaller one can
+ * switch split-K off).  The channel window is ignored for SG_TG_CONVT_FWD.
+ *   route   SG_TG_PLAIN : one GEMM over all KS*KS taps (stride 1, 1x1 kernels, the folded form): ncls = 1, taps[0] = KS*KS,
+ *                         PH/PW[0] = the whole pixel grid, ph0 = pw0 = 0
+ *           SG_TG_PARITY: stride 2, KS >= 3: one GEMM per non-empty parity class, in launch order; class c reduces over
+ *                         taps[c] taps (K[c] = channels * taps[c]) and writes pixels (ph0[c] + 2i, pw0[c] + 2j), i < PH[c], j < PW[c]
+ *   loader  SG_TG_TABLE : taps from the k-table;  SG_TG_FIXED: taps fixed per thread (LoadFixedKN)
+ *   a_vec   1: the weight matrix is read as float4, 0: scalar
+ *   bm x bn the tile;  splits: split-K slabs (1 = none);  M: rows of the GEMM
+ * Not reported (they depend on the CU count): the parity split (option par_split) and the tail split (w43_tail_split). */
+enum { SG_TG_CONVT_FWD = 0, SG_TG_CONV_DGRAD = 1, SG_TG_DGRAD_FOLDED = 2 };
+enum { SG_TG_PLAIN = 0, SG_TG_PARITY = 1 };
+enum { SG_TG_TABLE = 0, SG_TG_FIXED = 1 };
+typedef struct sgTGatherPlan {
+  int32_t route, ncls;
+  int32_t taps[4], PH[4], PW[4], ph0[4], pw0[4], K[4];
+  int32_t loader, a_vec, bm, bn, splits, M;
+} sgTGatherPlan;
+int sg_conv2d_tgather_plan(const sgConvDesc* d, int entry, int c_begin, int c_end, int ws_mod16, size_t ws_bytes,
+                           sgTGatherPlan* plan);
 /* Interpolate(x2, nearest) + Conv2d(C, Cout, 3, padding=1) (mask_net, reference generators.py:20-21, layers.py:304-314) as a
  * SUB-PIXEL transposed convolution: every output pixel (2i+a, 2j+b) only sees a 2x2 neighbourhood of the stored input, with
  * the 3x3 taps that land on the same source pixel summed -- conv3x3(up2(x); w) == convT(k4, s2, p1)(x; wt) with

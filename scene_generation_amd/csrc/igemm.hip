@@ -101,15 +101,12 @@ extern "C" int sg_conv2d_dgrad(const sgConvDesc* d, const float* gy, const float
   SG_ARG_CHECK(ws_bytes >= (size_t)d->Cout * Cin * R * sizeof(float) + ktab_bytes(d->Cout * R),
                "sg_conv2d_dgrad: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  // gradient w.r.t. the logical (upsampled, reflect-padded) input grid
-  const int GH = d->H * d->upsample + (d->pad_reflect ? 2 * d->pad : 0);
-  const int GW = d->W * d->upsample + (d->pad_reflect ? 2 * d->pad : 0);
-  const int pad = d->pad_reflect ? 0 : d->pad;
-  Gather g = make_gather(gy, nullptr, d->Cout, 0, d->OH, d->OW, 1, GH, GW, d->stride, pad, 0);
-  const int M = c_end - c_begin, K = d->Cout * R;
+  const TgArgs ta = tg_args(d, SG_TG_CONV_DGRAD, c_begin, c_end);
+  Gather g = make_gather(gy, nullptr, d->Cout, 0, d->OH, d->OW, 1, ta.PH, ta.PW, d->stride, ta.pad, 0);
+  const int M = ta.M;
   // algorithmic flops of a dgrad = those of the forward conv restricted to the requested input channels
   const double flops = 2.0 * M * (double)d->Cout * R * d->N * d->OH * d->OW;
-  if (d->stride == 2 && d->KS >= 3) {          // parity classes: only the taps that can hit each output pixel
+  if (ta.parity) {
     SG_ARG_CHECK(ws_bytes >= parity_ws(M, d->Cout, R), "sg_conv2d_dgrad: workspace too small");
     int rc = sgk::kn_parity_run(d->KS, w, d->Cout, Cin, c_begin, M, g, d->N, nullptr, gx, M, SG_ACT_NONE, 0.f, flops, ws,
                               ws_bytes, s);
@@ -119,8 +116,8 @@ extern "C" int sg_conv2d_dgrad(const sgConvDesc* d, const float* gy, const float
   float* wt = reinterpret_cast<float*>(ws);      // [Cin][Cout][R]
   const size_t nw = (size_t)d->Cout * Cin * R;
   hipLaunchKernelGGL(permute_w_kernel, dim3(sg_cdiv(nw, 256)), dim3(256), 0, s, w, wt, d->Cout, Cin, R);
-  int rc = sgk::kn1_run(d->KS, wt + (size_t)c_begin * K, M, K, g, d->N, nullptr, gx, M, SG_ACT_NONE, 0.f, flops,
-                        wt + nw, ws_bytes - nw * sizeof(float), 0u, s);
+  int rc = sgk::kn1_run(d->KS, wt + ta.a_off, M, ta.K, g, d->N, nullptr, gx, M, SG_ACT_NONE, 0.f, flops,
+                        reinterpret_cast<char*>(ws) + ta.ws_off, ws_bytes - ta.ws_off, 0u, s);
   SG_LAUNCH_CHECK("sg_conv2d_dgrad");
   return rc;
 }
@@ -150,16 +147,16 @@ extern "C" int sg_conv2d_dgrad_folded(const sgConvDesc* d, const float* gy, cons
   float* wt = reinterpret_cast<float*>(ws);      // [Cin][Cout][R]
   const size_t nw = (size_t)d->Cout * Cin * R;
   hipLaunchKernelGGL(permute_w_kernel, dim3(sg_cdiv(nw, 256)), dim3(256), 0, s, w, wt, d->Cout, Cin, R);
+  const TgArgs ta = tg_args(d, SG_TG_DGRAD_FOLDED, c_begin, c_end);
   float* V = wt + ((nw + 63) / 64) * 64;         // nine pre-folded copies of gy
   const size_t VS = (size_t)d->N * d->Cout * d->OH * d->OW;
   hipLaunchKernelGGL(reflect_variants_kernel, dim3(sg_cdiv(VS, 256)), dim3(256), 0, s, gy, V, (size_t)d->N * d->Cout, d->OH,
                      d->OW, VS);
-  Gather g = make_gather(V, nullptr, d->Cout, 0, d->OH, d->OW, 1, d->H, d->W, 1, 1, 0);
-  const int M = c_end - c_begin, K = d->Cout * R;
+  Gather g = make_gather(V, nullptr, d->Cout, 0, d->OH, d->OW, 1, ta.PH, ta.PW, 1, ta.pad, 0);
+  const int M = ta.M;
   const double flops = 2.0 * M * (double)d->Cout * R * d->N * d->OH * d->OW;
-  char* rest = reinterpret_cast<char*>(V + 9 * VS);
-  int rc = sgk::kn1_run(3, wt + (size_t)c_begin * K, M, K, g, d->N, nullptr, gx, M, SG_ACT_NONE, 0.f, flops, rest,
-                        ws_bytes - (size_t)(rest - reinterpret_cast<char*>(ws)), (unsigned)VS, s);
+  int rc = sgk::kn1_run(3, wt + ta.a_off, M, ta.K, g, d->N, nullptr, gx, M, SG_ACT_NONE, 0.f, flops,
+                        reinterpret_cast<char*>(ws) + ta.ws_off, ws_bytes - ta.ws_off, ta.variants, s);
   SG_LAUNCH_CHECK("sg_conv2d_dgrad_folded");
   return rc;
 }
@@ -275,11 +272,12 @@ extern "C" int sg_convT2d_fwd(const sgConvDesc* d, const float* x, const float* 
   SG_ARG_CHECK(ws_bytes >= (size_t)d->Cout * Cin * R * sizeof(float) + ktab_bytes(Cin * R),
                "sg_convT2d_fwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  Gather g = make_gather(x, nullptr, Cin, 0, d->H, d->W, 1, d->OH, d->OW, d->stride, d->pad, 0);
+  const TgArgs ta = tg_args(d, SG_TG_CONVT_FWD, 0, 0);
+  Gather g = make_gather(x, nullptr, Cin, 0, d->H, d->W, 1, ta.PH, ta.PW, d->stride, ta.pad, 0);
   const double flops = 2.0 * d->Cout * Cin * R * (double)d->N * d->H * d->W;
-  if (d->stride == 2 && d->KS >= 3) {
+  if (ta.parity) {
     SG_ARG_CHECK(ws_bytes >= parity_ws(d->Cout, Cin, R), "sg_convT2d_fwd: workspace too small");
-    int rc = sgk::kn_parity_run(d->KS, w, Cin, d->Cout, 0, d->Cout, g, d->N, bias, y, d->Cout, SG_ACT_NONE, 0.f, flops, ws,
+    int rc = sgk::kn_parity_run(d->KS, w, Cin, d->Cout, 0, ta.M, g, d->N, bias, y, d->Cout, SG_ACT_NONE, 0.f, flops, ws,
                               ws_bytes, s);
     SG_LAUNCH_CHECK("sg_convT2d_fwd");
     return rc;
@@ -287,8 +285,8 @@ extern "C" int sg_convT2d_fwd(const sgConvDesc* d, const float* x, const float* 
   float* wt = reinterpret_cast<float*>(ws);      // [Cout][Cin][R]
   const size_t nw = (size_t)d->Cout * Cin * R;
   hipLaunchKernelGGL(permute_w_kernel, dim3(sg_cdiv(nw, 256)), dim3(256), 0, s, w, wt, Cin, d->Cout, R);
-  int rc = sgk::kn1_run(d->KS, wt, d->Cout, Cin * R, g, d->N, bias, y, d->Cout, SG_ACT_NONE, 0.f, flops, wt + nw,
-                        ws_bytes - nw * sizeof(float), 0u, s);
+  int rc = sgk::kn1_run(d->KS, wt + ta.a_off, ta.M, ta.K, g, d->N, bias, y, d->Cout, SG_ACT_NONE, 0.f, flops,
+                        reinterpret_cast<char*>(ws) + ta.ws_off, ws_bytes - ta.ws_off, 0u, s);
   SG_LAUNCH_CHECK("sg_convT2d_fwd");
   return rc;
 }
@@ -299,6 +297,7 @@ extern "C" int sg_convT2d_dgrad(const sgConvDesc* d, const float* gy, const floa
   if (check_desc(d, "sg_convT2d_dgrad")) return -1;
   sgk::t_alg_bytes = 4.0 * ((double)d->N * (d->C1) * d->H * d->W + (double)d->Cout * (d->C1) * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(gy && w && gx && ws, "sg_convT2d_dgrad: null pointer");
+  SG_ARG_CHECK(d->C2 == 0 && d->upsample == 1 && !d->pad_reflect, "sg_convT2d_dgrad: unsupported desc");
   SG_ARG_CHECK(ws_bytes >= ktab_bytes(d->Cout * d->KS * d->KS), "sg_convT2d_dgrad: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int R = d->KS * d->KS;
@@ -315,6 +314,7 @@ extern "C" int sg_convT2d_wgrad(const sgConvDesc* d, const float* gy, const floa
   if (check_desc(d, "sg_convT2d_wgrad")) return -1;
   sgk::t_alg_bytes = 4.0 * ((double)d->N * (d->C1) * d->H * d->W + (double)d->Cout * (d->C1) * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(gy && x && gw, "sg_convT2d_wgrad: null pointer");
+  SG_ARG_CHECK(d->C2 == 0 && d->upsample == 1 && !d->pad_reflect, "sg_convT2d_wgrad: unsupported desc");
   hipStream_t s = (hipStream_t)stream;
   Gather g = make_gather(gy, nullptr, d->Cout, 0, d->OH, d->OW, 1, d->H, d->W, d->stride, d->pad, 0);
   if (int rc = sgk::nk_run(d->KS, x, d->C1, d->C1, g, d->N, gw, ws, ws ? ws_bytes : 0,

@@ -1968,20 +1968,43 @@ inline size_t kn_slab_bytes(int M, int Npix, int K) {
 
 inline size_t ktab_bytes(int K) { return (size_t)(sg_cdiv(K, 64) * 64 + 128) * sizeof(KEntry); }
 
+// THE launch plan of a conv-shaped GEMM (run_kn launches exactly this; sg_conv2d_tgather_plan reports it for the transposed
+// gathers).  full_m: the launch writes every row of the result (Mtot == M: split-K allowed); a16: A is 16-byte aligned;
+// two / reflect: the gather's second source / reflection padding; vstride: per-tap source copies (kn1_run); ws_avail: bytes behind
+// the k-table workspace pointer (table + split-K slabs)
+struct KnPlan { bool vec; int tile; bool nomask; int splits; bool fixed; };
+inline KnPlan kn_plan(int KS, int MODE, int M, int K, int Npix, bool full_m, bool a16, bool two, bool reflect, unsigned vstride,
+                      size_t ws_avail) {
+  KnPlan p;
+  p.vec = (K % 4 == 0) && a16;
+  p.tile = pick_tile(M, Npix);
+  if (!p.vec && p.tile == 0) p.tile = 1;            // the scalar-A variant is only instantiated for the small tiles
+  const int tBM = p.tile == 0 ? 128 : (p.tile == 2 ? 32 : 64), tBN = p.tile == 1 ? 64 : 128;
+  // mask-free kernels: reflection padding (every tap valid), full pixel tiles, full M tiles; a K tail is legal because
+  // the A operand... would need masking -- so also require K % 16 == 0
+  p.nomask = MODE == 0 && p.vec && reflect && (Npix % tBN == 0) && (M % tBM == 0) && (K % BK == 0);
+  p.splits = full_m ? kn_splits(M, Npix, K) : 1;
+  if (p.splits > 1 && ws_avail < ktab_bytes(K) + (size_t)p.splits * M * Npix * sizeof(float)) p.splits = 1;
+  if (p.splits > 1) {
+    // launch_cfg rounds a k-chunk up to whole k-tiles: count the chunks that exist.  The counts kn_splits chooses always do
+    // (chunks of >= split_kmin / 2); a count forced through the option splits can exceed them, and the slab reduction would
+    // then add slabs no workgroup wrote
+    const int bkt = BK * SG_NSUB, kchunk = sg_cdiv(sg_cdiv(K, p.splits), bkt) * bkt;
+    p.splits = sg_cdiv(K, kchunk);
+  }
+  // 4x4 and 1x1 kernels on one source with whole channels per k-tile: fixed taps per thread (LoadFixedKN)
+  p.fixed = fixed_taps_enabled() && (KS == 4 || KS == 1) && p.vec && !two && K % BK == 0 && vstride == 0;
+  return p;
+}
+
 template <int KS, int MODE>
 int run_kn(const float* A, int M, int K, const Gather& g, int NB, const float* bias, float* out, int Mtot, int act,
            float slope, double flops, void* ktab_ws, size_t ws_avail, hipStream_t s) {
   const int Npix = NB * g.PH * g.PW;
-  const bool vec = (K % 4 == 0) && aligned16(A);
-  int tile = pick_tile(M, Npix);
-  if (!vec && tile == 0) tile = 1;                  // the scalar-A variant is only instantiated for the small tiles
-  const int tBM = tile == 0 ? 128 : (tile == 2 ? 32 : 64), tBN = tile == 1 ? 64 : 128;
-  // mask-free kernels: reflection padding (every tap valid), full pixel tiles, full M tiles; a K tail is legal because
-  // the A operand... would need masking -- so also require K % 16 == 0
-  const bool nomask = MODE == 0 && vec && g.reflect && (Npix % tBN == 0) && (M % tBM == 0) && (K % BK == 0);
+  const KnPlan pl = kn_plan(KS, MODE, M, K, Npix, Mtot == M, aligned16(A), g.C2 > 0, g.reflect != 0, t_variant_stride, ws_avail);
+  const bool vec = pl.vec, nomask = pl.nomask;
+  const int tile = pl.tile, splits = pl.splits;
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ktab_ws) + ktab_bytes(K));
-  int splits = (Mtot == M) ? kn_splits(M, Npix, K) : 1;
-  if (splits > 1 && ws_avail < ktab_bytes(K) + (size_t)splits * M * Npix * sizeof(float)) splits = 1;
   const int Kpad = sg_cdiv(K, 64) * 64 + 128;      // the k-loop prefetches entries up to two tiles past the end
   const unsigned shw_ = (unsigned)(g.SH * g.SW), vstride = t_variant_stride;
   const KEntry* ktab = reinterpret_cast<const KEntry*>(cached_table(
@@ -1994,10 +2017,8 @@ int run_kn(const float* A, int M, int K, const Gather& g, int NB, const float* b
   const size_t nout = (size_t)M * Npix;
   EpNCHW ep{out, bias, g.PH * g.PW, Mtot, M, Npix, act, slope, 0, 0, 1, 0, 0, 0, 0};
   if (splits > 1) ep = EpNCHW{slabs, nullptr, g.PH * g.PW, Mtot, M, Npix, SG_ACT_NONE, 0.f, nout, 0, 1, 0, 0, 0, 0};
-  // 4x4 and 1x1 kernels on one source with whole channels per k-tile: fixed taps per thread (LoadFixedKN)
   const FixedTaps fixed{KS == 4 ? 4 : 0, 0u};
-  const bool use_fixed = fixed_taps_enabled() && (KS == 4 || KS == 1) && vec && g.C2 == 0 && K % BK == 0 && vstride == 0;
-  const FixedTaps* fx = use_fixed ? &fixed : nullptr;
+  const FixedTaps* fx = pl.fixed ? &fixed : nullptr;
   {
     SgProfScope prof(sg_igemm_kind(MODE, KS, tile), s, flops, 0);
     switch (tile) {
@@ -2030,6 +2051,39 @@ int run_kn_ks(int KS, const float* A, int M, int K, const Gather& g, int NB, con
     case 7: return run_kn<7, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
   }
   return -1;
+}
+
+// What an entry point of the transposed-gather family (sg_convT2d_fwd, sg_conv2d_dgrad, sg_conv2d_dgrad_folded) hands to
+// kn_parity_run / kn1_run, as a function of the desc and the channel window alone -- shared by the entry points and by
+// sg_conv2d_tgather_plan.  parity: the stride-2 parity-class route; Rdim: channels reduced over; M rows of K = Rdim * KS^2;
+// PH x PW: the pixel grid written (pad: of the transposed gather); a_off: floats from the workspace start to the A operand of the
+// plain route (the permuted weights [..][Rdim][KS^2], row c_begin); ws_off: bytes from the workspace start to the k-table / slab area
+struct TgArgs { bool parity; int KS, Rdim, M, K, PH, PW, pad; size_t a_off, ws_off; unsigned variants; };
+inline TgArgs tg_args(const sgConvDesc* d, int entry, int c_begin, int c_end) {
+  TgArgs t = {};
+  const int R = d->KS * d->KS, Cin = d->C1 + d->C2;
+  const size_t nw = (size_t)d->Cout * Cin * R;
+  t.KS = d->KS;
+  t.parity = entry != SG_TG_DGRAD_FOLDED && d->stride == 2 && d->KS >= 3;   // parity classes: only the taps that can hit each output pixel
+  if (entry == SG_TG_CONVT_FWD) {
+    t.Rdim = d->C1; t.M = d->Cout; t.PH = d->OH; t.PW = d->OW; t.pad = d->pad;
+  } else if (entry == SG_TG_CONV_DGRAD) {       // gradient w.r.t. the logical (upsampled, reflect-padded) input grid
+    t.Rdim = d->Cout; t.M = c_end - c_begin;
+    t.PH = d->H * d->upsample + (d->pad_reflect ? 2 * d->pad : 0);
+    t.PW = d->W * d->upsample + (d->pad_reflect ? 2 * d->pad : 0);
+    t.pad = d->pad_reflect ? 0 : d->pad;
+  } else {
+    t.Rdim = d->Cout; t.M = c_end - c_begin; t.PH = d->H; t.PW = d->W; t.pad = 1;
+  }
+  t.K = t.Rdim * R;
+  t.a_off = t.parity ? 0 : (entry == SG_TG_CONVT_FWD ? 0 : (size_t)c_begin * t.K);
+  t.ws_off = t.parity ? 0 : nw * sizeof(float);
+  if (entry == SG_TG_DGRAD_FOLDED) {            // [weights, padded to 64 floats][nine pre-folded copies of gy][k-table, slabs]
+    const size_t VS = (size_t)d->N * d->Cout * d->OH * d->OW;
+    t.variants = (unsigned)VS;
+    t.ws_off = (((nw + 63) / 64) * 64 + 9 * VS) * sizeof(float);
+  }
+  return t;
 }
 
 inline int sparse_kc(int L, int KS2) { return sg_cdiv(L * KS2, BK) * BK; }

@@ -556,6 +556,12 @@ class ConvTranspose2dFn(Function):
 
 
 def conv_transpose2d(x, weight, bias=None, stride=2, pad=1, out_pad=1):
+    if not 0 <= out_pad < stride:          # (what torch refuses: the padded rows would belong to the next stride step)
+        raise ValueError('conv_transpose2d: output padding %d must be in [0, stride = %d)' % (out_pad, stride))
+    KS = weight.size(2)
+    OH, OW = [(n - 1) * stride - 2 * pad + KS + out_pad for n in (x.size(2), x.size(3))]
+    if OH <= 0 or OW <= 0:
+        raise ValueError('conv_transpose2d: output size %d x %d is not positive' % (OH, OW))
     return ConvTranspose2dFn.apply(x, weight, bias, stride, pad, out_pad)
 
 
