@@ -121,7 +121,8 @@ int sg_conv2d_wgrad_sparse(const sgConvDesc* d, const float* gy, const float* x1
 /* Winograd F(2x2, 3x3) forward / data gradient / weight gradient for 3x3 stride-1 pad-1 convs (reflection padding: the
    ResnetBlock convs, layers.py:251-270; zero padding: the VGG19 convs of VGGLoss, losses.py:183-198, and -- behind the folded
    nearest x2 upsample -- mask_net, generators.py:20-22) with >= 128 channels on both sides, whose channel counts and tile count
-   N*(OH/2)*(OW/2) are all multiples of 128 or all multiples of 64: 2.25x fewer MACs; fp32 throughout, results agree with
+   N*(OH/2)*(OW/2) are all multiples of 128 (other counts, mask_net's 192 channels among them, run the direct kernels): 2.25x
+   fewer MACs; fp32 throughout, results agree with
    sg_conv2d_fwd / _dgrad / _wgrad to fp32 rounding (gb via sg_channel_sum). */
 int sg_conv2d_wino_supported(const sgConvDesc* d);
 size_t sg_conv2d_wino_ws_bytes(const sgConvDesc* d);
@@ -197,6 +198,47 @@ int sg_conv2d_wino24_dgrad(const sgConvDesc* d, const float* gy, const float* w,
                            sgStream stream);
 int sg_conv2d_wino24_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, void* ws, size_t ws_bytes,
                            sgStream stream);
+/* host-only query of the launch plan of a Winograd entry point: which form and which kernels sg_conv2d_wino_* / sg_conv2d_wino24_*
+ * run for this desc under the current options, from the same predicates the launchers use.  Never touches the device.
+ *   entry       SG_WINO_*: the entry point
+ *   align_mask  SG_WA_* bits of the operands whose address is 16-byte aligned: X (x), W (w), Y (y; ypre / out / skip of the fused
+ *               forward), GY (gy; gout / ypre / gconv of the fused backward), GX (gx), GW (gw)
+ *   saved_mask  SG_WS_* bits of the saved operands passed: UT (ut_save / ut_saved), V (v_save / v_saved), YTP (ytp_save / ytp_saved)
+ * Returns non-zero for a bad entry, a null plan, an unsupported desc and for what the entry point itself rejects before its
+ * first launch: an unaligned operand on an F(4x4,3x3) shape or on a fused entry, a saved operand the desc cannot use.
+ *   form        SG_WF_F23_GENERIC: F(2x2,3x3) over the (padded) grid -- every forward and weight gradient that is not F(4x4,3x3),
+ *               and the data gradient on the padded gradient grid followed by sg_pad_upsample_bwd; SG_WF_F23_ADJOINT: the data
+ *               gradient over the output tiles + reflection fold; SG_WF_F43: F(4x4,3x3); SG_WF_F24: F(2x2,4x4)
+ *   P / Ps      tiles of the forward / weight gradient and the columns their GEMM runs on (padded to whole tiles)
+ *   Pd / Pds    the same for the data gradient (F23 generic on a reflect desc: the (H/2+1) x (W/2+1) tiles of the padded grid)
+ *   in_kernel   transform of the entry's moving operand (x: forward, gy: data gradient; both: a weight gradient that rebuilds its
+ *               operands): SG_WK_IN_LDS (small planes staged in LDS) or SG_WK_IN_GENERAL; SG_WK_NONE: weight gradient on saved operands
+ *   wt_kernel   filter transform: SG_WK_WT_LDS, SG_WK_WT_PLAIN, SG_WK_NONE (saved operand used; weight gradient)
+ *   fold_kernel data gradient: SG_WK_FOLD_CELLS / SG_WK_FOLD_WALK (F23 adjoint), SG_WK_FOLD_F43, SG_WK_FOLD_PAD_UPSAMPLE
+ *               (sg_pad_upsample_bwd behind the generic form), SG_WK_NONE
+ *   bm x bn     GEMM tile;  nsub: k-tile depth / 16;  kfold: chunk of the channel sum (0 = one chain, 128, 256);
+ *   pipe        main loop of the 128x128 K-contiguous GEMM (option wino_pipe: 1 or 2), 0 elsewhere
+ *   wgrad_src   weight gradient: SG_WSRC_SAVED (GEMM over the x-contiguous saved operands) or SG_WSRC_REBUILT; 0 elsewhere
+ *   norm_tiles  fused entries: tiles per thread of the output transform + InstanceNorm kernel (1 or 4); 0 elsewhere
+ *   TH .. Pc    F(2x2,4x4): tile grid of the output (TH x TW) and of the input (THd x TWd), k-chunks S of Pc tiles each
+ * Not reported: the F(4x4,3x3) tail split (option w43_tail_split) -- it depends on the CU count. */
+enum { SG_WINO_FWD = 0, SG_WINO_DGRAD = 1, SG_WINO_WGRAD = 2, SG_WINO_FWD_INSTNORM = 3, SG_WINO_DGRAD_INSTNORM = 4,
+       SG_WINO24_FWD = 5, SG_WINO24_DGRAD = 6, SG_WINO24_WGRAD = 7 };
+enum { SG_WA_X = 1, SG_WA_W = 2, SG_WA_Y = 4, SG_WA_GY = 8, SG_WA_GX = 16, SG_WA_GW = 32, SG_WA_ALL = 63 };
+enum { SG_WS_UT = 1, SG_WS_V = 2, SG_WS_YTP = 4 };
+enum { SG_WF_UNSUPPORTED = 0, SG_WF_F23_GENERIC = 1, SG_WF_F23_ADJOINT = 2, SG_WF_F43 = 3, SG_WF_F24 = 4 };
+enum { SG_WK_NONE = 0, SG_WK_IN_LDS = 1, SG_WK_IN_GENERAL = 2, SG_WK_WT_LDS = 1, SG_WK_WT_PLAIN = 2,
+       SG_WK_FOLD_CELLS = 1, SG_WK_FOLD_WALK = 2, SG_WK_FOLD_F43 = 3, SG_WK_FOLD_PAD_UPSAMPLE = 4 };
+enum { SG_WSRC_SAVED = 1, SG_WSRC_REBUILT = 2 };
+typedef struct sgWinoPlan {
+  int32_t form;
+  int32_t P, Ps, Pd, Pds;
+  int32_t in_kernel, wt_kernel, fold_kernel;
+  int32_t bm, bn, nsub, kfold, pipe;
+  int32_t wgrad_src, norm_tiles;
+  int32_t TH, TW, THd, TWd, S, Pc;
+} sgWinoPlan;
+int sg_conv2d_wino_plan(const sgConvDesc* d, int entry, int align_mask, int saved_mask, sgWinoPlan* plan);
 /* Direct (vector-ALU) kernels for ReflectionPad2d(3) + Conv2d(C, Cout <= 4, 7) [+ act]: the generator's RGB head
    (reference generators.py:88-90).  Same results as sg_conv2d_fwd / sg_conv2d_wgrad (gb via sg_channel_sum). */
 int sg_conv2d_smallm_supported(const sgConvDesc* d);

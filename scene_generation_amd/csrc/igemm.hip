@@ -548,8 +548,9 @@ __global__ void __launch_bounds__(256) wino_weight_lds_kernel(const float* __res
 
 // one entry for the three call sites (SG_WINO_WT=0 keeps the per-thread kernel).  ``UT``: see wino_weight_lds_kernel; returns
 // whether it was written
+inline bool wino_weight_lds(int R, int Cc, bool w16) { return sg_opt(SG_OPT_WINO_WT) && R % 32 == 0 && Cc % 32 == 0 && w16; }
 inline bool wino_weight(const float* w, float* U, int R, int Cc, int flip, hipStream_t s, float* UT = nullptr) {
-  if (sg_opt(SG_OPT_WINO_WT) && R % 32 == 0 && Cc % 32 == 0 && aligned16(w)) {
+  if (wino_weight_lds(R, Cc, aligned16(w))) {
     hipLaunchKernelGGL(wino_weight_lds_kernel, dim3((R / 32) * (Cc / 32)), dim3(256), 0, s, w, U, R, Cc, flip,
                        flip == 0 ? UT : nullptr);
     return flip == 0 && UT != nullptr;
@@ -807,11 +808,14 @@ __global__ void wino_wgrad_output_kernel(const float* __restrict__ T, float* __r
 }
 
 // V[xi][p][c] of x (logical H x W plane, ush = folded upsample shift): LDS-staged kernel for small planes, general otherwise
+inline bool wino_input_small(int C, int H, int W, int ush, bool x16) {
+  return ush == 0 && H * W <= 256 && (H * W) % 4 == 0 && C % 64 == 0 && x16;
+}
 void wino_input_pc(const float* x, float* V, int N, int C, int H, int W, int TH, int TW, int off, int zero_pad, size_t Pstride,
                    int ush, hipStream_t s) {
   const int HW = H * W;
   SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)N * C * (H >> ush) * (W >> ush) + 16.0 * (double)Pstride * C));
-  if (ush == 0 && HW <= 256 && HW % 4 == 0 && C % 64 == 0 && aligned16(x)) {
+  if (wino_input_small(C, H, W, ush, aligned16(x))) {
     const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
     if (lds > 48 * 1024)
       hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_input_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -857,10 +861,12 @@ using CfgDI64SF256 = TileCfg<64, 64, 2, 1, 2, 256, 1>;
 using CfgDI64F128 = TileCfg<64, 64, 2, 2, 2, 128, 1>;
 using CfgDI64SF128 = TileCfg<64, 64, 2, 1, 2, 128, 1>;
 // kfold (0 / 128 / 256) x k-tile depth -> one of the six 64x64 instantiations
+inline int w43_kfold(int K) { return (K > 256 || (K > 128 && sg_opt(SG_OPT_W43_KFOLD) == 128)) ? sg_opt(SG_OPT_W43_KFOLD) : 0; }
+inline bool w43_deep() { return sg_opt(SG_OPT_W43_NSUB) != 1; }
 template <class AL, class BL>
 int launch_w43(const AL& al, const BL& bl, const EpRowMajorPlain& ep, int M, int N, int K, hipStream_t s) {
-  const int kf = (K > 256 || (K > 128 && sg_opt(SG_OPT_W43_KFOLD) == 128)) ? sg_opt(SG_OPT_W43_KFOLD) : 0;
-  const bool deep = sg_opt(SG_OPT_W43_NSUB) != 1;
+  const int kf = w43_kfold(K);
+  const bool deep = w43_deep();
   if (kf == 256) return deep ? launch_cfg<CfgDI64F256>(al, bl, ep, M, N, K, 1, s) : launch_cfg<CfgDI64SF256>(al, bl, ep, M, N, K, 1, s);
   if (kf == 128) return deep ? launch_cfg<CfgDI64F128>(al, bl, ep, M, N, K, 1, s) : launch_cfg<CfgDI64SF128>(al, bl, ep, M, N, K, 1, s);
   return deep ? launch_cfg<CfgDI64>(al, bl, ep, M, N, K, 1, s) : launch_cfg<CfgDI64S>(al, bl, ep, M, N, K, 1, s);
@@ -892,9 +898,14 @@ void wino_bgemm_tile(int tile, const float* A, const float* B, float* Cout, int 
 
 // C[m][b*cols + j] = sum_k A[b][m][k] * B[b*cols + j][k]   (NB batches -- 16 for F(2x2,3x3), 25 (x k-chunks) for F(2x2,4x4) --,
 // everything a multiple of the tile)
-void wino_bgemm(const float* A, const float* B, float* Cout, int M, int cols, int K, double flops, hipStream_t s, int NB = 16) {
+// tile of wino_bgemm: 1 = 64x128, 2 = 64x64 (wino_bgemm_tile), 0 = the 128x128 default
+inline int wino_bgemm_sel(int NB, int M, int cols, int K) {
   const int tsel = NB == 16 ? sg_opt(SG_OPT_WINO_GEMM_TILE) : sg_opt(SG_OPT_W24_GEMM_TILE);
-  if ((tsel == 1 || tsel == 2) && M % 64 == 0 && cols % 128 == 0 && K % 32 == 0) {
+  return ((tsel == 1 || tsel == 2) && M % 64 == 0 && cols % 128 == 0 && K % 32 == 0) ? tsel : 0;
+}
+void wino_bgemm(const float* A, const float* B, float* Cout, int M, int cols, int K, double flops, hipStream_t s, int NB = 16) {
+  const int tsel = wino_bgemm_sel(NB, M, cols, K);
+  if (tsel != 0) {
     wino_bgemm_tile(tsel, A, B, Cout, M, cols, K, flops, s, NB, NB == 16 ? SG_K_WINO_GEMM_128 : SG_K_WINO24_GEMM);
     return;
   }
@@ -1513,18 +1524,25 @@ void w43_gemm_dgrad(const float* Ytp, const float* U, float* G, int P, int C, in
   }
   t_batch = BatchInfo{};
 }
+// tile of the F(4x4,3x3) weight-gradient GEMM: 1 = 128x128, 2 = 64x128, 0 = 64x64
+inline int w43_wgrad_sel(int M, int C, int P) {
+  const int wt = sg_opt(SG_OPT_W43_WGRAD_TILE);
+  if (wt == 1 && M % 128 == 0 && C % 128 == 0 && P % 32 == 0) return 1;
+  if (wt == 2 && C % 128 == 0 && P % 32 == 0) return 2;
+  return 0;
+}
 void w43_gemm_wgrad(const float* Ytp, const float* V, float* T, int M, int C, int P, hipStream_t s) {
   sgk::t_alg_bytes = 4.0 * 36 * ((double)M * P + (double)C * P + (double)M * C);
   t_batch = BatchInfo{}; t_batch.cols_per_batch = C; t_batch.nbatch = 36; t_batch.a_stride = P * M; t_batch.b_stride = P * C;
   t_batch.batch_major = 1;
   {
     SgProfScope prof(SG_K_WINO43_GEMM, s, 2.0 * 36.0 * M * (double)C * P, 0);
-    const int wt = sg_opt(SG_OPT_W43_WGRAD_TILE);
-    if (wt == 1 && M % 128 == 0 && C % 128 == 0 && P % 32 == 0)
+    const int wt = w43_wgrad_sel(M, C, P);
+    if (wt == 1)
       launch_cfg<CfgDI128>(LoadXContigS<128>{Ytp, M, 0}, LoadXContigS<128>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
-    else if (wt == 2 && C % 128 == 0 && P % 32 == 0)
+    else if (wt == 2)
       launch_cfg<CfgDI64W>(LoadXContigS<64>{Ytp, M, 0}, LoadXContigS<128>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
-    else if (sg_opt(SG_OPT_W43_NSUB) == 1)
+    else if (!w43_deep())
       launch_cfg<CfgDI64S>(LoadXContigS<64>{Ytp, M, 0}, LoadXContigS<64>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
     else
       launch_cfg<CfgDI64>(LoadXContigS<64>{Ytp, M, 0}, LoadXContigS<64>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
@@ -1693,23 +1711,30 @@ __global__ void __launch_bounds__(256) w24_input_small_kernel(const float* __res
     for (size_t p = P + g; p < Pstride; p += 4)
       for (int xi = 0; xi < 25; ++xi) V[((size_t)xi * Pstride + p) * C + c0 + lane] = 0.f;
 }
+// whether the LDS-staged input transform runs, and its geometry
+inline bool w24_input_small(int N, int C, int H, int W, int TH, int* rows_per_out, int* pitch_out) {
+  if (!(sg_opt(SG_OPT_W24_SMALL) && H * W >= 144 && W <= 64 && C % 64 == 0)) return false;
+  // tile rows per workgroup: as few as keep ~2048 workgroups busy (each stages 2*rows + 3 input rows of 64 planes: <= ~24 KB)
+  int rows_per = (int)(((long)(C / 64) * N * TH + 2047) / 2048);
+  if (rows_per < 1) rows_per = 1;
+  const int nrows = std::min(H, 2 * rows_per + 3);
+  const int pitch = (nrows * W) | 1;
+  if ((size_t)64 * pitch * sizeof(float) > 64 * 1024) return false;
+  if (rows_per_out) *rows_per_out = rows_per;
+  if (pitch_out) *pitch_out = pitch;
+  return true;
+}
 void w24_input_pc(const float* x, float* V, int N, int C, int H, int W, int TH, int TW, int off, size_t Pstride, hipStream_t s) {
   const int HW = H * W;
   SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)N * C * HW + 25.0 * (double)Pstride * C));
-  if (sg_opt(SG_OPT_W24_SMALL) && HW >= 144 && W <= 64 && C % 64 == 0) {
-    // tile rows per workgroup: as few as keep ~2048 workgroups busy (each stages 2*rows + 3 input rows of 64 planes: <= ~24 KB)
-    int rows_per = (int)(((long)(C / 64) * N * TH + 2047) / 2048);
-    if (rows_per < 1) rows_per = 1;
-    const int nrows = std::min(H, 2 * rows_per + 3);
-    const int pitch = (nrows * W) | 1;
+  int rows_per = 0, pitch = 0;
+  if (w24_input_small(N, C, H, W, TH, &rows_per, &pitch)) {
     const size_t lds = (size_t)64 * pitch * sizeof(float);
-    if (lds <= 64 * 1024) {
-      if (lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&w24_input_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(w24_input_small_kernel, dim3(C / 64, N, sg_cdiv(TH, rows_per)), dim3(256), lds, s, x, V, N, C, H, W, TH, TW, off,
-                         Pstride, rows_per, pitch);
-      return;
-    }
+    if (lds > 48 * 1024)
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&w24_input_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(w24_input_small_kernel, dim3(C / 64, N, sg_cdiv(TH, rows_per)), dim3(256), lds, s, x, V, N, C, H, W, TH, TW, off,
+                       Pstride, rows_per, pitch);
+    return;
   }
   hipLaunchKernelGGL(w24_input_kernel<0>, dim3(sg_cdiv(Pstride * C, 256)), dim3(256), 0, s, x, V, N, C, H, W, TH, TW, off, Pstride, 0, 1);
 }
@@ -1921,6 +1946,8 @@ static bool wino_adjoint_shape(const sgConvDesc* d) {
   return sg_opt(SG_OPT_WINO_ADJOINT) && wino_ok(d) && d->pad_reflect && d->upsample == 1 && d->H * d->W <= 256 && (d->H * d->W) % 4 == 0 &&
          d->C1 % 64 == 0 && d->Cout % 64 == 0;
 }
+// the F(2x2,3x3) data gradient runs the adjoint form only on aligned gy / gx (float4 staging): else the generic padded-grid form
+static bool wino_dgrad_adjoint(const sgConvDesc* d, bool gy16, bool gx16) { return wino_adjoint_shape(d) && gy16 && gx16; }
 // F(4x4,3x3) instead of F(2x2,3x3): the adjoint-form shapes whose planes split into 4x4 output tiles and whose tile count fills
 // whole 64-column GEMM tiles
 static bool wino43_shape(const sgConvDesc* d) {
@@ -1986,7 +2013,7 @@ extern "C" int sg_conv2d_wino_dgrad(const sgConvDesc* d, const float* gy, const 
     SG_LAUNCH_CHECK("sg_conv2d_wino_dgrad");
     return 0;
   }
-  if (wino_adjoint_shape(d) && aligned16(gy) && aligned16(gx)) {
+  if (wino_dgrad_adjoint(d, aligned16(gy), aligned16(gx))) {
     // adjoint Winograd over the output tiles (see wino_gy_small_kernel / wino_patch_fold_kernel)
     const int HW = d->H * d->W;
     const size_t P = (size_t)d->N * (d->H / 2) * (d->W / 2);
@@ -2151,6 +2178,9 @@ extern "C" int sg_conv2d_wino_in_supported(const sgConvDesc* d) {
   return (NT <= 16 && sg_opt(SG_OPT_WINO_REUSE)) ? 1 : 0;      // <= 4 tiles per thread: planes up to 16x16
 }
 
+// tiles per thread of w43_output_in_kernel
+static int w43_norm_tiles(const sgConvDesc* d) { return (d->H / 4) * (d->W / 4) <= 4 ? 1 : 4; }
+
 extern "C" int sg_conv2d_wino_fwd_instnorm(const sgConvDesc* d, const float* x, const float* w, const float* bias, const float* skip,
                                            float* ypre, float* out, float* mean, float* rstd, float eps, int act, float slope,
                                            float* ut_save, float* v_save, void* ws, size_t ws_bytes, sgStream stream) {
@@ -2177,7 +2207,7 @@ extern "C" int sg_conv2d_wino_fwd_instnorm(const sgConvDesc* d, const float* x, 
   wino_bgemm_tile(w43_tile(), V, U, Mx, (int)P, M, C, 2.0 * 36.0 * M * (double)P * C, s, 36, SG_K_WINO43_GEMM);
   { SgProfScope xf(SG_K_INSTNORM, s, 0, 4.0 * (36.0 * (double)P * M + (double)d->N * M * HW * (skip ? 3.0 : 2.0)));
     const size_t lds = (size_t)(128 * (HW + 1) + 256) * sizeof(float);
-    if (NT <= 4) {
+    if (w43_norm_tiles(d) == 1) {
       w43_lds_attr(&w43_output_in_kernel<1>, lds);
       hipLaunchKernelGGL(w43_output_in_kernel<1>, dim3(M / 64, d->N), dim3(256), lds, s, (const float*)Mx, bias, skip, ypre, out, mean,
                          rstd, d->N, M, d->H, d->W, eps, act, slope);
@@ -2307,6 +2337,135 @@ extern "C" int sg_conv2d_wino24_wgrad(const sgConvDesc* d, const float* gy, cons
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (25.0 * p.S + 16.0) * (double)M * C);
     hipLaunchKernelGGL(w24_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T, gw, M, C, p.S); }
   SG_LAUNCH_CHECK("sg_conv2d_wino24_wgrad");
+  return 0;
+}
+
+// ---- host-only: the plan of a Winograd entry point (see the header), from the predicates the launchers above call -------------
+namespace {
+void wino_plan_gemm(sgWinoPlan* p, int bm, int bn, int nsub, int kfold, int pipe) {
+  p->bm = bm; p->bn = bn; p->nsub = nsub; p->kfold = kfold; p->pipe = pipe;
+}
+// wino_bgemm(A, B, C, M, cols, K, .., NB)
+void wino_plan_bgemm(sgWinoPlan* p, int NB, int M, int cols, int K) {
+  const int t = wino_bgemm_sel(NB, M, cols, K);
+  if (t == 1) wino_plan_gemm(p, 64, 128, 2, 0, 0);
+  else if (t == 2) wino_plan_gemm(p, 64, 64, 2, 0, 0);
+  else wino_plan_gemm(p, 128, 128, 2, 0, sg_opt(SG_OPT_WINO_PIPE) == 2 ? 2 : 1);
+}
+// launch_w43 over a reduction of K
+void wino_plan_w43(sgWinoPlan* p, int K) { wino_plan_gemm(p, 64, 64, w43_deep() ? 2 : 1, w43_kfold(K), 0); }
+}  // namespace
+
+extern "C" int sg_conv2d_wino_plan(const sgConvDesc* d, int entry, int align_mask, int saved_mask, sgWinoPlan* plan) {
+  SG_ARG_CHECK(d && plan && entry >= SG_WINO_FWD && entry <= SG_WINO24_WGRAD, "sg_conv2d_wino_plan: bad arguments");
+  SG_ARG_CHECK((align_mask & ~SG_WA_ALL) == 0 && (saved_mask & ~(SG_WS_UT | SG_WS_V | SG_WS_YTP)) == 0, "sg_conv2d_wino_plan: bad mask");
+  const bool x16 = align_mask & SG_WA_X, w16 = align_mask & SG_WA_W, y16 = align_mask & SG_WA_Y, gy16 = align_mask & SG_WA_GY,
+             gx16 = align_mask & SG_WA_GX, gw16 = align_mask & SG_WA_GW;
+  const bool ut = saved_mask & SG_WS_UT, v = saved_mask & SG_WS_V, ytp = saved_mask & SG_WS_YTP;
+  sgWinoPlan p = {};
+  if (entry >= SG_WINO24_FWD) {
+    W24Plan w;
+    SG_ARG_CHECK(w24_plan(d, &w), "sg_conv2d_wino_plan: unsupported desc");
+    SG_ARG_CHECK(saved_mask == 0, "sg_conv2d_wino_plan: F(2x2,4x4) takes no saved operands");
+    p.form = SG_WF_F24;
+    p.P = (int)w.P; p.Ps = (int)w.Ps; p.Pd = (int)w.Pd; p.Pds = (int)w.Pds;
+    p.TH = w.TH; p.TW = w.TW; p.THd = w.THd; p.TWd = w.TWd; p.S = w.S; p.Pc = w.Pc;
+    if (entry == SG_WINO24_FWD) {
+      p.in_kernel = w24_input_small(d->N, d->C1, d->H, d->W, w.TH, nullptr, nullptr) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+      p.wt_kernel = SG_WK_WT_PLAIN;
+      wino_plan_bgemm(&p, 25, d->Cout, (int)w.Ps, d->C1);
+    } else if (entry == SG_WINO24_DGRAD) {
+      p.in_kernel = w24_input_small(d->N, d->Cout, d->OH, d->OW, w.THd, nullptr, nullptr) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+      p.wt_kernel = SG_WK_WT_PLAIN;
+      wino_plan_bgemm(&p, 25, d->C1, (int)w.Pds, d->Cout);
+    } else {
+      SG_ARG_CHECK(gw16, "sg_conv2d_wino_plan: gw must be 16-byte aligned");
+      p.in_kernel = SG_WK_IN_GENERAL;
+      p.wgrad_src = SG_WSRC_REBUILT;
+      wino_plan_bgemm(&p, 25 * w.S, d->Cout, d->C1, w.Pc);
+    }
+    *plan = p;
+    return 0;
+  }
+  SG_ARG_CHECK(wino_ok(d), "sg_conv2d_wino_plan: unsupported desc");
+  const bool fused = entry == SG_WINO_FWD_INSTNORM || entry == SG_WINO_DGRAD_INSTNORM;
+  SG_ARG_CHECK(!fused || sg_conv2d_wino_in_supported(d), "sg_conv2d_wino_plan: unsupported desc");
+  const int LH = d->H * d->upsample, LW = d->W * d->upsample, refl = d->pad_reflect;
+  const bool f43 = wino43_shape(d);
+  if (f43) {
+    p.form = SG_WF_F43;
+    p.P = p.Ps = p.Pd = p.Pds = d->N * (d->H / 4) * (d->W / 4);
+    if (entry == SG_WINO_FWD || entry == SG_WINO_FWD_INSTNORM) {
+      SG_ARG_CHECK(x16 && w16 && y16, "sg_conv2d_wino_plan: F(4x4,3x3) shapes need 16-byte aligned x / y / w");
+      SG_ARG_CHECK(!ytp, "sg_conv2d_wino_plan: the forward takes no ytp_save");
+      p.in_kernel = SG_WK_IN_LDS; p.wt_kernel = SG_WK_WT_LDS;
+      wino_plan_w43(&p, d->C1);
+      if (fused) p.norm_tiles = w43_norm_tiles(d);
+    } else if (entry == SG_WINO_DGRAD || entry == SG_WINO_DGRAD_INSTNORM) {
+      SG_ARG_CHECK(gy16 && gx16 && w16, "sg_conv2d_wino_plan: F(4x4,3x3) shapes need 16-byte aligned gy / gx / w");
+      SG_ARG_CHECK(!v, "sg_conv2d_wino_plan: the data gradient takes no v_save");
+      p.in_kernel = SG_WK_IN_LDS; p.wt_kernel = ut ? SG_WK_NONE : SG_WK_WT_LDS; p.fold_kernel = SG_WK_FOLD_F43;
+      wino_plan_w43(&p, d->Cout);
+    } else {
+      SG_ARG_CHECK(x16 && gy16, "sg_conv2d_wino_plan: F(4x4,3x3) shapes need 16-byte aligned x / gy");
+      SG_ARG_CHECK(!ut, "sg_conv2d_wino_plan: the weight gradient takes no ut_save");
+      const bool saved = v && ytp;
+      p.wgrad_src = saved ? SG_WSRC_SAVED : SG_WSRC_REBUILT;
+      p.in_kernel = saved ? SG_WK_NONE : SG_WK_IN_LDS;
+      const int t = w43_wgrad_sel(d->Cout, d->C1, p.P);
+      if (t == 1) wino_plan_gemm(&p, 128, 128, 2, 0, 0);
+      else if (t == 2) wino_plan_gemm(&p, 64, 128, 2, 0, 0);
+      else wino_plan_gemm(&p, 64, 64, w43_deep() ? 2 : 1, 0, 0);
+    }
+    *plan = p;
+    return 0;
+  }
+  p.P = p.Ps = d->N * (LH / 2) * (LW / 2);
+  p.Pd = d->N * (LH / 2 + (refl ? 1 : 0)) * (LW / 2 + (refl ? 1 : 0));
+  p.Pds = (int)wino_dgrad_tiles(d);
+  if (entry == SG_WINO_FWD) {
+    SG_ARG_CHECK(!ytp, "sg_conv2d_wino_plan: the forward takes no ytp_save");
+    SG_ARG_CHECK(!v || sg_conv2d_wino_v_floats(d) > 0, "sg_conv2d_wino_plan: v_save given but unused by this desc");
+    SG_ARG_CHECK(!ut || sg_conv2d_wino_ut_floats(d) > 0, "sg_conv2d_wino_plan: ut_save given but unused by this desc");
+    const bool lds = wino_weight_lds(d->Cout, d->C1, w16);
+    SG_ARG_CHECK(!ut || lds, "sg_conv2d_wino_plan: the transposed filter transform needs the LDS weight kernel");
+    p.form = SG_WF_F23_GENERIC;
+    p.wt_kernel = lds ? SG_WK_WT_LDS : SG_WK_WT_PLAIN;
+    p.in_kernel = wino_input_small(d->C1, LH, LW, d->upsample == 2 ? 1 : 0, x16) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+    wino_plan_bgemm(&p, 16, d->Cout, p.P, d->C1);
+  } else if (entry == SG_WINO_DGRAD) {
+    SG_ARG_CHECK(!v, "sg_conv2d_wino_plan: the data gradient takes no v_save");
+    const int M = d->C1, K = d->Cout;
+    if (wino_dgrad_adjoint(d, gy16, gx16)) {
+      p.form = SG_WF_F23_ADJOINT;
+      p.Pd = p.Pds = p.P;                 // over the output tiles
+      p.in_kernel = SG_WK_IN_LDS;
+      p.wt_kernel = ut ? SG_WK_NONE : (wino_weight_lds(M, K, w16) ? SG_WK_WT_LDS : SG_WK_WT_PLAIN);
+      p.fold_kernel = sg_opt(SG_OPT_WINO_FOLD_CELLS) ? SG_WK_FOLD_CELLS : SG_WK_FOLD_WALK;
+      wino_plan_bgemm(&p, 16, p.P, M, K);
+    } else {
+      SG_ARG_CHECK(!ytp, "sg_conv2d_wino_plan: ytp_save given but this desc does not run the adjoint form");
+      p.form = SG_WF_F23_GENERIC;
+      p.wt_kernel = wino_weight_lds(M, K, w16) ? SG_WK_WT_LDS : SG_WK_WT_PLAIN;       // (a ut_saved is not read by this form)
+      p.in_kernel = wino_input_small(K, LH, LW, 0, gy16) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+      p.fold_kernel = (!refl && d->upsample == 1) ? SG_WK_NONE : SG_WK_FOLD_PAD_UPSAMPLE;
+      wino_plan_bgemm(&p, 16, M, p.Pds, K);
+    }
+  } else {
+    SG_ARG_CHECK(entry == SG_WINO_WGRAD, "sg_conv2d_wino_plan: unsupported desc");
+    SG_ARG_CHECK(!ut, "sg_conv2d_wino_plan: the weight gradient takes no ut_save");
+    p.form = SG_WF_F23_GENERIC;
+    if (v && ytp) {
+      SG_ARG_CHECK(sg_conv2d_wino_v_floats(d) > 0 && p.P % 32 == 0, "sg_conv2d_wino_plan: saved operands given but unused by this desc");
+      p.wgrad_src = SG_WSRC_SAVED;
+      wino_plan_gemm(&p, 128, 128, 2, 0, 0);         // wino_bgemm_x
+    } else {
+      p.wgrad_src = SG_WSRC_REBUILT;
+      p.in_kernel = SG_WK_IN_GENERAL;
+      wino_plan_bgemm(&p, 16, d->Cout, d->C1, p.P);
+    }
+  }
+  *plan = p;
   return 0;
 }
 

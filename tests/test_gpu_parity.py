@@ -148,8 +148,8 @@ CONV_CASES = [
     (8, 128, 0, 8, 8, 128, 3, 1, 1, True, 1, 0),       # Winograd F(2x2,3x3) path (channels, tiles multiples of 128)
     (2, 256, 0, 16, 16, 128, 3, 1, 1, True, 1, 1),     # Winograd, Cin != Cout, fused ReLU
     (2, 128, 0, 16, 16, 256, 3, 1, 1, False, 1, 1),    # Winograd, ZERO padding (VGG19 convs), fused ReLU
-    (8, 128, 0, 8, 12, 128, 3, 1, 1, False, 1, 0),     # Winograd, zero padding, non-square plane (tiles 8*4*6 = 192: 64-tiles)
-    (3, 192, 0, 8, 8, 192, 3, 1, 1, False, 2, 0),      # Winograd behind the folded x2 upsample, 192 channels (mask_net), 64-tiles
+    (8, 128, 0, 8, 12, 128, 3, 1, 1, False, 1, 0),     # zero padding, non-square plane; 8*4*6 = 192 tiles is no multiple of 128: the direct kernel (wino_tile() = 0)
+    (3, 192, 0, 8, 8, 192, 3, 1, 1, False, 2, 0),      # folded x2 upsample, 192 channels (mask_net): no multiple of 128, the direct / sub-pixel kernels
     (4, 64, 0, 16, 16, 64, 3, 1, 1, False, 1, 1),      # 64 channels: stays on the direct kernel (VGG conv1_2)
     (2, 3, 0, 32, 32, 64, 3, 1, 1, False, 1, 1),       # VGG conv1_1
     (2, 16, 0, 15, 17, 8, 3, 2, 1, False, 1, 0),       # stride-2 dgrad: four parity classes of different sizes in one launch
