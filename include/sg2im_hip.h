@@ -603,6 +603,51 @@ int sg_sgd_momentum_step(float* p, const float* g, float* buf, int64_t n, float 
  * equals its target (scripts/sample_images.py:233-239 with ignore_label = 0); ignore_label = -1 counts every row. */
 int sg_classify_stats(const float* logits, const int64_t* target, int rows, int classes, int64_t ignore_label, int64_t* preds,
                       int64_t* acc, sgStream stream);
+/* ---- the Inception score (inception.hip; scene_generation_amd/inception.py) ----------------------------------------------------------
+ * What torchvision's Inception-v3 and scripts/inception_score.py need beyond the entry points above.  Forward only, fp32 (the score
+ * in fp64).  No wrapper synchronises; no float atomics: every result is bit-identical from run to run.  Base pointers may be
+ * unaligned (the convolution takes 16-byte loads of the weights only when they allow it).
+ *
+ * sg_conv2d_rect_fwd: y[n, out_c0 + co, oh, ow] = act(sum_{c, kh, kw} x[n, c, oh * stride - padH + kh, ow * stride - padW + kw] *
+ * w[co, c, kh, kw] + bias[co]) with x [N, C, H, W], w [Cout, C, KH, KW], bias [Cout] or NULL, y [N, out_ctot, OH, OW]: the channels
+ * outside [out_c0, out_c0 + Cout) are not touched (the branches of an Inception block write their slices of one tensor).  Zero
+ * padding, 0 <= pad < kernel extent; stride 1 or 2; KH * KW <= 25; OH = (H + 2 padH - KH) / stride + 1, OW likewise; act is
+ * SG_ACT_NONE or SG_ACT_RELU.  An implicit GEMM on the fp32 matrix cores over K = C * KH * KW.  ws >= sg_conv2d_rect_ws_bytes(d)
+ * (0 unless the plan splits K; the slabs of a split are added in ascending k order).
+ * sg_conv2d_rect_plan (host only): the launch plan of a desc -- tile (SG_RECT_TILE_*) of bm output channels x bn pixels, vec (16-byte
+ * weight loads: K % 4 == 0 and w_aligned16), splits k-chunks of kchunk elements each (1: no split, kchunk = K). */
+typedef struct sgRectDesc {
+  int32_t N, C, H, W, Cout, KH, KW, stride, padH, padW, OH, OW;
+  int32_t out_c0, out_ctot;
+} sgRectDesc;
+enum { SG_RECT_TILE_64X64 = 1, SG_RECT_TILE_32X128 = 2, SG_RECT_TILE_64X128 = 3 };
+typedef struct sgRectPlan {
+  int32_t tile, bm, bn, vec, splits, kchunk;
+} sgRectPlan;
+int sg_conv2d_rect_plan(const sgRectDesc* d, int w_aligned16, sgRectPlan* plan);
+size_t sg_conv2d_rect_ws_bytes(const sgRectDesc* d);
+int sg_conv2d_rect_fwd(const sgRectDesc* d, const float* x, const float* w, const float* bias, float* y, int act, void* ws,
+                       size_t ws_bytes, sgStream stream);
+/* max_pool2d(3, stride=2) WITHOUT padding (sg_maxpool3s2_* pads by 1): x [N, C, H, W] -> y[n, out_c0 + c, oh, ow] of
+ * y [N, out_ctot, OH, OW], OH = (H - 3) / 2 + 1, OW likewise; H, W >= 3.  A NaN in a window wins, as in torch. */
+int sg_maxpool3s2v_fwd(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, int out_c0, int out_ctot,
+                       sgStream stream);
+/* avg_pool2d(3, stride=1, padding=1) with count_include_pad=True (sg_avgpool3s2_* excludes the padding) on [NC, H, W]: the taps
+ * inside the plane are added in (kh, kw) order -- rows, then columns -- starting from 0, and the sum is divided by 9 everywhere. */
+int sg_avgpool3s1_fwd(const float* x, float* y, int NC, int H, int W, sgStream stream);
+/* F.interpolate(mode='bilinear', align_corners=False) of [NC, H, W] to [NC, OH, OW]: src = (dst + 0.5) * in / out - 0.5, clamped
+ * below at 0; taps floor(src) and floor(src) + 1, the upper one clamped to the last row / column. */
+int sg_resize_bilinear_fwd(const float* x, float* y, int NC, int H, int W, int OH, int OW, sgStream stream);
+/* softmax over the classes of logits [rows, classes] (the row maximum subtracted), written to rows [row0, row0 + rows) of
+ * out [capacity, classes]; the other rows are not touched. */
+int sg_softmax_rows(const float* logits, int rows, int classes, float* out, int row0, int capacity, sgStream stream);
+/* scripts/inception_score.py:48-62 on probs [n, classes] fp32: out (fp64 [2 + splits], 8-byte aligned) = {mean, std, score_0, ...}.
+ * Part k = rows [k * (n / splits), (k + 1) * (n / splits)) (the tail rows are dropped); py = the part's column mean; per row
+ * KL = sum_j ph log(ph / qh) with ph = p / sum(p), qh = py / sum(py) (scipy.stats.entropy normalises both; a term with p = 0 is
+ * 0); score_k = exp(mean KL); mean and POPULATION std over the splits.  Every sum in fp64 in a fixed order.  n / splits == 0
+ * gives NaN for both.  ws >= sg_inception_score_ws_bytes(n, classes, splits), 8-byte aligned. */
+size_t sg_inception_score_ws_bytes(int n, int classes, int splits);
+int sg_inception_score(const float* probs, int n, int classes, int splits, void* out, void* ws, size_t ws_bytes, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

@@ -116,6 +116,10 @@ enum {
   // the object-accuracy classifier (classifier.hip): padded max-pool (both directions), relu(a + b), BatchNorm fold, SGD step,
   // argmax + accuracy record
   SG_K_MAXPOOL3S2, SG_K_ADD_RELU, SG_K_BN_FOLD, SG_K_SGD, SG_K_CLASSIFY_STATS,
+  // the Inception score (inception.hip): the rectangular convolutions per tile (64x64, 32x128, 64x128), their split-K reduction, the
+  // unpadded max-pool / count_include_pad average pool, the bilinear resize, the softmax rows and the score itself
+  SG_K_RECT_CONV_T64, SG_K_RECT_CONV_T32, SG_K_RECT_CONV_T64W, SG_K_RECT_REDUCE, SG_K_INCEPTION_POOL, SG_K_RESIZE_BILINEAR,
+  SG_K_SOFTMAX_ROWS, SG_K_INCEPTION_SCORE,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

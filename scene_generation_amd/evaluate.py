@@ -2,9 +2,9 @@
 (``check_model``: test-mode forward + box IoU), the IoU itself (scene_generation/metrics.py:19-35) and the appearance feature
 bank of /root/reference/scripts/encode_features.py:103-146 (``repr_net(image_encoder(crops))`` grouped by class, then
 k-means centres ordered along a 1-D t-SNE).  The network work runs on the HIP modules (test-mode compositing, crop, encoder,
-MLP); the box arithmetic is a few element-wise lines on O x 4 numbers.  The Inception score stays out of scope (needs the
-pretrained Inception network): ``check_model`` drives any object with the reference's ``clean() / __call__ / compute_score``
-interface, or none."""
+MLP); the box arithmetic is a few element-wise lines on O x 4 numbers.  ``check_model`` drives any object with the reference's
+``clean() / __call__ / compute_score`` interface, or none: ``scene_generation_amd.inception.InceptionScore`` is that object on this
+stack (native Inception-v3, softmax rows kept on the device, one host read in ``compute_score``)."""
 import numpy as np
 import torch
 

@@ -1,0 +1,485 @@
+"""The Inception score: the reference's last evaluation figure (scripts/inception_score.py, train.py:177-225) on this stack.
+
+    python -m scene_generation_amd.inception --dir DIR --weights PATH [--splits 5] [--batch_size 32]     -> mean and std
+
+* ``InceptionV3``: torchvision's Inception-v3 (``inception_v3(transform_input=False)``) with its ``state_dict`` keys and shapes, so
+  the published ``inception_v3_google-*.pth`` loads with ``strict=True``.  Inference only: every conv + BatchNorm + ReLU is ONE
+  sg_conv2d_rect_fwd launch (the BatchNorm folded into weights and bias by sg_bn_fold, cached), and every branch of a block writes
+  straight into its channel slice of the block's output -- no concatenation, no BatchNorm pass.  The auxiliary head exists so the
+  file loads and never runs.
+* ``InceptionScore``: the reference's object -- ``clean()``, ``__call__(imgs)``, ``compute_score(splits) -> (mean, std)`` -- that
+  ``evaluate.check_model`` and ``Trainer`` drive.  Softmax rows accumulate in a device buffer that grows by doubling; ``__call__``
+  never synchronises, ``compute_score`` does the one host read.
+* Nothing is ever downloaded: ``weights`` is a local ``state_dict`` file; without it the network keeps a seeded random
+  initialisation and says loudly that the score is then meaningless.
+"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+from . import layers, ops
+from .accuracy import _folded, _strip_module_prefix
+
+__all__ = ['InceptionV3', 'InceptionScore', 'load_inception', 'conv_units', 'main', 'DEFAULT_WEIGHTS']
+
+# the state_dict file ``InceptionScore(weights=None)`` loads: for callers whose constructor call cannot be changed (the reference's
+# train.py:177); None: random weights and a warning
+DEFAULT_WEIGHTS = None
+
+
+class BasicConv2d(nn.Module):
+    """conv (no bias) + BatchNorm(eps=0.001) + ReLU; holds the parameters under torchvision's names, runs as one folded launch"""
+
+    def __init__(self, cin, cout, kernel_size, stride=1, padding=0):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, kernel_size, stride=stride, padding=padding, bias=False)
+        self.bn = nn.BatchNorm2d(cout, eps=0.001)
+        self.name = ''
+
+    def forward(self, x):
+        raise NotImplementedError('a BasicConv2d runs through InceptionV3.forward (one folded launch per unit)')
+
+
+# ---- two executors of the same network walk: the kernels, and a shape trace (the list of conv units with their geometry) ----------
+class _Kernels(object):
+    def __init__(self, fold):
+        self.fold = fold
+
+    @staticmethod
+    def shape(x):
+        return tuple(x.shape)
+
+    @staticmethod
+    def alloc(x, C, H, W):
+        return torch.empty(x.size(0), C, H, W, dtype=torch.float32, device=x.device)
+
+    def conv(self, unit, x, out=None, c0=0):
+        w, b = _folded(unit.conv, unit.bn, self.fold)
+        return ops.conv2d_rect(x, w, b, stride=unit.conv.stride[0], pad=unit.conv.padding, act=ops.ACT_RELU, out=out, out_c0=c0)
+
+    @staticmethod
+    def maxpool(x, out=None, c0=0):
+        return ops.maxpool3s2v(x, out, c0)
+
+    @staticmethod
+    def avgpool(x):
+        return ops.avgpool3s1(x)
+
+
+class _Trace(object):
+    """tensors are (N, C, H, W) tuples; ``units`` collects one record per conv unit in launch order"""
+
+    def __init__(self):
+        self.units = []
+
+    @staticmethod
+    def shape(x):
+        return x
+
+    @staticmethod
+    def alloc(x, C, H, W):
+        return (x[0], C, H, W)
+
+    def conv(self, unit, x, out=None, c0=0):
+        N, C, H, W = x
+        c = unit.conv
+        (kh, kw), (ph, pw), s = c.kernel_size, c.padding, c.stride[0]
+        assert C == c.in_channels, (unit.name, C, c.in_channels)
+        oh, ow = ops.conv_out_size(H, kh, s, ph), ops.conv_out_size(W, kw, s, pw)
+        ctot = c.out_channels if out is None else out[1]
+        assert out is None or (out[2], out[3]) == (oh, ow), (unit.name, out, oh, ow)
+        self.units.append(dict(name=unit.name, N=N, C=C, H=H, W=W, Cout=c.out_channels, KH=kh, KW=kw, stride=s, padH=ph, padW=pw,
+                               OH=oh, OW=ow, out_c0=c0, out_ctot=ctot))
+        return (N, c.out_channels, oh, ow) if out is None else out
+
+    @staticmethod
+    def maxpool(x, out=None, c0=0):
+        N, C, H, W = x
+        return (N, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1) if out is None else out
+
+    @staticmethod
+    def avgpool(x):
+        return x
+
+
+class InceptionA(nn.Module):
+    def __init__(self, cin, pool_features):
+        super().__init__()
+        self.branch1x1 = BasicConv2d(cin, 64, 1)
+        self.branch5x5_1 = BasicConv2d(cin, 48, 1)
+        self.branch5x5_2 = BasicConv2d(48, 64, 5, padding=2)
+        self.branch3x3dbl_1 = BasicConv2d(cin, 64, 1)
+        self.branch3x3dbl_2 = BasicConv2d(64, 96, 3, padding=1)
+        self.branch3x3dbl_3 = BasicConv2d(96, 96, 3, padding=1)
+        self.branch_pool = BasicConv2d(cin, pool_features, 1)
+        self.cout = 64 + 64 + 96 + pool_features
+
+    def run(self, E, x):
+        _, _, H, W = E.shape(x)
+        out = E.alloc(x, self.cout, H, W)
+        E.conv(self.branch1x1, x, out, 0)
+        E.conv(self.branch5x5_2, E.conv(self.branch5x5_1, x), out, 64)
+        E.conv(self.branch3x3dbl_3, E.conv(self.branch3x3dbl_2, E.conv(self.branch3x3dbl_1, x)), out, 128)
+        E.conv(self.branch_pool, E.avgpool(x), out, 224)
+        return out
+
+
+class InceptionB(nn.Module):
+    def __init__(self, cin):
+        super().__init__()
+        self.branch3x3 = BasicConv2d(cin, 384, 3, stride=2)
+        self.branch3x3dbl_1 = BasicConv2d(cin, 64, 1)
+        self.branch3x3dbl_2 = BasicConv2d(64, 96, 3, padding=1)
+        self.branch3x3dbl_3 = BasicConv2d(96, 96, 3, stride=2)
+        self.cout = 384 + 96 + cin
+
+    def run(self, E, x):
+        _, _, H, W = E.shape(x)
+        out = E.alloc(x, self.cout, (H - 3) // 2 + 1, (W - 3) // 2 + 1)
+        E.conv(self.branch3x3, x, out, 0)
+        E.conv(self.branch3x3dbl_3, E.conv(self.branch3x3dbl_2, E.conv(self.branch3x3dbl_1, x)), out, 384)
+        E.maxpool(x, out, 480)
+        return out
+
+
+class InceptionC(nn.Module):
+    def __init__(self, cin, channels_7x7):
+        super().__init__()
+        c7 = channels_7x7
+        self.branch1x1 = BasicConv2d(cin, 192, 1)
+        self.branch7x7_1 = BasicConv2d(cin, c7, 1)
+        self.branch7x7_2 = BasicConv2d(c7, c7, (1, 7), padding=(0, 3))
+        self.branch7x7_3 = BasicConv2d(c7, 192, (7, 1), padding=(3, 0))
+        self.branch7x7dbl_1 = BasicConv2d(cin, c7, 1)
+        self.branch7x7dbl_2 = BasicConv2d(c7, c7, (7, 1), padding=(3, 0))
+        self.branch7x7dbl_3 = BasicConv2d(c7, c7, (1, 7), padding=(0, 3))
+        self.branch7x7dbl_4 = BasicConv2d(c7, c7, (7, 1), padding=(3, 0))
+        self.branch7x7dbl_5 = BasicConv2d(c7, 192, (1, 7), padding=(0, 3))
+        self.branch_pool = BasicConv2d(cin, 192, 1)
+        self.cout = 768
+
+    def run(self, E, x):
+        _, _, H, W = E.shape(x)
+        out = E.alloc(x, self.cout, H, W)
+        E.conv(self.branch1x1, x, out, 0)
+        E.conv(self.branch7x7_3, E.conv(self.branch7x7_2, E.conv(self.branch7x7_1, x)), out, 192)
+        t = E.conv(self.branch7x7dbl_3, E.conv(self.branch7x7dbl_2, E.conv(self.branch7x7dbl_1, x)))
+        E.conv(self.branch7x7dbl_5, E.conv(self.branch7x7dbl_4, t), out, 384)
+        E.conv(self.branch_pool, E.avgpool(x), out, 576)
+        return out
+
+
+class InceptionD(nn.Module):
+    def __init__(self, cin):
+        super().__init__()
+        self.branch3x3_1 = BasicConv2d(cin, 192, 1)
+        self.branch3x3_2 = BasicConv2d(192, 320, 3, stride=2)
+        self.branch7x7x3_1 = BasicConv2d(cin, 192, 1)
+        self.branch7x7x3_2 = BasicConv2d(192, 192, (1, 7), padding=(0, 3))
+        self.branch7x7x3_3 = BasicConv2d(192, 192, (7, 1), padding=(3, 0))
+        self.branch7x7x3_4 = BasicConv2d(192, 192, 3, stride=2)
+        self.cout = 320 + 192 + cin
+
+    def run(self, E, x):
+        _, _, H, W = E.shape(x)
+        out = E.alloc(x, self.cout, (H - 3) // 2 + 1, (W - 3) // 2 + 1)
+        E.conv(self.branch3x3_2, E.conv(self.branch3x3_1, x), out, 0)
+        t = E.conv(self.branch7x7x3_3, E.conv(self.branch7x7x3_2, E.conv(self.branch7x7x3_1, x)))
+        E.conv(self.branch7x7x3_4, t, out, 320)
+        E.maxpool(x, out, 512)
+        return out
+
+
+class InceptionE(nn.Module):
+    def __init__(self, cin):
+        super().__init__()
+        self.branch1x1 = BasicConv2d(cin, 320, 1)
+        self.branch3x3_1 = BasicConv2d(cin, 384, 1)
+        self.branch3x3_2a = BasicConv2d(384, 384, (1, 3), padding=(0, 1))
+        self.branch3x3_2b = BasicConv2d(384, 384, (3, 1), padding=(1, 0))
+        self.branch3x3dbl_1 = BasicConv2d(cin, 448, 1)
+        self.branch3x3dbl_2 = BasicConv2d(448, 384, 3, padding=1)
+        self.branch3x3dbl_3a = BasicConv2d(384, 384, (1, 3), padding=(0, 1))
+        self.branch3x3dbl_3b = BasicConv2d(384, 384, (3, 1), padding=(1, 0))
+        self.branch_pool = BasicConv2d(cin, 192, 1)
+        self.cout = 2048
+
+    def run(self, E, x):
+        _, _, H, W = E.shape(x)
+        out = E.alloc(x, self.cout, H, W)
+        E.conv(self.branch1x1, x, out, 0)
+        t = E.conv(self.branch3x3_1, x)
+        E.conv(self.branch3x3_2a, t, out, 320)
+        E.conv(self.branch3x3_2b, t, out, 704)
+        t = E.conv(self.branch3x3dbl_2, E.conv(self.branch3x3dbl_1, x))
+        E.conv(self.branch3x3dbl_3a, t, out, 1088)
+        E.conv(self.branch3x3dbl_3b, t, out, 1472)
+        E.conv(self.branch_pool, E.avgpool(x), out, 1856)
+        return out
+
+
+class InceptionAux(nn.Module):
+    """the auxiliary classifier of the training recipe: parameters only (the published file holds them); never run"""
+
+    def __init__(self, cin, num_classes):
+        super().__init__()
+        self.conv0 = BasicConv2d(cin, 128, 1)
+        self.conv1 = BasicConv2d(128, 768, 5)
+        self.fc = nn.Linear(768, num_classes)
+
+    def forward(self, x):
+        raise NotImplementedError('the auxiliary head of Inception-v3 is a training device; this network is inference only')
+
+
+_BLOCKS = ('Mixed_5b', 'Mixed_5c', 'Mixed_5d', 'Mixed_6a', 'Mixed_6b', 'Mixed_6c', 'Mixed_6d', 'Mixed_6e', 'Mixed_7a', 'Mixed_7b',
+           'Mixed_7c')
+
+
+class InceptionV3(nn.Module):
+    """torchvision.models.Inception3(num_classes, aux_logits, transform_input=False), inference only.
+
+    ``forward(x)`` -> logits [N, num_classes]; ``features(x)`` -> the pooled [N, 2048] vector (where an FID would start).  Both run
+    under ``no_grad`` on the running statistics; ``train(True)`` raises.  Inputs of any size from 75 x 75 up (299 is the
+    network's own).  The folded weights are cached; the cache is dropped by ``load_state_dict()``, ``.to()`` / ``.cuda()`` and
+    ``drop_fold()``, and an entry is rebuilt when one of its tensors was replaced or written through torch (version counters).
+
+    Random initialisation: He-normal convolutions (fan-in), BatchNorm at identity -- torchvision's truncated normal of fixed
+    std 0.1 is a starting point for TRAINING under batch statistics and overflows in eval mode."""
+
+    def __init__(self, num_classes=1000, aux_logits=True):
+        super().__init__()
+        self.Conv2d_1a_3x3 = BasicConv2d(3, 32, 3, stride=2)
+        self.Conv2d_2a_3x3 = BasicConv2d(32, 32, 3)
+        self.Conv2d_2b_3x3 = BasicConv2d(32, 64, 3, padding=1)
+        self.Conv2d_3b_1x1 = BasicConv2d(64, 80, 1)
+        self.Conv2d_4a_3x3 = BasicConv2d(80, 192, 3)
+        self.Mixed_5b = InceptionA(192, 32)
+        self.Mixed_5c = InceptionA(256, 64)
+        self.Mixed_5d = InceptionA(288, 64)
+        self.Mixed_6a = InceptionB(288)
+        self.Mixed_6b = InceptionC(768, 128)
+        self.Mixed_6c = InceptionC(768, 160)
+        self.Mixed_6d = InceptionC(768, 160)
+        self.Mixed_6e = InceptionC(768, 192)
+        if aux_logits:
+            self.AuxLogits = InceptionAux(768, num_classes)
+        self.Mixed_7a = InceptionD(768)
+        self.Mixed_7b = InceptionE(1280)
+        self.Mixed_7c = InceptionE(2048)
+        self.avgpool = layers.GlobalAvgPool()
+        self.fc = layers.Linear(2048, num_classes)
+        self._fold_cache = {}
+        for name, m in self.named_modules():
+            if isinstance(m, BasicConv2d):
+                m.name = name
+                nn.init.kaiming_normal_(m.conv.weight, mode='fan_in', nonlinearity='relu')
+        super().train(False)
+
+    # ---- inference only -----------------------------------------------------------------------------------------------------------
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError('InceptionV3 is inference only (folded BatchNorm, no backward, no auxiliary head): train(True) '
+                                      'is not available')
+        return super().train(False)
+
+    def drop_fold(self):
+        self._fold_cache.clear()
+
+    def load_state_dict(self, *args, **kwargs):
+        self.drop_fold()
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):          # .to() / .cuda(): the tensors move, the folded copies would not
+        self.drop_fold()
+        return super()._apply(fn, *args, **kwargs)
+
+    def _walk(self, E, x):
+        """the network up to the 8 x 8 x 2048 grid, on executor ``E``"""
+        x = E.conv(self.Conv2d_1a_3x3, x)
+        x = E.conv(self.Conv2d_2a_3x3, x)
+        x = E.conv(self.Conv2d_2b_3x3, x)
+        x = E.maxpool(x)
+        x = E.conv(self.Conv2d_3b_1x1, x)
+        x = E.conv(self.Conv2d_4a_3x3, x)
+        x = E.maxpool(x)
+        for name in _BLOCKS:
+            x = getattr(self, name).run(E, x)
+        return x
+
+    def features(self, x):
+        if x.dim() != 4 or x.size(1) != 3 or min(x.shape[2:]) < 75:
+            raise ValueError('InceptionV3: input [N, 3, H >= 75, W >= 75], got %s' % (tuple(x.shape),))
+        with torch.no_grad():
+            return self.avgpool(self._walk(_Kernels(self._fold_cache), x)).flatten(1)
+
+    def forward(self, x):
+        with torch.no_grad():
+            return self.fc(self.features(x))
+
+
+def conv_units(size=299, n=1, net=None):
+    """the conv units ``InceptionV3.forward`` launches on an n x 3 x size x size input, in launch order: one dict per unit with its
+    name and the fields of its sgRectDesc (94 units; the two of the auxiliary head never run)"""
+    net = net if net is not None else _skeleton()
+    tr = _Trace()
+    net._walk(tr, (n, 3, size, size))
+    return tr.units
+
+
+_SKELETON = []
+
+
+def _skeleton():
+    """a network built once on the meta device (shapes only, no storage) for ``conv_units``"""
+    if not _SKELETON:
+        with torch.device('meta'):
+            _SKELETON.append(InceptionV3())
+    return _SKELETON[0]
+
+
+def unit_plan(u, w_aligned16=True):
+    """the launch plan (ops.conv2d_rect_plan) of one ``conv_units`` record"""
+    d = ops.rect_desc(u['N'], u['C'], u['H'], u['W'], u['Cout'], u['KH'], u['KW'], u['stride'], u['padH'], u['padW'], u['out_c0'],
+                      u['out_ctot'])
+    return ops.conv2d_rect_plan(d, w_aligned16)
+
+
+def load_inception(path, device='cuda'):
+    """an ``InceptionV3`` with the ``state_dict`` file ``path`` loaded strictly (torchvision's ``inception_v3_google-*.pth``, or a
+    save of this class; a DataParallel ``module.`` prefix is stripped), on ``device``"""
+    sd = _strip_module_prefix(dict(torch.load(path, map_location='cpu')))
+    net = InceptionV3(num_classes=int(sd['fc.weight'].shape[0]), aux_logits=any(k.startswith('AuxLogits.') for k in sd))
+    net.load_state_dict(sd, strict=True)
+    return net.to(device)
+
+
+class InceptionScore(nn.Module):
+    """scripts/inception_score.py:15-62.  ``imgs`` are [N, 3, H, W] in [-1, 1]; ``resize=True`` resizes them to 299 x 299 on the
+    device (sg_resize_bilinear_fwd).  Each call adds softmax rows to a device buffer (doubled when full); nothing is read back
+    until ``compute_score``, which reads two numbers.
+
+    ``weights``: the path of a ``state_dict`` file (``load_inception``), an ``InceptionV3`` instance, or None.  None takes the
+    module attribute ``DEFAULT_WEIGHTS`` -- process-wide state: every scorer built afterwards without ``weights`` loads that file
+    (it exists for callers whose constructor call cannot be changed) -- and, when that is None too, builds a
+    random network under a fixed seed and warns."""
+
+    def __init__(self, cuda=True, batch_size=32, resize=False, weights=None, device=None):
+        super().__init__()
+        assert batch_size > 0
+        if device is None:
+            if not cuda:
+                raise RuntimeError('InceptionScore: the HIP path has no CPU fallback (cuda=False)')
+            device = 'cuda'
+        self.resize, self.batch_size, self.device = resize, batch_size, torch.device(device)
+        weights = weights if weights is not None else DEFAULT_WEIGHTS
+        if weights is not None:
+            self.inception_model = load_inception(weights, self.device) if isinstance(weights, str) else weights.to(self.device)
+        else:
+            print('WARNING: InceptionScore is built WITHOUT pretrained weights (weights=None): a seeded random initialisation. '
+                  'Its scores are MEANINGLESS as Inception scores; pass the path of inception_v3_google-*.pth.', file=sys.stderr)
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(0)
+                self.inception_model = InceptionV3().to(self.device)
+        self.inception_model.eval()
+        self.classes = self.inception_model.fc.out_features
+        self.probs, self.count = None, 0
+        self.clean()
+
+    def clean(self):
+        self.count = 0
+
+    def _reserve(self, rows):
+        need = self.count + rows
+        cap = 0 if self.probs is None else self.probs.size(0)
+        if need <= cap:
+            return
+        new_cap = max(cap, 4 * self.batch_size)
+        while new_cap < need:
+            new_cap *= 2
+        buf = torch.empty(new_cap, self.classes, dtype=torch.float32, device=self.device)
+        if self.count:
+            buf[:self.count].copy_(self.probs[:self.count])
+        self.probs = buf
+
+    def get_pred(self, x):
+        """logits of one chunk (resized first when ``resize``)"""
+        if self.resize and tuple(x.shape[2:]) != (299, 299):
+            x = ops.resize_bilinear(x, (299, 299))
+        return self.inception_model(x)
+
+    def forward(self, imgs):
+        imgs = imgs.detach().to(self.device, torch.float32)
+        for a in range(0, imgs.size(0), self.batch_size):
+            logits = self.get_pred(imgs[a:a + self.batch_size])
+            self._reserve(logits.size(0))
+            ops.softmax_rows(logits, self.probs, self.count)
+            self.count += logits.size(0)
+
+    def scores(self, splits=1):
+        """float64 device tensor {mean, std, per-split scores}; no host read"""
+        probs = self.probs if self.probs is not None else torch.empty(1, self.classes, dtype=torch.float32, device=self.device)
+        return ops.inception_score(probs, self.count, splits)
+
+    def compute_score(self, splits=1):
+        mean, std = self.scores(splits)[:2].tolist()              # the one host read
+        return mean, std
+
+
+# ---- command line ---------------------------------------------------------------------------------------------------------------------
+_EXT = ('.png', '.jpg', '.jpeg', '.bmp', '.ppm', '.webp')
+
+
+def find_images(root):
+    """every image file under ``root``, recursively, in sorted order"""
+    out = []
+    for d, _, files in sorted(os.walk(root)):
+        out += [os.path.join(d, f) for f in sorted(files) if f.lower().endswith(_EXT)]
+    return out
+
+
+def read_image(path):
+    """[3, H, W] float32 in [-1, 1]: ToTensor + Normalize(0.5, 0.5) of the reference's ``__main__``"""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.asarray(im.convert('RGB'), dtype=np.float32)
+    return (torch.from_numpy(a).permute(2, 0, 1) / 255.0 - 0.5) / 0.5
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog='python -m scene_generation_amd.inception',
+                                description='Inception score of the images under --dir (resized to 299 x 299 on the device)')
+    p.add_argument('--dir', required=True, type=str)
+    p.add_argument('--weights', default=None, type=str, help='state_dict file of torchvision\'s inception_v3 (never downloaded)')
+    p.add_argument('--splits', default=5, type=int)
+    p.add_argument('--batch_size', default=32, type=int)
+    p.add_argument('--device', default='cuda', type=str)
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    paths = find_images(args.dir)
+    if not paths:
+        raise SystemExit('no images under %s' % args.dir)
+    scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=args.weights, device=args.device)
+    print('Calculating Inception Score...')
+    group, shape = [], None
+    for path in paths + [None]:
+        img = read_image(path) if path is not None else None
+        if group and (img is None or tuple(img.shape) != shape or len(group) == args.batch_size):      # one chunk per image size
+            scorer(torch.stack(group))
+            group = []
+        if img is not None:
+            group.append(img)
+            shape = tuple(img.shape)
+    mean, std = scorer.compute_score(splits=args.splits)
+    print('Inception {} {}'.format(mean, std))
+    return mean, std
+
+
+if __name__ == '__main__':
+    main()

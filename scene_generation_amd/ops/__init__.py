@@ -4,7 +4,7 @@ PyTorch-ROCm is used here as plumbing only: device allocation (torch.empty), the
 Every forward / backward is one or a few hand-written gfx950 kernel launches through ctypes; there is no eager / CPU fallback --
 a CPU tensor raises.
 
-One namespace, nine modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
+One namespace, ten modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
   _core    ctypes call helpers, stream handle, workspace, parameter-gradient sinks (GradOut), path switches, layout hints,
            flat-buffer updates (Adam, fill, fold), profiler front end
   conv     Conv2d / ConvTranspose2d / sub-pixel up-conv / Linear (implicit GEMM, Winograd, head, skinny kernels)
@@ -16,6 +16,8 @@ One namespace, nine modules (the single 1 741-line ops.py of rounds 1-3, split b
   kmeans   segmented k-means of the appearance bank (assign / update / relocate / k-means++ round)
   scenegraph  scene graphs from layouts: mask centroids, attribute bits, geometric predicates, partner draw, agreement counters
   classifier  the accuracy network's own operators: padded 3x3 stride-2 max-pool, relu(a + b), BatchNorm fold, SGD step, accuracy record
+  inception   the Inception score's own operators: rectangular conv into a channel slice, unpadded max-pool, count_include_pad average
+              pool, bilinear resize, softmax rows, the score
 Everything is re-exported here, so ``ops.conv2d``, ``ops.GradOut``, ``ops._call`` ... keep working.  The path switches
 (``ops.WINOGRAD``, ``ops.FACTORED_LAYOUT``, ``ops.UPCONV``, ``ops.HEADCONV``, ``ops.WINOGRAD24``, ``ops.COND_FOLD``) are WRITABLE through this
 namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator modules read (``_core.WINOGRAD``).
@@ -23,9 +25,9 @@ namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator mod
 import sys
 import types
 
-from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier
+from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception
 
-_MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier)
+_MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception)
 _FLAGS = ('HEADCONV', 'WINOGRAD', 'WINOGRAD24', 'FACTORED_LAYOUT', 'UPCONV', 'COND_FOLD')
 
 for _m in _MODULES:

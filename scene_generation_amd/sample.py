@@ -15,6 +15,9 @@ scene_generation/data/utils.py it needs).
   (scene_generation_amd.scenegraph), accumulated on the device next to the IoU totals and read once by ``graph_summary``.
 * ``accuracy`` (an ``accuracy.AccuracyMeter``, off by default): the object classifier's verdict on the crops of the generated images
   (sample_images.py:224-239), accumulated on the device and read once; ``--accuracy_model_path`` on the command line.
+* ``inception`` (an ``inception.InceptionScore``, off by default): the Inception score of the generated images (train.py:177-225
+  applies it to validation batches; here to whatever is sampled), softmax rows accumulated on the device and read once by
+  ``inception_summary``; ``--inception_weights`` on the command line.
 * ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
   (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
 Not here: scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
@@ -78,9 +81,10 @@ class Sampler(object):
     factored test-mode layout (Model.factored_test_layout).  ON by default: measured on MI355X at N = 32 / 128 x 128, 6.82 against
     7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
 
-    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None):
+    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None):
         self.model, self.features, self.factored = model, features, bool(factored)
         self.accuracy = accuracy             # accuracy.AccuracyMeter fed by sample_batch, or None
+        self.inception = inception           # inception.InceptionScore fed by every forward, or None
         self.graph_metrics = bool(graph_metrics)
         self.graph_counts = None             # running agreement counters (scenegraph.new_counts), on the device
         self.device = next(model.parameters()).device
@@ -99,6 +103,8 @@ class Sampler(object):
                 imgs_pred, boxes_pred, masks_pred, _, layout, _ = fn()
                 if score is not None:                       # the accuracy network reads the network's output, before deprocessing
                     score(imgs_pred, boxes_pred)
+                if self.inception is not None:              # likewise the Inception network (no host synchronisation)
+                    self.inception(imgs_pred)
                 images = ops.deprocess_images(imgs_pred, rescale=True, uint8=True)
                 rgb = None
                 if want_layout_rgb:
@@ -179,6 +185,14 @@ class Sampler(object):
     def accuracy_summary(self):
         """the ONE device-to-host read of the accuracy record (AccuracyMeter.summary); None without a meter"""
         return self.accuracy.summary() if self.accuracy is not None else None
+
+    def inception_summary(self, splits=5):
+        """the ONE device-to-host read of the Inception score over everything sampled since the scorer's ``clean()``:
+        {'mean', 'std', 'images', 'splits'}; None without a scorer"""
+        if self.inception is None:
+            return None
+        mean, std = self.inception.compute_score(splits=splits)
+        return {'mean': mean, 'std': std, 'images': self.inception.count, 'splits': splits}
 
     def graph_summary(self):
         """the ONE device-to-host read of the graph metrics (scenegraph.summary); None when they are off or nothing was sampled"""
@@ -318,7 +332,13 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         from .accuracy import AccuracyMeter, load_model
         meter = AccuracyMeter(load_model(acc_path, getattr(args, 'accuracy_model_name', 'resnet101'), n_class=None, device=device),
                               input_shape=getattr(args, 'accuracy_input_shape', 224))
-    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter)
+    scorer = None
+    inc_path = getattr(args, 'inception_weights', None)
+    if inc_path is not None:
+        from .inception import InceptionScore
+        scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=inc_path, device=device)
+    sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter,
+                      inception=scorer)
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -369,6 +389,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if meter is not None and meter.acc is not None:
         result['accuracy'] = meter.summary()
         print('Accuracy {}'.format(result['accuracy']['accuracy']))
+    if scorer is not None:
+        result['inception'] = sampler.inception_summary(getattr(args, 'inception_splits', 5))
+        print('Inception {} {}'.format(result['inception']['mean'], result['inception']['std']))
     if metrics:
         graph = result['graph'] = sampler.graph_summary()
         if graph is not None:
@@ -407,6 +430,10 @@ def make_parser():
                    'train, or the reference\'s resnet101_172_classes.pth): prints the Accuracy line of sample_images.py')
     p.add_argument('--accuracy_model_name', default='resnet101', help='its architecture: resnet18 / 34 / 50 / 101 / 152')
     p.add_argument('--accuracy_input_shape', default=224, type=int, help='side of the crops the classifier sees')
+    p.add_argument('--inception_weights', default=None, help='state_dict file of torchvision\'s inception_v3 (never downloaded): '
+                   'prints one "Inception MEAN STD" line over the sampled images (python -m scene_generation_amd.inception scores a '
+                   'directory of images)')
+    p.add_argument('--inception_splits', default=5, type=int, help='splits of the Inception score (train.py uses 5)')
     return p
 
 
