@@ -198,8 +198,8 @@ int sg_conv2d_wino24_dgrad(const sgConvDesc* d, const float* gy, const float* w,
                            sgStream stream);
 int sg_conv2d_wino24_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, void* ws, size_t ws_bytes,
                            sgStream stream);
-/* host-only query of the launch plan of a Winograd entry point: which form and which kernels sg_conv2d_wino_* / sg_conv2d_wino24_*
- * run for this desc under the current options, from the same predicates the launchers use.  Never touches the device.
+/* host-only query of THE launch plan of a Winograd entry point (sg_conv2d_wino_* / sg_conv2d_wino24_* launch exactly this; the
+ * query reports it): which form, kernels and GEMM tiles run for this desc under the current options.  Never touches the device.
  *   entry       SG_WINO_*: the entry point
  *   align_mask  SG_WA_* bits of the operands whose address is 16-byte aligned: X (x), W (w), Y (y; ypre / out / skip of the fused
  *               forward), GY (gy; gout / ypre / gconv of the fused backward), GX (gx), GW (gw)

@@ -546,17 +546,19 @@ __global__ void __launch_bounds__(256) wino_weight_lds_kernel(const float* __res
   }
 }
 
-// one entry for the three call sites (SG_WINO_WT=0 keeps the per-thread kernel).  ``UT``: see wino_weight_lds_kernel; returns
-// whether it was written
-inline bool wino_weight_lds(int R, int Cc, bool w16) { return sg_opt(SG_OPT_WINO_WT) && R % 32 == 0 && Cc % 32 == 0 && w16; }
-inline bool wino_weight(const float* w, float* U, int R, int Cc, int flip, hipStream_t s, float* UT = nullptr) {
-  if (wino_weight_lds(R, Cc, aligned16(w))) {
-    hipLaunchKernelGGL(wino_weight_lds_kernel, dim3((R / 32) * (Cc / 32)), dim3(256), 0, s, w, U, R, Cc, flip,
-                       flip == 0 ? UT : nullptr);
-    return flip == 0 && UT != nullptr;
-  }
-  hipLaunchKernelGGL(wino_weight_kernel, dim3(sg_cdiv((size_t)R * Cc, 256)), dim3(256), 0, s, w, U, R, Cc, flip);
-  return false;
+// dynamic LDS beyond the 48 KB a kernel gets without asking
+template <class K> inline void wino_lds_attr(K kernel, size_t lds) {
+  if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// one entry for the three call sites; ``kernel``: the plan's wt_kernel.  ``UT`` (flip == 0, SG_WK_WT_LDS only -- the plan rejects
+// the rest): see wino_weight_lds_kernel
+inline void wino_weight(int kernel, const float* w, float* U, int R, int Cc, int flip, hipStream_t s, float* UT = nullptr) {
+  SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (25.0 + (UT ? 16.0 : 0.0)) * (double)R * Cc);
+  if (kernel == SG_WK_WT_LDS)
+    hipLaunchKernelGGL(wino_weight_lds_kernel, dim3((R / 32) * (Cc / 32)), dim3(256), 0, s, w, U, R, Cc, flip, UT);
+  else
+    hipLaunchKernelGGL(wino_weight_kernel, dim3(sg_cdiv((size_t)R * Cc, 256)), dim3(256), 0, s, w, U, R, Cc, flip);
 }
 
 // y[n][m][2ti+a][2tj+b] = act((A^T Mx A)[a][b] + bias[m]),  Mx[m][xi*Pstride + p]
@@ -807,19 +809,15 @@ __global__ void wino_wgrad_output_kernel(const float* __restrict__ T, float* __r
   }
 }
 
-// V[xi][p][c] of x (logical H x W plane, ush = folded upsample shift): LDS-staged kernel for small planes, general otherwise
-inline bool wino_input_small(int C, int H, int W, int ush, bool x16) {
-  return ush == 0 && H * W <= 256 && (H * W) % 4 == 0 && C % 64 == 0 && x16;
-}
-void wino_input_pc(const float* x, float* V, int N, int C, int H, int W, int TH, int TW, int off, int zero_pad, size_t Pstride,
-                   int ush, hipStream_t s) {
+// V[xi][p][c] of x (logical H x W plane, ush = folded upsample shift); ``kernel``: the plan's in_kernel -- the LDS-staged kernel
+// for small planes (SG_WK_IN_LDS), the general one otherwise
+void wino_input_pc(int kernel, const float* x, float* V, int N, int C, int H, int W, int TH, int TW, int off, int zero_pad,
+                   size_t Pstride, int ush, hipStream_t s) {
   const int HW = H * W;
   SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)N * C * (H >> ush) * (W >> ush) + 16.0 * (double)Pstride * C));
-  if (wino_input_small(C, H, W, ush, aligned16(x))) {
+  if (kernel == SG_WK_IN_LDS) {
     const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
-    if (lds > 48 * 1024)
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_input_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds);
+    wino_lds_attr(&wino_input_small_kernel, lds);
     hipLaunchKernelGGL(wino_input_small_kernel, dim3(C / 64, N), dim3(256), lds, s, x, V, N, C, H, W, TH, TW, off, zero_pad, Pstride);
     return;
   }
@@ -847,95 +845,66 @@ int wino_tile(const sgConvDesc* d) {
 }
 bool wino_ok(const sgConvDesc* d) { return wino_tile(d) != 0; }
 
-// The batched GEMM of wino_bgemm() below on a choice of tiles: sg_batched_gemm_nt (tools/bench_wino_gemm.py), the F(4x4,3x3)
-// convs (36 x [1024 x 1024] x [1024 x 128] at the trunk: 128x128 tiles would give 288 workgroups for 256 CUs) and the A/B
-// switch wino_gemm_tile.  tile: 0 = 128x128, 1 = 64x128, 2 = 64x64; all 32-deep, software-pipelined, plain epilogue.
+// The batched GEMMs of every Winograd form, C[m][b*cols + j] = sum_k A[b][m][k] * B[b][j][k] over NB batches (16 for F(2x2,3x3), 36
+// for F(4x4,3x3), 25 (x k-chunks) for F(2x2,4x4); everything a multiple of the tile), on a choice of tiles: 128x128, 64x128 and
+// 64x64 (the F(4x4,3x3) convs: 36 x [1024 x 1024] x [1024 x 128] at the trunk, where 128x128 tiles would give 288 workgroups for 256
+// CUs); all software-pipelined, plain epilogue.
 using CfgDI64W = TileCfg<64, 128, 2, 2, 2>;
 using CfgDI64 = TileCfg<64, 64, 2, 2, 2>;
 // 16-deep k-tiles: 20 KB of LDS per workgroup instead of 40 -- the 1152 workgroups of an F(4x4,3x3) GEMM (4.5 per CU) are then
 // all resident at once (32-deep: 4 per CU by LDS = 1024 slots, the other 128 run as a second, nearly empty round)
 using CfgDI64S = TileCfg<64, 64, 2, 1, 2>;
-// ... with the channel sum accumulated in chunks (TileCfg::KFOLD): the F(4x4,3x3) forward / data-gradient GEMMs (w43_kfold)
+// ... with the channel sum accumulated in chunks (TileCfg::KFOLD): the F(4x4,3x3) forward / data-gradient GEMMs (w43_gemm_sel)
 using CfgDI64F256 = TileCfg<64, 64, 2, 2, 2, 256, 1>;
 using CfgDI64SF256 = TileCfg<64, 64, 2, 1, 2, 256, 1>;
 using CfgDI64F128 = TileCfg<64, 64, 2, 2, 2, 128, 1>;
 using CfgDI64SF128 = TileCfg<64, 64, 2, 1, 2, 128, 1>;
-// kfold (0 / 128 / 256) x k-tile depth -> one of the six 64x64 instantiations
-inline int w43_kfold(int K) { return (K > 256 || (K > 128 && sg_opt(SG_OPT_W43_KFOLD) == 128)) ? sg_opt(SG_OPT_W43_KFOLD) : 0; }
-inline bool w43_deep() { return sg_opt(SG_OPT_W43_NSUB) != 1; }
-template <class AL, class BL>
-int launch_w43(const AL& al, const BL& bl, const EpRowMajorPlain& ep, int M, int N, int K, hipStream_t s) {
-  const int kf = w43_kfold(K);
-  const bool deep = w43_deep();
-  if (kf == 256) return deep ? launch_cfg<CfgDI64F256>(al, bl, ep, M, N, K, 1, s) : launch_cfg<CfgDI64SF256>(al, bl, ep, M, N, K, 1, s);
-  if (kf == 128) return deep ? launch_cfg<CfgDI64F128>(al, bl, ep, M, N, K, 1, s) : launch_cfg<CfgDI64SF128>(al, bl, ep, M, N, K, 1, s);
-  return deep ? launch_cfg<CfgDI64>(al, bl, ep, M, N, K, 1, s) : launch_cfg<CfgDI64S>(al, bl, ep, M, N, K, 1, s);
-}
-void wino_bgemm_tile(int tile, const float* A, const float* B, float* Cout, int M, int cols, int K, double flops, hipStream_t s, int NB,
-                     int kind = SG_K_OTHER) {
-  sgk::t_alg_bytes = 4.0 * NB * ((double)M * K + (double)cols * K + (double)M * cols);
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = cols; t_batch.nbatch = NB; t_batch.a_stride = M * K; t_batch.batch_major = 1;
-  {
-    SgProfScope prof(kind, s, flops, 0);
-    if (tile == 1)
-      launch_cfg<CfgDI64W>(LoadKContig<64, true, false>{A, K, M}, LoadKContig<128, true, false>{B, K, NB * cols},
-                           EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, 1, s);
-    else if ((tile == 2 || tile == 3) && kind == SG_K_WINO43_GEMM)        // F(4x4,3x3) forward: chunked channel sum (w43_kfold)
-      launch_w43(LoadKContig<64, true, false>{A, K, M}, LoadKContig<64, true, false>{B, K, NB * cols},
-                 EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, s);
-    else if (tile == 2)
-      launch_cfg<CfgDI64>(LoadKContig<64, true, false>{A, K, M}, LoadKContig<64, true, false>{B, K, NB * cols},
-                          EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, 1, s);
-    else if (tile == 3)
-      launch_cfg<CfgDI64S>(LoadKContig<64, true, false>{A, K, M}, LoadKContig<64, true, false>{B, K, NB * cols},
-                           EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, 1, s);
-    else
-      launch_cfg<CfgDI128>(LoadKContig<128, true, false>{A, K, M}, LoadKContig<128, true, false>{B, K, NB * cols},
-                           EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, 1, s);
-  }
-  t_batch = BatchInfo{};
-}
 
-// C[m][b*cols + j] = sum_k A[b][m][k] * B[b*cols + j][k]   (NB batches -- 16 for F(2x2,3x3), 25 (x k-chunks) for F(2x2,4x4) --,
-// everything a multiple of the tile)
-// tile of wino_bgemm: 1 = 64x128, 2 = 64x64 (wino_bgemm_tile), 0 = the 128x128 default
-inline int wino_bgemm_sel(int NB, int M, int cols, int K) {
-  const int tsel = NB == 16 ? sg_opt(SG_OPT_WINO_GEMM_TILE) : sg_opt(SG_OPT_W24_GEMM_TILE);
-  return ((tsel == 1 || tsel == 2) && M % 64 == 0 && cols % 128 == 0 && K % 32 == 0) ? tsel : 0;
+// operand forms: A and B k-contiguous (A[b][m][k], B[b*cols + j][k]); A k-contiguous and B x-contiguous (B[b][k][j]: the
+// F(4x4,3x3) data gradient reads the forward's U this way); both x-contiguous (A[b][k][m], B[b][k][j]: the weight gradients over
+// the tile-major operands the forward and the adjoint data gradient built, K = the tiles)
+enum { WG_KK = 0, WG_KX = 1, WG_XX = 2 };
+template <int FORM, class CFG>
+int wino_gemm_cfg(const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, hipStream_t s) {
+  const EpRowMajorPlain ep{Cm, NB * cols};
+  if constexpr (FORM == WG_KK)
+    return launch_cfg<CFG>(LoadKContig<CFG::BM, true, false>{A, K, M}, LoadKContig<CFG::BN, true, false>{B, K, NB * cols}, ep, M, NB * cols, K, 1, s);
+  else if constexpr (FORM == WG_KX)
+    return launch_cfg<CFG>(LoadKContig<CFG::BM, true, false>{A, K, M}, LoadXContigS<CFG::BN>{B, cols, cols}, ep, M, NB * cols, K, 1, s);
+  else
+    return launch_cfg<CFG>(LoadXContigS<CFG::BM>{A, M, 0}, LoadXContigS<CFG::BN>{B, cols, cols}, ep, M, NB * cols, K, 1, s);
 }
-void wino_bgemm(const float* A, const float* B, float* Cout, int M, int cols, int K, double flops, hipStream_t s, int NB = 16) {
-  const int tsel = wino_bgemm_sel(NB, M, cols, K);
-  if (tsel != 0) {
-    wino_bgemm_tile(tsel, A, B, Cout, M, cols, K, flops, s, NB, NB == 16 ? SG_K_WINO_GEMM_128 : SG_K_WINO24_GEMM);
-    return;
-  }
-  sgk::t_alg_bytes = 4.0 * NB * ((double)M * K + (double)cols * K + (double)M * cols);
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = cols; t_batch.nbatch = NB; t_batch.a_stride = M * K; t_batch.batch_major = 1;
-  {
-    SgProfScope prof(NB == 16 ? SG_K_WINO_GEMM_128 : SG_K_WINO24_GEMM, s, flops, 0);
+// THE GEMM launch of the Winograd code: the plan's (bm, bn, nsub, kfold, pipe) -> the TileCfg instantiation.  Only the
+// combinations wino_launch_plan can produce exist: 128-wide tiles for WG_KK / WG_XX, the chunked sum for WG_KK / WG_KX, the
+// wino_pipe == 1 loop for the 128x128 WG_KK GEMM.
+#define WG_RUN(CFG) wino_gemm_cfg<FORM, CFG>(A, B, Cm, M, cols, K, NB, s)
+template <int FORM>
+int wino_gemm_pick(const sgWinoPlan& g, const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, hipStream_t s) {
+  const bool deep = g.nsub == 2;
+  if constexpr (FORM != WG_KX) {
     // 128x128 tiles, 32-deep k-tiles, software-pipelined fragment reads, unconditional epilogue (the variants this replaced --
     // 128x64 tiles, 16-deep tiles, the plain loop, the general epilogue -- measured 1.5..9 % slower: profiles/r03_sweep_tiles.txt)
-    if (sg_opt(SG_OPT_WINO_PIPE) == 2)
-      launch_cfg<CfgDI128>(LoadKContig<128, true, false>{A, K, M}, LoadKContig<128, true, false>{B, K, NB * cols},
-                           EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, 1, s);
-    else
-      launch_cfg<CfgDP128>(LoadKContig<128, true, false>{A, K, M}, LoadKContig<128, true, false>{B, K, NB * cols},
-                           EpRowMajorPlain{Cout, NB * cols}, M, NB * cols, K, 1, s);
+    if constexpr (FORM == WG_KK)
+      if (g.bm == 128 && g.pipe == 1) return WG_RUN(CfgDP128);
+    if (g.bm == 128) return WG_RUN(CfgDI128);
+    if (g.bn == 128) return WG_RUN(CfgDI64W);
   }
-  t_batch = BatchInfo{};
+  if constexpr (FORM != WG_XX) {
+    if (g.kfold == 256) return deep ? WG_RUN(CfgDI64F256) : WG_RUN(CfgDI64SF256);
+    if (g.kfold == 128) return deep ? WG_RUN(CfgDI64F128) : WG_RUN(CfgDI64SF128);
+  }
+  return deep ? WG_RUN(CfgDI64) : WG_RUN(CfgDI64S);
 }
-
-
-// T[m][xi*Cc + c] = sum_p Ytp[xi][p][m] * V[xi][p][c]: the Winograd weight gradient straight from the operands the forward (V) and
-// the adjoint data gradient (Ytp) of the same conv already built -- both tile-major, i.e. x-contiguous for a GEMM over p
-// (LoadXContigS): no second input / gradient transform (2 launches and 2 x 41 MB per ResnetBlock conv saved)
-void wino_bgemm_x(const float* Ytp, const float* V, float* T, int M, int Cc, int P, double flops, hipStream_t s) {
-  sgk::t_alg_bytes = 4.0 * 16 * ((double)M * P + (double)Cc * P + (double)M * Cc);
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = Cc; t_batch.nbatch = 16; t_batch.a_stride = P * M; t_batch.b_stride = P * Cc;
-  t_batch.batch_major = 1;
+#undef WG_RUN
+template <int FORM>
+void wino_bgemm(const sgWinoPlan& g, int kind, const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, double flops,
+                hipStream_t s) {
+  sgk::t_alg_bytes = 4.0 * NB * ((double)M * K + (double)cols * K + (double)M * cols);
+  t_batch = BatchInfo{}; t_batch.cols_per_batch = cols; t_batch.nbatch = NB; t_batch.a_stride = M * K; t_batch.batch_major = 1;
+  if (FORM != WG_KK) t_batch.b_stride = K * cols;
   {
-    SgProfScope prof(SG_K_WINO_GEMM_128, s, flops, 0);
-    launch_cfg<CfgDI128>(LoadXContigS<128>{Ytp, M, 0}, LoadXContigS<128>{V, Cc, Cc}, EpRowMajorPlain{T, 16 * Cc}, M, 16 * Cc, P, 1, s);
+    SgProfScope prof(kind, s, flops, 0);
+    wino_gemm_pick<FORM>(g, A, B, Cm, M, cols, K, NB, s);
   }
   t_batch = BatchInfo{};
 }
@@ -1506,51 +1475,32 @@ __global__ void w43_wgrad_output_kernel(const float* __restrict__ T, float* __re
     for (int b = 0; b < 3; ++b) dst[a * 3 + b] = o[a][b];
 }
 
-// the three batched GEMMs (36 batches, 64x64 tiles, 32-deep software-pipelined k-tiles)
+// the three batched GEMMs (36 batches; wino_bgemm, tiles per w43_gemm_sel / w43_wgrad_sel)
 //   forward:          Mx[m][xi*P + p]  = sum_c U[xi][m][c] * V[xi][p][c]        (both K-contiguous)
 //   data gradient:    G[p][xi*C + c]   = sum_k Ytp[xi][p][k] * U[xi][k][c]      (A K-contiguous, B x-contiguous)
 //   weight gradient:  T[m][xi*C + c]   = sum_p Ytp[xi][p][m] * V[xi][p][c]      (both x-contiguous, K = P)
-inline int w43_tile() { return sg_opt(SG_OPT_W43_NSUB) == 1 ? 3 : 2; }
-void w43_gemm_fwd(const float* U, const float* V, float* Mx, int M, int P, int C, hipStream_t s) {
-  wino_bgemm_tile(w43_tile(), U, V, Mx, M, P, C, 2.0 * 36.0 * M * (double)P * C, s, 36, SG_K_WINO43_GEMM);
+// and the four LDS-staged transforms around them, one launch helper each (P: the N * (H/4) * (W/4) tiles)
+void w43_launch_weight(const float* w, float* U, int R, int Cc, hipStream_t s) {
+  SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 45.0 * (double)R * Cc);
+  hipLaunchKernelGGL(w43_weight_kernel, dim3((R / 32) * (Cc / 32)), dim3(256), 0, s, w, U, R, Cc);
 }
-void w43_gemm_dgrad(const float* Ytp, const float* U, float* G, int P, int C, int K, hipStream_t s) {
-  sgk::t_alg_bytes = 4.0 * 36 * ((double)P * K + (double)C * K + (double)P * C);
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = C; t_batch.nbatch = 36; t_batch.a_stride = P * K; t_batch.b_stride = K * C;
-  t_batch.batch_major = 1;
-  {
-    SgProfScope prof(SG_K_WINO43_GEMM, s, 2.0 * 36.0 * P * (double)C * K, 0);
-    launch_w43(LoadKContig<64, true, false>{Ytp, K, P}, LoadXContigS<64>{U, C, C}, EpRowMajorPlain{G, 36 * C}, P, 36 * C, K, s);
-  }
-  t_batch = BatchInfo{};
+void w43_launch_input(const float* x, float* V, int N, int C, int H, int W, size_t P, hipStream_t s) {
+  SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)N * C * H * W + 36.0 * (double)P * C));
+  const size_t lds = (size_t)64 * (H * W + 1) * sizeof(float);
+  wino_lds_attr(&w43_input_kernel, lds);
+  hipLaunchKernelGGL(w43_input_kernel, dim3(C / 64, N), dim3(256), lds, s, x, V, N, C, H, W);
 }
-// tile of the F(4x4,3x3) weight-gradient GEMM: 1 = 128x128, 2 = 64x128, 0 = 64x64
-inline int w43_wgrad_sel(int M, int C, int P) {
-  const int wt = sg_opt(SG_OPT_W43_WGRAD_TILE);
-  if (wt == 1 && M % 128 == 0 && C % 128 == 0 && P % 32 == 0) return 1;
-  if (wt == 2 && C % 128 == 0 && P % 32 == 0) return 2;
-  return 0;
+void w43_launch_gy(const float* gy, float* Ytp, int N, int M, int H, int W, size_t P, hipStream_t s) {
+  SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)N * M * H * W + 36.0 * (double)P * M));
+  const size_t lds = (size_t)64 * (H * W + 1) * sizeof(float);
+  wino_lds_attr(&w43_gy_kernel, lds);
+  hipLaunchKernelGGL(w43_gy_kernel, dim3(M / 64, N), dim3(256), lds, s, gy, Ytp, N, M, H, W);
 }
-void w43_gemm_wgrad(const float* Ytp, const float* V, float* T, int M, int C, int P, hipStream_t s) {
-  sgk::t_alg_bytes = 4.0 * 36 * ((double)M * P + (double)C * P + (double)M * C);
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = C; t_batch.nbatch = 36; t_batch.a_stride = P * M; t_batch.b_stride = P * C;
-  t_batch.batch_major = 1;
-  {
-    SgProfScope prof(SG_K_WINO43_GEMM, s, 2.0 * 36.0 * M * (double)C * P, 0);
-    const int wt = w43_wgrad_sel(M, C, P);
-    if (wt == 1)
-      launch_cfg<CfgDI128>(LoadXContigS<128>{Ytp, M, 0}, LoadXContigS<128>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
-    else if (wt == 2)
-      launch_cfg<CfgDI64W>(LoadXContigS<64>{Ytp, M, 0}, LoadXContigS<128>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
-    else if (!w43_deep())
-      launch_cfg<CfgDI64S>(LoadXContigS<64>{Ytp, M, 0}, LoadXContigS<64>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
-    else
-      launch_cfg<CfgDI64>(LoadXContigS<64>{Ytp, M, 0}, LoadXContigS<64>{V, C, C}, EpRowMajorPlain{T, 36 * C}, M, 36 * C, P, 1, s);
-  }
-  t_batch = BatchInfo{};
-}
-template <class K> inline void w43_lds_attr(K kernel, size_t lds) {
-  if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+void w43_launch_fold(const float* G, float* gx, int N, int C, int H, int W, size_t P, hipStream_t s) {
+  SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (36.0 * (double)P * C + (double)N * C * H * W));
+  const size_t lds = (size_t)64 * ((H + 2) * (W + 2) + 1 + H * W + 1) * sizeof(float);
+  wino_lds_attr(&w43_fold_kernel, lds);
+  hipLaunchKernelGGL(w43_fold_kernel, dim3(C / 64, N), dim3(256), lds, s, G, gx, N, C, H, W);
 }
 }  // namespace
 
@@ -1711,27 +1661,28 @@ __global__ void __launch_bounds__(256) w24_input_small_kernel(const float* __res
     for (size_t p = P + g; p < Pstride; p += 4)
       for (int xi = 0; xi < 25; ++xi) V[((size_t)xi * Pstride + p) * C + c0 + lane] = 0.f;
 }
-// whether the LDS-staged input transform runs, and its geometry
-inline bool w24_input_small(int N, int C, int H, int W, int TH, int* rows_per_out, int* pitch_out) {
-  if (!(sg_opt(SG_OPT_W24_SMALL) && H * W >= 144 && W <= 64 && C % 64 == 0)) return false;
+// geometry of the LDS-staged input transform; false: its 64 planes do not fit 64 KB of LDS
+inline bool w24_small_geom(int N, int C, int H, int W, int TH, int* rows_per_out, int* pitch_out) {
   // tile rows per workgroup: as few as keep ~2048 workgroups busy (each stages 2*rows + 3 input rows of 64 planes: <= ~24 KB)
   int rows_per = (int)(((long)(C / 64) * N * TH + 2047) / 2048);
   if (rows_per < 1) rows_per = 1;
   const int nrows = std::min(H, 2 * rows_per + 3);
   const int pitch = (nrows * W) | 1;
   if ((size_t)64 * pitch * sizeof(float) > 64 * 1024) return false;
-  if (rows_per_out) *rows_per_out = rows_per;
-  if (pitch_out) *pitch_out = pitch;
+  *rows_per_out = rows_per;
+  *pitch_out = pitch;
   return true;
 }
-void w24_input_pc(const float* x, float* V, int N, int C, int H, int W, int TH, int TW, int off, size_t Pstride, hipStream_t s) {
+// ``kernel``: the plan's in_kernel
+void w24_input_pc(int kernel, const float* x, float* V, int N, int C, int H, int W, int TH, int TW, int off, size_t Pstride,
+                  hipStream_t s) {
   const int HW = H * W;
   SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)N * C * HW + 25.0 * (double)Pstride * C));
-  int rows_per = 0, pitch = 0;
-  if (w24_input_small(N, C, H, W, TH, &rows_per, &pitch)) {
+  if (kernel == SG_WK_IN_LDS) {
+    int rows_per = 0, pitch = 0;
+    w24_small_geom(N, C, H, W, TH, &rows_per, &pitch);
     const size_t lds = (size_t)64 * pitch * sizeof(float);
-    if (lds > 48 * 1024)
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&w24_input_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    wino_lds_attr(&w24_input_small_kernel, lds);
     hipLaunchKernelGGL(w24_input_small_kernel, dim3(C / 64, N, sg_cdiv(TH, rows_per)), dim3(256), lds, s, x, V, N, C, H, W, TH, TW, off,
                        Pstride, rows_per, pitch);
     return;
@@ -1900,8 +1851,261 @@ bool w24_plan(const sgConvDesc* d, W24Plan* pl) {
   if (pl) *pl = p;
   return true;
 }
+
+// ================================================================================================
+// THE launch plan of a Winograd entry point (the eight sg_conv2d_wino* launchers run exactly this; sg_conv2d_wino_plan reports it).
+// Every option read and every alignment test that selects a form, a kernel or a GEMM tile is in this section; the launchers
+// and the helpers above dispatch on the plan's fields alone.
+// ================================================================================================
+// ---- what a desc can run: a function of the desc ALONE (the saved-operand sizes sg_conv2d_wino_{ut,v,ytp}_floats follow from it,
+// so an unaligned operand can never switch the layouts).  SG_WF_UNSUPPORTED; SG_WF_F23_GENERIC: F(2x2,3x3) with the data gradient
+// on the padded gradient grid; SG_WF_F23_ADJOINT: F(2x2,3x3) whose data gradient can run the adjoint form over the output tiles
+// (small reflection-padded planes, 64 channel planes staged per workgroup); SG_WF_F43: F(4x4,3x3) -- the adjoint-form shapes
+// whose planes split into 4x4 output tiles and whose tile count fills whole 64-column GEMM tiles
+int wino_class(const sgConvDesc* d) {
+  if (!wino_ok(d)) return SG_WF_UNSUPPORTED;
+  if (!(sg_opt(SG_OPT_WINO_ADJOINT) && d->pad_reflect && d->upsample == 1 && d->H * d->W <= 256 && (d->H * d->W) % 4 == 0 &&
+        d->C1 % 64 == 0 && d->Cout % 64 == 0))
+    return SG_WF_F23_GENERIC;
+  if (!sg_opt(SG_OPT_WINO43) || d->H % 4 != 0 || d->W % 4 != 0) return SG_WF_F23_ADJOINT;
+  const double P = (double)d->N * (d->H / 4) * (d->W / 4), Cmax = d->C1 > d->Cout ? d->C1 : d->Cout;
+  return ((long)P % 64 == 0 && 36.0 * P * Cmax < SG_MAX_ELEMS && 36.0 * d->C1 * d->Cout < SG_MAX_ELEMS) ? SG_WF_F43 : SG_WF_F23_ADJOINT;
+}
+// tiles of the forward / weight gradient: 2x2 output tiles of the logical plane, 4x4 for F(4x4,3x3)
+size_t wino_tiles(const sgConvDesc* d, int t) { return (size_t)d->N * (d->H * d->upsample / t) * (d->W * d->upsample / t); }
+// columns of the generic F(2x2,3x3) data-gradient GEMM.  Reflect: the tiles of the (H+2) x (W+2) padded gradient grid
+size_t wino_dgrad_tiles(const sgConvDesc* d) {
+  const size_t T = (size_t)wino_tile(d);
+  const size_t P = d->pad_reflect ? (size_t)d->N * (d->H * d->upsample / 2 + 1) * (d->W * d->upsample / 2 + 1) : wino_tiles(d, 2);
+  return (P + T - 1) / T * T;
+}
+// floats of the filter transform the forward can hand to the data gradient (0: that conv's data gradient does not use it):
+// F(2x2,3x3) -- the transposed twin UT[16][C1][Cout]; F(4x4,3x3) -- U[36][Cout][C1] itself (read x-contiguous)
+size_t wino_ut_floats(const sgConvDesc* d, int cls) {
+  return cls == SG_WF_F43 ? (size_t)36 * d->C1 * d->Cout : cls == SG_WF_F23_ADJOINT ? (size_t)16 * d->C1 * d->Cout : 0;
+}
+// floats of the input transform V (ch = C1) / the gradient transform Ytp (ch = Cout) a conv can hand from its forward / data
+// gradient to its weight gradient (0: that conv's weight gradient rebuilds its operands)
+size_t wino_kept_floats(const sgConvDesc* d, int cls, int ch) {
+  if (!sg_opt(SG_OPT_WINO_REUSE) || cls < SG_WF_F23_ADJOINT) return 0;
+  return cls == SG_WF_F43 ? 36 * wino_tiles(d, 4) * ch : 16 * wino_tiles(d, 2) * ch;
+}
+// the fused conv + InstanceNorm pair: F(4x4,3x3) planes up to 16x16 (<= 4 tiles per thread of w43_output_in_kernel)
+bool wino_in_ok(const sgConvDesc* d, int cls) {
+  return sg_opt(SG_OPT_WINO_IN_FUSE) && cls == SG_WF_F43 && (d->H / 4) * (d->W / 4) <= 16 && sg_opt(SG_OPT_WINO_REUSE);
+}
+
+// ---- kernel choices ---------------------------------------------------------------------------------------------------------
+// filter transform: the LDS-staged kernel (SG_WINO_WT=0 keeps the per-thread one)
+bool wino_weight_lds(int R, int Cc, bool w16) { return sg_opt(SG_OPT_WINO_WT) && R % 32 == 0 && Cc % 32 == 0 && w16; }
+// input transform: the LDS-staged kernel for small planes (float4 staging)
+bool wino_input_small(int C, int H, int W, int ush, bool x16) {
+  return ush == 0 && H * W <= 256 && (H * W) % 4 == 0 && C % 64 == 0 && x16;
+}
+bool w24_input_small(int N, int C, int H, int W, int TH) {
+  int rows_per, pitch;
+  return sg_opt(SG_OPT_W24_SMALL) && H * W >= 144 && W <= 64 && C % 64 == 0 && w24_small_geom(N, C, H, W, TH, &rows_per, &pitch);
+}
+void wino_set_gemm(sgWinoPlan* p, int bm, int bn, int nsub, int kfold, int pipe) {
+  p->bm = bm; p->bn = bn; p->nsub = nsub; p->kfold = kfold; p->pipe = pipe;
+}
+// the K-contiguous GEMMs of F(2x2,3x3) (NB == 16) and F(2x2,4x4): the option's 64x128 / 64x64 tiles where they divide the
+// problem, else 128x128 with the main loop of wino_pipe
+void wino_gemm_sel(sgWinoPlan* p, int NB, int M, int cols, int K) {
+  const int t = NB == 16 ? sg_opt(SG_OPT_WINO_GEMM_TILE) : sg_opt(SG_OPT_W24_GEMM_TILE);
+  const bool fits = M % 64 == 0 && cols % 128 == 0 && K % 32 == 0;
+  if (t == 1 && fits) wino_set_gemm(p, 64, 128, 2, 0, 0);
+  else if (t == 2 && fits) wino_set_gemm(p, 64, 64, 2, 0, 0);
+  else wino_set_gemm(p, 128, 128, 2, 0, sg_opt(SG_OPT_WINO_PIPE) == 2 ? 2 : 1);
+}
+// the F(4x4,3x3) forward / data-gradient GEMM over a reduction of K: 64x64 tiles, k-tile depth by w43_nsub, the channel sum in
+// chunks of w43_kfold once it is longer than a chunk
+bool w43_deep() { return sg_opt(SG_OPT_W43_NSUB) != 1; }
+void w43_gemm_sel(sgWinoPlan* p, int K) {
+  const int kf = sg_opt(SG_OPT_W43_KFOLD);
+  wino_set_gemm(p, 64, 64, w43_deep() ? 2 : 1, (K > 256 || (K > 128 && kf == 128)) ? kf : 0, 0);
+}
+// the F(4x4,3x3) weight-gradient GEMM (K = the P tiles): w43_wgrad_tile 1 = 128x128, 2 = 64x128 where they divide, else 64x64
+void w43_wgrad_sel(sgWinoPlan* p, int M, int C, int P) {
+  const int wt = sg_opt(SG_OPT_W43_WGRAD_TILE);
+  if (wt == 1 && M % 128 == 0 && C % 128 == 0 && P % 32 == 0) wino_set_gemm(p, 128, 128, 2, 0, 0);
+  else if (wt == 2 && C % 128 == 0 && P % 32 == 0) wino_set_gemm(p, 64, 128, 2, 0, 0);
+  else wino_set_gemm(p, 64, 64, w43_deep() ? 2 : 1, 0, 0);
+}
+
+// ---- the plan -----------------------------------------------------------------------------------------------------------------
+// align_mask: SG_WA_* bits of the operands as passed; saved_mask: SG_WS_* bits of the non-null saved operands.  Non-zero with
+// *err set for everything an entry point rejects before its first launch.
+#define WP_CHECK(cond, msg) do { if (!(cond)) { *err = (msg); return -1; } } while (0)
+int wino_launch_plan(const sgConvDesc* d, int entry, int align_mask, int saved_mask, sgWinoPlan* out, const char** err) {
+  const bool x16 = align_mask & SG_WA_X, w16 = align_mask & SG_WA_W, y16 = align_mask & SG_WA_Y, gy16 = align_mask & SG_WA_GY,
+             gx16 = align_mask & SG_WA_GX, gw16 = align_mask & SG_WA_GW;
+  const bool ut = saved_mask & SG_WS_UT, v = saved_mask & SG_WS_V, ytp = saved_mask & SG_WS_YTP;
+  sgWinoPlan p = {};
+  if (entry >= SG_WINO24_FWD) {
+    W24Plan w;
+    WP_CHECK(w24_plan(d, &w), "unsupported desc");
+    WP_CHECK(saved_mask == 0, "F(2x2,4x4) takes no saved operands");
+    p.form = SG_WF_F24;
+    p.P = (int)w.P; p.Ps = (int)w.Ps; p.Pd = (int)w.Pd; p.Pds = (int)w.Pds;
+    p.TH = w.TH; p.TW = w.TW; p.THd = w.THd; p.TWd = w.TWd; p.S = w.S; p.Pc = w.Pc;
+    if (entry == SG_WINO24_FWD) {
+      p.in_kernel = w24_input_small(d->N, d->C1, d->H, d->W, w.TH) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+      p.wt_kernel = SG_WK_WT_PLAIN;
+      wino_gemm_sel(&p, 25, d->Cout, (int)w.Ps, d->C1);
+    } else if (entry == SG_WINO24_DGRAD) {
+      p.in_kernel = w24_input_small(d->N, d->Cout, d->OH, d->OW, w.THd) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+      p.wt_kernel = SG_WK_WT_PLAIN;
+      wino_gemm_sel(&p, 25, d->C1, (int)w.Pds, d->Cout);
+    } else {
+      WP_CHECK(gw16, "gw must be 16-byte aligned");
+      p.in_kernel = SG_WK_IN_GENERAL;
+      p.wgrad_src = SG_WSRC_REBUILT;
+      wino_gemm_sel(&p, 25 * w.S, d->Cout, d->C1, w.Pc);
+    }
+    *out = p;
+    return 0;
+  }
+  const int cls = wino_class(d);
+  const bool fused = entry == SG_WINO_FWD_INSTNORM || entry == SG_WINO_DGRAD_INSTNORM;
+  WP_CHECK(cls != SG_WF_UNSUPPORTED && (!fused || wino_in_ok(d, cls)), "unsupported desc");
+  const int LH = d->H * d->upsample, LW = d->W * d->upsample, refl = d->pad_reflect;
+  if (cls == SG_WF_F43) {
+    // an unaligned operand on an F(4x4,3x3) shape is an argument error, not a silent switch to the F(2x2,3x3) layouts
+    p.form = SG_WF_F43;
+    p.P = p.Ps = p.Pd = p.Pds = (int)wino_tiles(d, 4);
+    if (entry == SG_WINO_FWD || entry == SG_WINO_FWD_INSTNORM) {
+      WP_CHECK(x16 && w16 && y16, fused ? "operands must be 16-byte aligned" : "F(4x4,3x3) shapes need 16-byte aligned x / y / w");
+      WP_CHECK(!ytp, "the forward takes no ytp_save");
+      p.in_kernel = SG_WK_IN_LDS; p.wt_kernel = SG_WK_WT_LDS;
+      w43_gemm_sel(&p, d->C1);
+      if (fused) p.norm_tiles = (d->H / 4) * (d->W / 4) <= 4 ? 1 : 4;       // tiles per thread of w43_output_in_kernel
+    } else if (entry == SG_WINO_DGRAD || entry == SG_WINO_DGRAD_INSTNORM) {
+      WP_CHECK(gy16 && gx16 && w16, fused ? "operands must be 16-byte aligned" : "F(4x4,3x3) shapes need 16-byte aligned gy / gx / w");
+      WP_CHECK(!v, "the data gradient takes no v_save");
+      p.in_kernel = SG_WK_IN_LDS; p.wt_kernel = ut ? SG_WK_NONE : SG_WK_WT_LDS; p.fold_kernel = SG_WK_FOLD_F43;
+      w43_gemm_sel(&p, d->Cout);
+    } else {
+      WP_CHECK(x16 && gy16, "F(4x4,3x3) shapes need 16-byte aligned x / gy");
+      WP_CHECK(!ut, "the weight gradient takes no ut_save");
+      // the operands come from this conv's forward / data gradient when the caller kept both, else they are rebuilt
+      const bool saved = v && ytp;
+      p.wgrad_src = saved ? SG_WSRC_SAVED : SG_WSRC_REBUILT;
+      p.in_kernel = saved ? SG_WK_NONE : SG_WK_IN_LDS;
+      w43_wgrad_sel(&p, d->Cout, d->C1, p.P);
+    }
+    *out = p;
+    return 0;
+  }
+  p.P = p.Ps = (int)wino_tiles(d, 2);
+  p.Pd = d->N * (LH / 2 + (refl ? 1 : 0)) * (LW / 2 + (refl ? 1 : 0));
+  p.Pds = (int)wino_dgrad_tiles(d);
+  if (entry == SG_WINO_FWD) {
+    WP_CHECK(!ytp, "the forward takes no ytp_save");
+    WP_CHECK(!v || wino_kept_floats(d, cls, d->C1) > 0, "v_save given but unused by this desc");
+    WP_CHECK(!ut || wino_ut_floats(d, cls) > 0, "ut_save given but unused by this desc");
+    const bool lds = wino_weight_lds(d->Cout, d->C1, w16);
+    WP_CHECK(!ut || lds, "the transposed filter transform needs the LDS weight kernel");
+    p.form = SG_WF_F23_GENERIC;
+    p.wt_kernel = lds ? SG_WK_WT_LDS : SG_WK_WT_PLAIN;
+    p.in_kernel = wino_input_small(d->C1, LH, LW, d->upsample == 2 ? 1 : 0, x16) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+    wino_gemm_sel(&p, 16, d->Cout, p.P, d->C1);
+  } else if (entry == SG_WINO_DGRAD) {
+    WP_CHECK(!v, "the data gradient takes no v_save");
+    const int M = d->C1, K = d->Cout;
+    // the adjoint form runs only on aligned gy / gx (float4 staging): else the generic padded-grid form
+    if (cls == SG_WF_F23_ADJOINT && gy16 && gx16) {
+      p.form = SG_WF_F23_ADJOINT;
+      p.Pd = p.Pds = p.P;                 // over the output tiles
+      p.in_kernel = SG_WK_IN_LDS;
+      p.wt_kernel = ut ? SG_WK_NONE : (wino_weight_lds(M, K, w16) ? SG_WK_WT_LDS : SG_WK_WT_PLAIN);
+      p.fold_kernel = sg_opt(SG_OPT_WINO_FOLD_CELLS) ? SG_WK_FOLD_CELLS : SG_WK_FOLD_WALK;
+      wino_gemm_sel(&p, 16, p.P, M, K);
+    } else {
+      WP_CHECK(!ytp, "ytp_save given but this desc does not run the adjoint form");
+      p.form = SG_WF_F23_GENERIC;
+      p.wt_kernel = wino_weight_lds(M, K, w16) ? SG_WK_WT_LDS : SG_WK_WT_PLAIN;       // (a ut_saved is not read by this form)
+      p.in_kernel = wino_input_small(K, LH, LW, 0, gy16) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
+      p.fold_kernel = (!refl && d->upsample == 1) ? SG_WK_NONE : SG_WK_FOLD_PAD_UPSAMPLE;
+      wino_gemm_sel(&p, 16, M, p.Pds, K);
+    }
+  } else {
+    WP_CHECK(entry == SG_WINO_WGRAD, "unsupported desc");
+    WP_CHECK(!ut, "the weight gradient takes no ut_save");
+    p.form = SG_WF_F23_GENERIC;
+    if (v && ytp) {
+      // operands already built by the forward (V) and the adjoint data gradient (Ytp) of this conv in this step
+      WP_CHECK(wino_kept_floats(d, cls, d->C1) > 0 && p.P % 32 == 0, "saved operands given but unused by this desc");
+      p.wgrad_src = SG_WSRC_SAVED;
+      wino_set_gemm(&p, 128, 128, 2, 0, 0);          // over the x-contiguous operands
+    } else {
+      p.wgrad_src = SG_WSRC_REBUILT;
+      p.in_kernel = SG_WK_IN_GENERAL;
+      wino_gemm_sel(&p, 16, d->Cout, d->C1, p.P);
+    }
+  }
+  *out = p;
+  return 0;
+}
+#undef WP_CHECK
+// the plan of an entry point, or the entry point's own argument error
+int wino_plan_for(const char* who, const sgConvDesc* d, int entry, int align_mask, int saved_mask, sgWinoPlan* p) {
+  const char* err = nullptr;
+  SG_ARG_CHECK(wino_launch_plan(d, entry, align_mask, saved_mask, p, &err) == 0, "%s: %s", who, err);
+  return 0;
+}
+inline int wa_bit(int bit, const void* ptr) { return aligned16(ptr) ? bit : 0; }      // (a null operand counts as aligned)
+inline int ws_bit(int bit, const void* ptr) { return ptr ? bit : 0; }
+
+// ---- workspace layouts: float offsets of up to four consecutive regions and the end.  The launchers take their pointers from
+// these and the *_ws_bytes queries return the largest end, so a region can never lie behind what the query promised.
+struct WinoLayout { size_t at[4], end; };
+inline WinoLayout wino_regions(size_t n0, size_t n1, size_t n2, size_t n3 = 0) { return {{0, n0, n0 + n1, n0 + n1 + n2}, n0 + n1 + n2 + n3}; }
+// F(2x2,3x3)  forward:            U[16][Cout][C1]  | V[16][P][C1]      | Mx[Cout][16][P]
+//             weight gradient:    T[Cout][16][C1]  | Vp[16][C1][P]     | Yt[16][Cout][P]      (on saved operands: T alone is used)
+//             dgrad, adjoint:     UT[16][C1][Cout] | Ytp[16][P][Cout]  | G[P][16][C1]
+//             dgrad, generic:     U[16][C1][Cout]  | V[16][Pds][Cout]  | Mx[C1][16][Pds] | gpad[N][C1][LH+2][LW+2]
+WinoLayout wino23_layout(const sgConvDesc* d, int entry, bool adjoint) {
+  const size_t M = d->Cout, C = d->C1, P = wino_tiles(d, 2), Pds = wino_dgrad_tiles(d);
+  if (entry == SG_WINO_DGRAD && !adjoint)
+    return wino_regions(16 * M * C, 16 * Pds * M, 16 * Pds * C, (size_t)d->N * C * (d->H * d->upsample + 2) * (d->W * d->upsample + 2));
+  if (entry == SG_WINO_DGRAD) return wino_regions(16 * M * C, 16 * P * M, 16 * P * C);
+  return wino_regions(16 * M * C, 16 * P * C, 16 * P * M);
+}
+// F(4x4,3x3)  forward (plain, fused): U[36][Cout][C1] | V[36][P][C1]     | Mx[Cout][36][P] (fused: [P][36][Cout])
+//             weight gradient:        T[Cout][36][C1] | V[36][P][C1]     | Ytp[36][P][Cout]
+//             dgrad (plain, fused):   U[36][Cout][C1] | Ytp[36][P][Cout] | G[P][36][C1]    | fused: gb_part[N][Cout]
+// (the second region is max(C1, Cout) wide in every entry)
+WinoLayout wino43_layout(const sgConvDesc* d, int entry) {
+  const size_t M = d->Cout, C = d->C1, P = wino_tiles(d, 4), mx = M > C ? M : C;
+  if (entry == SG_WINO_DGRAD) return wino_regions(36 * M * C, 36 * P * mx, 36 * P * C);
+  if (entry == SG_WINO_DGRAD_INSTNORM) return wino_regions(36 * M * C, 36 * P * mx, 36 * P * C, (size_t)d->N * M);
+  return wino_regions(36 * M * C, 36 * P * mx, 36 * P * M);
+}
+// F(2x2,4x4)  forward:  U[25][Cout][C1] | V[25][Ps][C1]    | Mx[Cout][25][Ps]
+//             dgrad:    U[25][C1][Cout] | V[25][Pds][Cout] | Mx[C1][25][Pds]
+//             wgrad:    Yt[25 S][Cout][Pc] | V[25 S][C1][Pc] | T[Cout][25 S][C1]
+WinoLayout wino24_layout(const sgConvDesc* d, const sgWinoPlan& p, int entry) {
+  const size_t M = d->Cout, C = d->C1, Ps = p.Ps, Pds = p.Pds, Pall = (size_t)p.S * p.Pc;      // Pall: incl. the zero padding of the last k-chunk
+  if (entry == SG_WINO24_FWD) return wino_regions(25 * M * C, 25 * Ps * C, 25 * Ps * M);
+  if (entry == SG_WINO24_DGRAD) return wino_regions(25 * M * C, 25 * Pds * M, 25 * Pds * C);
+  return wino_regions(25 * Pall * M, 25 * Pall * C, 25 * (size_t)p.S * M * C);
+}
+// sg_conv2d_wino24_ws_bytes of a plan (any F(2x2,4x4) entry's: the tile counts are the desc's): the largest end + slack
+size_t wino24_ws_bytes(const sgConvDesc* d, const sgWinoPlan& p) {
+  size_t m = 0;
+  for (int e : {SG_WINO24_FWD, SG_WINO24_DGRAD, SG_WINO24_WGRAD}) m = std::max(m, wino24_layout(d, p, e).end);
+  return m * sizeof(float) + 256;
+}
+// the caller's workspace holds what the query promised, and with it the entry's own layout
+inline bool wino_ws_holds(size_t ws_bytes, size_t query_bytes, const WinoLayout& l) {
+  return ws_bytes >= query_bytes && ws_bytes >= l.end * sizeof(float);
+}
 }  // namespace
 
+// ================================================================================================
+// C ABI
+// ================================================================================================
 extern "C" int sg_batched_gemm_nt(const float* a, const float* b, float* c, int nbatch, int M, int cols, int K, int tile,
                                   sgStream stream) {
   SG_ARG_CHECK(a && b && c && nbatch > 0 && M > 0 && cols > 0 && K > 0 && tile >= 0 && tile <= 3, "sg_batched_gemm_nt: bad arguments");
@@ -1909,310 +2113,218 @@ extern "C" int sg_batched_gemm_nt(const float* a, const float* b, float* c, int 
   SG_ARG_CHECK(M % bm == 0 && cols % bn == 0 && K % 32 == 0, "sg_batched_gemm_nt: M, cols, K must be multiples of the tile (%d, %d, 32)", bm, bn);
   SG_ARG_CHECK(aligned16(a) && aligned16(b) && aligned16(c), "sg_batched_gemm_nt: operands must be 16-byte aligned");
   SG_ARG_CHECK((double)nbatch * M * K < SG_MAX_ELEMS && (double)nbatch * cols * K < SG_MAX_ELEMS, "sg_batched_gemm_nt: operand too large");
-  // (the 64x64 tiles are the F(4x4,3x3) GEMMs: same launch path, incl. the chunked channel sum selected by w43_kfold)
-  wino_bgemm_tile(tile, a, b, c, M, cols, K, 2.0 * nbatch * (double)M * cols * K, (hipStream_t)stream, nbatch,
-                  tile >= 2 ? SG_K_WINO43_GEMM : SG_K_OTHER);
+  // (the 64x64 tiles are the F(4x4,3x3) GEMMs: same launch path, incl. the k-tile depth and the chunked channel sum of w43_gemm_sel)
+  sgWinoPlan g = {};
+  if (tile >= 2) w43_gemm_sel(&g, K);
+  else wino_set_gemm(&g, bm, bn, 2, 0, 0);
+  wino_bgemm<WG_KK>(g, tile >= 2 ? SG_K_WINO43_GEMM : SG_K_OTHER, a, b, c, M, cols, K, nbatch, 2.0 * nbatch * (double)M * cols * K,
+                    (hipStream_t)stream);
   SG_LAUNCH_CHECK("sg_batched_gemm_nt");
   return 0;
 }
 
 extern "C" int sg_conv2d_wino_supported(const sgConvDesc* d) { return wino_ok(d) ? 1 : 0; }
+extern "C" int sg_conv2d_wino_in_supported(const sgConvDesc* d) { return wino_in_ok(d, wino_class(d)) ? 1 : 0; }
+extern "C" size_t sg_conv2d_wino_ut_floats(const sgConvDesc* d) { return wino_ut_floats(d, wino_class(d)); }
+extern "C" size_t sg_conv2d_wino_v_floats(const sgConvDesc* d) { return wino_kept_floats(d, wino_class(d), d ? d->C1 : 0); }
+extern "C" size_t sg_conv2d_wino_ytp_floats(const sgConvDesc* d) { return wino_kept_floats(d, wino_class(d), d ? d->Cout : 0); }
 
-static size_t wino_dgrad_tiles(const sgConvDesc* d) {      // reflect: tiles of the (H+2) x (W+2) padded gradient grid
-  const size_t T = (size_t)wino_tile(d);
-  const size_t LH = (size_t)d->H * d->upsample, LW = (size_t)d->W * d->upsample;
-  const size_t P = d->pad_reflect ? (size_t)d->N * (LH / 2 + 1) * (LW / 2 + 1) : (size_t)d->N * (LH / 2) * (LW / 2);
-  return (P + T - 1) / T * T;
-}
+// The largest end over the entries.  The F(2x2,3x3) and the F(4x4,3x3) layouts both count: the switch can change between the
+// query and the call.
 extern "C" size_t sg_conv2d_wino_ws_bytes(const sgConvDesc* d) {
   if (!wino_ok(d)) return 0;
-  const size_t LH = (size_t)d->H * d->upsample, LW = (size_t)d->W * d->upsample;
-  const size_t P = (size_t)d->N * (LH / 2) * (LW / 2), M = d->Cout, C = d->C1, Pd = wino_dgrad_tiles(d);
-  const size_t a = 16 * (M * C + P * C + M * P);
-  const size_t b = 16 * (M * C + Pd * M + C * Pd) + (size_t)d->N * C * (LH + 2) * (LW + 2);
-  // F(4x4,3x3) (wino43_shape; the switch can change between the query and the call: always room for both forms):
-  // U[36][M][C] + max(V + Mx (forward), Ytp + G (data gradient), T + V + Ytp (weight gradient without saved operands))
-  const size_t P4 = (size_t)d->N * (LH / 4) * (LW / 4), mx = M > C ? M : C;
-  const size_t c = 36 * (M * C + 2 * P4 * mx + M * C);
-  const size_t m = a > b ? (a > c ? a : c) : (b > c ? b : c);
+  const size_t M = d->Cout, C = d->C1, mx = M > C ? M : C;
+  // never less than the F(4x4,3x3) size this query has always returned (U + T + two operand regions: callers keep buffers of it)
+  size_t m = 36 * (2 * M * C + 2 * wino_tiles(d, 4) * mx);
+  for (int e : {SG_WINO_FWD, SG_WINO_DGRAD, SG_WINO_WGRAD, SG_WINO_DGRAD_INSTNORM}) {
+    m = std::max(m, wino43_layout(d, e).end);
+    if (e != SG_WINO_DGRAD_INSTNORM) m = std::max({m, wino23_layout(d, e, false).end, wino23_layout(d, e, true).end});
+  }
   return m * sizeof(float) + 1024;
 }
 
-// gx [N, C1, H, W].  Reflection padding: Winograd over the (H+2) x (W+2) gradient of the reflect-padded input (correlation of
-// the zero-extended gy with the rotated filter), then the reflection fold (sg_pad_upsample_bwd); 1.44x fewer MACs than the
-// direct folded form.  Zero padding: the same correlation straight on the H x W grid (2.25x fewer MACs); behind a folded x2
-// upsample the result is on the upsampled grid and is summed back 2x2.
-static bool wino_adjoint_shape(const sgConvDesc* d) {
-  return sg_opt(SG_OPT_WINO_ADJOINT) && wino_ok(d) && d->pad_reflect && d->upsample == 1 && d->H * d->W <= 256 && (d->H * d->W) % 4 == 0 &&
-         d->C1 % 64 == 0 && d->Cout % 64 == 0;
-}
-// the F(2x2,3x3) data gradient runs the adjoint form only on aligned gy / gx (float4 staging): else the generic padded-grid form
-static bool wino_dgrad_adjoint(const sgConvDesc* d, bool gy16, bool gx16) { return wino_adjoint_shape(d) && gy16 && gx16; }
-// F(4x4,3x3) instead of F(2x2,3x3): the adjoint-form shapes whose planes split into 4x4 output tiles and whose tile count fills
-// whole 64-column GEMM tiles
-static bool wino43_shape(const sgConvDesc* d) {
-  if (!sg_opt(SG_OPT_WINO43) || !wino_adjoint_shape(d) || d->H % 4 != 0 || d->W % 4 != 0) return false;
-  const double P = (double)d->N * (d->H / 4) * (d->W / 4), Cmax = d->C1 > d->Cout ? d->C1 : d->Cout;
-  return (long)P % 64 == 0 && 36.0 * P * Cmax < SG_MAX_ELEMS && 36.0 * d->C1 * d->Cout < SG_MAX_ELEMS;
-}
-// floats of the filter transform sg_conv2d_wino_fwd can hand to sg_conv2d_wino_dgrad (0: that conv's data gradient does not use
-// it): F(2x2,3x3) -- the transposed twin UT[16][C1][Cout]; F(4x4,3x3) -- U[36][Cout][C1] itself (read x-contiguous)
-extern "C" size_t sg_conv2d_wino_ut_floats(const sgConvDesc* d) {
-  if (wino43_shape(d)) return (size_t)36 * d->C1 * d->Cout;
-  return (wino_adjoint_shape(d) && d->C1 % 32 == 0 && d->Cout % 32 == 0) ? (size_t)16 * d->C1 * d->Cout : 0;
-}
-
-// floats of the input transform V / the gradient transform Ytp a conv can hand from its forward / data gradient to its weight
-// gradient (0: that conv's weight gradient rebuilds its operands)
-extern "C" size_t sg_conv2d_wino_v_floats(const sgConvDesc* d) {
-  if (!sg_opt(SG_OPT_WINO_REUSE) || !wino_adjoint_shape(d)) return 0;
-  if (wino43_shape(d)) return (size_t)36 * d->N * (d->H / 4) * (d->W / 4) * d->C1;
-  return (size_t)16 * d->N * (d->H / 2) * (d->W / 2) * d->C1;
-}
-extern "C" size_t sg_conv2d_wino_ytp_floats(const sgConvDesc* d) {
-  if (!sg_opt(SG_OPT_WINO_REUSE) || !wino_adjoint_shape(d)) return 0;
-  if (wino43_shape(d)) return (size_t)36 * d->N * (d->H / 4) * (d->W / 4) * d->Cout;
-  return (size_t)16 * d->N * (d->H / 2) * (d->W / 2) * d->Cout;
-}
-
-extern "C" int sg_conv2d_wino_dgrad(const sgConvDesc* d, const float* gy, const float* w, float* gx, const float* ut_saved,
-                                    float* ytp_save, void* ws, size_t ws_bytes, sgStream stream) {
-  SG_ARG_CHECK(wino_ok(d), "sg_conv2d_wino_dgrad: unsupported desc");
-  SG_ARG_CHECK(gy && w && gx && ws && ws_bytes >= sg_conv2d_wino_ws_bytes(d), "sg_conv2d_wino_dgrad: bad arguments");
+extern "C" int sg_conv2d_wino_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, int act,
+                                  float slope, float* ut_save, float* v_save, void* ws, size_t ws_bytes, sgStream stream) {
+  sgWinoPlan p;
+  if (wino_plan_for("sg_conv2d_wino_fwd", d, SG_WINO_FWD, wa_bit(SG_WA_X, x) | wa_bit(SG_WA_W, w) | wa_bit(SG_WA_Y, y),
+                    ws_bit(SG_WS_UT, ut_save) | ws_bit(SG_WS_V, v_save), &p))
+    return -1;
+  const bool f43 = p.form == SG_WF_F43;
+  const WinoLayout l = f43 ? wino43_layout(d, SG_WINO_FWD) : wino23_layout(d, SG_WINO_FWD, false);
+  SG_ARG_CHECK(x && w && y && ws && wino_ws_holds(ws_bytes, sg_conv2d_wino_ws_bytes(d), l), "sg_conv2d_wino_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const int M = d->C1, K = d->Cout;                 // rows = input channels, reduction over output channels
+  const int M = d->Cout, C = d->C1, P = p.P;
   const int LH = d->H * d->upsample, LW = d->W * d->upsample;
-  const int refl = d->pad_reflect;
-  // the form is a function of the desc ALONE (the saved-operand sizes sg_conv2d_wino_{ut,v,ytp}_floats are): an unaligned operand
-  // on an F(4x4,3x3) shape is an argument error, not a silent switch to the F(2x2,3x3) layouts
-  SG_ARG_CHECK(!wino43_shape(d) || (aligned16(gy) && aligned16(gx) && aligned16(w)),
-               "sg_conv2d_wino_dgrad: F(4x4,3x3) shapes need 16-byte aligned gy / gx / w");
-  if (wino43_shape(d)) {
-    // F(4x4,3x3), adjoint form: Ytp = A gy A^T, G = Ytp x U (U from the forward, x-contiguous), overlap-add of B G B^T + fold
-    const int HW = d->H * d->W;
-    const size_t P = (size_t)d->N * (d->H / 4) * (d->W / 4);
-    float* Uw = reinterpret_cast<float*>(ws);       // [36][Cout][C1]
-    float* Ytp_ws = Uw + 36 * (size_t)M * K;        // [36][P][Cout]
-    float* G = Ytp_ws + 36 * P * (size_t)(K > M ? K : M);      // [P][36][C1]
-    float* Ytp = ytp_save ? ytp_save : Ytp_ws;
-    const float* U = ut_saved;
-    if (U == nullptr) {
-      SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 45.0 * (double)M * K);
-      hipLaunchKernelGGL(w43_weight_kernel, dim3((K / 32) * (M / 32)), dim3(256), 0, s, w, Uw, K, M);
-      U = Uw;
-    }
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * K * HW + 36.0 * (double)P * K));
-      const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
-      w43_lds_attr(&w43_gy_kernel, lds);
-      hipLaunchKernelGGL(w43_gy_kernel, dim3(K / 64, d->N), dim3(256), lds, s, gy, Ytp, d->N, K, d->H, d->W); }
-    w43_gemm_dgrad(Ytp, U, G, (int)P, M, K, s);
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (36.0 * (double)P * M + (double)d->N * M * HW));
-      const size_t lds = (size_t)64 * ((d->H + 2) * (d->W + 2) + 1 + HW + 1) * sizeof(float);
-      w43_lds_attr(&w43_fold_kernel, lds);
-      hipLaunchKernelGGL(w43_fold_kernel, dim3(M / 64, d->N), dim3(256), lds, s, (const float*)G, gx, d->N, M, d->H, d->W); }
-    SG_LAUNCH_CHECK("sg_conv2d_wino_dgrad");
+  float* base = reinterpret_cast<float*>(ws);
+  float* U = f43 && ut_save ? ut_save : base + l.at[0];
+  float* V = v_save ? v_save : base + l.at[1];      // kept for the weight gradient when the caller wants it
+  float* Mx = base + l.at[2];
+  if (f43) {
+    // F(4x4,3x3): U = G g G^T (into ut_save when the data gradient follows), V = B^T d B, 36 GEMMs, y = A^T Mx A + bias
+    w43_launch_weight(w, U, M, C, s);
+    w43_launch_input(x, V, d->N, C, d->H, d->W, P, s);
+    wino_bgemm<WG_KK>(p, SG_K_WINO43_GEMM, U, V, Mx, M, P, C, 36, 2.0 * 36.0 * M * (double)P * C, s);
+    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (36.0 * (double)P * M + (double)d->N * M * d->H * d->W));
+      hipLaunchKernelGGL(w43_output_kernel, dim3(sg_cdiv((size_t)P * M, 256)), dim3(256), 0, s, (const float*)Mx, bias, y, d->N, M, d->H,
+                         d->W, act, slope); }
+    SG_LAUNCH_CHECK("sg_conv2d_wino_fwd");
     return 0;
   }
-  if (wino_dgrad_adjoint(d, aligned16(gy), aligned16(gx))) {
-    // adjoint Winograd over the output tiles (see wino_gy_small_kernel / wino_patch_fold_kernel)
-    const int HW = d->H * d->W;
-    const size_t P = (size_t)d->N * (d->H / 2) * (d->W / 2);
-    float* UTw = reinterpret_cast<float*>(ws);      // [16][C1][Cout]
-    float* Ytp_ws = UTw + 16 * (size_t)M * K;       // [16][P][Cout]
-    float* G = Ytp_ws + 16 * P * K;                 // [P][16][C1]
-    float* Ytp = ytp_save ? ytp_save : Ytp_ws;      // kept for the weight gradient of the same conv when the caller wants it
-    const float* UT = ut_saved;                     // built by the forward pass of this step (same weights) when given
-    if (UT == nullptr) {
-      SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 25.0 * (double)M * K);
-      wino_weight(w, UTw, M, K, 2, s);
-      UT = UTw;
+  wino_weight(p.wt_kernel, w, U, M, C, 0, s, ut_save);      // (+ the transposed twin UT for the adjoint data gradient)
+  wino_input_pc(p.in_kernel, x, V, d->N, C, LH, LW, LH / 2, LW / 2, -1, d->pad_reflect ? 0 : 1, P, d->upsample == 2 ? 1 : 0, s);
+  wino_bgemm<WG_KK>(p, SG_K_WINO_GEMM_128, U, V, Mx, M, P, C, 16, 2.0 * M * (double)C * 16.0 * P, s);
+  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (16.0 * (double)P * M + (double)d->N * M * LH * LW));
+    hipLaunchKernelGGL(wino_output_kernel, dim3(sg_cdiv((size_t)P * M, 256)), dim3(256), 0, s, (const float*)Mx, bias, y, d->N, M, LH, LW,
+                       (size_t)P, act, slope); }
+  SG_LAUNCH_CHECK("sg_conv2d_wino_fwd");
+  return 0;
+}
+
+// gx [N, C1, H, W].  F(4x4,3x3) and the F(2x2,3x3) adjoint form: over the output tiles, overlap-add + reflection fold.  Generic
+// form, reflection padding: Winograd over the (H+2) x (W+2) gradient of the reflect-padded input (correlation of the
+// zero-extended gy with the rotated filter), then the reflection fold (sg_pad_upsample_bwd); 1.44x fewer MACs than the direct
+// folded form.  Zero padding: the same correlation straight on the H x W grid (2.25x fewer MACs); behind a folded x2 upsample the
+// result is on the upsampled grid and is summed back 2x2.
+extern "C" int sg_conv2d_wino_dgrad(const sgConvDesc* d, const float* gy, const float* w, float* gx, const float* ut_saved,
+                                    float* ytp_save, void* ws, size_t ws_bytes, sgStream stream) {
+  sgWinoPlan p;
+  if (wino_plan_for("sg_conv2d_wino_dgrad", d, SG_WINO_DGRAD, wa_bit(SG_WA_GY, gy) | wa_bit(SG_WA_GX, gx) | wa_bit(SG_WA_W, w),
+                    ws_bit(SG_WS_UT, ut_saved) | ws_bit(SG_WS_YTP, ytp_save), &p))
+    return -1;
+  const WinoLayout l = p.form == SG_WF_F43 ? wino43_layout(d, SG_WINO_DGRAD) : wino23_layout(d, SG_WINO_DGRAD, p.form == SG_WF_F23_ADJOINT);
+  SG_ARG_CHECK(gy && w && gx && ws && wino_ws_holds(ws_bytes, sg_conv2d_wino_ws_bytes(d), l), "sg_conv2d_wino_dgrad: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const int M = d->C1, K = d->Cout;                 // rows = input channels, reduction over output channels
+  float* base = reinterpret_cast<float*>(ws);
+  if (p.form != SG_WF_F23_GENERIC) {
+    // over the output tiles: Ytp = A gy A^T (kept for the weight gradient of the same conv when the caller wants it), G = Ytp x U
+    // (the filter transform of this step's forward when given -- F(4x4,3x3): U read x-contiguous, F(2x2,3x3): its transposed
+    // twin UT), overlap-add of B G B^T + reflection fold
+    const int HW = d->H * d->W, P = p.P;
+    float* Ytp = ytp_save ? ytp_save : base + l.at[1];
+    float* G = base + l.at[2];
+    const float* U = ut_saved;
+    if (p.form == SG_WF_F43) {
+      if (p.wt_kernel != SG_WK_NONE) { w43_launch_weight(w, base + l.at[0], K, M, s); U = base + l.at[0]; }
+      w43_launch_gy(gy, Ytp, d->N, K, d->H, d->W, P, s);
+      wino_bgemm<WG_KX>(p, SG_K_WINO43_GEMM, Ytp, U, G, P, M, K, 36, 2.0 * 36.0 * P * (double)M * K, s);
+      w43_launch_fold(G, gx, d->N, M, d->H, d->W, P, s);
+      SG_LAUNCH_CHECK("sg_conv2d_wino_dgrad");
+      return 0;
     }
+    if (p.wt_kernel != SG_WK_NONE) { wino_weight(p.wt_kernel, w, base + l.at[0], M, K, 2, s); U = base + l.at[0]; }
     { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * K * HW + 16.0 * (double)P * K));
       const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
-      if (lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_gy_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      wino_lds_attr(&wino_gy_small_kernel, lds);
       hipLaunchKernelGGL(wino_gy_small_kernel, dim3(K / 64, d->N), dim3(256), lds, s, gy, Ytp, d->N, K, d->H, d->W); }
     // G[p][xi*C1 + ci] = sum_co Ytp[xi][p][co] * UT[xi][ci][co]
-    wino_bgemm(Ytp, UT, G, (int)P, M, K, 2.0 * M * (double)K * 16.0 * P, s);
+    wino_bgemm<WG_KK>(p, SG_K_WINO_GEMM_128, Ytp, U, G, P, M, K, 16, 2.0 * M * (double)K * 16.0 * P, s);
     { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (16.0 * (double)P * M + (double)d->N * M * HW));
       const size_t lds = (size_t)64 * ((d->H + 2) * (d->W + 2) + 1 + HW + 1) * sizeof(float);
-      if (lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_patch_fold_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (sg_opt(SG_OPT_WINO_FOLD_CELLS)) {
-        if (lds > 48 * 1024)
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_patch_fold_cells_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (p.fold_kernel == SG_WK_FOLD_CELLS) {
+        wino_lds_attr(&wino_patch_fold_cells_kernel, lds);
         hipLaunchKernelGGL(wino_patch_fold_cells_kernel, dim3(M / 64, d->N), dim3(256), lds, s, (const float*)G, gx, d->N, M, d->H, d->W);
       } else {
+        wino_lds_attr(&wino_patch_fold_kernel, lds);
         hipLaunchKernelGGL(wino_patch_fold_kernel, dim3(M / 64, d->N), dim3(64), lds, s, (const float*)G, gx, d->N, M, d->H, d->W);
       } }
     SG_LAUNCH_CHECK("sg_conv2d_wino_dgrad");
     return 0;
   }
-  SG_ARG_CHECK(ytp_save == nullptr, "sg_conv2d_wino_dgrad: ytp_save given but this desc does not run the adjoint form");
+  const int LH = d->H * d->upsample, LW = d->W * d->upsample, refl = d->pad_reflect;
   const int TH = LH / 2 + (refl ? 1 : 0), TW = LW / 2 + (refl ? 1 : 0);
-  const size_t Pd = wino_dgrad_tiles(d);
-  float* U = reinterpret_cast<float*>(ws);          // [16][C1][Cout]
-  float* V = U + 16 * (size_t)M * K;                // [16][Pd][Cout]
-  float* Mx = V + 16 * Pd * K;                      // [C1][16][Pd]
-  float* gpad = Mx + 16 * Pd * M;                   // [N][C1][LH+2][LW+2] (reflect) / [N][C1][LH][LW] (upsample)
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 25.0 * (double)M * K); wino_weight(w, U, M, K, 1, s); }
-  wino_input_pc(gy, V, d->N, K, LH, LW, TH, TW, refl ? -2 : -1, 1, Pd, 0, s);
-  wino_bgemm(U, V, Mx, M, (int)Pd, K, 2.0 * M * (double)K * 16.0 * ((double)d->N * TH * TW), s);   // flops of the real tiles
-  const bool direct = !refl && d->upsample == 1;
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (16.0 * (double)Pd * M + (double)d->N * M * 4.0 * TH * TW)); hipLaunchKernelGGL(wino_output_kernel, dim3(sg_cdiv((size_t)d->N * TH * TW * M, 256)), dim3(256), 0, s, (const float*)Mx,
-                     (const float*)nullptr, direct ? gx : gpad, d->N, M, 2 * TH, 2 * TW, Pd, SG_ACT_NONE, 0.f); }
+  const size_t Pds = (size_t)p.Pds;
+  float *U = base + l.at[0], *V = base + l.at[1], *Mx = base + l.at[2];
+  float* gpad = base + l.at[3];                     // [N][C1][LH+2][LW+2] (reflect) / [N][C1][LH][LW] (upsample)
+  wino_weight(p.wt_kernel, w, U, M, K, 1, s);
+  wino_input_pc(p.in_kernel, gy, V, d->N, K, LH, LW, TH, TW, refl ? -2 : -1, 1, Pds, 0, s);
+  wino_bgemm<WG_KK>(p, SG_K_WINO_GEMM_128, U, V, Mx, M, (int)Pds, K, 16, 2.0 * M * (double)K * 16.0 * p.Pd, s);   // flops of the real tiles
+  const bool direct = p.fold_kernel == SG_WK_NONE;
+  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (16.0 * (double)Pds * M + (double)d->N * M * 4.0 * TH * TW));
+    hipLaunchKernelGGL(wino_output_kernel, dim3(sg_cdiv((size_t)p.Pd * M, 256)), dim3(256), 0, s, (const float*)Mx, (const float*)nullptr,
+                       direct ? gx : gpad, d->N, M, 2 * TH, 2 * TW, Pds, SG_ACT_NONE, 0.f); }
   SG_LAUNCH_CHECK("sg_conv2d_wino_dgrad");
   if (direct) return 0;
   return sg_pad_upsample_bwd(gpad, gx, d->N * M, d->H, d->W, refl ? 1 : 0, d->upsample, stream);
 }
 
-extern "C" int sg_conv2d_wino_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, int act,
-                                  float slope, float* ut_save, float* v_save, void* ws, size_t ws_bytes, sgStream stream) {
-  SG_ARG_CHECK(wino_ok(d), "sg_conv2d_wino_fwd: unsupported desc");
-  SG_ARG_CHECK(x && w && y && ws && ws_bytes >= sg_conv2d_wino_ws_bytes(d), "sg_conv2d_wino_fwd: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const int M = d->Cout, C = d->C1;
-  const int LH = d->H * d->upsample, LW = d->W * d->upsample;
-  SG_ARG_CHECK(!wino43_shape(d) || (aligned16(x) && aligned16(y) && aligned16(w)),
-               "sg_conv2d_wino_fwd: F(4x4,3x3) shapes need 16-byte aligned x / y / w");
-  if (wino43_shape(d)) {
-    // F(4x4,3x3): U = G g G^T (into ut_save when the data gradient follows), V = B^T d B, 36 GEMMs, y = A^T Mx A + bias
-    const int HW = d->H * d->W;
-    const size_t P = (size_t)d->N * (d->H / 4) * (d->W / 4);
-    float* U_ws = reinterpret_cast<float*>(ws);
-    float* V_ws = U_ws + 36 * (size_t)M * C;
-    float* Mx = V_ws + 36 * P * (size_t)(C > M ? C : M);
-    float* U = ut_save ? ut_save : U_ws;
-    float* V = v_save ? v_save : V_ws;
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 45.0 * (double)M * C);
-      hipLaunchKernelGGL(w43_weight_kernel, dim3((M / 32) * (C / 32)), dim3(256), 0, s, w, U, M, C); }
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * C * HW + 36.0 * (double)P * C));
-      const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
-      w43_lds_attr(&w43_input_kernel, lds);
-      hipLaunchKernelGGL(w43_input_kernel, dim3(C / 64, d->N), dim3(256), lds, s, x, V, d->N, C, d->H, d->W); }
-    w43_gemm_fwd(U, V, Mx, M, (int)P, C, s);
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (36.0 * (double)P * M + (double)d->N * M * HW));
-      hipLaunchKernelGGL(w43_output_kernel, dim3(sg_cdiv(P * M, 256)), dim3(256), 0, s, (const float*)Mx, bias, y, d->N, M, d->H, d->W,
-                         act, slope); }
-    SG_LAUNCH_CHECK("sg_conv2d_wino_fwd");
-    return 0;
-  }
-  const size_t P = (size_t)d->N * (LH / 2) * (LW / 2);
-  float* U = reinterpret_cast<float*>(ws);
-  float* V_ws = U + 16 * (size_t)M * C;
-  float* Mx = V_ws + 16 * P * C;
-  SG_ARG_CHECK(v_save == nullptr || sg_conv2d_wino_v_floats(d) > 0, "sg_conv2d_wino_fwd: v_save given but unused by this desc");
-  float* V = v_save ? v_save : V_ws;               // [16][P][C1]: kept for the weight gradient when the caller wants it
-  SG_ARG_CHECK(ut_save == nullptr || sg_conv2d_wino_ut_floats(d) > 0, "sg_conv2d_wino_fwd: ut_save given but unused by this desc");
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (25.0 + (ut_save ? 16.0 : 0.0)) * (double)M * C);
-    const bool wrote = wino_weight(w, U, M, C, 0, s, ut_save);
-    SG_ARG_CHECK(ut_save == nullptr || wrote, "sg_conv2d_wino_fwd: the transposed filter transform needs the LDS weight kernel"); }
-  wino_input_pc(x, V, d->N, C, LH, LW, LH / 2, LW / 2, -1, d->pad_reflect ? 0 : 1, P, d->upsample == 2 ? 1 : 0, s);
-  wino_bgemm(U, V, Mx, M, (int)P, C, 2.0 * M * (double)C * 16.0 * P, s);
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (16.0 * (double)P * M + (double)d->N * M * LH * LW)); hipLaunchKernelGGL(wino_output_kernel, dim3(sg_cdiv(P * M, 256)), dim3(256), 0, s, (const float*)Mx, bias, y, d->N, M, LH, LW, P,
-                     act, slope); }
-  SG_LAUNCH_CHECK("sg_conv2d_wino_fwd");
-  return 0;
-}
-
 extern "C" int sg_conv2d_wino_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, const float* v_saved,
                                     const float* ytp_saved, void* ws, size_t ws_bytes, sgStream stream) {
-  SG_ARG_CHECK(wino_ok(d), "sg_conv2d_wino_wgrad: unsupported desc");
-  SG_ARG_CHECK(gy && x && gw && ws && ws_bytes >= sg_conv2d_wino_ws_bytes(d), "sg_conv2d_wino_wgrad: bad arguments");
+  sgWinoPlan p;
+  if (wino_plan_for("sg_conv2d_wino_wgrad", d, SG_WINO_WGRAD, wa_bit(SG_WA_X, x) | wa_bit(SG_WA_GY, gy),
+                    ws_bit(SG_WS_V, v_saved) | ws_bit(SG_WS_YTP, ytp_saved), &p))
+    return -1;
+  const bool f43 = p.form == SG_WF_F43;
+  const WinoLayout l = f43 ? wino43_layout(d, SG_WINO_WGRAD) : wino23_layout(d, SG_WINO_WGRAD, false);
+  SG_ARG_CHECK(gy && x && gw && ws && wino_ws_holds(ws_bytes, sg_conv2d_wino_ws_bytes(d), l), "sg_conv2d_wino_wgrad: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const int M = d->Cout, C = d->C1;
+  const int M = d->Cout, C = d->C1, P = p.P;
   const int LH = d->H * d->upsample, LW = d->W * d->upsample;
-  const size_t P = (size_t)d->N * (LH / 2) * (LW / 2);
-  SG_ARG_CHECK(!wino43_shape(d) || (aligned16(x) && aligned16(gy)),
-               "sg_conv2d_wino_wgrad: F(4x4,3x3) shapes need 16-byte aligned x / gy");
-  if (wino43_shape(d)) {
-    // F(4x4,3x3): T = Ytp^T x V over the tiles, gw = G^T T G; the operands come from this conv's forward / data gradient when
-    // the caller kept them, else they are rebuilt here
-    const int HW = d->H * d->W;
-    const size_t P4 = (size_t)d->N * (d->H / 4) * (d->W / 4);
-    float* T4 = reinterpret_cast<float*>(ws);       // [M][36][C]
-    const float* V = v_saved;
-    const float* Ytp = ytp_saved;
-    if (!(V && Ytp)) {
-      float* Vw = T4 + 36 * (size_t)M * C;
-      float* Yw = Vw + 36 * P4 * (size_t)(C > M ? C : M);
-      const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
-      { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * C * HW + 36.0 * (double)P4 * C));
-        w43_lds_attr(&w43_input_kernel, lds);
-        hipLaunchKernelGGL(w43_input_kernel, dim3(C / 64, d->N), dim3(256), lds, s, x, Vw, d->N, C, d->H, d->W); }
-      { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * M * HW + 36.0 * (double)P4 * M));
-        w43_lds_attr(&w43_gy_kernel, lds);
-        hipLaunchKernelGGL(w43_gy_kernel, dim3(M / 64, d->N), dim3(256), lds, s, gy, Yw, d->N, M, d->H, d->W); }
-      V = Vw; Ytp = Yw;
+  float* base = reinterpret_cast<float*>(ws);
+  float* T = base + l.at[0];                        // [M][16 or 36][C]
+  float *Vw = base + l.at[1], *Yw = base + l.at[2];
+  const bool saved = p.wgrad_src == SG_WSRC_SAVED;
+  if (f43) {
+    // F(4x4,3x3): T = Ytp^T x V over the tiles, gw = G^T T G
+    if (!saved) {
+      w43_launch_input(x, Vw, d->N, C, d->H, d->W, P, s);
+      w43_launch_gy(gy, Yw, d->N, M, d->H, d->W, P, s);
     }
-    w43_gemm_wgrad(Ytp, V, T4, M, C, (int)P4, s);
+    wino_bgemm<WG_XX>(p, SG_K_WINO43_GEMM, saved ? ytp_saved : Yw, saved ? v_saved : Vw, T, M, C, P, 36, 2.0 * 36.0 * M * (double)C * P, s);
     { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 45.0 * (double)M * C);
-      hipLaunchKernelGGL(w43_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T4, gw, M, C); }
+      hipLaunchKernelGGL(w43_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T, gw, M, C); }
     SG_LAUNCH_CHECK("sg_conv2d_wino_wgrad");
     return 0;
   }
-  float* T = reinterpret_cast<float*>(ws);          // [M][16][C]
-  if (v_saved && ytp_saved) {
-    // operands already built by the forward (V) and the adjoint data gradient (Ytp) of this conv in this step
-    SG_ARG_CHECK(sg_conv2d_wino_v_floats(d) > 0 && P % 32 == 0, "sg_conv2d_wino_wgrad: saved operands given but unused by this desc");
-    wino_bgemm_x(ytp_saved, v_saved, T, M, C, (int)P, 2.0 * M * (double)C * 16.0 * P, s);
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 25.0 * (double)M * C); hipLaunchKernelGGL(wino_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T, gw, M, C); }
-    SG_LAUNCH_CHECK("sg_conv2d_wino_wgrad");
-    return 0;
+  if (saved) {
+    // T[m][xi*C + c] = sum_p Ytp[xi][p][m] * V[xi][p][c]: straight from the tile-major operands the forward (V) and the adjoint
+    // data gradient (Ytp) of this conv built -- x-contiguous for a GEMM over p: no second input / gradient transform (2 launches
+    // and 2 x 41 MB per ResnetBlock conv saved)
+    wino_bgemm<WG_XX>(p, SG_K_WINO_GEMM_128, ytp_saved, v_saved, T, M, C, P, 16, 2.0 * M * (double)C * 16.0 * P, s);
+  } else {
+    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * C * d->H * d->W + 16.0 * (double)P * C));
+      hipLaunchKernelGGL(wino_input_kernel<1>, dim3(sg_cdiv((size_t)P * C, 256)), dim3(256), 0, s, x, Vw, d->N, C, LH, LW, LH / 2, LW / 2, -1,
+                         d->pad_reflect ? 0 : 1, (size_t)P, d->upsample == 2 ? 1 : 0); }
+    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * M * LH * LW + 16.0 * (double)P * M));
+      hipLaunchKernelGGL(wino_gy_kernel, dim3(sg_cdiv((size_t)P * M, 256)), dim3(256), 0, s, gy, Yw, d->N, M, LH, LW); }
+    wino_bgemm<WG_KK>(p, SG_K_WINO_GEMM_128, Yw, Vw, T, M, C, P, 16, 2.0 * M * (double)C * 16.0 * P, s);
   }
-  float* Vp = T + 16 * (size_t)M * C;               // [16][C][P]
-  float* Yt = Vp + 16 * P * C;                      // [16][M][P]
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * C * d->H * d->W + 16.0 * (double)P * C)); hipLaunchKernelGGL(wino_input_kernel<1>, dim3(sg_cdiv(P * C, 256)), dim3(256), 0, s, x, Vp, d->N, C, LH, LW, LH / 2, LW / 2, -1,
-                     d->pad_reflect ? 0 : 1, P, d->upsample == 2 ? 1 : 0); }
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * M * LH * LW + 16.0 * (double)P * M)); hipLaunchKernelGGL(wino_gy_kernel, dim3(sg_cdiv(P * M, 256)), dim3(256), 0, s, gy, Yt, d->N, M, LH, LW); }
-  wino_bgemm(Yt, Vp, T, M, C, (int)P, 2.0 * M * (double)C * 16.0 * P, s);
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 25.0 * (double)M * C); hipLaunchKernelGGL(wino_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T, gw, M, C); }
+  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 25.0 * (double)M * C);
+    hipLaunchKernelGGL(wino_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T, gw, M, C); }
   SG_LAUNCH_CHECK("sg_conv2d_wino_wgrad");
   return 0;
 }
 
 // ---- F(4x4,3x3) conv + InstanceNorm (see w43_output_in_kernel / w43_gy_in_kernel) ------------------------------------------------
-extern "C" int sg_conv2d_wino_in_supported(const sgConvDesc* d) {
-  if (!sg_opt(SG_OPT_WINO_IN_FUSE) || !wino43_shape(d)) return 0;
-  const int NT = (d->H / 4) * (d->W / 4);
-  return (NT <= 16 && sg_opt(SG_OPT_WINO_REUSE)) ? 1 : 0;      // <= 4 tiles per thread: planes up to 16x16
-}
-
-// tiles per thread of w43_output_in_kernel
-static int w43_norm_tiles(const sgConvDesc* d) { return (d->H / 4) * (d->W / 4) <= 4 ? 1 : 4; }
-
 extern "C" int sg_conv2d_wino_fwd_instnorm(const sgConvDesc* d, const float* x, const float* w, const float* bias, const float* skip,
                                            float* ypre, float* out, float* mean, float* rstd, float eps, int act, float slope,
                                            float* ut_save, float* v_save, void* ws, size_t ws_bytes, sgStream stream) {
-  SG_ARG_CHECK(sg_conv2d_wino_in_supported(d), "sg_conv2d_wino_fwd_instnorm: unsupported desc");
-  SG_ARG_CHECK(x && w && ypre && out && mean && rstd && ws && ws_bytes >= sg_conv2d_wino_ws_bytes(d),
+  sgWinoPlan p;
+  if (wino_plan_for("sg_conv2d_wino_fwd_instnorm", d, SG_WINO_FWD_INSTNORM,
+                    wa_bit(SG_WA_X, x) | wa_bit(SG_WA_W, w) | (aligned16(ypre) && aligned16(out) && aligned16(skip) ? SG_WA_Y : 0),
+                    ws_bit(SG_WS_UT, ut_save) | ws_bit(SG_WS_V, v_save), &p))
+    return -1;
+  const WinoLayout l = wino43_layout(d, SG_WINO_FWD_INSTNORM);
+  SG_ARG_CHECK(x && w && ypre && out && mean && rstd && ws && wino_ws_holds(ws_bytes, sg_conv2d_wino_ws_bytes(d), l),
                "sg_conv2d_wino_fwd_instnorm: bad arguments");
-  SG_ARG_CHECK(aligned16(x) && aligned16(w) && aligned16(ypre) && aligned16(out) && (!skip || aligned16(skip)),
-               "sg_conv2d_wino_fwd_instnorm: operands must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const int M = d->Cout, C = d->C1, HW = d->H * d->W, NT = (d->H / 4) * (d->W / 4);
-  const size_t P = (size_t)d->N * NT;
-  float* U_ws = reinterpret_cast<float*>(ws);
-  float* V_ws = U_ws + 36 * (size_t)M * C;
-  float* Mx = V_ws + 36 * P * (size_t)(C > M ? C : M);        // [P][36][M]
-  float* U = ut_save ? ut_save : U_ws;
-  float* V = v_save ? v_save : V_ws;
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 45.0 * (double)M * C);
-    hipLaunchKernelGGL(w43_weight_kernel, dim3((M / 32) * (C / 32)), dim3(256), 0, s, w, U, M, C); }
-  { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * C * HW + 36.0 * (double)P * C));
-    const size_t lds = (size_t)64 * (HW + 1) * sizeof(float);
-    w43_lds_attr(&w43_input_kernel, lds);
-    hipLaunchKernelGGL(w43_input_kernel, dim3(C / 64, d->N), dim3(256), lds, s, x, V, d->N, C, d->H, d->W); }
+  const int M = d->Cout, C = d->C1, HW = d->H * d->W, P = p.P;
+  float* base = reinterpret_cast<float*>(ws);
+  float* U = ut_save ? ut_save : base + l.at[0];
+  float* V = v_save ? v_save : base + l.at[1];
+  float* Mx = base + l.at[2];                       // [P][36][M]
+  w43_launch_weight(w, U, M, C, s);
+  w43_launch_input(x, V, d->N, C, d->H, d->W, P, s);
   // tile-major result Mx[p][xi*M + m] = sum_c V[xi][p][c] U[xi][m][c]: the same GEMM with the operand roles swapped
-  wino_bgemm_tile(w43_tile(), V, U, Mx, (int)P, M, C, 2.0 * 36.0 * M * (double)P * C, s, 36, SG_K_WINO43_GEMM);
+  wino_bgemm<WG_KK>(p, SG_K_WINO43_GEMM, V, U, Mx, P, M, C, 36, 2.0 * 36.0 * M * (double)P * C, s);
   { SgProfScope xf(SG_K_INSTNORM, s, 0, 4.0 * (36.0 * (double)P * M + (double)d->N * M * HW * (skip ? 3.0 : 2.0)));
     const size_t lds = (size_t)(128 * (HW + 1) + 256) * sizeof(float);
-    if (w43_norm_tiles(d) == 1) {
-      w43_lds_attr(&w43_output_in_kernel<1>, lds);
+    if (p.norm_tiles == 1) {
+      wino_lds_attr(&w43_output_in_kernel<1>, lds);
       hipLaunchKernelGGL(w43_output_in_kernel<1>, dim3(M / 64, d->N), dim3(256), lds, s, (const float*)Mx, bias, skip, ypre, out, mean,
                          rstd, d->N, M, d->H, d->W, eps, act, slope);
     } else {
-      w43_lds_attr(&w43_output_in_kernel<4>, lds);
+      wino_lds_attr(&w43_output_in_kernel<4>, lds);
       hipLaunchKernelGGL(w43_output_in_kernel<4>, dim3(M / 64, d->N), dim3(256), lds, s, (const float*)Mx, bias, skip, ypre, out, mean,
                          rstd, d->N, M, d->H, d->W, eps, act, slope);
     } }
@@ -2224,38 +2336,31 @@ extern "C" int sg_conv2d_wino_dgrad_instnorm(const sgConvDesc* d, const float* g
                                              const float* rstd, int act, float slope, const float* w, float* gconv, float* gx,
                                              float* gb, const float* ut_saved, float* ytp_save, void* ws, size_t ws_bytes,
                                              sgStream stream) {
-  SG_ARG_CHECK(sg_conv2d_wino_in_supported(d), "sg_conv2d_wino_dgrad_instnorm: unsupported desc");
-  SG_ARG_CHECK(gout && ypre && mean && rstd && w && gconv && ws && ws_bytes >= sg_conv2d_wino_ws_bytes(d),
+  sgWinoPlan p;
+  if (wino_plan_for("sg_conv2d_wino_dgrad_instnorm", d, SG_WINO_DGRAD_INSTNORM,
+                    (aligned16(gout) && aligned16(ypre) && aligned16(gconv) ? SG_WA_GY : 0) | wa_bit(SG_WA_GX, gx) | wa_bit(SG_WA_W, w),
+                    ws_bit(SG_WS_UT, ut_saved) | ws_bit(SG_WS_YTP, ytp_save), &p))
+    return -1;
+  const WinoLayout l = wino43_layout(d, SG_WINO_DGRAD_INSTNORM);
+  SG_ARG_CHECK(gout && ypre && mean && rstd && w && gconv && ws && wino_ws_holds(ws_bytes, sg_conv2d_wino_ws_bytes(d), l),
                "sg_conv2d_wino_dgrad_instnorm: bad arguments");
-  SG_ARG_CHECK(aligned16(gout) && aligned16(ypre) && aligned16(gconv) && aligned16(w) && (!gx || aligned16(gx)),
-               "sg_conv2d_wino_dgrad_instnorm: operands must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const int M = d->C1, K = d->Cout, HW = d->H * d->W;
-  const size_t P = (size_t)d->N * (d->H / 4) * (d->W / 4);
-  float* Uw = reinterpret_cast<float*>(ws);
-  float* Ytp_ws = Uw + 36 * (size_t)M * K;
-  float* G = Ytp_ws + 36 * P * (size_t)(K > M ? K : M);
-  float* Ytp = ytp_save ? ytp_save : Ytp_ws;
-  // [N][Cout] partial bias gradients: behind G in the workspace (the weight gradient's T region: free during this call)
-  float* gb_part = gb ? G + 36 * P * (size_t)M : nullptr;
+  const int M = d->C1, K = d->Cout, HW = d->H * d->W, P = p.P;
+  float* base = reinterpret_cast<float*>(ws);
+  float* Ytp = ytp_save ? ytp_save : base + l.at[1];
+  float* G = base + l.at[2];
+  float* gb_part = gb ? base + l.at[3] : nullptr;   // [N][Cout] partial bias gradients
   { SgProfScope xf(SG_K_INSTNORM_BWD, s, 0, 4.0 * ((double)d->N * K * HW * 3.0 + 36.0 * (double)P * K));
     const size_t lds = (size_t)(128 * (HW + 1) + 768) * sizeof(float);
-    w43_lds_attr(&w43_gy_in_kernel, lds);
+    wino_lds_attr(&w43_gy_in_kernel, lds);
     hipLaunchKernelGGL(w43_gy_in_kernel, dim3(K / 64, d->N), dim3(256), lds, s, gout, ypre, mean, rstd, gconv, Ytp, gb_part, d->N, K,
                        d->H, d->W, act, slope);
     if (gb) hipLaunchKernelGGL(w43_bias_sum_kernel, dim3(sg_cdiv(K, 256)), dim3(256), 0, s, (const float*)gb_part, gb, d->N, K); }
   if (gx) {
     const float* U = ut_saved;
-    if (U == nullptr) {
-      SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 45.0 * (double)M * K);
-      hipLaunchKernelGGL(w43_weight_kernel, dim3((K / 32) * (M / 32)), dim3(256), 0, s, w, Uw, K, M);
-      U = Uw;
-    }
-    w43_gemm_dgrad(Ytp, U, G, (int)P, M, K, s);
-    { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (36.0 * (double)P * M + (double)d->N * M * HW));
-      const size_t lds = (size_t)64 * ((d->H + 2) * (d->W + 2) + 1 + HW + 1) * sizeof(float);
-      w43_lds_attr(&w43_fold_kernel, lds);
-      hipLaunchKernelGGL(w43_fold_kernel, dim3(M / 64, d->N), dim3(256), lds, s, (const float*)G, gx, d->N, M, d->H, d->W); }
+    if (p.wt_kernel != SG_WK_NONE) { w43_launch_weight(w, base + l.at[0], K, M, s); U = base + l.at[0]; }
+    wino_bgemm<WG_KX>(p, SG_K_WINO43_GEMM, Ytp, U, G, P, M, K, 36, 2.0 * 36.0 * P * (double)M * K, s);
+    w43_launch_fold(G, gx, d->N, M, d->H, d->W, P, s);
   }
   SG_LAUNCH_CHECK("sg_conv2d_wino_dgrad_instnorm");
   return 0;
@@ -2266,205 +2371,86 @@ extern "C" int sg_conv2d_wino24_supported(const sgConvDesc* d) {
   return (sg_opt(SG_OPT_WINO24) && w24_plan(d, nullptr)) ? 1 : 0;
 }
 extern "C" size_t sg_conv2d_wino24_ws_bytes(const sgConvDesc* d) {
-  W24Plan p;
-  if (!w24_plan(d, &p)) return 0;
-  const size_t M = d->Cout, C = d->C1;
-  const size_t f = 25 * (M * C + p.Ps * C + p.Ps * M);
-  const size_t g = 25 * (M * C + p.Pds * M + p.Pds * C);
-  const size_t w = 25 * (size_t)p.S * ((size_t)p.Pc * (M + C) + M * C);
-  const size_t mx = f > g ? (f > w ? f : w) : (g > w ? g : w);
-  return mx * sizeof(float) + 256;
+  sgWinoPlan p;
+  const char* err;
+  return wino_launch_plan(d, SG_WINO24_FWD, SG_WA_ALL, 0, &p, &err) == 0 ? wino24_ws_bytes(d, p) : 0;
 }
+namespace {
+// the shared head of the three F(2x2,4x4) launchers: plan, layout, workspace
+int w24_begin(const char* who, const sgConvDesc* d, int entry, const float* gw, bool ptrs_ok, size_t ws_bytes, sgWinoPlan* p, WinoLayout* l) {
+  if (wino_plan_for(who, d, entry, wa_bit(SG_WA_GW, gw), 0, p)) return -1;
+  *l = wino24_layout(d, *p, entry);
+  SG_ARG_CHECK(ptrs_ok && wino_ws_holds(ws_bytes, wino24_ws_bytes(d, *p), *l), "%s: bad arguments", who);
+  return 0;
+}
+}  // namespace
 extern "C" int sg_conv2d_wino24_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, int act,
                                     float slope, void* ws, size_t ws_bytes, sgStream stream) {
-  W24Plan p;
-  SG_ARG_CHECK(w24_plan(d, &p), "sg_conv2d_wino24_fwd: unsupported desc");
-  SG_ARG_CHECK(x && w && y && ws && ws_bytes >= sg_conv2d_wino24_ws_bytes(d), "sg_conv2d_wino24_fwd: bad arguments");
+  sgWinoPlan p;
+  WinoLayout l;
+  if (w24_begin("sg_conv2d_wino24_fwd", d, SG_WINO24_FWD, nullptr, x && w && y && ws, ws_bytes, &p, &l)) return -1;
   hipStream_t s = (hipStream_t)stream;
   const int M = d->Cout, C = d->C1;
-  float* U = reinterpret_cast<float*>(ws);
-  float* V = U + (size_t)25 * M * C;
-  float* Mx = V + 25 * p.Ps * C;
+  float* base = reinterpret_cast<float*>(ws);
+  float *U = base + l.at[0], *V = base + l.at[1], *Mx = base + l.at[2];
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 26.0 * (double)M * C);
     hipLaunchKernelGGL(w24_weight_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, w, U, M, C, 0); }
-  w24_input_pc(x, V, d->N, C, d->H, d->W, p.TH, p.TW, -d->pad, p.Ps, s);
-  wino_bgemm(U, V, Mx, M, (int)p.Ps, C, 2.0 * M * (double)C * 25.0 * p.P, s, 25);
+  w24_input_pc(p.in_kernel, x, V, d->N, C, d->H, d->W, p.TH, p.TW, -d->pad, (size_t)p.Ps, s);
+  wino_bgemm<WG_KK>(p, SG_K_WINO24_GEMM, U, V, Mx, M, p.Ps, C, 25, 2.0 * M * (double)C * 25.0 * p.P, s);
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (25.0 * (double)p.P * M + (double)d->N * M * d->OH * d->OW));
-    hipLaunchKernelGGL(w24_output_kernel, dim3(sg_cdiv(p.P * M, 256)), dim3(256), 0, s, (const float*)Mx, bias, y, d->N, M, d->OH,
-                       d->OW, p.TH, p.TW, p.Ps, act, slope); }
+    hipLaunchKernelGGL(w24_output_kernel, dim3(sg_cdiv((size_t)p.P * M, 256)), dim3(256), 0, s, (const float*)Mx, bias, y, d->N, M, d->OH,
+                       d->OW, p.TH, p.TW, (size_t)p.Ps, act, slope); }
   SG_LAUNCH_CHECK("sg_conv2d_wino24_fwd");
   return 0;
 }
 extern "C" int sg_conv2d_wino24_dgrad(const sgConvDesc* d, const float* gy, const float* w, float* gx, void* ws, size_t ws_bytes,
                                       sgStream stream) {
-  W24Plan p;
-  SG_ARG_CHECK(w24_plan(d, &p), "sg_conv2d_wino24_dgrad: unsupported desc");
-  SG_ARG_CHECK(gy && w && gx && ws && ws_bytes >= sg_conv2d_wino24_ws_bytes(d), "sg_conv2d_wino24_dgrad: bad arguments");
+  sgWinoPlan p;
+  WinoLayout l;
+  if (w24_begin("sg_conv2d_wino24_dgrad", d, SG_WINO24_DGRAD, nullptr, gy && w && gx && ws, ws_bytes, &p, &l)) return -1;
   hipStream_t s = (hipStream_t)stream;
   const int M = d->C1, K = d->Cout;             // gx[ci] = sum_co rot(w[co][ci]) * gy[co], padding 3 - pad
-  float* U = reinterpret_cast<float*>(ws);
-  float* V = U + (size_t)25 * M * K;
-  float* Mx = V + 25 * p.Pds * K;
+  float* base = reinterpret_cast<float*>(ws);
+  float *U = base + l.at[0], *V = base + l.at[1], *Mx = base + l.at[2];
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * 26.0 * (double)M * K);
     hipLaunchKernelGGL(w24_weight_kernel, dim3(sg_cdiv((size_t)M * K, 256)), dim3(256), 0, s, w, U, M, K, 1); }
-  w24_input_pc(gy, V, d->N, K, d->OH, d->OW, p.THd, p.TWd, -(3 - d->pad), p.Pds, s);
-  wino_bgemm(U, V, Mx, M, (int)p.Pds, K, 2.0 * M * (double)K * 25.0 * p.Pd, s, 25);
+  w24_input_pc(p.in_kernel, gy, V, d->N, K, d->OH, d->OW, p.THd, p.TWd, -(3 - d->pad), (size_t)p.Pds, s);
+  wino_bgemm<WG_KK>(p, SG_K_WINO24_GEMM, U, V, Mx, M, p.Pds, K, 25, 2.0 * M * (double)K * 25.0 * p.Pd, s);
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (25.0 * (double)p.Pd * M + (double)d->N * M * d->H * d->W));
-    hipLaunchKernelGGL(w24_output_kernel, dim3(sg_cdiv(p.Pd * M, 256)), dim3(256), 0, s, (const float*)Mx, (const float*)nullptr, gx,
-                       d->N, M, d->H, d->W, p.THd, p.TWd, p.Pds, SG_ACT_NONE, 0.f); }
+    hipLaunchKernelGGL(w24_output_kernel, dim3(sg_cdiv((size_t)p.Pd * M, 256)), dim3(256), 0, s, (const float*)Mx, (const float*)nullptr, gx,
+                       d->N, M, d->H, d->W, p.THd, p.TWd, (size_t)p.Pds, SG_ACT_NONE, 0.f); }
   SG_LAUNCH_CHECK("sg_conv2d_wino24_dgrad");
   return 0;
 }
 extern "C" int sg_conv2d_wino24_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, void* ws, size_t ws_bytes,
                                       sgStream stream) {
-  W24Plan p;
-  SG_ARG_CHECK(w24_plan(d, &p), "sg_conv2d_wino24_wgrad: unsupported desc");
-  SG_ARG_CHECK(gy && x && gw && ws && ws_bytes >= sg_conv2d_wino24_ws_bytes(d), "sg_conv2d_wino24_wgrad: bad arguments");
-  SG_ARG_CHECK(aligned16(gw), "sg_conv2d_wino24_wgrad: gw must be 16-byte aligned");
+  sgWinoPlan p;
+  WinoLayout l;
+  if (w24_begin("sg_conv2d_wino24_wgrad", d, SG_WINO24_WGRAD, gw, gy && x && gw && ws, ws_bytes, &p, &l)) return -1;
   hipStream_t s = (hipStream_t)stream;
   const int M = d->Cout, C = d->C1;
   const size_t Pall = (size_t)p.S * p.Pc;       // tiles incl. the zero padding of the last k-chunk
-  float* Yt = reinterpret_cast<float*>(ws);
-  float* V = Yt + 25 * Pall * M;
-  float* T = V + 25 * Pall * C;
+  float* base = reinterpret_cast<float*>(ws);
+  float *Yt = base + l.at[0], *V = base + l.at[1], *T = base + l.at[2];
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * M * d->OH * d->OW + 25.0 * (double)Pall * M));
     hipLaunchKernelGGL(w24_gy_kernel, dim3(sg_cdiv(Pall * M, 256)), dim3(256), 0, s, gy, Yt, d->N, M, d->OH, d->OW, p.TH, p.TW, Pall,
                        p.Pc, p.S); }
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * ((double)d->N * C * d->H * d->W + 25.0 * (double)Pall * C));
     hipLaunchKernelGGL(w24_input_kernel<1>, dim3(sg_cdiv(Pall * C, 256)), dim3(256), 0, s, x, V, d->N, C, d->H, d->W, p.TH, p.TW,
                        -d->pad, Pall, p.Pc, p.S); }
-  wino_bgemm(Yt, V, T, M, C, p.Pc, 2.0 * M * (double)C * 25.0 * p.P, s, 25 * p.S);
+  wino_bgemm<WG_KK>(p, SG_K_WINO24_GEMM, Yt, V, T, M, C, p.Pc, 25 * p.S, 2.0 * M * (double)C * 25.0 * p.P, s);
   { SgProfScope xf(SG_K_WINO_XFORM, s, 0, 4.0 * (25.0 * p.S + 16.0) * (double)M * C);
     hipLaunchKernelGGL(w24_wgrad_output_kernel, dim3(sg_cdiv((size_t)M * C, 256)), dim3(256), 0, s, (const float*)T, gw, M, C, p.S); }
   SG_LAUNCH_CHECK("sg_conv2d_wino24_wgrad");
   return 0;
 }
 
-// ---- host-only: the plan of a Winograd entry point (see the header), from the predicates the launchers above call -------------
-namespace {
-void wino_plan_gemm(sgWinoPlan* p, int bm, int bn, int nsub, int kfold, int pipe) {
-  p->bm = bm; p->bn = bn; p->nsub = nsub; p->kfold = kfold; p->pipe = pipe;
-}
-// wino_bgemm(A, B, C, M, cols, K, .., NB)
-void wino_plan_bgemm(sgWinoPlan* p, int NB, int M, int cols, int K) {
-  const int t = wino_bgemm_sel(NB, M, cols, K);
-  if (t == 1) wino_plan_gemm(p, 64, 128, 2, 0, 0);
-  else if (t == 2) wino_plan_gemm(p, 64, 64, 2, 0, 0);
-  else wino_plan_gemm(p, 128, 128, 2, 0, sg_opt(SG_OPT_WINO_PIPE) == 2 ? 2 : 1);
-}
-// launch_w43 over a reduction of K
-void wino_plan_w43(sgWinoPlan* p, int K) { wino_plan_gemm(p, 64, 64, w43_deep() ? 2 : 1, w43_kfold(K), 0); }
-}  // namespace
-
+// ---- host-only: THE launch plan of a Winograd entry point, as wino_launch_plan makes it for the launchers above (see the header)
 extern "C" int sg_conv2d_wino_plan(const sgConvDesc* d, int entry, int align_mask, int saved_mask, sgWinoPlan* plan) {
   SG_ARG_CHECK(d && plan && entry >= SG_WINO_FWD && entry <= SG_WINO24_WGRAD, "sg_conv2d_wino_plan: bad arguments");
   SG_ARG_CHECK((align_mask & ~SG_WA_ALL) == 0 && (saved_mask & ~(SG_WS_UT | SG_WS_V | SG_WS_YTP)) == 0, "sg_conv2d_wino_plan: bad mask");
-  const bool x16 = align_mask & SG_WA_X, w16 = align_mask & SG_WA_W, y16 = align_mask & SG_WA_Y, gy16 = align_mask & SG_WA_GY,
-             gx16 = align_mask & SG_WA_GX, gw16 = align_mask & SG_WA_GW;
-  const bool ut = saved_mask & SG_WS_UT, v = saved_mask & SG_WS_V, ytp = saved_mask & SG_WS_YTP;
-  sgWinoPlan p = {};
-  if (entry >= SG_WINO24_FWD) {
-    W24Plan w;
-    SG_ARG_CHECK(w24_plan(d, &w), "sg_conv2d_wino_plan: unsupported desc");
-    SG_ARG_CHECK(saved_mask == 0, "sg_conv2d_wino_plan: F(2x2,4x4) takes no saved operands");
-    p.form = SG_WF_F24;
-    p.P = (int)w.P; p.Ps = (int)w.Ps; p.Pd = (int)w.Pd; p.Pds = (int)w.Pds;
-    p.TH = w.TH; p.TW = w.TW; p.THd = w.THd; p.TWd = w.TWd; p.S = w.S; p.Pc = w.Pc;
-    if (entry == SG_WINO24_FWD) {
-      p.in_kernel = w24_input_small(d->N, d->C1, d->H, d->W, w.TH, nullptr, nullptr) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
-      p.wt_kernel = SG_WK_WT_PLAIN;
-      wino_plan_bgemm(&p, 25, d->Cout, (int)w.Ps, d->C1);
-    } else if (entry == SG_WINO24_DGRAD) {
-      p.in_kernel = w24_input_small(d->N, d->Cout, d->OH, d->OW, w.THd, nullptr, nullptr) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
-      p.wt_kernel = SG_WK_WT_PLAIN;
-      wino_plan_bgemm(&p, 25, d->C1, (int)w.Pds, d->Cout);
-    } else {
-      SG_ARG_CHECK(gw16, "sg_conv2d_wino_plan: gw must be 16-byte aligned");
-      p.in_kernel = SG_WK_IN_GENERAL;
-      p.wgrad_src = SG_WSRC_REBUILT;
-      wino_plan_bgemm(&p, 25 * w.S, d->Cout, d->C1, w.Pc);
-    }
-    *plan = p;
-    return 0;
-  }
-  SG_ARG_CHECK(wino_ok(d), "sg_conv2d_wino_plan: unsupported desc");
-  const bool fused = entry == SG_WINO_FWD_INSTNORM || entry == SG_WINO_DGRAD_INSTNORM;
-  SG_ARG_CHECK(!fused || sg_conv2d_wino_in_supported(d), "sg_conv2d_wino_plan: unsupported desc");
-  const int LH = d->H * d->upsample, LW = d->W * d->upsample, refl = d->pad_reflect;
-  const bool f43 = wino43_shape(d);
-  if (f43) {
-    p.form = SG_WF_F43;
-    p.P = p.Ps = p.Pd = p.Pds = d->N * (d->H / 4) * (d->W / 4);
-    if (entry == SG_WINO_FWD || entry == SG_WINO_FWD_INSTNORM) {
-      SG_ARG_CHECK(x16 && w16 && y16, "sg_conv2d_wino_plan: F(4x4,3x3) shapes need 16-byte aligned x / y / w");
-      SG_ARG_CHECK(!ytp, "sg_conv2d_wino_plan: the forward takes no ytp_save");
-      p.in_kernel = SG_WK_IN_LDS; p.wt_kernel = SG_WK_WT_LDS;
-      wino_plan_w43(&p, d->C1);
-      if (fused) p.norm_tiles = w43_norm_tiles(d);
-    } else if (entry == SG_WINO_DGRAD || entry == SG_WINO_DGRAD_INSTNORM) {
-      SG_ARG_CHECK(gy16 && gx16 && w16, "sg_conv2d_wino_plan: F(4x4,3x3) shapes need 16-byte aligned gy / gx / w");
-      SG_ARG_CHECK(!v, "sg_conv2d_wino_plan: the data gradient takes no v_save");
-      p.in_kernel = SG_WK_IN_LDS; p.wt_kernel = ut ? SG_WK_NONE : SG_WK_WT_LDS; p.fold_kernel = SG_WK_FOLD_F43;
-      wino_plan_w43(&p, d->Cout);
-    } else {
-      SG_ARG_CHECK(x16 && gy16, "sg_conv2d_wino_plan: F(4x4,3x3) shapes need 16-byte aligned x / gy");
-      SG_ARG_CHECK(!ut, "sg_conv2d_wino_plan: the weight gradient takes no ut_save");
-      const bool saved = v && ytp;
-      p.wgrad_src = saved ? SG_WSRC_SAVED : SG_WSRC_REBUILT;
-      p.in_kernel = saved ? SG_WK_NONE : SG_WK_IN_LDS;
-      const int t = w43_wgrad_sel(d->Cout, d->C1, p.P);
-      if (t == 1) wino_plan_gemm(&p, 128, 128, 2, 0, 0);
-      else if (t == 2) wino_plan_gemm(&p, 64, 128, 2, 0, 0);
-      else wino_plan_gemm(&p, 64, 64, w43_deep() ? 2 : 1, 0, 0);
-    }
-    *plan = p;
-    return 0;
-  }
-  p.P = p.Ps = d->N * (LH / 2) * (LW / 2);
-  p.Pd = d->N * (LH / 2 + (refl ? 1 : 0)) * (LW / 2 + (refl ? 1 : 0));
-  p.Pds = (int)wino_dgrad_tiles(d);
-  if (entry == SG_WINO_FWD) {
-    SG_ARG_CHECK(!ytp, "sg_conv2d_wino_plan: the forward takes no ytp_save");
-    SG_ARG_CHECK(!v || sg_conv2d_wino_v_floats(d) > 0, "sg_conv2d_wino_plan: v_save given but unused by this desc");
-    SG_ARG_CHECK(!ut || sg_conv2d_wino_ut_floats(d) > 0, "sg_conv2d_wino_plan: ut_save given but unused by this desc");
-    const bool lds = wino_weight_lds(d->Cout, d->C1, w16);
-    SG_ARG_CHECK(!ut || lds, "sg_conv2d_wino_plan: the transposed filter transform needs the LDS weight kernel");
-    p.form = SG_WF_F23_GENERIC;
-    p.wt_kernel = lds ? SG_WK_WT_LDS : SG_WK_WT_PLAIN;
-    p.in_kernel = wino_input_small(d->C1, LH, LW, d->upsample == 2 ? 1 : 0, x16) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
-    wino_plan_bgemm(&p, 16, d->Cout, p.P, d->C1);
-  } else if (entry == SG_WINO_DGRAD) {
-    SG_ARG_CHECK(!v, "sg_conv2d_wino_plan: the data gradient takes no v_save");
-    const int M = d->C1, K = d->Cout;
-    if (wino_dgrad_adjoint(d, gy16, gx16)) {
-      p.form = SG_WF_F23_ADJOINT;
-      p.Pd = p.Pds = p.P;                 // over the output tiles
-      p.in_kernel = SG_WK_IN_LDS;
-      p.wt_kernel = ut ? SG_WK_NONE : (wino_weight_lds(M, K, w16) ? SG_WK_WT_LDS : SG_WK_WT_PLAIN);
-      p.fold_kernel = sg_opt(SG_OPT_WINO_FOLD_CELLS) ? SG_WK_FOLD_CELLS : SG_WK_FOLD_WALK;
-      wino_plan_bgemm(&p, 16, p.P, M, K);
-    } else {
-      SG_ARG_CHECK(!ytp, "sg_conv2d_wino_plan: ytp_save given but this desc does not run the adjoint form");
-      p.form = SG_WF_F23_GENERIC;
-      p.wt_kernel = wino_weight_lds(M, K, w16) ? SG_WK_WT_LDS : SG_WK_WT_PLAIN;       // (a ut_saved is not read by this form)
-      p.in_kernel = wino_input_small(K, LH, LW, 0, gy16) ? SG_WK_IN_LDS : SG_WK_IN_GENERAL;
-      p.fold_kernel = (!refl && d->upsample == 1) ? SG_WK_NONE : SG_WK_FOLD_PAD_UPSAMPLE;
-      wino_plan_bgemm(&p, 16, M, p.Pds, K);
-    }
-  } else {
-    SG_ARG_CHECK(entry == SG_WINO_WGRAD, "sg_conv2d_wino_plan: unsupported desc");
-    SG_ARG_CHECK(!ut, "sg_conv2d_wino_plan: the weight gradient takes no ut_save");
-    p.form = SG_WF_F23_GENERIC;
-    if (v && ytp) {
-      SG_ARG_CHECK(sg_conv2d_wino_v_floats(d) > 0 && p.P % 32 == 0, "sg_conv2d_wino_plan: saved operands given but unused by this desc");
-      p.wgrad_src = SG_WSRC_SAVED;
-      wino_plan_gemm(&p, 128, 128, 2, 0, 0);         // wino_bgemm_x
-    } else {
-      p.wgrad_src = SG_WSRC_REBUILT;
-      p.in_kernel = SG_WK_IN_GENERAL;
-      wino_plan_bgemm(&p, 16, d->Cout, d->C1, p.P);
-    }
-  }
+  sgWinoPlan p;
+  if (wino_plan_for("sg_conv2d_wino_plan", d, entry, align_mask, saved_mask, &p)) return -1;
   *plan = p;
   return 0;
 }

@@ -425,6 +425,51 @@ def test_fused_conv_instnorm_pair(L, name, act, with_skip):
     fused_pair(L, WC.BY_NAME[name], act, with_skip, noter('F43_fused'))
 
 
+def test_fused_backward_bias_partials_stay_inside_the_workspace(L):
+    """The fused data gradient keeps its [N][Cout] partial bias gradients in the workspace, behind G.  Per-object convolutions on
+    4x4 planes are where that region is largest against the rest (N = 4672 > 36 * C1: 598 016 floats where the filter-sized block
+    behind G has 589 824).  gx = NULL: no GEMM runs, so the reference is the InstanceNorm backward and a sum in float64.  The
+    workspace is exactly what sg_conv2d_wino_ws_bytes reports, with guard values behind it."""
+    N, C, H, W, act, slope = 4672, 128, 4, 4, 2, 0.2
+    d = WC.make_desc(N, C, H, W, C, 3, 1, 1, True, 1, H, W)
+    plan = WC.wino_plan(L, d, WC.WINO_DGRAD_INSTNORM, WC.WA_ALL, 0)
+    assert plan is not None, L.sg_last_error_string().decode()
+    assert (plan['form'], plan['P'], plan['wt_kernel'], plan['fold_kernel']) == (WC.WF_F43, N * (H // 4) * (W // 4), WC.WK_WT_LDS, WC.WK_FOLD_F43), plan
+    rng = WC.rng_of('fused backward, 4672 images of 4x4')
+    gout, ypre = WC.f32(rng, (N, C, H, W)), WC.f32(rng, (N, C, H, W))
+    y64 = ypre.astype(np.float64)
+    mean = y64.mean(axis=(2, 3)).astype(np.float32)
+    rstd = (1.0 / np.sqrt(y64.var(axis=(2, 3)) + EPS)).astype(np.float32)
+    nbytes = int(L.sg_conv2d_wino_ws_bytes(dref(d)))
+    assert nbytes > 0 and nbytes % 4 == 0
+    guards = 1024
+    ws = torch.empty(nbytes // 4 + guards, dtype=torch.float32, device=DEV)
+    assert ws.data_ptr() % 16 == 0
+    ws[nbytes // 4:].fill_(G.GUARD)
+    god, yd, md, rd, wd = place(gout), place(ypre), place(mean), place(rstd), place(np.zeros(C * C * 9, dtype=np.float32))
+    gconv_d, gb_d = outbuf(N * C * H * W), outbuf(C)
+    call(L, 'sg_conv2d_wino_dgrad_instnorm', dref(d), ptr(god), ptr(yd), ptr(md), ptr(rd), act, slope, ptr(wd), ptr(gconv_d), None,
+         ptr(gb_d), None, None, ptr(ws), nbytes, stream())
+    gconv, gb = take(gconv_d, (N, C, H, W)), take(gb_d, (C,))
+    assert bool((ws[nbytes // 4:] == G.GUARD).all()), 'the fused data gradient wrote behind its workspace'
+    # the norm's gradient in float64 of the operands as passed (mean / rstd rounded to fp32); units at the activation kink left out
+    r64 = rstd.astype(np.float64)[:, :, None, None]
+    z = (y64 - mean.astype(np.float64)[:, :, None, None]) * r64
+    gz = gout.astype(np.float64) * _act_grad(z, act, slope)
+    g64 = r64 * (gz - gz.mean(axis=(2, 3), keepdims=True) - z * (gz * z).mean(axis=(2, 3), keepdims=True))
+    kink = np.abs(z) <= 1e-5
+    assert kink.mean() <= 1e-4, '%d of %d units at the kink' % (int(kink.sum()), kink.size)
+    close(torch.from_numpy(np.where(kink, g64, gconv)), g64, 1e-4, 'fused backward 4672x4x4 gconv')
+    # gb: the sum of the GPU's own gconv, reduction length N * H * W; baseline of the rms line: the same sum in float32, per image
+    # and then over the images in ascending order (w43_bias_sum_kernel's order)
+    c64 = gconv.astype(np.float64)
+    gb64 = c64.sum(axis=(0, 2, 3))
+    gbound = WC.gamma(N * H * W) * np.abs(c64).sum(axis=(0, 2, 3))
+    per_image = gconv.reshape(N, C, H * W).sum(axis=2, dtype=np.float32)
+    gb32 = np.cumsum(per_image, axis=0, dtype=np.float32)[-1]
+    WC.check(gb, gb64, gbound, WC.rms(gb32.astype(np.float64) - gb64), 'fused backward 4672x4x4 gb', noter('fused_gb_large_n'))
+
+
 # =============================================================================================
 # argument checks: non-zero before any launch, outputs untouched
 # =============================================================================================
