@@ -93,6 +93,9 @@ int sg_conv2d_dgrad(const sgConvDesc* d, const float* gy, const float* w, float*
 int sg_conv2d_fwd_perimage(const sgConvDesc* d, const float* x1, const float* x2, const float* wimg, const float* bias,
                            const int32_t* chan_list, const int32_t* chan_cnt, int L, float* y, int act, float slope,
                            void* ws, size_t ws_bytes, sgStream stream);
+/* (reflection-padded 7x7 stride-1 convs: sg_conv2d_sparse_ws_bytes(d, L, 2) includes room for reflect-padded copies of the listed
+   planes, which the weight gradient then gathers from -- option wgrad_padded; a smaller workspace that still holds the gather
+   route's bytes is accepted and runs the gather route, same result bit for bit) */
 int sg_conv2d_wgrad_perimage(const sgConvDesc* d, const float* gy, const float* x1, const float* x2,
                              const int32_t* chan_list, const int32_t* chan_cnt, int L, float* gwimg, void* ws,
                              size_t ws_bytes, sgStream stream);

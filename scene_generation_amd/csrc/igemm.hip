@@ -186,12 +186,22 @@ static int check_sparse(const sgConvDesc* d, const int32_t* list, const int32_t*
   SG_ARG_CHECK(L > 0 && L <= d->C1 + d->C2, "%s: L=%d outside (0, %d]", who, L, d->C1 + d->C2);
   return 0;
 }
+// what the gather routes of the sparse / per-image weight gradients need (and all they needed before the padded planes)
+static size_t sparse_wgrad_base_ws(const sgConvDesc* d, int L) {
+  const size_t a = sparse_wgrad_ws(d->N, d->Cout, d->C1 + d->C2, L, d->KS * d->KS), cs = sg_channel_sum_ws_bytes(d->Cout);
+  return a > cs ? a : cs;
+}
+static size_t sparse_wgrad_padded_bytes(const sgConvDesc* d, int L) {
+  return nk_padded_bytes(d->KS, d->N, L, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
+}
 extern "C" size_t sg_conv2d_sparse_ws_bytes(const sgConvDesc* d, int L, int kind) {
   if (!d || L <= 0) return 0;
   const int KS2 = d->KS * d->KS;
   if (kind == 0) return sparse_fwd_ws(d->N, d->Cout, L, KS2);
-  const size_t a = sparse_wgrad_ws(d->N, d->Cout, d->C1 + d->C2, L, KS2), cs = sg_channel_sum_ws_bytes(d->Cout);
-  return a > cs ? a : cs;
+  // + the reflect-padded planes of the factored stem's per-image weight gradient, behind the gather route's bytes (a caller that
+  // offers only those gets the gather route)
+  const size_t base = sparse_wgrad_base_ws(d, L), pb = sparse_wgrad_padded_bytes(d, L);
+  return pb ? nk_padded_offset(base) + pb : base;
 }
 extern "C" int sg_conv2d_fwd_sparse(const sgConvDesc* d, const float* x1, const float* x2, const float* w,
                                     const float* bias, const int32_t* chan_list, const int32_t* chan_cnt, int L, float* y,
@@ -217,7 +227,7 @@ extern "C" int sg_conv2d_wgrad_sparse(const sgConvDesc* d, const float* gy, cons
   sgk::t_alg_bytes = 4.0 * ((double)d->N * L * d->H * d->W + (double)d->N * d->Cout * L * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(gy && x1 && gw && ws, "sg_conv2d_wgrad_sparse: null pointer");
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_wgrad_sparse: C2>0 but x2 null");
-  SG_ARG_CHECK(ws_bytes >= sg_conv2d_sparse_ws_bytes(d, L, 2), "sg_conv2d_wgrad_sparse: workspace too small");
+  SG_ARG_CHECK(ws_bytes >= sparse_wgrad_base_ws(d, L), "sg_conv2d_wgrad_sparse: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
   g.bcast2 = d->x2_broadcast;
@@ -252,11 +262,14 @@ extern "C" int sg_conv2d_wgrad_perimage(const sgConvDesc* d, const float* gy, co
   sgk::t_alg_bytes = 4.0 * ((double)d->N * L * d->H * d->W + (double)d->N * d->Cout * L * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(gy && x1 && gwimg && ws, "sg_conv2d_wgrad_perimage: null pointer");
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_wgrad_perimage: C2>0 but x2 null");
-  SG_ARG_CHECK(ws_bytes >= sg_conv2d_sparse_ws_bytes(d, L, 2), "sg_conv2d_wgrad_perimage: workspace too small");
+  // the gather route's bytes are required; the padded planes are taken only when the workspace also holds them
+  const size_t base = sparse_wgrad_base_ws(d, L), pb = sparse_wgrad_padded_bytes(d, L);
+  SG_ARG_CHECK(ws_bytes >= base, "sg_conv2d_wgrad_perimage: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
   g.bcast2 = d->x2_broadcast;
-  const Sparse sp{chan_list, chan_cnt, L, nullptr, gwimg};
+  Sparse sp{chan_list, chan_cnt, L, nullptr, gwimg};
+  if (pb && ws_bytes >= nk_padded_offset(base) + pb) sp.pad_off = nk_padded_offset(base);
   if (int rc = sgk::nk_run(d->KS, gy, d->Cout, d->Cout, g, d->N, nullptr, ws, ws_bytes, 0.0, s, &sp)) return rc;
   SG_LAUNCH_CHECK("sg_conv2d_wgrad_perimage");
   return 0;

@@ -31,7 +31,8 @@ struct Gather {
 struct KEntry { unsigned choff; unsigned tapsel; };     // channel-plane offset ; tap row | second-source << 8
 // per-image ascending active-channel lists; wimg / gwimg (optional): per-image weights [N][M][L][KS2] in list order instead
 // of one shared weight tensor (factored layout convs: the channels are the objects of the image)
-struct Sparse { const int* list; const int* cnt; int L; const float* wimg; float* gwimg; };
+// pad_off > 0 (per-image weight gradient): the workspace has room for reflect-padded planes at this byte offset (nk_padded_bytes)
+struct Sparse { const int* list; const int* cnt; int L; const float* wimg; float* gwimg; size_t pad_off = 0; };
 // Shape-only index tables (k-split tables) are built once per shape and kept: the key holds everything the table
 // depends on, the table lives in device memory owned by the library (the one exception to "the caller owns every buffer":
 // sg_plan_cache_bytes / sg_plan_cache_clear in the header).  A table built on stream A is made visible to a later launch on
@@ -933,6 +934,64 @@ struct LoadTapNK {
     const bool ok = !MASK || st.ok != 0u;
 #pragma unroll
     for (int j = 0; j < COLS; ++j) T[(nr_ + 16 * j) * LDK + kl_] = ok ? st.r[j] : 0.f;
+  }
+};
+
+// B operand of wgrad, (channel, tap) column order like LoadGatherNK, over planes that were reflect-padded beforehand
+// (reflect_pad_planes_kernel, igemm_nk.hip: pp[img][L][PH + KS - 1][PW + KS - 1], plane j of an image = its j-th listed channel;
+// stride 1, no upsampling).  Element (k, n) = pp[pix(k) + col(n)] with pix(k) = img*L*PP + ph*PWp + pw and
+// col(n) = j*PP + kh*PWp + kw: no reflection, no bounds inside a plane.  pix(k) is decoded per 256-pixel block into a
+// double-buffered LDS table (KBLK, as in LoadTapNK), col(n) stays in registers: a gathered element costs one add and one buffer
+// load.  Masking is the buffer's range check: the descriptor covers exactly the planes (at most PAD_MAX_BYTES), pixels beyond the
+// k range and columns beyond the image's channel list carry an offset of PAD_INVALID elements, and PAD_MAX_BYTES <=
+// 4 PAD_INVALID, 8 PAD_INVALID + PAD_MAX_BYTES <= 2^32 keep every such sum outside the descriptor without wrapping.
+constexpr unsigned PAD_INVALID = 1u << 28;
+constexpr size_t PAD_MAX_BYTES = (size_t)1 << 30;
+template <int BN, int KS, int NS = SG_NSUB>
+struct LoadPaddedNK {
+  const float* pp; unsigned bytes;                      // the padded planes and their size
+  int PQ, PW, PWp, PP, L;                               // gy grid (PQ = PH*PW), padded row pitch and plane size, planes per image
+  const int* chan_cnt;                                  // listed channels per image
+  FastDiv dPQ, dPW;
+  static constexpr int KS2 = KS * KS;
+  static constexpr int LDS_INTS = 2 * KBLK;
+  static constexpr int COLS = BN / 16;
+  struct Stage { float r[COLS]; };
+  int kl_, tid_, nr_, kbeg_, kend_;
+  unsigned coloff_[COLS];
+  int* lds_;
+  __device__ __forceinline__ void set_batch(int, int, int) {}
+  __device__ __forceinline__ void init(int n0, int tid, int* lds, int kbeg, int kend) {
+    kl_ = tid & 15; nr_ = tid >> 4; tid_ = tid; lds_ = lds; kbeg_ = kbeg; kend_ = kend;
+    const int ncols = chan_cnt[kbeg / PQ] * KS2;        // (the image comes from kbeg: see LoadGatherNK::init)
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) {
+      const int n = n0 + nr_ + 16 * j;
+      const int cj = n / KS2, t = n - cj * KS2;
+      const int kh = t / KS, kw = t - kh * KS;
+      coloff_[j] = n < ncols ? (unsigned)(cj * PP + kh * PWp + kw) : PAD_INVALID;
+    }
+  }
+  __device__ __forceinline__ void prefetch(Stage&, int k0) const {
+    const int rel = k0 - kbeg_;
+    if ((rel & (KBLK - 1)) != 0) return;
+    const int k = k0 + tid_;
+    const unsigned kk = k < kend_ ? (unsigned)k : 0u;
+    const unsigned img = dPQ.div(kk), pix = kk - img * (unsigned)PQ;
+    const unsigned ph = dPW.div(pix), pw = pix - ph * (unsigned)PW;
+    lds_[((rel / KBLK) & 1) * KBLK + tid_] = k < kend_ ? (int)(img * (unsigned)(L * PP) + ph * (unsigned)PWp + pw) : (int)PAD_INVALID;
+  }
+  __device__ __forceinline__ void load(Stage& st, int k0, int) const {
+    const int rel = k0 - kbeg_;
+    const unsigned p0 = (unsigned)lds_[((rel / KBLK) & 1) * KBLK + (rel & (KBLK - 1)) + kl_];
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pp), 0, bytes, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < COLS; ++j)
+      st.r[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)((p0 + coloff_[j]) << 2), 0, 0));
+  }
+  __device__ __forceinline__ void store(const Stage& st, float* T) const {
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) T[(nr_ + 16 * j) * LDK + kl_] = st.r[j];
   }
 };
 
@@ -2095,6 +2154,17 @@ inline size_t parity_ws(int M, int Rdim, int KS2) { return (size_t)M * Rdim * KS
 inline size_t sparse_wgrad_ws(int NB, int M, int C, int L, int KS2) {
   return (size_t)NB * M * (sg_cdiv(L, 128) * 128) * KS2 * sizeof(float) + (size_t)NB * C * sizeof(int);
 }
+// Bytes of the reflect-padded planes [NB][L][SH + 2 pad][SW + 2 pad] the per-image weight gradient of a factored conv gathers from
+// (LoadPaddedNK), or 0 when the conv does not take that route: reflection padding, one source, stride 1, no upsampling, the 7x7
+// stem (the KS = 3 / 4 factored convs of the discriminators are zero-padded and strided).  Shared by the workspace query
+// (sg_conv2d_sparse_ws_bytes) and the launcher: the planes sit behind the bytes the gather route is entitled to.
+inline size_t nk_padded_bytes(int KS, int NB, int L, int C2, int SH, int SW, int ups, int PH, int PW, int stride, int pad, int reflect) {
+  if (!(KS == 7 && reflect && C2 == 0 && ups == 1 && stride == 1 && pad >= 1 && pad < SH && pad < SW && NB > 0 && L > 0)) return 0;
+  if (PH != SH + 2 * pad - KS + 1 || PW != SW + 2 * pad - KS + 1 || PH < 1 || PW < 1) return 0;
+  const size_t b = (size_t)NB * L * (SH + 2 * pad) * (SW + 2 * pad) * sizeof(float);
+  return b <= PAD_MAX_BYTES ? b : 0;
+}
+inline size_t nk_padded_offset(size_t base_bytes) { return (base_bytes + 255) / 256 * 256; }
 // launch plan of a weight-gradient GEMM (shared by the workspace query and the launcher)
 struct NkPlan { int tile; bool tap; int cpad; int splits; };
 inline NkPlan nk_plan(int M, int C, int KS2, int Kpix, bool two) {

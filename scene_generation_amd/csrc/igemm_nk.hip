@@ -69,6 +69,37 @@ __global__ void wgrad_unpermute_reduce_kernel(const float* __restrict__ slabs, f
   const float v = sg_sum_strided(p, zs, S);
   gw[(size_t)m * C * KS2 + j] = v;
 }
+// pp[b][j][PHp][PWp] = ReflectionPad2d(pad) of plane list[b][j] of image b, j < cnt[b] (planes beyond the list are never read:
+// LoadPaddedNK masks their columns).  grid (ceil(PHp PWp / 256), L, N): one 32-bit multiply-high per element, coalesced stores.
+__global__ void reflect_pad_planes_kernel(const float* __restrict__ x, const int* __restrict__ list, const int* __restrict__ cnt,
+                                          float* __restrict__ pp, int C, int L, int H, int W, int pad, int PWp, int PP,
+                                          FastDiv dPWp) {
+  const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y, b = blockIdx.z;
+  if (e >= (unsigned)PP || j >= cnt[b]) return;
+  const unsigned oh = dPWp.div(e), ow = e - oh * (unsigned)PWp;
+  int ih = (int)oh - pad, iw = (int)ow - pad;
+  ih = ih < 0 ? -ih : (ih >= H ? 2 * H - 2 - ih : ih);
+  iw = iw < 0 ? -iw : (iw >= W ? 2 * W - 2 - iw : iw);
+  const int c = list[b * L + j];
+  pp[((size_t)b * L + j) * PP + e] = x[((size_t)b * C + c) * ((size_t)H * W) + (unsigned)(ih * W + iw)];
+}
+// the per-image weight gradient of the factored 7x7 stem over padded planes: launch_nk_general's three forms with LoadPaddedNK
+void launch_nk_padded(int tile, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep, int Kpix,
+                      hipStream_t s, const Sparse& sp, const float* pp) {
+  float* const rowsum = nullptr;
+  const FastDiv dPQ((unsigned)PQ), dPW((unsigned)g.PW);
+  const int PWp = g.SW + 2 * g.pad, PP = (g.SH + 2 * g.pad) * PWp;
+  const unsigned bytes = (unsigned)((size_t)(Kpix / PQ) * sp.L * PP * sizeof(float));
+#define SG_PAD_B(BNv) LoadPaddedNK<BNv, 7, NSW>{pp, bytes, PQ, g.PW, PWp, PP, sp.L, sp.cnt, dPQ, dPW}
+  if (tile == 2)
+    launch_cfg<CfgW32>(LoadPixK<32>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(128), ep, M, Ncols, Kpix, 1, s);
+  else if ((PQ % 4 == 0) && aligned16(A))
+    launch_cfg<CfgW64>(LoadPixKVec<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s);
+  else
+    launch_cfg<CfgW64>(LoadPixK<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s);
+#undef SG_PAD_B
+}
 // general (c, tap)-ordered loader: only for few-channel inputs (RGB crops / images)
 template <int KS>
 void launch_nk_general(int tile, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep,
@@ -141,7 +172,21 @@ int run_nk_ks(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, 
     t_batch = BatchInfo{}; t_batch.kimg = PQ; t_batch.ksplit = S; t_batch.kcs = kcs;
     t_grid_z = NB * S;
     t_xcd_z = sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0;      // (image, chunk) slices pinned to XCDs when grid.z % 8 == 0 (launch_cfg)
-    {
+    // Reflection-padded 7x7 stem: the gather below decodes every one of the L*49 columns' elements with reflection arithmetic --
+    // vector-ALU work the f32 MFMA cannot overlap (the launch ran at 45 TFLOP/s, every other weight gradient of the step at
+    // 90-105).  When the workspace has room (Sparse::pad_off) the listed planes are reflect-padded once, behind the slabs, and the
+    // same GEMM -- same tiles, k-chunks, k order, epilogue -- gathers from them with one add per element: bit-identical.
+    const size_t pbytes = nk_padded_bytes(KS, NB, Ccols, g.C2, g.SH, g.SW, g.ushift ? 2 : 1, g.PH, g.PW, g.stride, g.pad, g.reflect);
+    const bool padded = sg_opt(SG_OPT_WGRAD_PADDED) && pbytes > 0 && sp->pad_off >= mnc * sizeof(float) * (size_t)S * NB &&
+                        g.pstep == 1 && NB <= 65535 && ws_bytes >= sp->pad_off + pbytes;
+    if (padded) {
+      float* pp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + sp->pad_off);
+      const int PWp = g.SW + 2 * g.pad, PP = (g.SH + 2 * g.pad) * PWp;
+      hipLaunchKernelGGL(reflect_pad_planes_kernel, dim3(sg_cdiv(PP, 256), Ccols, NB), dim3(256), 0, s, g.src1, sp->list, sp->cnt, pp,
+                         g.C1, Ccols, g.SH, g.SW, g.pad, PWp, PP, FastDiv((unsigned)PWp));
+      SgProfScope prof(sg_igemm_kind(2, KS, tile), s, 2.0 * M * (double)Ncols * Kpix, 0);
+      launch_nk_padded(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, s, *sp, pp);
+    } else {
       SgProfScope prof(sg_igemm_kind(2, KS, tile), s, 2.0 * M * (double)Ncols * Kpix, 0);
       switch (KS) {
         case 1: launch_nk_general<1>(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;

@@ -1088,6 +1088,75 @@ __global__ void pad_upsample_bwd_kernel(const float* __restrict__ gp, float* __r
   gx[nc * H * W + j] = s;
 }
 
+// The fold without upsampling (adjoint of ReflectionPad2d), workgroups in two roles (block-uniform: no wave runs both).
+// INTERIOR outputs (pad < l < L - 1 - pad on both axes: 88 % of the 128 x 128 gradient behind the RGB head's pad) have exactly one
+// source: the first ``iblocks`` workgroups copy them, a thread per four consecutive outputs of a row (the 4-aligned column range
+// [wq0, wq1) of the rows [hq0, hq1)) -- a 16-byte load and a 16-byte store where the addresses allow it (0.f + v: the sum starts
+// from +0, so -0 is stored as +0 like before).  The remaining workgroups run the RING, a thread per output: whole rows above
+// and below, then the columns left and right of the quads.  It adds the up to 3 x 3 candidates in the order of the kernel above
+// (rows outer, columns inner), all nine loads issued at once: a dead candidate reads the always-live one and adds +0.f, which
+// leaves the sum as it is bit for bit (a sum that starts from +0 is never -0).  grid (iblocks + ring blocks, planes).
+struct FoldPlan {
+  int hq0, hq1, wq0, wq1, iblocks;      // interior quads; hq0 == hq1 == 0: none
+  FastDiv dnq, dW, dWb;                 // quads per interior row, W, ring columns per interior row
+};
+__global__ void __launch_bounds__(256) reflect_fold_kernel(const float* __restrict__ gp, float* __restrict__ gx, int H, int W,
+                                                           int pad, FoldPlan fp) {
+  const size_t nc = blockIdx.y;
+  const int PW = W + 2 * pad, PH = H + 2 * pad;
+  const float* g = gp + nc * PH * PW;
+  float* o = gx + nc * H * W;
+  const int rows = fp.hq1 - fp.hq0, nq = (fp.wq1 - fp.wq0) >> 2;
+  if ((int)blockIdx.x < fp.iblocks) {
+    const unsigned id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= (unsigned)(rows * nq)) return;
+    const unsigned r = fp.dnq.div(id), q = id - r * (unsigned)nq;
+    const int h = fp.hq0 + (int)r, w0 = fp.wq0 + 4 * (int)q;
+    const float* src = g + (unsigned)((h + pad) * PW + pad + w0);
+    float* dst = o + (unsigned)(h * W + w0);
+    float4 v;
+    if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) v = *reinterpret_cast<const float4*>(src);
+    else v = make_float4(src[0], src[1], src[2], src[3]);
+    v = make_float4(0.f + v.x, 0.f + v.y, 0.f + v.z, 0.f + v.w);
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) *reinterpret_cast<float4*>(dst) = v;
+    else { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; }
+    return;
+  }
+  const unsigned id = (blockIdx.x - (unsigned)fp.iblocks) * 256u + threadIdx.x;
+  const int Wb = W - 4 * nq, ntb = (H - rows) * W;
+  if (id >= (unsigned)(ntb + rows * Wb)) return;
+  int h, w;
+  if (id < (unsigned)ntb) {
+    const unsigned r = fp.dW.div(id);
+    w = (int)(id - r * (unsigned)W);
+    h = (int)r < fp.hq0 ? (int)r : (int)r - fp.hq0 + fp.hq1;
+  } else {
+    const unsigned e = id - (unsigned)ntb, r = fp.dWb.div(e);
+    const int c = (int)(e - r * (unsigned)Wb);
+    h = fp.hq0 + (int)r;
+    w = c < fp.wq0 ? c : c - fp.wq0 + fp.wq1;
+  }
+  const int ih[3] = {h + pad, pad - h, pad + 2 * H - 2 - h};
+  const bool lh[3] = {true, h >= 1 && h <= pad, h <= H - 2 && h >= H - 1 - pad};
+  const int iw[3] = {w + pad, pad - w, pad + 2 * W - 2 - w};
+  const bool lw[3] = {true, w >= 1 && w <= pad, w <= W - 2 && w >= W - 1 - pad};
+  float v[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const bool live = lh[a] && lw[b];
+      v[a][b] = g[live ? ih[a] * PW + iw[b] : ih[0] * PW + iw[0]];
+      v[a][b] = live ? v[a][b] : 0.f;
+    }
+  float s = 0.f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) s += v[a][b];
+  o[h * W + w] = s;
+}
+
 __global__ void concat_channels_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out,
                                        size_t total, int Ca, int Cb, int HW) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1533,6 +1602,19 @@ extern "C" int sg_pad_upsample_bwd(const float* gp, float* gx, int NC, int H, in
   for (int n0 = 0; n0 < NC; n0 += 65535) {                  // (grid.y limit)
     const int nn = NC - n0 < 65535 ? NC - n0 : 65535;
     const size_t PP = (size_t)(H * upsample + 2 * pad) * (W * upsample + 2 * pad);
+    if (upsample == 1) {
+      // interior quads: rows (pad, H - 1 - pad), 4-aligned columns inside (pad, W - 1 - pad); everything else is ring
+      FoldPlan fp;
+      fp.hq0 = pad + 1; fp.hq1 = H - 1 - pad; fp.wq0 = (pad + 1 + 3) & ~3; fp.wq1 = (W - 1 - pad) & ~3;
+      if (fp.hq1 <= fp.hq0 || fp.wq1 <= fp.wq0) { fp.hq0 = fp.hq1 = 0; fp.wq0 = fp.wq1 = 0; }
+      const int rows = fp.hq1 - fp.hq0, nq = (fp.wq1 - fp.wq0) / 4, Wb = W - 4 * nq;
+      fp.iblocks = sg_cdiv(rows * nq, 256);
+      fp.dnq = FastDiv((unsigned)(nq > 0 ? nq : 1)); fp.dW = FastDiv((unsigned)W); fp.dWb = FastDiv((unsigned)(Wb > 0 ? Wb : 1));
+      const int ring = (H - rows) * W + rows * Wb;
+      hipLaunchKernelGGL(reflect_fold_kernel, dim3(fp.iblocks + sg_cdiv(ring, 256), nn), dim3(256), 0, (hipStream_t)stream,
+                         gp + (size_t)n0 * PP, gx + (size_t)n0 * H * W, H, W, pad, fp);
+      continue;
+    }
     hipLaunchKernelGGL(pad_upsample_bwd_kernel, dim3(sg_cdiv(H * W, 256), nn), dim3(256), 0, (hipStream_t)stream,
                        gp + (size_t)n0 * PP, gx + (size_t)n0 * H * W, H, W, pad, upsample);
   }
