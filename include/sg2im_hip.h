@@ -651,6 +651,30 @@ int sg_softmax_rows(const float* logits, int rows, int classes, float* out, int 
  * gives NaN for both.  ws >= sg_inception_score_ws_bytes(n, classes, splits), 8-byte aligned. */
 size_t sg_inception_score_ws_bytes(int n, int classes, int splits);
 int sg_inception_score(const float* probs, int n, int classes, int splits, void* out, void* ws, size_t ws_bytes, sgStream stream);
+/* The FID form of the network (pytorch-fid's FIDInceptionA / C / E_1 and E_2) needs two more pools on [NC, H, W]:
+ * sg_avgpool3s1x_fwd: avg_pool2d(3, stride=1, padding=1, count_include_pad=False) -- the taps of sg_avgpool3s1_fwd in the same
+ * (kh, kw) order from 0, divided by the number of taps inside the plane.
+ * sg_maxpool3s1_fwd: max_pool2d(3, stride=1, padding=1) -- the taps inside the plane scanned in (kh, kw) order from -inf; a NaN in
+ * a window wins, as in the other max-pools. */
+int sg_avgpool3s1x_fwd(const float* x, float* y, int NC, int H, int W, sgStream stream);
+int sg_maxpool3s1_fwd(const float* x, float* y, int NC, int H, int W, sgStream stream);
+/* ---- the Frechet Inception Distance (fid.hip; scene_generation_amd/fid.py) ---------------------------------------------------------
+ * The float64 raw moments of feature rows, accumulated on the device over a whole evaluation.
+ *
+ * sg_fid_moments_update: sum[j] += sum_k x[k][j] and outer[i][j] += sum_k x[k][i] * x[k][j] for i <= j, with x fp32 [rows, D] of row
+ * stride ldx >= D elements (any 4-byte aligned base), sum fp64 [D], outer fp64 [D, D] (both 8-byte aligned, zeroed by the caller
+ * before the first call).  The lower triangle of outer is unspecified until finalize (whole 64 x 64 diagonal tiles are written).
+ * Each fp32 value is converted to fp64, so every product is exact; the sums are fp64 on the f64 matrix cores
+ * (v_mfma_f64_16x16x4_f64), k ascending, the call's total added to the stored value once.  One workgroup per tile pair of the block
+ * upper triangle, no atomics: the same call sequence gives bit-identical moments.  rows == 0 returns 0 and launches nothing.  A null
+ * pointer, D < 1, ldx < D or a misaligned fp64 pointer returns a negative code (sg_last_error_string) and launches nothing.  The call
+ * never synchronises and never allocates.  Raw moments, no shift: two accumulators merge by adding counts, sums and outers.
+ *
+ * sg_fid_moments_finalize: mu = sum / n and the full symmetric sigma[i][j] = sigma[j][i] = (outer[i][j] - sum[i] * sum[j] / n) /
+ * (n - 1) read from i <= j only -- numpy.cov(rowvar=False), ddof = 1; sigma equals its transpose bit for bit.  mu fp64 [D], sigma
+ * fp64 [D, D], distinct from sum and outer.  n < 2 returns a negative code. */
+int sg_fid_moments_update(const float* x, int rows, int D, int ldx, double* sum, double* outer, sgStream stream);
+int sg_fid_moments_finalize(const double* sum, const double* outer, long long n, int D, double* mu, double* sigma, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

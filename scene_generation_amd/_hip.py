@@ -35,8 +35,10 @@ def _ctype(decl):
         if re.match(r'(const\s+)?int64_t\s*\*\s*(launches)?$', decl) and 'launches' in decl:
             return ctypes.POINTER(ctypes.c_int64)
         return ctypes.c_void_p
-    base = decl.replace('const', '').split()[0]
-    return _SCALARS[base]
+    words = decl.replace('const', '').split()
+    if words[:2] == ['long', 'long']:
+        return ctypes.c_longlong
+    return _SCALARS[words[0]]
 
 
 def parse_header(path=HEADER):

@@ -121,6 +121,8 @@ enum {
   // unpadded max-pool / count_include_pad average pool, the bilinear resize, the softmax rows and the score itself
   SG_K_RECT_CONV_T64, SG_K_RECT_CONV_T32, SG_K_RECT_CONV_T64W, SG_K_RECT_REDUCE, SG_K_INCEPTION_POOL, SG_K_RESIZE_BILINEAR,
   SG_K_SOFTMAX_ROWS, SG_K_INCEPTION_SCORE,
+  // the Frechet Inception Distance (fid.hip): the fp64 moment update (f64 MFMA) and its finalize
+  SG_K_FID_MOMENTS,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -7,6 +7,8 @@
 //                           total channel count, so a slice is its ``out`` pointer moved by out_c0 planes
 //   sg_maxpool3s2v_fwd      max_pool2d(3, stride=2) without padding, into a channel slice
 //   sg_avgpool3s1_fwd       avg_pool2d(3, stride=1, padding=1), count_include_pad=True
+//   sg_avgpool3s1x_fwd      the same with count_include_pad=False, and
+//   sg_maxpool3s1_fwd       max_pool2d(3, stride=1, padding=1): the branch pools of the FID form of the network
 //   sg_resize_bilinear_fwd  F.interpolate(mode='bilinear', align_corners=False)
 //   sg_softmax_rows         softmax of logits rows into a row window of a caller-owned buffer
 //   sg_inception_score      exp(mean KL(p(y|x) || p(y))) per split, mean and population std over the splits, in fp64
@@ -202,6 +204,57 @@ __global__ void __launch_bounds__(TPB) avgpool3s1_kernel(const float* __restrict
     }
   }
   y[i] = sum / 9.f;
+}
+
+// ---- avg_pool2d(3, stride=1, padding=1), count_include_pad=False (the FID form of the network) ----------------------------------------
+// the same taps in the same order as avgpool3s1_kernel; the divisor is the number of taps inside the plane
+__global__ void __launch_bounds__(TPB) avgpool3s1x_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned total, int H, int W,
+                                                         FastDiv fw, FastDiv fh) {
+  const unsigned i = blockIdx.x * TPB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned r = fw.div(i), w = i - r * (unsigned)W;
+  const unsigned nc = fh.div(r), h = r - nc * (unsigned)H;
+  const float* xp = x + (size_t)nc * H * W;
+  float sum = 0.f;
+  int taps = 0;
+#pragma unroll
+  for (int kh = -1; kh <= 1; ++kh) {
+    const int ih = (int)h + kh;
+    if (ih < 0 || ih >= H) continue;
+#pragma unroll
+    for (int kw = -1; kw <= 1; ++kw) {
+      const int iw = (int)w + kw;
+      if (iw < 0 || iw >= W) continue;
+      sum += xp[ih * W + iw];
+      ++taps;
+    }
+  }
+  y[i] = sum / (float)taps;
+}
+
+// ---- max_pool2d(3, stride=1, padding=1) (the FID form of the network) ------------------------------------------------------------------
+// the scan of maxpool3s2v_kernel over the taps inside the plane (the padding is -inf: it never wins)
+__global__ void __launch_bounds__(TPB) maxpool3s1_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned total, int H, int W,
+                                                        FastDiv fw, FastDiv fh) {
+  const unsigned i = blockIdx.x * TPB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned r = fw.div(i), w = i - r * (unsigned)W;
+  const unsigned nc = fh.div(r), h = r - nc * (unsigned)H;
+  const float* xp = x + (size_t)nc * H * W;
+  float m = -__builtin_inff();
+#pragma unroll
+  for (int kh = -1; kh <= 1; ++kh) {
+    const int ih = (int)h + kh;
+    if (ih < 0 || ih >= H) continue;
+#pragma unroll
+    for (int kw = -1; kw <= 1; ++kw) {
+      const int iw = (int)w + kw;
+      if (iw < 0 || iw >= W) continue;
+      const float v = xp[ih * W + iw];
+      if (v > m || is_nan(v)) m = v;
+    }
+  }
+  y[i] = m;
 }
 
 // ---- F.interpolate(mode='bilinear', align_corners=False) ----------------------------------------------------------------------------
@@ -430,6 +483,32 @@ extern "C" int sg_avgpool3s1_fwd(const float* x, float* y, int NC, int H, int W,
   hipLaunchKernelGGL(avgpool3s1_kernel, dim3(sg_cdiv(total, TPB)), dim3(TPB), 0, s, x, y, total, H, W, FastDiv((unsigned)W),
                      FastDiv((unsigned)H));
   SG_LAUNCH_CHECK("sg_avgpool3s1_fwd");
+  return 0;
+}
+
+extern "C" int sg_avgpool3s1x_fwd(const float* x, float* y, int NC, int H, int W, sgStream stream) {
+  SG_ARG_CHECK(NC >= 0 && H >= 1 && W >= 1 && (double)NC * H * W < 2147483647.0, "sg_avgpool3s1x_fwd: bad sizes (NC=%d H=%d W=%d)", NC, H, W);
+  if (NC == 0) return 0;
+  SG_ARG_CHECK(x && y, "sg_avgpool3s1x_fwd: null operand");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned total = (unsigned)NC * H * W;
+  SgProfScope prof(SG_K_INCEPTION_POOL, s, 0.0, 8.0 * (double)total);
+  hipLaunchKernelGGL(avgpool3s1x_kernel, dim3(sg_cdiv(total, TPB)), dim3(TPB), 0, s, x, y, total, H, W, FastDiv((unsigned)W),
+                     FastDiv((unsigned)H));
+  SG_LAUNCH_CHECK("sg_avgpool3s1x_fwd");
+  return 0;
+}
+
+extern "C" int sg_maxpool3s1_fwd(const float* x, float* y, int NC, int H, int W, sgStream stream) {
+  SG_ARG_CHECK(NC >= 0 && H >= 1 && W >= 1 && (double)NC * H * W < 2147483647.0, "sg_maxpool3s1_fwd: bad sizes (NC=%d H=%d W=%d)", NC, H, W);
+  if (NC == 0) return 0;
+  SG_ARG_CHECK(x && y, "sg_maxpool3s1_fwd: null operand");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned total = (unsigned)NC * H * W;
+  SgProfScope prof(SG_K_INCEPTION_POOL, s, 0.0, 8.0 * (double)total);
+  hipLaunchKernelGGL(maxpool3s1_kernel, dim3(sg_cdiv(total, TPB)), dim3(TPB), 0, s, x, y, total, H, W, FastDiv((unsigned)W),
+                     FastDiv((unsigned)H));
+  SG_LAUNCH_CHECK("sg_maxpool3s1_fwd");
   return 0;
 }
 

@@ -28,15 +28,21 @@ def jaccard(bbox_pred, bbox_gt):
     return iou.sum(), int((iou > 0.5).sum()), int((iou > 0.3).sum())
 
 
-def check_model(args, loader, model, inception_score=None, use_gt=True, device=None):
+def check_model(args, loader, model, inception_score=None, use_gt=True, device=None, fid=None):
     """train.py:80-116: run the model the way it ran during training but in test mode (``use_gt``: ground-truth boxes and
     masks, attributes kept; else predicted boxes and masks, attributes zeroed), accumulate the box IoU against the
     ground truth over ``args.num_val_samples`` images, feed the images to ``inception_score``.
-    Returns (avg_iou, inception_mean, inception_std, fid) with fid None like the reference."""
+    Returns (avg_iou, inception_mean, inception_std, fid) with fid None like the reference -- unless ``fid`` (a
+    ``fid.FrechetInceptionDistance``) is given: its fake side is cleared and fed the generated images (through ``inception_score``
+    when that scorer shares its forward with it, ``inception_score.fid is fid``), its real side is fed the batches' own images
+    while it ``needs_real`` (the first pass), and the fourth value is ``fid.compute()``."""
     device = device or next(model.parameters()).device
     total_iou, total_boxes, seen = None, 0, 0
     if inception_score is not None:
         inception_score.clean()
+    fid_shared = fid is not None and inception_score is not None and getattr(inception_score, 'fid', None) is fid
+    if fid is not None:
+        fid.clean()
     with torch.no_grad():
         for batch in loader:
             imgs, objs, boxes, masks, triples, obj_to_img, triple_to_img, attributes = [t.to(device) for t in batch]
@@ -50,8 +56,12 @@ def check_model(args, loader, model, inception_score=None, use_gt=True, device=N
             iou = jaccard(boxes_pred, boxes)[0]
             total_iou = iou if total_iou is None else total_iou + iou
             total_boxes += boxes_pred.size(0)
+            if fid is not None and fid.needs_real:
+                fid.add_real(imgs)
             if inception_score is not None:
                 inception_score(imgs_pred)
+            if fid is not None and not fid_shared:
+                fid(imgs_pred)
             seen += imgs.size(0)
             if seen >= args.num_val_samples:
                 break
@@ -59,7 +69,7 @@ def check_model(args, loader, model, inception_score=None, use_gt=True, device=N
     if inception_score is not None:
         mean, std = inception_score.compute_score(splits=5)
     avg_iou = float(total_iou) / total_boxes if total_boxes else float('nan')      # the loop's only host synchronisation
-    return avg_iou, mean, std, None
+    return avg_iou, mean, std, (fid.compute() if fid is not None else None)
 
 
 def encode_features(model, loader, object_size=64, device=None, max_objects=None):

@@ -28,6 +28,7 @@ __all__ = ['InceptionV3', 'InceptionScore', 'load_inception', 'conv_units', 'mai
 # the state_dict file ``InceptionScore(weights=None)`` loads: for callers whose constructor call cannot be changed (the reference's
 # train.py:177); None: random weights and a warning
 DEFAULT_WEIGHTS = None
+FID_CLASSES = 1008          # the class count of the TF-ported FID weights: what ``load_inception`` recognises them by
 
 
 class BasicConv2d(nn.Module):
@@ -68,6 +69,14 @@ class _Kernels(object):
     def avgpool(x):
         return ops.avgpool3s1(x)
 
+    @staticmethod
+    def avgpool3s1x(x):
+        return ops.avgpool3s1x(x)
+
+    @staticmethod
+    def maxpool3s1(x):
+        return ops.maxpool3s1(x)
+
 
 class _Trace(object):
     """tensors are (N, C, H, W) tuples; ``units`` collects one record per conv unit in launch order"""
@@ -104,6 +113,8 @@ class _Trace(object):
     def avgpool(x):
         return x
 
+    avgpool3s1x = maxpool3s1 = avgpool          # the FID form's branch pools keep the plane too
+
 
 class InceptionA(nn.Module):
     def __init__(self, cin, pool_features):
@@ -116,6 +127,7 @@ class InceptionA(nn.Module):
         self.branch3x3dbl_3 = BasicConv2d(96, 96, 3, padding=1)
         self.branch_pool = BasicConv2d(cin, pool_features, 1)
         self.cout = 64 + 64 + 96 + pool_features
+        self.pool = 'avgpool'               # the executor's branch pool; InceptionV3(fid_variant=True) changes it
 
     def run(self, E, x):
         _, _, H, W = E.shape(x)
@@ -123,7 +135,7 @@ class InceptionA(nn.Module):
         E.conv(self.branch1x1, x, out, 0)
         E.conv(self.branch5x5_2, E.conv(self.branch5x5_1, x), out, 64)
         E.conv(self.branch3x3dbl_3, E.conv(self.branch3x3dbl_2, E.conv(self.branch3x3dbl_1, x)), out, 128)
-        E.conv(self.branch_pool, E.avgpool(x), out, 224)
+        E.conv(self.branch_pool, getattr(E, self.pool)(x), out, 224)
         return out
 
 
@@ -160,6 +172,7 @@ class InceptionC(nn.Module):
         self.branch7x7dbl_5 = BasicConv2d(c7, 192, (1, 7), padding=(0, 3))
         self.branch_pool = BasicConv2d(cin, 192, 1)
         self.cout = 768
+        self.pool = 'avgpool'               # the executor's branch pool; InceptionV3(fid_variant=True) changes it
 
     def run(self, E, x):
         _, _, H, W = E.shape(x)
@@ -168,7 +181,7 @@ class InceptionC(nn.Module):
         E.conv(self.branch7x7_3, E.conv(self.branch7x7_2, E.conv(self.branch7x7_1, x)), out, 192)
         t = E.conv(self.branch7x7dbl_3, E.conv(self.branch7x7dbl_2, E.conv(self.branch7x7dbl_1, x)))
         E.conv(self.branch7x7dbl_5, E.conv(self.branch7x7dbl_4, t), out, 384)
-        E.conv(self.branch_pool, E.avgpool(x), out, 576)
+        E.conv(self.branch_pool, getattr(E, self.pool)(x), out, 576)
         return out
 
 
@@ -206,6 +219,7 @@ class InceptionE(nn.Module):
         self.branch3x3dbl_3b = BasicConv2d(384, 384, (3, 1), padding=(1, 0))
         self.branch_pool = BasicConv2d(cin, 192, 1)
         self.cout = 2048
+        self.pool = 'avgpool'               # the executor's branch pool; InceptionV3(fid_variant=True) changes it
 
     def run(self, E, x):
         _, _, H, W = E.shape(x)
@@ -217,7 +231,7 @@ class InceptionE(nn.Module):
         t = E.conv(self.branch3x3dbl_2, E.conv(self.branch3x3dbl_1, x))
         E.conv(self.branch3x3dbl_3a, t, out, 1088)
         E.conv(self.branch3x3dbl_3b, t, out, 1472)
-        E.conv(self.branch_pool, E.avgpool(x), out, 1856)
+        E.conv(self.branch_pool, getattr(E, self.pool)(x), out, 1856)
         return out
 
 
@@ -247,10 +261,15 @@ class InceptionV3(nn.Module):
     ``drop_fold()``, and an entry is rebuilt when one of its tensors was replaced or written through torch (version counters).
 
     Random initialisation: He-normal convolutions (fan-in), BatchNorm at identity -- torchvision's truncated normal of fixed
-    std 0.1 is a starting point for TRAINING under batch statistics and overflows in eval mode."""
+    std 0.1 is a starting point for TRAINING under batch statistics and overflows in eval mode.
 
-    def __init__(self, num_classes=1000, aux_logits=True):
+    ``fid_variant=True`` is the form every published FID is computed with (the TF-ported pt_inception-2015-12-05 weights: 1008
+    classes, no auxiliary head): the branch pools of InceptionA, InceptionC and Mixed_7b average over the taps INSIDE the plane
+    (count_include_pad=False) and the branch pool of Mixed_7c is a max-pool.  Nothing else changes; the default is torchvision's."""
+
+    def __init__(self, num_classes=1000, aux_logits=True, fid_variant=False):
         super().__init__()
+        self.fid_variant = bool(fid_variant)
         self.Conv2d_1a_3x3 = BasicConv2d(3, 32, 3, stride=2)
         self.Conv2d_2a_3x3 = BasicConv2d(32, 32, 3)
         self.Conv2d_2b_3x3 = BasicConv2d(32, 64, 3, padding=1)
@@ -272,6 +291,10 @@ class InceptionV3(nn.Module):
         self.avgpool = layers.GlobalAvgPool()
         self.fc = layers.Linear(2048, num_classes)
         self._fold_cache = {}
+        if self.fid_variant:                # pytorch-fid's FIDInceptionA / C / E_1 and E_2: four kinds of branch pool, nothing else
+            for name in _BLOCKS:
+                if hasattr(getattr(self, name), 'pool'):
+                    getattr(self, name).pool = 'maxpool3s1' if name == 'Mixed_7c' else 'avgpool3s1x'
         for name, m in self.named_modules():
             if isinstance(m, BasicConv2d):
                 m.name = name
@@ -349,9 +372,15 @@ def unit_plan(u, w_aligned16=True):
 
 def load_inception(path, device='cuda'):
     """an ``InceptionV3`` with the ``state_dict`` file ``path`` loaded strictly (torchvision's ``inception_v3_google-*.pth``, or a
-    save of this class; a DataParallel ``module.`` prefix is stripped), on ``device``"""
+    save of this class; a DataParallel ``module.`` prefix is stripped), on ``device``.  A file whose ``fc.weight`` has 1008 rows is
+    the TF-ported FID network (pt_inception-2015-12-05: 1008 classes, no auxiliary head): it is loaded, strictly, into the FID form
+    (``fid_variant=True, aux_logits=False``)."""
     sd = _strip_module_prefix(dict(torch.load(path, map_location='cpu')))
-    net = InceptionV3(num_classes=int(sd['fc.weight'].shape[0]), aux_logits=any(k.startswith('AuxLogits.') for k in sd))
+    classes = int(sd['fc.weight'].shape[0])
+    if classes == FID_CLASSES:
+        net = InceptionV3(num_classes=classes, aux_logits=False, fid_variant=True)
+    else:
+        net = InceptionV3(num_classes=classes, aux_logits=any(k.startswith('AuxLogits.') for k in sd))
     net.load_state_dict(sd, strict=True)
     return net.to(device)
 
@@ -364,11 +393,15 @@ class InceptionScore(nn.Module):
     ``weights``: the path of a ``state_dict`` file (``load_inception``), an ``InceptionV3`` instance, or None.  None takes the
     module attribute ``DEFAULT_WEIGHTS`` -- process-wide state: every scorer built afterwards without ``weights`` loads that file
     (it exists for callers whose constructor call cannot be changed) -- and, when that is None too, builds a
-    random network under a fixed seed and warns."""
+    random network under a fixed seed and warns.
 
-    def __init__(self, cuda=True, batch_size=32, resize=False, weights=None, device=None):
+    ``fid``: a ``fid.FrechetInceptionDistance``; every chunk's pooled features then also go to its fake side (``add_features``), so
+    the score and the distance share one forward of THIS scorer's network.  The logits, and the score, are bit-identical."""
+
+    def __init__(self, cuda=True, batch_size=32, resize=False, weights=None, device=None, fid=None):
         super().__init__()
         assert batch_size > 0
+        self.fid = fid                      # a fid.FrechetInceptionDistance whose fake side shares this scorer's forward, or None
         if device is None:
             if not cuda:
                 raise RuntimeError('InceptionScore: the HIP path has no CPU fallback (cuda=False)')
@@ -408,7 +441,12 @@ class InceptionScore(nn.Module):
         """logits of one chunk (resized first when ``resize``)"""
         if self.resize and tuple(x.shape[2:]) != (299, 299):
             x = ops.resize_bilinear(x, (299, 299))
-        return self.inception_model(x)
+        if self.fid is None:
+            return self.inception_model(x)
+        f = self.inception_model.features(x)                # one forward for both numbers: forward() is fc(features(x))
+        self.fid.add_features(f)
+        with torch.no_grad():
+            return self.inception_model.fc(f)
 
     def forward(self, imgs):
         imgs = imgs.detach().to(self.device, torch.float32)

@@ -4,7 +4,7 @@ PyTorch-ROCm is used here as plumbing only: device allocation (torch.empty), the
 Every forward / backward is one or a few hand-written gfx950 kernel launches through ctypes; there is no eager / CPU fallback --
 a CPU tensor raises.
 
-One namespace, ten modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
+One namespace, eleven modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
   _core    ctypes call helpers, stream handle, workspace, parameter-gradient sinks (GradOut), path switches, layout hints,
            flat-buffer updates (Adam, fill, fold), profiler front end
   conv     Conv2d / ConvTranspose2d / sub-pixel up-conv / Linear (implicit GEMM, Winograd, head, skinny kernels)
@@ -18,6 +18,8 @@ One namespace, ten modules (the single 1 741-line ops.py of rounds 1-3, split by
   classifier  the accuracy network's own operators: padded 3x3 stride-2 max-pool, relu(a + b), BatchNorm fold, SGD step, accuracy record
   inception   the Inception score's own operators: rectangular conv into a channel slice, unpadded max-pool, count_include_pad average
               pool, bilinear resize, softmax rows, the score
+  fid         the Frechet Inception Distance's own operators: the float64 moment update (f64 matrix cores) and its finalize, the two
+              branch pools of the FID form of the network
 Everything is re-exported here, so ``ops.conv2d``, ``ops.GradOut``, ``ops._call`` ... keep working.  The path switches
 (``ops.WINOGRAD``, ``ops.FACTORED_LAYOUT``, ``ops.UPCONV``, ``ops.HEADCONV``, ``ops.WINOGRAD24``, ``ops.COND_FOLD``) are WRITABLE through this
 namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator modules read (``_core.WINOGRAD``).
@@ -25,9 +27,9 @@ namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator mod
 import sys
 import types
 
-from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception
+from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid
 
-_MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception)
+_MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid)
 _FLAGS = ('HEADCONV', 'WINOGRAD', 'WINOGRAD24', 'FACTORED_LAYOUT', 'UPCONV', 'COND_FOLD')
 
 for _m in _MODULES:

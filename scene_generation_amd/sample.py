@@ -18,6 +18,9 @@ scene_generation/data/utils.py it needs).
 * ``inception`` (an ``inception.InceptionScore``, off by default): the Inception score of the generated images (train.py:177-225
   applies it to validation batches; here to whatever is sampled), softmax rows accumulated on the device and read once by
   ``inception_summary``; ``--inception_weights`` on the command line.
+* ``fid`` (a ``fid.FrechetInceptionDistance``, off by default): the Frechet Inception Distance of the generated images to the real
+  statistics the object holds, float64 moments accumulated on the device and read once by ``fid_summary``; ``--fid_stats`` on the
+  command line.
 * ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
   (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
 Not here: scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
@@ -81,10 +84,12 @@ class Sampler(object):
     factored test-mode layout (Model.factored_test_layout).  ON by default: measured on MI355X at N = 32 / 128 x 128, 6.82 against
     7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
 
-    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None):
+    def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None,
+                 fid=None):
         self.model, self.features, self.factored = model, features, bool(factored)
         self.accuracy = accuracy             # accuracy.AccuracyMeter fed by sample_batch, or None
         self.inception = inception           # inception.InceptionScore fed by every forward, or None
+        self.fid = fid                       # fid.FrechetInceptionDistance whose fake side every forward feeds, or None
         self.graph_metrics = bool(graph_metrics)
         self.graph_counts = None             # running agreement counters (scenegraph.new_counts), on the device
         self.device = next(model.parameters()).device
@@ -105,6 +110,8 @@ class Sampler(object):
                     score(imgs_pred, boxes_pred)
                 if self.inception is not None:              # likewise the Inception network (no host synchronisation)
                     self.inception(imgs_pred)
+                if self.fid is not None and getattr(self.inception, 'fid', None) is not self.fid:      # (else fed by the scorer's forward)
+                    self.fid(imgs_pred)
                 images = ops.deprocess_images(imgs_pred, rescale=True, uint8=True)
                 rgb = None
                 if want_layout_rgb:
@@ -193,6 +200,13 @@ class Sampler(object):
             return None
         mean, std = self.inception.compute_score(splits=splits)
         return {'mean': mean, 'std': std, 'images': self.inception.count, 'splits': splits}
+
+    def fid_summary(self):
+        """the Frechet Inception Distance of everything sampled since the FID's ``clean()`` (one finalize launch, one device-to-host
+        copy, the eigen-decompositions on the host): {'fid', 'images'}; None without one"""
+        if self.fid is None:
+            return None
+        return {'fid': self.fid.compute(), 'images': self.fid.fake.count}
 
     def graph_summary(self):
         """the ONE device-to-host read of the graph metrics (scenegraph.summary); None when they are off or nothing was sampled"""
@@ -336,9 +350,19 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     inc_path = getattr(args, 'inception_weights', None)
     if inc_path is not None:
         from .inception import InceptionScore
+    fid, fid_stats = None, getattr(args, 'fid_stats', None)
+    if fid_stats is not None:
+        if inc_path is None:
+            raise ValueError('--fid_stats needs --inception_weights (the network whose features the statistics are of)')
+        from .fid import FrechetInceptionDistance
+        from .inception import load_inception
+        net = load_inception(inc_path, device)              # one network, one forward per batch, for both numbers
+        fid = FrechetInceptionDistance(weights=net, real_stats=fid_stats, resize=True, batch_size=args.batch_size, device=device)
+        scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=net, device=device, fid=fid)
+    elif inc_path is not None:
         scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=inc_path, device=device)
     sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter,
-                      inception=scorer)
+                      inception=scorer, fid=fid)
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -392,6 +416,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if scorer is not None:
         result['inception'] = sampler.inception_summary(getattr(args, 'inception_splits', 5))
         print('Inception {} {}'.format(result['inception']['mean'], result['inception']['std']))
+    if fid is not None:
+        result['fid'] = sampler.fid_summary()
+        print('FID {}'.format(result['fid']['fid']))
     if metrics:
         graph = result['graph'] = sampler.graph_summary()
         if graph is not None:
@@ -433,6 +460,9 @@ def make_parser():
     p.add_argument('--inception_weights', default=None, help='state_dict file of torchvision\'s inception_v3 (never downloaded): '
                    'prints one "Inception MEAN STD" line over the sampled images (python -m scene_generation_amd.inception scores a '
                    'directory of images)')
+    p.add_argument('--fid_stats', default=None, help='.npz with mu and sigma of the real images (python -m scene_generation_amd.fid '
+                   '--save_stats, or a pytorch-fid statistics file): prints one "FID x" line; needs --inception_weights, and only the '
+                   'pt_inception weights give numbers comparable with published ones')
     p.add_argument('--inception_splits', default=5, type=int, help='splits of the Inception score (train.py uses 5)')
     return p
 

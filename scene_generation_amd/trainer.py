@@ -339,6 +339,9 @@ class Trainer:
             self.writer.add_scalar('checkpoint/val_iou', val_avg_iou, index)
             self.writer.add_scalar('checkpoint/val_inception_mean', val_inception_mean, index)
             self.writer.add_scalar('checkpoint/val_inception_std', val_inception_std, index)
+            if len(val_results) > 3 and val_results[3] is not None:      # check_model(fid=...): otherwise exactly the keys above
+                self.writer.add_scalar('checkpoint/val_fid', val_results[3], index)
+                checkpoint.setdefault('val_fid', []).append(val_results[3])
         if self.obj_discriminator is not None:
             checkpoint['d_obj_state'] = self.obj_discriminator.state_dict()
             checkpoint['d_obj_optim_state'] = self.optimizer_d_obj.state_dict()
