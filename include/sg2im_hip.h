@@ -675,6 +675,34 @@ int sg_maxpool3s1_fwd(const float* x, float* y, int NC, int H, int W, sgStream s
  * fp64 [D, D], distinct from sum and outer.  n < 2 returns a negative code. */
 int sg_fid_moments_update(const float* x, int rows, int D, int ldx, double* sum, double* outer, sgStream stream);
 int sg_fid_moments_finalize(const double* sum, const double* outer, long long n, int D, double* mu, double* sigma, sgStream stream);
+/* ---- the diversity score: LPIPS on AlexNet / VGG-16 (lpips.hip; scene_generation_amd/lpips.py) ------------------------------------------
+ * Forward only.  No wrapper synchronises or allocates (the wide convolution keeps its k-split table in the plan cache like every
+ * gather); no float atomics: the same calls give bit-identical results.  Base pointers of fp32 operands may be unaligned.  A bad
+ * argument returns a negative code (sg_last_error_string) and launches nothing.
+ *
+ * sg_conv2d_wide_fwd / _plan / _ws_bytes: the contract, descriptor, plan struct and output-slice semantics of sg_conv2d_rect_*, for
+ * KH, KW <= 11 (up to 121 taps) and stride 1..4 -- AlexNet's 11 x 11 stride-4 stem.  The same implicit GEMM on the fp32 matrix cores
+ * over K = C * KH * KW (k ascending), zero padding, bias + SG_ACT_NONE / SG_ACT_RELU in the epilogue.  The plan's tile is always
+ * SG_RECT_TILE_64X64: the 121-tap LDS table of a 64-pixel tile leaves room for three workgroups per compute unit, that of a 128-pixel
+ * tile for one. */
+int sg_conv2d_wide_plan(const sgRectDesc* d, int w_aligned16, sgRectPlan* plan);
+size_t sg_conv2d_wide_ws_bytes(const sgRectDesc* d);
+int sg_conv2d_wide_fwd(const sgRectDesc* d, const float* x, const float* w, const float* bias, float* y, int act, void* ws,
+                       size_t ws_bytes, sgStream stream);
+/* The scaling layer of LPIPS: y[n, c, i] = (v - shift[c]) / scale[c] with shift = (-.030, -.088, -.188), scale = (.458, .448, .450),
+ * x [N, 3, HW] -- or, x_nhwc != 0, [N, HW, 3], the pictures a sampler hands out -- fp32 in [-1, 1] (v = x) or, x_uint8 != 0, uint8
+ * (v = x / 127.5 - 1); y fp32 [N, 3, HW].  Each operation is rounded to fp32 on its own (no fused multiply-add, no reciprocal). */
+int sg_lpips_input(const void* x, int x_uint8, int x_nhwc, int N, int HW, float* y, sgStream stream);
+/* One tap of the LPIPS distance.  f0, f1 fp32 [P, C, HW] (the two halves of one 2P forward; they may be the same pointer), w fp32 [C]
+ * (>= 0; NULL: all ones), out fp64 [P], 8-byte aligned: out[p] (accumulate != 0: +)= mean over the HW pixels of
+ *   s = sum_c w[c] * (f0_c / (n0 + eps) - f1_c / (n1 + eps))^2,   n = sqrt(sum_c f_c^2) per side,
+ * in the direct form (normalise, then difference) in fp32, both sides by the same code in the same order, so f0 == f1 gives exactly
+ * 0.0; a pixel of all zeros contributes 0 / (0 + eps) = 0.  The spatial sum is fp64 in a fixed order.  Every feature element is read
+ * from memory once for C <= 512.  ws >= sg_lpips_layer_ws_bytes(P, C, HW), 8-byte aligned (0 when a pair's pixels fit one workgroup:
+ * one launch; two otherwise).  P == 0 returns 0 and launches nothing. */
+size_t sg_lpips_layer_ws_bytes(int P, int C, int HW);
+int sg_lpips_layer(const float* f0, const float* f1, const float* w, int P, int C, int HW, float eps, double* out, int accumulate,
+                   void* ws, size_t ws_bytes, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

@@ -123,6 +123,8 @@ enum {
   SG_K_SOFTMAX_ROWS, SG_K_INCEPTION_SCORE,
   // the Frechet Inception Distance (fid.hip): the fp64 moment update (f64 MFMA) and its finalize
   SG_K_FID_MOMENTS,
+  // the diversity score (lpips.hip): the wide (up to 11 x 11, stride <= 4) convolution, the scaling layer, one tap of the distance
+  SG_K_WIDE_CONV, SG_K_LPIPS_INPUT, SG_K_LPIPS_LAYER,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -1,0 +1,300 @@
+"""The diversity score: the mean LPIPS distance (richzhang/PerceptualSimilarity) between two pictures generated from the same scene
+graph with different appearance draws -- the "Diversity" column of the reference's results table.
+
+    python -m scene_generation_amd.lpips --net alex --backbone W --lin L --dir0 A --dir1 B   -> Diversity MEAN STD
+
+* ``AlexFeatures`` / ``Vgg16Features``: the two backbones, inference only, parameters under torchvision's names
+  (``features.<i>.weight|bias``), five taps each.  AlexNet's 11 x 11 stride-4 stem is ``ops.conv2d_wide``, its other convs
+  ``ops.conv2d_rect``, its pools ``ops.maxpool3s2v``; VGG-16 runs the conv + ReLU and 2 x 2 pool launches ``losses.Vgg19`` runs.
+* ``LPIPS``: the scaling layer (``ops.lpips_input``), ONE forward of the 2P pictures of P pairs, five ``ops.lpips_layer`` launches
+  that add the taps into a float64 [P] device tensor.  No host synchronisation.
+* ``Diversity``: the scorer ``Sampler(diversity=...)`` drives -- distances gathered in a device buffer, read once by ``compute()``.
+* Published numbers come from the package's pretrained backbone and its learned "lin" weights.  Nothing is ever downloaded: both are
+  local files.  Without lin weights the unweighted baseline runs, with a loud warning.
+"""
+import argparse
+import re
+import sys
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from .accuracy import _strip_module_prefix
+from .inception import find_images, read_image
+
+__all__ = ['AlexFeatures', 'Vgg16Features', 'LPIPS', 'Diversity', 'load_lin_weights', 'backbone_state_dict', 'pair_files', 'main']
+
+# (torchvision ``features`` index, cin, cout, kernel, stride, pad, 3 x 3 stride-2 max-pool in front)
+_ALEX_CONVS = ((0, 3, 64, 11, 4, 2, False), (3, 64, 192, 5, 1, 2, True), (6, 192, 384, 3, 1, 1, True), (8, 384, 256, 3, 1, 1, False),
+               (10, 256, 256, 3, 1, 1, False))
+_VGG16_CFG = (64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512)
+_VGG16_SLICES = ((0, 4), (4, 9), (9, 16), (16, 23), (23, 30))          # end behind relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+CHANNELS = {'alex': (64, 192, 384, 256, 256), 'vgg': (64, 128, 256, 512, 512)}
+
+
+# ---- weights ----------------------------------------------------------------------------------------------------------------------------
+def _state_dict(src):
+    """a state_dict from a path (``torch.load``) or a mapping, a DataParallel ``module.`` prefix stripped"""
+    if isinstance(src, str):
+        src = torch.load(src, map_location='cpu')
+    return _strip_module_prefix(dict(src))
+
+
+def backbone_state_dict(src):
+    """the ``features.<i>.weight|bias`` entries of a backbone file: a torchvision ``alexnet`` / ``vgg16`` state_dict (its
+    ``classifier.*`` entries are dropped) or a whole LPIPS module's, where the backbone sits under ``net.slice<j>.<i>.*`` with
+    torchvision's index ``i`` kept.  -> dict, or None when ``src`` holds no backbone entry"""
+    out = {}
+    for k, v in _state_dict(src).items():
+        m = re.match(r'(?:features|net\.slice\d+)\.(\d+)\.(weight|bias)$', k)
+        if m:
+            out['features.%s.%s' % (m.group(1), m.group(2))] = v
+    return out or None
+
+
+def load_lin_weights(src, channels):
+    """the five learned "lin" weight vectors of an LPIPS file as float32 tensors [C_k]: ``lin<k>.model.1.weight`` (the package's
+    weights/v0.1/<net>.pth) or ``lins.<k>.model.1.weight`` (a whole module's state_dict), each [1, C_k, 1, 1].  A negative weight
+    is refused: the distance is a weighted sum of squares and the package clamps its weights at zero during training."""
+    sd = _state_dict(src)
+    out = []
+    for k, C in enumerate(channels):
+        w = sd.get('lin%d.model.1.weight' % k, sd.get('lins.%d.model.1.weight' % k))
+        if w is None:
+            raise KeyError('LPIPS lin weights: no lin%d.model.1.weight / lins.%d.model.1.weight' % (k, k))
+        w = torch.as_tensor(w, dtype=torch.float32).reshape(-1)
+        if w.numel() != C:
+            raise ValueError('LPIPS lin weights: tap %d has %d weights, the backbone %d channels' % (k, w.numel(), C))
+        if bool((w < 0).any()) or not bool(torch.isfinite(w).all()):
+            raise ValueError('LPIPS lin weights: tap %d holds a negative or non-finite weight' % k)
+        out.append(w.contiguous())
+    return out
+
+
+class _Backbone(nn.Module):
+    def load_backbone(self, src):
+        """``src``: a path or a state_dict in one of ``backbone_state_dict``'s forms; loaded strictly"""
+        sd = backbone_state_dict(src)
+        if sd is None:
+            raise KeyError('%s: no features.<i>.weight (or net.slice<j>.<i>.weight) entry' % type(self).__name__)
+        self.load_state_dict(sd, strict=True)
+        return self
+
+    def _he_init(self, seed):
+        g = torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for m in self.features:
+                if isinstance(m, nn.Conv2d):
+                    fan_in = m.in_channels * m.kernel_size[0] * m.kernel_size[1]
+                    m.weight.copy_(torch.randn(m.weight.shape, generator=g) * (2.0 / fan_in) ** 0.5)
+                    m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.05)
+        for p in self.parameters():
+            p.requires_grad = False
+
+
+class AlexFeatures(_Backbone):
+    """torchvision ``alexnet().features`` up to the ReLU behind conv 10 -> the five taps behind the ReLUs of convs 0, 3, 6, 8, 10.
+    Only the convs are modules (under torchvision's indices); ReLU is the conv launch's epilogue."""
+    channels = CHANNELS['alex']
+
+    def __init__(self, seed=11):
+        super().__init__()
+        self.features = nn.Sequential()
+        for idx, cin, cout, k, s, p, _ in _ALEX_CONVS:
+            self.features.add_module(str(idx), nn.Conv2d(cin, cout, k, stride=s, padding=p))
+        self._he_init(seed)
+
+    def forward(self, x):
+        taps = []
+        with torch.no_grad():
+            for idx, _, _, k, s, p, pool in _ALEX_CONVS:
+                c = getattr(self.features, str(idx))
+                if pool:
+                    x = ops.maxpool3s2v(x)
+                conv = ops.conv2d_wide if idx == 0 else ops.conv2d_rect
+                x = conv(x, c.weight, c.bias, stride=s, pad=(p, p), act=ops.ACT_RELU)
+                taps.append(x)
+        return taps
+
+
+class Vgg16Features(_Backbone):
+    """torchvision ``vgg16().features[0:30]`` -> relu1_2, relu2_2, relu3_3, relu4_3, relu5_3: conv3x3(pad 1) + ReLU in one launch and
+    MaxPool2d(2), the layers and container of ``losses.Vgg19``, under torchvision's indices."""
+    channels = CHANNELS['vgg']
+
+    def __init__(self, seed=16):
+        super().__init__()
+        from .layers import Conv2d, FusedSequential, MaxPool2d, ReLU
+        self.features = FusedSequential()
+        cin, idx = 3, 0
+        for v in _VGG16_CFG:
+            if v == 'M':
+                self.features.add_module(str(idx), MaxPool2d(2, 2))
+                idx += 1
+            else:
+                self.features.add_module(str(idx), Conv2d(cin, v, kernel_size=3, padding=1))
+                self.features.add_module(str(idx + 1), ReLU(True))
+                cin, idx = v, idx + 2
+        assert idx == 30
+        self._he_init(seed)
+
+    def forward(self, x):
+        taps = []
+        with torch.no_grad():
+            for lo, hi in _VGG16_SLICES:
+                x = self.features(x, start=lo, end=hi)
+                taps.append(x)
+        return taps
+
+
+# ---- the distance -----------------------------------------------------------------------------------------------------------------------
+class LPIPS(nn.Module):
+    """``forward(x0, x1)`` -> float64 [P] on the device: the LPIPS distance of each pair of pictures [P, 3, H, W], float32 in [-1, 1]
+    or uint8 (``channels_last=True``: [P, H, W, 3]).
+
+    ``net``: 'alex' or 'vgg'.  ``backbone_weights``: a torchvision ``alexnet`` / ``vgg16`` state_dict (path or mapping; never
+    downloaded), or None -- then the backbone of ``lin_weights`` when that is a whole LPIPS module's state_dict, else a seeded random
+    network and a loud warning.  ``lin_weights``: the package's lin file or a whole module's state_dict (``load_lin_weights``), or
+    None for the unweighted form (w = 1), which does NOT compare with published numbers."""
+
+    def __init__(self, net='alex', backbone_weights=None, lin_weights=None, device='cuda'):
+        super().__init__()
+        if net not in CHANNELS:
+            raise ValueError("LPIPS: net must be 'alex' or 'vgg', got %r (the SqueezeNet variant is not built)" % (net,))
+        self.net_name = net
+        self.net = AlexFeatures() if net == 'alex' else Vgg16Features()
+        lin_sd = _state_dict(lin_weights) if lin_weights is not None else None
+        if backbone_weights is None and lin_sd is not None and backbone_state_dict(lin_sd) is not None:
+            backbone_weights = lin_sd
+        if backbone_weights is not None:
+            self.net.load_backbone(backbone_weights)
+        else:
+            print('WARNING: LPIPS(%s) is built WITHOUT pretrained backbone weights: a seeded random initialisation. Its distances '
+                  'are MEANINGLESS as LPIPS; pass the path of a torchvision %s state_dict.'
+                  % (net, 'alexnet' if net == 'alex' else 'vgg16'), file=sys.stderr)
+        if lin_sd is not None:
+            lins = load_lin_weights(lin_sd, self.net.channels)
+        else:
+            print('WARNING: LPIPS(%s) runs WITHOUT lin weights (lin_weights=None): the unweighted baseline, every channel weight 1. '
+                  'ITS NUMBERS DO NOT COMPARE WITH PUBLISHED LPIPS / DIVERSITY VALUES.' % net, file=sys.stderr)
+            lins = [None] * 5
+        for k, w in enumerate(lins):
+            self.register_buffer('lin%d' % k, w)
+        self.to(device)
+        self.eval()
+
+    def lin(self, k):
+        return getattr(self, 'lin%d' % k)
+
+    def forward(self, x0, x1, channels_last=False):
+        if x0.shape != x1.shape or x0.dtype != x1.dtype:
+            raise ValueError('LPIPS: two picture batches of one shape and type, got %s %s and %s %s'
+                             % (x0.dtype, tuple(x0.shape), x1.dtype, tuple(x1.shape)))
+        P = x0.size(0)
+        device = self.lin_device()
+        x = ops.lpips_input(torch.cat([x0.detach().to(device), x1.detach().to(device)]), channels_last=channels_last)
+        out = torch.empty(P, dtype=torch.float64, device=device)
+        for k, t in enumerate(self.net(x)):
+            ops.lpips_layer(t[:P], t[P:], self.lin(k), out=out, accumulate=k > 0)
+        return out
+
+    def lin_device(self):
+        return next(self.net.parameters()).device
+
+
+class Diversity(object):
+    """mean and population std of the LPIPS distance over pairs of pictures.  ``__call__(imgs0, imgs1)``: two batches of one shape,
+    float32 [N, 3, H, W] in [-1, 1], uint8 [N, 3, H, W], or uint8 [N, H, W, 3] (what ``SampleOut.images`` holds); the distances go
+    into a float64 device buffer (doubled when full); nothing is read back until ``compute()``."""
+
+    def __init__(self, lpips, batch_size=32):
+        assert batch_size > 0
+        self.lpips, self.batch_size = lpips, int(batch_size)
+        self.dist, self.count = None, 0
+
+    def clean(self):
+        self.count = 0
+
+    def _reserve(self, rows, device):
+        need = self.count + rows
+        cap = 0 if self.dist is None else self.dist.numel()
+        if need <= cap:
+            return
+        new_cap = max(cap, 4 * self.batch_size)
+        while new_cap < need:
+            new_cap *= 2
+        buf = torch.empty(new_cap, dtype=torch.float64, device=device)
+        if self.count:
+            buf[:self.count].copy_(self.dist[:self.count])
+        self.dist = buf
+
+    def __call__(self, imgs0, imgs1):
+        channels_last = imgs0.dim() == 4 and imgs0.dtype == torch.uint8 and imgs0.size(3) == 3 and imgs0.size(1) != 3
+        for a in range(0, imgs0.size(0), self.batch_size):
+            d = self.lpips(imgs0[a:a + self.batch_size], imgs1[a:a + self.batch_size], channels_last=channels_last)
+            self._reserve(d.numel(), d.device)
+            self.dist[self.count:self.count + d.numel()].copy_(d)
+            self.count += d.numel()
+
+    def compute(self):
+        """{'mean', 'std', 'pairs'}: float64 mean and POPULATION std of the distances; the one device-to-host read"""
+        if self.count == 0:
+            return {'mean': float('nan'), 'std': float('nan'), 'pairs': 0}
+        d = self.dist[:self.count]
+        mean = d.mean()
+        std = ((d - mean) ** 2).mean().sqrt()
+        mean, std = torch.stack([mean, std]).tolist()
+        return {'mean': mean, 'std': std, 'pairs': self.count}
+
+
+# ---- command line -----------------------------------------------------------------------------------------------------------------------
+def pair_files(dir0, dir1):
+    """[(path in dir0, path in dir1)]: the image files of both directories (``inception.find_images``: recursive, sorted), the i-th
+    of one with the i-th of the other"""
+    a, b = find_images(dir0), find_images(dir1)
+    if not a:
+        raise SystemExit('no images under %s' % dir0)
+    if len(a) != len(b):
+        raise SystemExit('%d images under %s against %d under %s: the directories do not pair up' % (len(a), dir0, len(b), dir1))
+    return list(zip(a, b))
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog='python -m scene_generation_amd.lpips',
+                                description='Diversity: mean LPIPS distance between the pictures of two directories, paired by sorted name')
+    p.add_argument('--net', default='alex', choices=sorted(CHANNELS))
+    p.add_argument('--backbone', default=None, type=str, help='torchvision alexnet / vgg16 state_dict file (never downloaded)')
+    p.add_argument('--lin', default=None, type=str, help='the LPIPS lin weights (weights/v0.1/<net>.pth of the package, or a whole '
+                   'module\'s state_dict); without them the unweighted baseline runs and the number compares with nothing published')
+    p.add_argument('--dir0', required=True, type=str)
+    p.add_argument('--dir1', required=True, type=str)
+    p.add_argument('--batch_size', default=32, type=int)
+    p.add_argument('--device', default='cuda', type=str)
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    pairs = pair_files(args.dir0, args.dir1)
+    scorer = Diversity(LPIPS(args.net, backbone_weights=args.backbone, lin_weights=args.lin, device=args.device), args.batch_size)
+    g0, g1, shape = [], [], None
+    for pa, pb in pairs + [(None, None)]:
+        a = read_image(pa) if pa is not None else None
+        if g0 and (a is None or tuple(a.shape) != shape or len(g0) == args.batch_size):      # one chunk per image size
+            scorer(torch.stack(g0), torch.stack(g1))
+            g0, g1 = [], []
+        if a is not None:
+            b = read_image(pb)
+            if b.shape != a.shape:
+                raise SystemExit('%s and %s differ in size' % (pa, pb))
+            g0.append(a)
+            g1.append(b)
+            shape = tuple(a.shape)
+    r = scorer.compute()
+    print('Diversity {} {}'.format(r['mean'], r['std']))
+    return r['mean'], r['std']
+
+
+if __name__ == '__main__':
+    main()

@@ -4,7 +4,7 @@ PyTorch-ROCm is used here as plumbing only: device allocation (torch.empty), the
 Every forward / backward is one or a few hand-written gfx950 kernel launches through ctypes; there is no eager / CPU fallback --
 a CPU tensor raises.
 
-One namespace, eleven modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
+One namespace, twelve modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
   _core    ctypes call helpers, stream handle, workspace, parameter-gradient sinks (GradOut), path switches, layout hints,
            flat-buffer updates (Adam, fill, fold), profiler front end
   conv     Conv2d / ConvTranspose2d / sub-pixel up-conv / Linear (implicit GEMM, Winograd, head, skinny kernels)
@@ -20,6 +20,8 @@ One namespace, eleven modules (the single 1 741-line ops.py of rounds 1-3, split
               pool, bilinear resize, softmax rows, the score
   fid         the Frechet Inception Distance's own operators: the float64 moment update (f64 matrix cores) and its finalize, the two
               branch pools of the FID form of the network
+  lpips       the diversity score's own operators: the wide (up to 11 x 11, stride <= 4) convolution, the scaling layer of LPIPS, one tap
+              of its distance
 Everything is re-exported here, so ``ops.conv2d``, ``ops.GradOut``, ``ops._call`` ... keep working.  The path switches
 (``ops.WINOGRAD``, ``ops.FACTORED_LAYOUT``, ``ops.UPCONV``, ``ops.HEADCONV``, ``ops.WINOGRAD24``, ``ops.COND_FOLD``) are WRITABLE through this
 namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator modules read (``_core.WINOGRAD``).
@@ -27,9 +29,9 @@ namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator mod
 import sys
 import types
 
-from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid
+from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid, lpips
 
-_MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid)
+_MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid, lpips)
 _FLAGS = ('HEADCONV', 'WINOGRAD', 'WINOGRAD24', 'FACTORED_LAYOUT', 'UPCONV', 'COND_FOLD')
 
 for _m in _MODULES:

@@ -21,6 +21,10 @@ scene_generation/data/utils.py it needs).
 * ``fid`` (a ``fid.FrechetInceptionDistance``, off by default): the Frechet Inception Distance of the generated images to the real
   statistics the object holds, float64 moments accumulated on the device and read once by ``fid_summary``; ``--fid_stats`` on the
   command line.
+* ``diversity`` (an ``lpips.Diversity``, off by default): the mean LPIPS distance between two pictures of the same scene graph with
+  different appearance draws.  ``sample_pair`` runs ``sample_batch`` and then a second forward of the same batch with fresh bank
+  draws that feeds this scorer ONLY; read once by ``diversity_summary``; ``--diversity_backbone`` / ``--diversity_lin`` /
+  ``--diversity_net`` on the command line.
 * ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
   (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
 Not here: scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
@@ -85,7 +89,8 @@ class Sampler(object):
     7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
 
     def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None,
-                 fid=None):
+                 fid=None, diversity=None):
+        self.diversity = diversity           # lpips.Diversity fed by sample_pair, or None
         self.model, self.features, self.factored = model, features, bool(factored)
         self.accuracy = accuracy             # accuracy.AccuracyMeter fed by sample_batch, or None
         self.inception = inception           # inception.InceptionScore fed by every forward, or None
@@ -99,7 +104,8 @@ class Sampler(object):
         self.iou = None                      # running (sum IoU, > 0.5, > 0.3, boxes) of sample_batch, on the device
 
     # -- the forward + what follows the network -------------------------------------------------------------------------------------
-    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs, score=None):
+    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs, score=None, scored=True):
+        """``scored=False`` (the second forward of ``sample_pair``): no scorer sees the network's output"""
         m = self.model
         saved = (m.factored_test_layout, m.objs_host, m.obj_to_img_host)
         m.factored_test_layout, m.objs_host, m.obj_to_img_host = self.factored, objs_h, o2i_h
@@ -108,9 +114,9 @@ class Sampler(object):
                 imgs_pred, boxes_pred, masks_pred, _, layout, _ = fn()
                 if score is not None:                       # the accuracy network reads the network's output, before deprocessing
                     score(imgs_pred, boxes_pred)
-                if self.inception is not None:              # likewise the Inception network (no host synchronisation)
+                if scored and self.inception is not None:   # likewise the Inception network (no host synchronisation)
                     self.inception(imgs_pred)
-                if self.fid is not None and getattr(self.inception, 'fid', None) is not self.fid:      # (else fed by the scorer's forward)
+                if scored and self.fid is not None and getattr(self.inception, 'fid', None) is not self.fid:      # (else fed by the scorer's forward)
                     self.fid(imgs_pred)
                 images = ops.deprocess_images(imgs_pred, rescale=True, uint8=True)
                 rgb = None
@@ -130,10 +136,11 @@ class Sampler(object):
         return SampleOut(images, boxes_pred, masks_pred, rgb, layout if want_layout else None, objs)
 
     def sample_batch(self, batch, use_gt_boxes=False, use_gt_masks=False, use_gt_textures=False, use_gt_attr=False,
-                     want_layout_rgb=False, want_layout=False):
+                     want_layout_rgb=False, want_layout=False, _scored=True):
         """One collated batch (imgs, objs, boxes, masks, triples, obj_to_img, triple_to_img, attributes), the flags of
         sample_images.py:203-221.  Without ground-truth textures every object takes a random row of its class's bank, drawn with
-        ``random.randint`` in object order like the reference (``random.seed`` reproduces it)."""
+        ``random.randint`` in object order like the reference (``random.seed`` reproduces it).  (``_scored=False``, the second
+        forward of ``sample_pair``: the same forward with no scorer fed and no counter touched.)"""
         imgs, objs, boxes, masks, triples, obj_to_img, _, attributes = [t.to(self.device) for t in batch]
         objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()        # the call's one host synchronisation
         features = None
@@ -150,16 +157,35 @@ class Sampler(object):
             attributes = torch.zeros_like(attributes)
         m = self.model
         score = None
-        if self.accuracy is not None:        # sample_images.py:224-239: crops at the ground-truth boxes when they drive the layout
+        if _scored and self.accuracy is not None:        # sample_images.py:224-239: crops at the ground-truth boxes when they drive the layout
             def score(imgs_pred, boxes_pred):
                 self.accuracy.update(imgs_pred, boxes if use_gt_boxes else boxes_pred, obj_to_img, objs)
         out = self._forward(lambda: m(imgs, objs, triples, obj_to_img, boxes_gt=boxes, masks_gt=masks if use_gt_masks else None,
                                       attributes=attributes, test_mode=True, use_gt_box=use_gt_boxes, features=features),
-                            objs_h, o2i_h, want_layout_rgb, want_layout, objs, score)
+                            objs_h, o2i_h, want_layout_rgb, want_layout, objs, score, _scored)
+        if not _scored:
+            return out
         tot = iou_totals(out.boxes_pred, boxes, obj_to_img)
         self.iou = tot if self.iou is None else self.iou + tot
         self._graph_metrics(out, triples, given_attributes)
         return out
+
+    def sample_pair(self, batch, use_gt_boxes=False, use_gt_masks=False, use_gt_textures=False, use_gt_attr=False,
+                    want_layout_rgb=False, want_layout=False):
+        """``sample_batch`` (IoU, accuracy, Inception, FID and the graph counters see this forward only), then a second forward of
+        the same batch with fresh draws from the appearance bank; the two sets of pictures go to the diversity scorer as pairs (no
+        host synchronisation beyond the two forwards').  -> (SampleOut, SampleOut).  With ground-truth textures nothing is random and
+        both forwards give the same picture: that raises instead of reporting a diversity of 0.  (The second forward draws from
+        ``random`` like any forward -- the bank rows, and the model's appearance pool -- so the stream moves on.)"""
+        if self.diversity is None:
+            raise ValueError('sample_pair: the sampler was built without a diversity scorer (Sampler(diversity=...))')
+        if use_gt_textures:
+            raise ValueError('sample_pair: with use_gt_textures nothing is random -- both forwards would give the same picture and '
+                             'the diversity would be 0 by construction; diversity needs the appearance bank\'s draws')
+        first = self.sample_batch(batch, use_gt_boxes, use_gt_masks, False, use_gt_attr, want_layout_rgb, want_layout)
+        second = self.sample_batch(batch, use_gt_boxes, use_gt_masks, False, use_gt_attr, _scored=False)
+        self.diversity(first.images, second.images)
+        return first, second
 
     def sample_json(self, scene_graphs, want_layout_rgb=False, want_layout=False):
         """Scene graphs as dictionaries (Model.encode_scene_graphs, which APPENDS to them) -> SampleOut with ``objs``."""
@@ -207,6 +233,10 @@ class Sampler(object):
         if self.fid is None:
             return None
         return {'fid': self.fid.compute(), 'images': self.fid.fake.count}
+
+    def diversity_summary(self):
+        """the ONE device-to-host read of the diversity scorer (lpips.Diversity.compute): {'mean', 'std', 'pairs'}; None without one"""
+        return self.diversity.compute() if self.diversity is not None else None
 
     def graph_summary(self):
         """the ONE device-to-host read of the graph metrics (scenegraph.summary); None when they are off or nothing was sampled"""
@@ -361,8 +391,16 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=net, device=device, fid=fid)
     elif inc_path is not None:
         scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=inc_path, device=device)
+    diversity, div_backbone, div_lin = None, getattr(args, 'diversity_backbone', None), getattr(args, 'diversity_lin', None)
+    if div_backbone is not None or div_lin is not None:
+        if graphs or layouts or args.use_gt_textures:
+            raise ValueError('--diversity_backbone / --diversity_lin: diversity compares two appearance draws of a collated batch; '
+                             'it needs the bank (no --use_gt_textures, --scene_graphs or --layouts)')
+        from .lpips import LPIPS, Diversity
+        diversity = Diversity(LPIPS(getattr(args, 'diversity_net', 'alex'), backbone_weights=div_backbone, lin_weights=div_lin,
+                                    device=device), batch_size=args.batch_size)
     sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter,
-                      inception=scorer, fid=fid)
+                      inception=scorer, fid=fid, diversity=diversity)
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -402,6 +440,10 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
             imgs_gt = None
             if gt_dir is not None:
                 imgs_gt = ops.deprocess_images(batch[0].to(sampler.device), rescale=True, uint8=True).cpu().numpy()
+            if diversity is not None:
+                save(sampler.sample_pair(batch, args.use_gt_boxes, args.use_gt_masks, args.use_gt_textures, args.use_gt_attr,
+                                         want_layout_rgb=args.save_layout)[0], imgs_gt)
+                continue
             save(sampler.sample_batch(batch, args.use_gt_boxes, args.use_gt_masks, args.use_gt_textures, args.use_gt_attr,
                                       want_layout_rgb=args.save_layout), imgs_gt)
     summary = sampler.iou_summary()
@@ -419,6 +461,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if fid is not None:
         result['fid'] = sampler.fid_summary()
         print('FID {}'.format(result['fid']['fid']))
+    if diversity is not None:
+        result['diversity'] = sampler.diversity_summary()
+        print('Diversity {} {}'.format(result['diversity']['mean'], result['diversity']['std']))
     if metrics:
         graph = result['graph'] = sampler.graph_summary()
         if graph is not None:
@@ -463,6 +508,12 @@ def make_parser():
     p.add_argument('--fid_stats', default=None, help='.npz with mu and sigma of the real images (python -m scene_generation_amd.fid '
                    '--save_stats, or a pytorch-fid statistics file): prints one "FID x" line; needs --inception_weights, and only the '
                    'pt_inception weights give numbers comparable with published ones')
+    p.add_argument('--diversity_backbone', default=None, help='torchvision alexnet / vgg16 state_dict file (never downloaded): every '
+                   'batch is sampled twice with different appearance draws and one "Diversity MEAN STD" line (mean LPIPS distance '
+                   'of the pairs) is printed; python -m scene_generation_amd.lpips scores two directories of pictures')
+    p.add_argument('--diversity_lin', default=None, help='the LPIPS lin weights of --diversity_net (or a whole LPIPS module\'s '
+                   'state_dict, which also holds the backbone); without them the unweighted baseline runs')
+    p.add_argument('--diversity_net', default='alex', choices=['alex', 'vgg'])
     p.add_argument('--inception_splits', default=5, type=int, help='splits of the Inception score (train.py uses 5)')
     return p
 
