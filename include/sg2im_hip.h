@@ -703,6 +703,38 @@ int sg_lpips_input(const void* x, int x_uint8, int x_nhwc, int N, int HW, float*
 size_t sg_lpips_layer_ws_bytes(int P, int C, int HW);
 int sg_lpips_layer(const float* f0, const float* f1, const float* w, int P, int C, int HW, float eps, double* out, int accumulate,
                    void* ws, size_t ws_bytes, sgStream stream);
+/* ---- statistics of all pairs of feature rows (featsets.hip; scene_generation_amd/featsets.py) --------------------------------------------
+ * The Kernel Inception Distance's kernel sums and the k-NN manifold estimate (improved precision / recall, density / coverage).  Feature
+ * rows are fp32 [rows, D] with a row stride >= D elements (any 4-byte aligned base).  Every dot product is formed in fp64 from the
+ * converted fp32 operands on the f64 matrix cores (v_mfma_f64_16x16x4_f64), k ascending: the products are exact and only the sums
+ * round.  d2(a, b) = max(0, |a|^2 + |b|^2 - 2 a.b) with the norms computed in fp64 by the same unit.  No floating-point atomics:
+ * partial results go to ws and are combined in a fixed order; counts are integer atomics and minima are integer atomic minima of
+ * the bit patterns of non-negative doubles -- the same call gives bit-identical output.  No call synchronises or allocates.  ws is
+ * 8-byte aligned and at least the matching _ws_bytes; fp64 operands are 8-byte, int operands 4-byte aligned.  A null or misaligned
+ * pointer, a size < 1, a row stride < D or a k / degree out of range returns a negative code (sg_last_error_string) and launches
+ * nothing; zero work (S == 0; n == 0; n == 0 or m == 0) returns 0 without looking at the pointers and writes nothing.
+ *
+ * sg_feat_poly_sums: x [n, D], y [m, D]; ix, iy int32 [S, s] device tables of row numbers (ix into x, iy into y); out fp64 [S, 3]:
+ *   out[q] = ( sum_{i != j} k(x_ix[q,i], x_ix[q,j]),  sum_{i != j} k(y_iy[q,i], y_iy[q,j]),  sum_{i, j} k(x_ix[q,i], y_iy[q,j]) )
+ * with k(a, b) = (gamma a.b + coef0)^degree by repeated multiplication, degree in 1..4; i != j is by position in the subset.  Rows
+ * are gathered through the tables in the operand loader: no gathered copy and no s x s matrix is written.  An index outside its set
+ * reads as a zero row (no address is formed from it).  The symmetric sums run over tile pairs ti <= tj with off-diagonal tiles
+ * doubled.
+ *
+ * sg_feat_knn_radius: r2[i] = the k-th smallest of { d2(x_i, x_j) : j != i } (exclusion by index: duplicate rows count), fp64 [n],
+ * 1 <= k <= 8, k < n.  The columns are split over workgroups and the partial lists merged by a second kernel.
+ *
+ * sg_feat_manifold_counts: references a [n, D] with their radii r2 [n], queries b [m, D]:
+ *   count[j] = #{ i : d2(b_j, a_i) <= r2[i] }  (int32 [m]),    mind2[i] = min_j d2(a_i, b_j)  (fp64 [n]);
+ * both are initialised by the call. */
+size_t sg_feat_poly_sums_ws_bytes(int S, int s);
+int sg_feat_poly_sums(const float* x, int n, int ldx, const float* y, int m, int ldy, int D, const int* ix, const int* iy, int S, int s,
+                      double gamma, double coef0, int degree, double* out, void* ws, size_t ws_bytes, sgStream stream);
+size_t sg_feat_knn_radius_ws_bytes(int n);
+int sg_feat_knn_radius(const float* x, int n, int D, int ldx, int k, double* r2, void* ws, size_t ws_bytes, sgStream stream);
+size_t sg_feat_manifold_counts_ws_bytes(int n, int m);
+int sg_feat_manifold_counts(const float* a, int n, int lda, const double* r2, const float* b, int m, int ldb, int D, int* count,
+                            double* mind2, void* ws, size_t ws_bytes, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

@@ -125,6 +125,8 @@ enum {
   SG_K_FID_MOMENTS,
   // the diversity score (lpips.hip): the wide (up to 11 x 11, stride <= 4) convolution, the scaling layer, one tap of the distance
   SG_K_WIDE_CONV, SG_K_LPIPS_INPUT, SG_K_LPIPS_LAYER,
+  // statistics of all pairs of feature rows (featsets.hip): the KID kernel sums, the manifold radii and membership pass (f64 MFMA)
+  SG_K_FEAT_POLY, SG_K_FEAT_MANIFOLD,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -1,6 +1,7 @@
 """The Frechet Inception Distance: the fourth value of ``evaluate.check_model`` (the reference leaves it None, train.py:81).
 
-    python -m scene_generation_amd.fid --weights W --real DIR|STATS.npz --fake DIR [--save_stats OUT.npz] [--batch_size 32]   -> FID x
+    python -m scene_generation_amd.fid --weights W --real DIR|STATS.npz --fake DIR [--save_stats OUT.npz] [--save_features OUT.npy]
+                                       [--batch_size 32]   -> FID x
 
 * ``FeatureMoments``: count, sum and the upper triangle of the outer-product sum of feature rows, float64, on the device
   (sg_fid_moments_update on the f64 matrix cores: one launch per batch, no feature is kept or read back).  ``statistics()`` is one
@@ -127,10 +128,17 @@ class FrechetInceptionDistance(object):
     ``__call__(imgs)`` adds to the fake side (``add_features(f)`` takes pooled features directly: ``InceptionScore(fid=...)``);
     ``clean()`` clears the fake side only, ``clean_real()`` the real one; ``needs_real`` says whether the real side still has to be
     fed (an accumulated real side is closed by the first ``compute()``: a validation pass feeds it once and later passes reuse it);
-    ``compute()`` -> float.  No call but ``compute()`` synchronises."""
+    ``compute()`` -> float.  No call but ``compute()`` synchronises.
 
-    def __init__(self, weights=None, real_stats=None, resize=True, batch_size=32, device=None):
+    ``sets``: a ``featsets.FeatureSetMetrics`` (None: off, and nothing below runs).  Every pooled feature row this object sees is then
+    also handed to it -- fake rows through ``add_features`` / ``__call__``, real rows through ``add_real`` -- so KID and precision /
+    recall share this object's Inception forward; ``clean`` and ``clean_real`` clear its sides too.  The caller reads
+    ``fid.sets.compute()``.  With ``real_stats`` the real rows never pass through here: the attached object must then hold its own
+    (``FeatureSetMetrics(real_features=...)``)."""
+
+    def __init__(self, weights=None, real_stats=None, resize=True, batch_size=32, device=None, sets=None):
         assert batch_size > 0
+        self.sets = sets
         self.resize, self.batch_size, self.device = resize, batch_size, torch.device(device if device is not None else 'cuda')
         weights = weights if weights is not None else _inc.DEFAULT_WEIGHTS
         if weights is not None:
@@ -155,6 +163,14 @@ class FrechetInceptionDistance(object):
         else:
             self.real = FeatureMoments(dim, self.device)
             self._real_open = True
+        if sets is not None:
+            if sets.dim != dim:
+                raise ValueError('FrechetInceptionDistance: sets keeps features of %d dimensions, the network gives %d' % (sets.dim, dim))
+            if (real_stats is not None) != bool(sets.real_fixed):
+                raise ValueError('FrechetInceptionDistance: real_stats fixes the real side, so the attached FeatureSetMetrics needs '
+                                 'real_features= (the rows the statistics were made of) -- and only then' if real_stats is not None else
+                                 'FrechetInceptionDistance: the attached FeatureSetMetrics has real_features= but the real side here '
+                                 'is fed through add_real; give real_stats= as well, or leave real_features out')
 
     # ---- feeding ------------------------------------------------------------------------------------------------------------------------
     @property
@@ -172,10 +188,12 @@ class FrechetInceptionDistance(object):
     def add_features(self, feats):
         """pooled features [rows, dim] of fake images (the entry ``InceptionScore(fid=...)`` uses)"""
         self.fake.update(feats)
+        if self.sets is not None:
+            self.sets.add_features(feats)
 
     def __call__(self, imgs):
         for f in self._features(imgs):
-            self.fake.update(f)
+            self.add_features(f)
 
     def add_real(self, imgs):
         if self.real is None:
@@ -183,15 +201,21 @@ class FrechetInceptionDistance(object):
         self._real_stats, self._root = None, None
         for f in self._features(imgs):
             self.real.update(f)
+            if self.sets is not None:
+                self.sets.add_real_features(f)
 
     def clean(self):
         self.fake.clean()
+        if self.sets is not None:
+            self.sets.clean()
 
     def clean_real(self):
         if self.real is None:
             raise RuntimeError('FrechetInceptionDistance.clean_real: the real side is fixed by real_stats')
         self.real.clean()
         self._real_stats, self._root, self._real_open = None, None, True
+        if self.sets is not None:
+            self.sets.clean_real()
 
     # ---- the number ---------------------------------------------------------------------------------------------------------------------
     def real_statistics(self):
@@ -237,6 +261,8 @@ def build_parser():
     p.add_argument('--real', required=True, type=str, help='a directory of images, or an .npz with mu and sigma')
     p.add_argument('--fake', required=True, type=str, help='a directory of images')
     p.add_argument('--save_stats', default=None, type=str, help='write the statistics of --real (a directory) to this .npz')
+    p.add_argument('--save_features', default=None, type=str, help='write the pooled features of --real (a directory) to this .npy: '
+                   'the real side of python -m scene_generation_amd.featsets and of sample --real_features')
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
     return p
@@ -247,11 +273,24 @@ def main(argv=None):
     stats = args.real if args.real.lower().endswith('.npz') else None
     if stats is not None and args.save_stats:
         raise SystemExit('--save_stats needs --real to be a directory of images')
+    if stats is not None and args.save_features:
+        raise SystemExit('--save_features needs --real to be a directory of images')
     fid = FrechetInceptionDistance(weights=args.weights, real_stats=stats, resize=True, batch_size=args.batch_size, device=args.device)
     if stats is None:
-        _feed_dir(fid.add_real, args.real, args.batch_size)
+        feed_real = fid.add_real
+        if args.save_features:          # the rows are kept only on request: a plain run holds moments alone
+            from .featsets import FeatureBank
+            bank = FeatureBank(fid.fake.dim, fid.device)
+
+            def feed_real(imgs):
+                for f in fid._features(imgs):
+                    fid.real.update(f)
+                    bank.update(f)
+        _feed_dir(feed_real, args.real, args.batch_size)
         if args.save_stats:
             fid.real.save(args.save_stats)
+        if args.save_features:
+            bank.save(args.save_features)
     _feed_dir(fid, args.fake, args.batch_size)
     value = fid.compute()
     print('FID {}'.format(value))

@@ -21,6 +21,9 @@ scene_generation/data/utils.py it needs).
 * ``fid`` (a ``fid.FrechetInceptionDistance``, off by default): the Frechet Inception Distance of the generated images to the real
   statistics the object holds, float64 moments accumulated on the device and read once by ``fid_summary``; ``--fid_stats`` on the
   command line.
+* ``sets`` (a ``featsets.FeatureSetMetrics``, off by default): KID and precision / recall / density / coverage of the generated images
+  against the real feature rows the object holds, fed from the same Inception forward as ``fid`` / ``inception`` when one of them
+  carries it, read once by ``featsets_summary``; ``--real_features`` on the command line.
 * ``diversity`` (an ``lpips.Diversity``, off by default): the mean LPIPS distance between two pictures of the same scene graph with
   different appearance draws.  ``sample_pair`` runs ``sample_batch`` and then a second forward of the same batch with fresh bank
   draws that feeds this scorer ONLY; read once by ``diversity_summary``; ``--diversity_backbone`` / ``--diversity_lin`` /
@@ -89,8 +92,9 @@ class Sampler(object):
     7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
 
     def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None,
-                 fid=None, diversity=None):
+                 fid=None, diversity=None, sets=None):
         self.diversity = diversity           # lpips.Diversity fed by sample_pair, or None
+        self.sets = sets                     # featsets.FeatureSetMetrics whose fake side every forward feeds, or None
         self.model, self.features, self.factored = model, features, bool(factored)
         self.accuracy = accuracy             # accuracy.AccuracyMeter fed by sample_batch, or None
         self.inception = inception           # inception.InceptionScore fed by every forward, or None
@@ -118,6 +122,8 @@ class Sampler(object):
                     self.inception(imgs_pred)
                 if scored and self.fid is not None and getattr(self.inception, 'fid', None) is not self.fid:      # (else fed by the scorer's forward)
                     self.fid(imgs_pred)
+                if scored and self.sets is not None and not self._sets_shared():
+                    self.sets(imgs_pred)
                 images = ops.deprocess_images(imgs_pred, rescale=True, uint8=True)
                 rgb = None
                 if want_layout_rgb:
@@ -226,6 +232,15 @@ class Sampler(object):
             return None
         mean, std = self.inception.compute_score(splits=splits)
         return {'mean': mean, 'std': std, 'images': self.inception.count, 'splits': splits}
+
+    def _sets_shared(self):
+        """``sets`` is fed by the forward of ``fid`` (attached as its ``sets``) or of the scorer (in the place of its ``fid``)"""
+        return (self.fid is not None and getattr(self.fid, 'sets', None) is self.sets) or getattr(self.inception, 'fid', None) is self.sets
+
+    def featsets_summary(self):
+        """``FeatureSetMetrics.compute()`` over everything sampled since its ``clean()``: KID mean / std, precision, recall, density,
+        coverage and the row counts; None without one"""
+        return None if self.sets is None else self.sets.compute()
 
     def fid_summary(self):
         """the Frechet Inception Distance of everything sampled since the FID's ``clean()`` (one finalize launch, one device-to-host
@@ -359,6 +374,8 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     """sample_images.py:163-295 without COCO: sample every batch of ``loader`` (any iterable of collated batches; the synthetic
     generator when None) or the scene graphs of ``args.scene_graphs``, write one picture per image into output_dir/images
     (+ images_gt, layouts), print and return the IoU summary and the paths written."""
+    if getattr(args, 'real_features', None) is not None and getattr(args, 'inception_weights', None) is None:      # before any work
+        raise ValueError('--real_features needs --inception_weights (the network whose features the rows are)')
     model = build_model(args, checkpoint, device)
     graphs = getattr(args, 'scene_graphs', None)
     layouts = getattr(args, 'layouts', None)
@@ -381,14 +398,21 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if inc_path is not None:
         from .inception import InceptionScore
     fid, fid_stats = None, getattr(args, 'fid_stats', None)
-    if fid_stats is not None:
+    sets, real_features = None, getattr(args, 'real_features', None)
+    if fid_stats is not None or real_features is not None:
         if inc_path is None:
             raise ValueError('--fid_stats needs --inception_weights (the network whose features the statistics are of)')
-        from .fid import FrechetInceptionDistance
         from .inception import load_inception
-        net = load_inception(inc_path, device)              # one network, one forward per batch, for both numbers
-        fid = FrechetInceptionDistance(weights=net, real_stats=fid_stats, resize=True, batch_size=args.batch_size, device=device)
-        scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=net, device=device, fid=fid)
+        net = load_inception(inc_path, device)              # one network, one forward per batch, for every number
+        if real_features is not None:
+            from .featsets import FeatureSetMetrics
+            sets = FeatureSetMetrics(weights=net, real_features=real_features, resize=True, batch_size=args.batch_size, device=device)
+        if fid_stats is not None:
+            from .fid import FrechetInceptionDistance
+            fid = FrechetInceptionDistance(weights=net, real_stats=fid_stats, resize=True, batch_size=args.batch_size, device=device,
+                                           sets=sets)
+        # (without --fid_stats the feature rows go straight from the scorer's forward to the sets object: the same add_features)
+        scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=net, device=device, fid=fid if fid is not None else sets)
     elif inc_path is not None:
         scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=inc_path, device=device)
     diversity, div_backbone, div_lin = None, getattr(args, 'diversity_backbone', None), getattr(args, 'diversity_lin', None)
@@ -400,7 +424,7 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         diversity = Diversity(LPIPS(getattr(args, 'diversity_net', 'alex'), backbone_weights=div_backbone, lin_weights=div_lin,
                                     device=device), batch_size=args.batch_size)
     sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter,
-                      inception=scorer, fid=fid, diversity=diversity)
+                      inception=scorer, fid=fid, diversity=diversity, sets=sets)
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -461,6 +485,11 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if fid is not None:
         result['fid'] = sampler.fid_summary()
         print('FID {}'.format(result['fid']['fid']))
+    if sets is not None:
+        from .featsets import format_lines
+        result['featsets'] = sampler.featsets_summary()
+        for line in format_lines(result['featsets']):
+            print(line)
     if diversity is not None:
         result['diversity'] = sampler.diversity_summary()
         print('Diversity {} {}'.format(result['diversity']['mean'], result['diversity']['std']))
@@ -508,6 +537,9 @@ def make_parser():
     p.add_argument('--fid_stats', default=None, help='.npz with mu and sigma of the real images (python -m scene_generation_amd.fid '
                    '--save_stats, or a pytorch-fid statistics file): prints one "FID x" line; needs --inception_weights, and only the '
                    'pt_inception weights give numbers comparable with published ones')
+    p.add_argument('--real_features', default=None, help='.npy with the pooled Inception features of the real images (python -m '
+                   'scene_generation_amd.fid --save_features, or python -m scene_generation_amd.featsets --save_real): prints "KID mean '
+                   'std", "Precision p Recall r" and "Density d Coverage c" lines; needs --inception_weights; with or without --fid_stats')
     p.add_argument('--diversity_backbone', default=None, help='torchvision alexnet / vgg16 state_dict file (never downloaded): every '
                    'batch is sampled twice with different appearance draws and one "Diversity MEAN STD" line (mean LPIPS distance '
                    'of the pairs) is printed; python -m scene_generation_amd.lpips scores two directories of pictures')
