@@ -735,6 +735,51 @@ int sg_feat_knn_radius(const float* x, int n, int D, int ldx, int k, double* r2,
 size_t sg_feat_manifold_counts_ws_bytes(int n, int m);
 int sg_feat_manifold_counts(const float* a, int n, int lda, const double* r2, const float* b, int m, int ldb, int D, int* count,
                             double* mind2, void* ws, size_t ws_bytes, sgStream stream);
+/* ---- Pillow-exact antialiased resize of a ragged batch of uint8 RGB images (imageprep.hip; scene_generation_amd/imageprep.py) -----------
+ * ``Image.resize((OW, OH), BILINEAR | BICUBIC)`` of Pillow on 8-bit RGB, bit for bit (no ``box``, no ``reducing_gap``), with the
+ * loader's ToTensor + Normalize(0.5, 0.5) fused in as a table lookup.
+ *
+ * The arithmetic, per axis, with S = 1 (bilinear) or 2 (bicubic), in float64 with every operation rounded once (no fma contraction):
+ *   scale = in / out, fs = max(scale, 1), support = S fs; for output index xx: center = (xx + 0.5) scale,
+ *   xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in), tap x in [0, xmax - xmin) has weight
+ *   w = f((x + xmin - center + 0.5) (1 / fs)), f(t) = 1 - |t| below 1 (bilinear); with a = -0.5, ((a + 2)|t| - (a + 3)) |t| |t| + 1 below 1
+ *   and (((|t| - 5)|t| + 8)|t| - 4) a below 2 (bicubic); 0 beyond.  ww = the sum of w in tap order from 0.0; w / ww when ww != 0; the
+ *   coefficient is k = (int)(0.5 + w 2^22) for w >= 0 and (int)(-0.5 + w 2^22) below, (int) truncating toward zero.
+ *   An output byte is clip((2^21 + sum_j pixel[xmin + j] k[j]) >> 22, 0, 255), the sum in int32.
+ * The horizontal pass [H, W] -> [H, OW] runs first and is rounded to uint8, the vertical pass [H, OW] -> [OH, OW] follows; a pass whose
+ * input and output length are equal is skipped (the identity).  The tap count 2 ceil(support) + 1 is whatever the sizes imply (32 769
+ * for 16384 -> 1 bicubic): it is never capped.
+ *
+ * Limits: 1 <= H, W <= SG_PIL_MAX_IN; 1 <= OH, OW <= SG_PIL_MAX_OUT; N <= SG_PIL_MAX_IMAGES; at most 2^31 - 1 groups of 8 source rows.
+ *
+ * sg_pil_resize_plan (HOST only; nothing is launched): desc_host int64 [N][3] rows (byte offset, H, W) of images stored as tight
+ * [H][W][3] bytes in a buffer of packed_bytes bytes -- offsets are arbitrary (no alignment), every image must lie inside the buffer
+ * (a negative code otherwise).  Writes table_host int64 [N + 1][SG_PIL_TABLE_COLS] -- per image {offset, H, W, coefficient offset of
+ * the horizontal and of the vertical pass (-1: skipped), their tap strides, offset of the [H, OW, 3] intermediate (-1: none), first
+ * horizontal workgroup}; row N holds the workgroup total: the prefix the horizontal pass searches -- and totals_host int64 [4] =
+ * {coef_ints, inter_bytes, hblocks, workspace bytes}.
+ *
+ * sg_pil_resize: packed uint8 (device, 4-byte aligned base), table = the plan's table uploaded as it is (8-byte aligned), coef_ints /
+ * inter_bytes / hblocks its totals; lut fp32 [256] (device): the value of y for each byte (the caller builds it with the loader's own
+ * expression, so y is bitwise the loader's); y8 uint8 [N, OH, OW, 3] and / or y fp32 [N, 3, OH, OW] (either may be null, not both);
+ * ws 16-byte aligned and at least totals[3] bytes: the coefficients, then the ragged intermediates.  Three launches on ``stream``
+ * (coefficients of every (image, axis, output index) computed on the device from the table; horizontal; vertical), fewer when every
+ * image skips a pass.  ``phases`` = SG_PIL_ALL; a subset of its bits issues only those launches, for timing them one by one (the
+ * workspace must then hold what the omitted ones would have written).  No call synchronises or allocates; N == 0 returns 0 and
+ * launches nothing.  The horizontal pass stages SG_PIL_LDS_CHUNK bytes of a source row in LDS at once and
+ * walks longer tap spans chunk by chunk. */
+enum { SG_PIL_BILINEAR = 0, SG_PIL_BICUBIC = 1 };
+enum { SG_PIL_COEF = 1, SG_PIL_HORIZONTAL = 2, SG_PIL_VERTICAL = 4, SG_PIL_ALL = 7 };
+#define SG_PIL_MAX_IN 16384
+#define SG_PIL_MAX_OUT 4096
+#define SG_PIL_MAX_IMAGES 65536
+#define SG_PIL_TABLE_COLS 9
+#define SG_PIL_LDS_CHUNK 4096
+int sg_pil_resize_plan(const int64_t* desc_host, int N, int64_t packed_bytes, int OH, int OW, int filter, int64_t* table_host,
+                       int64_t* totals_host);
+int sg_pil_resize(const void* packed, int64_t packed_bytes, const int64_t* table, int N, int OH, int OW, int filter, int64_t coef_ints,
+                  int64_t inter_bytes, int64_t hblocks, const float* lut, void* y8, float* y, void* ws, size_t ws_bytes, int phases,
+                  sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

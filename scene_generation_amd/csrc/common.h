@@ -127,6 +127,8 @@ enum {
   SG_K_WIDE_CONV, SG_K_LPIPS_INPUT, SG_K_LPIPS_LAYER,
   // statistics of all pairs of feature rows (featsets.hip): the KID kernel sums, the manifold radii and membership pass (f64 MFMA)
   SG_K_FEAT_POLY, SG_K_FEAT_MANIFOLD,
+  // the Pillow-exact resize of a ragged uint8 batch (imageprep.hip): coefficients + horizontal + vertical pass of one call
+  SG_K_PIL_RESIZE,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -299,7 +299,8 @@ def build_parser():
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    return p
+    from .imageprep import add_arguments
+    return add_arguments(p)
 
 
 def main(argv=None):
@@ -309,14 +310,15 @@ def main(argv=None):
     sets = FeatureSetMetrics(weights=args.weights, real_features=args.real if real_npy else None, k=args.k,
                              kid_subsets=args.kid_subsets, kid_subset_size=args.kid_subset_size, seed=args.seed, resize=True,
                              batch_size=args.batch_size, device=args.device)
+    prep = dict(image_size=args.image_size, resize_filter=args.resize_filter, device=sets.device)
     if not real_npy:
-        _feed_dir(sets.add_real, args.real, args.batch_size)
+        _feed_dir(sets.add_real, args.real, args.batch_size, **prep)
     if args.save_real:
         sets.real.save(args.save_real)
     if fake_npy:
         sets.add_features(torch.from_numpy(load_features(args.fake)).to(sets.device))
     else:
-        _feed_dir(sets, args.fake, args.batch_size)
+        _feed_dir(sets, args.fake, args.batch_size, **prep)
     res = sets.compute()
     for line in format_lines(res):
         print(line)

@@ -1,7 +1,7 @@
 """The Frechet Inception Distance: the fourth value of ``evaluate.check_model`` (the reference leaves it None, train.py:81).
 
     python -m scene_generation_amd.fid --weights W --real DIR|STATS.npz --fake DIR [--save_stats OUT.npz] [--save_features OUT.npy]
-                                       [--batch_size 32]   -> FID x
+                                       [--batch_size 32] [--image_size H,W [--resize_filter bilinear|bicubic]]   -> FID x
 
 * ``FeatureMoments``: count, sum and the upper triangle of the outer-product sum of feature rows, float64, on the device
   (sg_fid_moments_update on the f64 matrix cores: one launch per batch, no feature is kept or read back).  ``statistics()`` is one
@@ -237,10 +237,18 @@ class FrechetInceptionDistance(object):
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------------
-def _feed_dir(feed, root, batch_size):
+def _feed_dir(feed, root, batch_size, *, image_size=None, resize_filter='bilinear', device='cuda'):
+    """``feed(imgs)`` over the images under ``root``.  Without ``image_size``: the files at their stored sizes, one chunk per run of
+    equal sizes.  With it: every file brought to ``image_size`` by the loader's resize on ``device`` (``imageprep.ImageDirFeeder``),
+    in full chunks of ``batch_size``."""
     paths = find_images(root)
     if not paths:
         raise SystemExit('no images under %s' % root)
+    if image_size is not None:
+        from .imageprep import ImageDirFeeder
+        for batch in ImageDirFeeder(root, batch_size, image_size, resize_filter, device):
+            feed(batch)
+        return len(paths)
     group, shape = [], None
     for path in paths + [None]:
         img = read_image(path) if path is not None else None
@@ -265,7 +273,8 @@ def build_parser():
                    'the real side of python -m scene_generation_amd.featsets and of sample --real_features')
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    return p
+    from .imageprep import add_arguments
+    return add_arguments(p)
 
 
 def main(argv=None):
@@ -276,6 +285,7 @@ def main(argv=None):
     if stats is not None and args.save_features:
         raise SystemExit('--save_features needs --real to be a directory of images')
     fid = FrechetInceptionDistance(weights=args.weights, real_stats=stats, resize=True, batch_size=args.batch_size, device=args.device)
+    prep = dict(image_size=args.image_size, resize_filter=args.resize_filter, device=fid.device)
     if stats is None:
         feed_real = fid.add_real
         if args.save_features:          # the rows are kept only on request: a plain run holds moments alone
@@ -286,12 +296,12 @@ def main(argv=None):
                 for f in fid._features(imgs):
                     fid.real.update(f)
                     bank.update(f)
-        _feed_dir(feed_real, args.real, args.batch_size)
+        _feed_dir(feed_real, args.real, args.batch_size, **prep)
         if args.save_stats:
             fid.real.save(args.save_stats)
         if args.save_features:
             bank.save(args.save_features)
-    _feed_dir(fid, args.fake, args.batch_size)
+    _feed_dir(fid, args.fake, args.batch_size, **prep)
     value = fid.compute()
     print('FID {}'.format(value))
     return value

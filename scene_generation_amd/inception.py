@@ -1,6 +1,7 @@
 """The Inception score: the reference's last evaluation figure (scripts/inception_score.py, train.py:177-225) on this stack.
 
     python -m scene_generation_amd.inception --dir DIR --weights PATH [--splits 5] [--batch_size 32]     -> mean and std
+                                             [--image_size H,W [--resize_filter bilinear|bicubic]]
 
 * ``InceptionV3``: torchvision's Inception-v3 (``inception_v3(transform_input=False)``) with its ``state_dict`` keys and shapes, so
   the published ``inception_v3_google-*.pth`` loads with ``strict=True``.  Inference only: every conv + BatchNorm + ReLU is ONE
@@ -495,7 +496,8 @@ def build_parser():
     p.add_argument('--splits', default=5, type=int)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    return p
+    from .imageprep import add_arguments
+    return add_arguments(p)
 
 
 def main(argv=None):
@@ -506,7 +508,12 @@ def main(argv=None):
     scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=args.weights, device=args.device)
     print('Calculating Inception Score...')
     group, shape = [], None
-    for path in paths + [None]:
+    if args.image_size is not None:             # every file through the loader's resize on the device: full batches of one size
+        from .imageprep import ImageDirFeeder
+        for batch in ImageDirFeeder(args.dir, args.batch_size, args.image_size, args.resize_filter, scorer.device):
+            scorer(batch)
+        paths = []
+    for path in (paths + [None] if paths else []):
         img = read_image(path) if path is not None else None
         if group and (img is None or tuple(img.shape) != shape or len(group) == args.batch_size):      # one chunk per image size
             scorer(torch.stack(group))

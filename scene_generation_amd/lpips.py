@@ -2,6 +2,7 @@
 graph with different appearance draws -- the "Diversity" column of the reference's results table.
 
     python -m scene_generation_amd.lpips --net alex --backbone W --lin L --dir0 A --dir1 B   -> Diversity MEAN STD
+                                         [--image_size H,W [--resize_filter bilinear|bicubic]]
 
 * ``AlexFeatures`` / ``Vgg16Features``: the two backbones, inference only, parameters under torchvision's names
   (``features.<i>.weight|bias``), five taps each.  AlexNet's 11 x 11 stride-4 stem is ``ops.conv2d_wide``, its other convs
@@ -271,7 +272,8 @@ def build_parser():
     p.add_argument('--dir1', required=True, type=str)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    return p
+    from .imageprep import add_arguments
+    return add_arguments(p)
 
 
 def main(argv=None):
@@ -279,7 +281,13 @@ def main(argv=None):
     pairs = pair_files(args.dir0, args.dir1)
     scorer = Diversity(LPIPS(args.net, backbone_weights=args.backbone, lin_weights=args.lin, device=args.device), args.batch_size)
     g0, g1, shape = [], [], None
-    for pa, pb in pairs + [(None, None)]:
+    if args.image_size is not None:             # both directories through the loader's resize on the device: full chunks of one size
+        from .imageprep import ImageDirFeeder
+        feeds = [ImageDirFeeder(d, args.batch_size, args.image_size, args.resize_filter, args.device) for d in (args.dir0, args.dir1)]
+        for a, b in zip(*feeds):
+            scorer(a, b)
+        pairs = []
+    for pa, pb in (pairs + [(None, None)] if pairs else []):
         a = read_image(pa) if pa is not None else None
         if g0 and (a is None or tuple(a.shape) != shape or len(g0) == args.batch_size):      # one chunk per image size
             scorer(torch.stack(g0), torch.stack(g1))
