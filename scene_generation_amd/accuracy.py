@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import layers, ops
 from .bilinear import crop_bbox_batch
+from .evalkit import FoldCache, folded, state_dict_of
 
 __all__ = ['BasicBlock', 'Bottleneck', 'ResNet', 'resnet18', 'resnet34', 'resnet50', 'resnet101', 'resnet152',
            'all_pretrained_models', 'load_model', 'train_model', 'StepLR', 'AccuracyMeter']
@@ -31,23 +32,8 @@ def _conv_bn(conv, bn, x, relu, fold):
     act = ops.ACT_RELU if relu else ops.ACT_NONE
     if fold is None:
         return bn(conv(x), act=act)
-    w, b = _folded(conv, bn, fold)
+    w, b = folded(conv, bn, fold)
     return ops.conv2d(x, w, b, stride=conv.stride[0], pad=conv.padding[0], act=act)
-
-
-def _fold_key(conv, bn):
-    ts = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    return tuple((t.data_ptr(), t._version) for t in ts) + (float(bn.eps),)
-
-
-def _folded(conv, bn, cache):
-    """the folded (weight, bias) of conv + bn from ``cache``, rebuilt when a tensor of the pair was replaced or written in place"""
-    key = _fold_key(conv, bn)
-    hit = cache.get(id(bn))
-    if hit is None or hit[0] != key:
-        w, b = ops.bn_fold(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-        hit = cache[id(bn)] = (key, w, b)
-    return hit[1], hit[2]
 
 
 def _conv(cin, cout, k, stride=1):
@@ -96,7 +82,7 @@ class Bottleneck(nn.Module):
         return ops.add_relu(out, idt)
 
 
-class ResNet(nn.Module):
+class ResNet(FoldCache):
     """torchvision.models.ResNet(block, layers, num_classes) with its ``state_dict`` keys: conv1, bn1, layer1..4, fc.
 
     Eval fast path (``fold_batchnorm``, a class attribute; ON by default: measured on MI355X, ResNet-101 at 224 in 64-crop chunks,
@@ -125,7 +111,6 @@ class ResNet(nn.Module):
         self.layer4 = self._make_layer(block, 512, layer_sizes[3], stride=2)
         self.avgpool = layers.GlobalAvgPool()
         self.fc = layers.Linear(512 * block.expansion, num_classes)
-        self._fold_cache = {}
         for m in self.modules():        # torchvision's init
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
@@ -144,21 +129,9 @@ class ResNet(nn.Module):
             mods.append(block(self.inplanes, planes))
         return nn.Sequential(*mods)
 
-    # ---- the fold cache ---------------------------------------------------------------------------------------------------------
-    def drop_fold(self):
-        self._fold_cache.clear()
-
-    def train(self, mode=True):
+    def train(self, mode=True):         # on top of evalkit.FoldCache: running statistics move in training mode
         self.drop_fold()
         return super().train(mode)
-
-    def load_state_dict(self, *args, **kwargs):
-        self.drop_fold()
-        return super().load_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):          # .to() / .cuda() / .float(): the tensors move, the folded copies would not
-        self.drop_fold()
-        return super()._apply(fn, *args, **kwargs)
 
     def _stages(self):
         return [[self.conv1, self.bn1], [self.layer1], [self.layer2], [self.layer3], [self.layer4]]
@@ -253,13 +226,6 @@ def conv_descs(name, size=224):
     return out
 
 
-def _strip_module_prefix(sd):
-    """the keys of a torch.nn.DataParallel save ('module.conv1.weight') without their prefix"""
-    if sd and all(k.startswith('module.') for k in sd):
-        return {k[len('module.'):]: v for k, v in sd.items()}
-    return sd
-
-
 def all_pretrained_models(n_class, name='resnet101', weights=None):
     """train_accuracy_net.py:62-101.  Every parameter is frozen, a fresh ``fc`` with ``n_class`` outputs is trainable, and every
     child after ``layer1`` is made trainable again: conv1, bn1 and layer1 stay frozen (their BatchNorms still run in training
@@ -271,8 +237,7 @@ def all_pretrained_models(n_class, name='resnet101', weights=None):
     print('[Building %s]' % name)
     model = _build(name, 1000)
     if weights is not None:
-        sd = torch.load(weights, map_location='cpu') if isinstance(weights, str) else weights
-        sd = {k: v for k, v in _strip_module_prefix(dict(sd)).items() if not k.startswith('fc.')}
+        sd = {k: v for k, v in state_dict_of(weights).items() if not k.startswith('fc.')}
         missing, unexpected = model.load_state_dict(sd, strict=False)
         missing = [k for k in missing if not k.startswith('fc.')]
         if missing or unexpected:
@@ -296,7 +261,7 @@ def all_pretrained_models(n_class, name='resnet101', weights=None):
 def load_model(path, name='resnet101', n_class=172, device='cuda'):
     """train_accuracy_net.py:237-242: the classifier saved by ``train`` (or by the reference), on ``device``, in eval mode.  Also
     accepts the ``module.`` prefix of a DataParallel save.  ``n_class=None`` takes the class count from the file's ``fc.weight``."""
-    sd = _strip_module_prefix(dict(torch.load(path, map_location='cpu')))
+    sd = state_dict_of(path)
     if n_class is None:
         n_class = int(sd['fc.weight'].shape[0])
     model = _build(name, n_class)

@@ -22,14 +22,14 @@ are kept -- on the device:
   for every number); ``check_model(fid=f)`` then fills it and the caller reads ``f.sets.compute()``.
 """
 import argparse
-import sys
 
 import numpy as np
 import torch
 
-from . import inception as _inc
 from . import ops
-from .inception import InceptionV3, load_inception
+from .evalkit import grow_rows
+from .imageprep import _feed_dir, add_arguments
+from .inception import inception_network, pooled_features
 
 __all__ = ['FeatureBank', 'FeatureSetMetrics', 'draw_subsets', 'kid_from_sums', 'manifold_metrics', 'load_features', 'main']
 
@@ -47,15 +47,6 @@ class FeatureBank(object):
     def clean(self):
         self.count = 0
 
-    def _reserve(self, rows):
-        cap = self.buf.size(0)
-        if self.count + rows > cap:
-            while cap < self.count + rows:
-                cap *= 2
-            grown = torch.empty(cap, self.dim, dtype=torch.float32, device=self.device)
-            grown[:self.count].copy_(self.buf[:self.count])
-            self.buf = grown
-
     def update(self, feats):
         """append the rows of ``feats`` (float32 [rows, dim]): one copy, no synchronisation"""
         if feats.dim() != 2 or feats.size(1) != self.dim:
@@ -63,7 +54,7 @@ class FeatureBank(object):
         if feats.dtype != torch.float32:
             raise TypeError('FeatureBank.update: features must be float32, got %s' % feats.dtype)
         rows = int(feats.size(0))
-        self._reserve(rows)
+        self.buf = grow_rows(self.buf, self.count, rows, 1, (self.dim,), torch.float32, self.device)     # (the capacity is never 0)
         self.buf[self.count:self.count + rows].copy_(feats.detach())
         self.count += rows
 
@@ -184,29 +175,15 @@ class FeatureSetMetrics(object):
 
     def _network(self):
         if self.inception_model is None:
-            weights = self._weights if self._weights is not None else _inc.DEFAULT_WEIGHTS
-            if weights is not None:
-                net = load_inception(weights, self.device) if isinstance(weights, str) else weights.to(self.device)
-            else:
-                print('WARNING: FeatureSetMetrics is built WITHOUT pretrained weights (weights=None): a seeded random initialisation. '
-                      'Its numbers are MEANINGLESS as KID / precision / recall; pass the path of pt_inception-2015-12-05-*.pth.',
-                      file=sys.stderr)
-                with torch.random.fork_rng(devices=[]):
-                    torch.manual_seed(0)
-                    net = InceptionV3(num_classes=_inc.FID_CLASSES, aux_logits=False, fid_variant=True).to(self.device)
+            net = inception_network(self._weights, self.device, 'FeatureSetMetrics', True,
+                                    'numbers are MEANINGLESS as KID / precision / recall')
             if net.fc.in_features != self.dim:
                 raise ValueError('FeatureSetMetrics: a network of %d features for banks of %d' % (net.fc.in_features, self.dim))
-            self.inception_model = net.eval()
+            self.inception_model = net
         return self.inception_model
 
     def _features(self, imgs):
-        net = self._network()
-        imgs = imgs.detach().to(self.device, torch.float32)
-        for a in range(0, imgs.size(0), self.batch_size):
-            x = imgs[a:a + self.batch_size]
-            if self.resize and tuple(x.shape[2:]) != (299, 299):
-                x = ops.resize_bilinear(x, (299, 299))
-            yield net.features(x)
+        return pooled_features(self._network(), imgs, self.batch_size, self.resize, self.device)
 
     def add_features(self, feats):
         """pooled features [rows, dim] of fake images"""
@@ -299,12 +276,10 @@ def build_parser():
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    from .imageprep import add_arguments
     return add_arguments(p)
 
 
 def main(argv=None):
-    from .fid import _feed_dir
     args = build_parser().parse_args(argv)
     real_npy, fake_npy = args.real.lower().endswith('.npy'), args.fake.lower().endswith('.npy')
     sets = FeatureSetMetrics(weights=args.weights, real_features=args.real if real_npy else None, k=args.k,

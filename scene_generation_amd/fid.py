@@ -15,14 +15,14 @@
   a paper's.  Nothing is ever downloaded: ``weights`` is a local file.
 """
 import argparse
-import sys
 
 import numpy as np
 import torch
 
-from . import inception as _inc
 from . import ops
-from .inception import InceptionV3, find_images, load_inception, read_image
+from .featsets import FeatureBank
+from .imageprep import _feed_dir, add_arguments
+from .inception import inception_network, pooled_features
 
 __all__ = ['FeatureMoments', 'FrechetInceptionDistance', 'frechet_distance', 'load_statistics', 'main']
 
@@ -140,17 +140,8 @@ class FrechetInceptionDistance(object):
         assert batch_size > 0
         self.sets = sets
         self.resize, self.batch_size, self.device = resize, batch_size, torch.device(device if device is not None else 'cuda')
-        weights = weights if weights is not None else _inc.DEFAULT_WEIGHTS
-        if weights is not None:
-            self.inception_model = load_inception(weights, self.device) if isinstance(weights, str) else weights.to(self.device)
-        else:
-            print('WARNING: FrechetInceptionDistance is built WITHOUT pretrained weights (weights=None): a seeded random '
-                  'initialisation. Its distances are MEANINGLESS as FIDs; pass the path of pt_inception-2015-12-05-*.pth.',
-                  file=sys.stderr)
-            with torch.random.fork_rng(devices=[]):
-                torch.manual_seed(0)
-                self.inception_model = InceptionV3(num_classes=_inc.FID_CLASSES, aux_logits=False, fid_variant=True).to(self.device)
-        self.inception_model.eval()
+        self.inception_model = inception_network(weights, self.device, 'FrechetInceptionDistance', True,
+                                                 'distances are MEANINGLESS as FIDs')
         dim = self.inception_model.fc.in_features
         self.fake = FeatureMoments(dim, self.device)
         self.real, self._real_stats, self._real_open, self._root = None, None, False, None
@@ -178,12 +169,7 @@ class FrechetInceptionDistance(object):
         return self._real_open
 
     def _features(self, imgs):
-        imgs = imgs.detach().to(self.device, torch.float32)
-        for a in range(0, imgs.size(0), self.batch_size):
-            x = imgs[a:a + self.batch_size]
-            if self.resize and tuple(x.shape[2:]) != (299, 299):
-                x = ops.resize_bilinear(x, (299, 299))
-            yield self.inception_model.features(x)
+        return pooled_features(self.inception_model, imgs, self.batch_size, self.resize, self.device)
 
     def add_features(self, feats):
         """pooled features [rows, dim] of fake images (the entry ``InceptionScore(fid=...)`` uses)"""
@@ -237,30 +223,6 @@ class FrechetInceptionDistance(object):
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------------
-def _feed_dir(feed, root, batch_size, *, image_size=None, resize_filter='bilinear', device='cuda'):
-    """``feed(imgs)`` over the images under ``root``.  Without ``image_size``: the files at their stored sizes, one chunk per run of
-    equal sizes.  With it: every file brought to ``image_size`` by the loader's resize on ``device`` (``imageprep.ImageDirFeeder``),
-    in full chunks of ``batch_size``."""
-    paths = find_images(root)
-    if not paths:
-        raise SystemExit('no images under %s' % root)
-    if image_size is not None:
-        from .imageprep import ImageDirFeeder
-        for batch in ImageDirFeeder(root, batch_size, image_size, resize_filter, device):
-            feed(batch)
-        return len(paths)
-    group, shape = [], None
-    for path in paths + [None]:
-        img = read_image(path) if path is not None else None
-        if group and (img is None or tuple(img.shape) != shape or len(group) == batch_size):      # one chunk per image size
-            feed(torch.stack(group))
-            group = []
-        if img is not None:
-            group.append(img)
-            shape = tuple(img.shape)
-    return len(paths)
-
-
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m scene_generation_amd.fid',
                                 description='Frechet Inception Distance between two sets of images (resized to 299 x 299 on the device)')
@@ -273,7 +235,6 @@ def build_parser():
                    'the real side of python -m scene_generation_amd.featsets and of sample --real_features')
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    from .imageprep import add_arguments
     return add_arguments(p)
 
 
@@ -289,7 +250,6 @@ def main(argv=None):
     if stats is None:
         feed_real = fid.add_real
         if args.save_features:          # the rows are kept only on request: a plain run holds moments alone
-            from .featsets import FeatureBank
             bank = FeatureBank(fid.fake.dim, fid.device)
 
             def feed_real(imgs):

@@ -10,6 +10,8 @@ Normalize(0.5, 0.5) -- on the device, bit for bit (``ops.pil_resize``, csrc/imag
   ``--image_size H,W`` of the evaluation command lines (inception, fid, featsets, lpips) reads every directory through it, so a real
   set and a generated set pass through the same chain, and the Inception forward runs at the full batch size whatever the sizes of
   the files are.
+* ``_feed_dir(feed, root, batch_size, ...)``: what those command lines read a directory with -- through the feeder under
+  ``--image_size``, else the files at their stored sizes (``evalkit.stored_size_chunks``).  ``fid._feed_dir`` is this function.
 """
 import argparse
 import ctypes
@@ -18,7 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .inception import find_images
+from .evalkit import find_images, stored_size_chunks
 
 __all__ = ['pack_images', 'resize_batch', 'ImageDirFeeder', 'add_arguments', 'size_arg', 'FILTERS']
 
@@ -71,21 +73,21 @@ def _size(image_size):
 
 def resize_batch(arrays, image_size, filter='bilinear', device='cuda'):
     """uint8 [H_i, W_i, 3] arrays -> float32 [n, 3, H, W] on ``device``: each image through ``Image.resize((W, H), filter)`` and
-    ToTensor + Normalize(0.5, 0.5), bitwise what Pillow and ``inception.read_image``'s expression give"""
+    ToTensor + Normalize(0.5, 0.5), bitwise what Pillow and ``evalkit.read_image``'s expression give"""
     size = _size(image_size)
     packed, table = pack_images(arrays)
     return ops.pil_resize(packed.to(torch.device(device), non_blocking=True), table, size, filter)
 
 
 def decode(path):
-    """the file as a uint8 [H, W, 3] array (``convert('RGB')``: what ``inception.read_image`` reads)"""
+    """the file as a uint8 [H, W, 3] array (``convert('RGB')``: what ``evalkit.read_image`` reads)"""
     from PIL import Image
     with Image.open(path) as im:
         return np.asarray(im.convert('RGB'), dtype=np.uint8)
 
 
 class ImageDirFeeder(object):
-    """Iterates float32 [n, 3, H, W] device batches over the images under ``root`` in ``inception.find_images`` order: n =
+    """Iterates float32 [n, 3, H, W] device batches over the images under ``root`` in ``evalkit.find_images`` order: n =
     ``batch_size`` but for the last one.  ``image_size`` = (H, W); ``filter`` 'bilinear' | 'bicubic'.
 
     The files are decoded with Pillow by ``workers`` threads (default: the thread count ``utils.respect_cpu_quota`` leaves in effect,
@@ -151,6 +153,22 @@ class ImageDirFeeder(object):
                 for slot in slots:                  # the staging slots are released here: their last copies must have read them
                     if slot.get('ev') is not None:
                         slot['ev'].synchronize()
+
+
+def _feed_dir(feed, root, batch_size, *, image_size=None, resize_filter='bilinear', device='cuda'):
+    """``feed(imgs)`` over the images under ``root`` -> their number.  Without ``image_size``: the files at their stored sizes, one
+    chunk per run of equal sizes (``evalkit.stored_size_chunks``).  With it: every file brought to ``image_size`` by the loader's resize
+    on ``device`` (``ImageDirFeeder``), in full chunks of ``batch_size``."""
+    paths = find_images(root)
+    if not paths:
+        raise SystemExit('no images under %s' % root)
+    if image_size is not None:
+        batches = ImageDirFeeder(root, batch_size, image_size, resize_filter, device)
+    else:
+        batches = (imgs for imgs, in stored_size_chunks([paths], batch_size))
+    for imgs in batches:
+        feed(imgs)
+    return len(paths)
 
 
 # ---- command lines ----------------------------------------------------------------------------------------------------------------------

@@ -11,18 +11,22 @@
 * ``InceptionScore``: the reference's object -- ``clean()``, ``__call__(imgs)``, ``compute_score(splits) -> (mean, std)`` -- that
   ``evaluate.check_model`` and ``Trainer`` drive.  Softmax rows accumulate in a device buffer that grows by doubling; ``__call__``
   never synchronises, ``compute_score`` does the one host read.
+* ``inception_network`` / ``pooled_features``: what the score, ``fid`` and ``featsets`` share -- the network a ``weights`` argument
+  stands for, and the chunk / resize / ``features`` loop.  File, image and buffer helpers live in ``evalkit``, directory feeding in
+  ``imageprep``.
 * Nothing is ever downloaded: ``weights`` is a local ``state_dict`` file; without it the network keeps a seeded random
   initialisation and says loudly that the score is then meaningless.
 """
 import argparse
-import os
 import sys
 
 import torch
 import torch.nn as nn
 
 from . import layers, ops
-from .accuracy import _folded, _strip_module_prefix
+from .evalkit import find_images, read_image      # noqa: F401 (importable from here as well: the command line's helpers)
+from .evalkit import FoldCache, folded, grow_rows, state_dict_of
+from .imageprep import _feed_dir, add_arguments
 
 __all__ = ['InceptionV3', 'InceptionScore', 'load_inception', 'conv_units', 'main', 'DEFAULT_WEIGHTS']
 
@@ -59,7 +63,7 @@ class _Kernels(object):
         return torch.empty(x.size(0), C, H, W, dtype=torch.float32, device=x.device)
 
     def conv(self, unit, x, out=None, c0=0):
-        w, b = _folded(unit.conv, unit.bn, self.fold)
+        w, b = folded(unit.conv, unit.bn, self.fold)
         return ops.conv2d_rect(x, w, b, stride=unit.conv.stride[0], pad=unit.conv.padding, act=ops.ACT_RELU, out=out, out_c0=c0)
 
     @staticmethod
@@ -253,7 +257,7 @@ _BLOCKS = ('Mixed_5b', 'Mixed_5c', 'Mixed_5d', 'Mixed_6a', 'Mixed_6b', 'Mixed_6c
            'Mixed_7c')
 
 
-class InceptionV3(nn.Module):
+class InceptionV3(FoldCache):
     """torchvision.models.Inception3(num_classes, aux_logits, transform_input=False), inference only.
 
     ``forward(x)`` -> logits [N, num_classes]; ``features(x)`` -> the pooled [N, 2048] vector (where an FID would start).  Both run
@@ -291,7 +295,6 @@ class InceptionV3(nn.Module):
         self.Mixed_7c = InceptionE(2048)
         self.avgpool = layers.GlobalAvgPool()
         self.fc = layers.Linear(2048, num_classes)
-        self._fold_cache = {}
         if self.fid_variant:                # pytorch-fid's FIDInceptionA / C / E_1 and E_2: four kinds of branch pool, nothing else
             for name in _BLOCKS:
                 if hasattr(getattr(self, name), 'pool'):
@@ -308,17 +311,6 @@ class InceptionV3(nn.Module):
             raise NotImplementedError('InceptionV3 is inference only (folded BatchNorm, no backward, no auxiliary head): train(True) '
                                       'is not available')
         return super().train(False)
-
-    def drop_fold(self):
-        self._fold_cache.clear()
-
-    def load_state_dict(self, *args, **kwargs):
-        self.drop_fold()
-        return super().load_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):          # .to() / .cuda(): the tensors move, the folded copies would not
-        self.drop_fold()
-        return super()._apply(fn, *args, **kwargs)
 
     def _walk(self, E, x):
         """the network up to the 8 x 8 x 2048 grid, on executor ``E``"""
@@ -376,7 +368,7 @@ def load_inception(path, device='cuda'):
     save of this class; a DataParallel ``module.`` prefix is stripped), on ``device``.  A file whose ``fc.weight`` has 1008 rows is
     the TF-ported FID network (pt_inception-2015-12-05: 1008 classes, no auxiliary head): it is loaded, strictly, into the FID form
     (``fid_variant=True, aux_logits=False``)."""
-    sd = _strip_module_prefix(dict(torch.load(path, map_location='cpu')))
+    sd = state_dict_of(path)
     classes = int(sd['fc.weight'].shape[0])
     if classes == FID_CLASSES:
         net = InceptionV3(num_classes=classes, aux_logits=False, fid_variant=True)
@@ -384,6 +376,43 @@ def load_inception(path, device='cuda'):
         net = InceptionV3(num_classes=classes, aux_logits=any(k.startswith('AuxLogits.') for k in sd))
     net.load_state_dict(sd, strict=True)
     return net.to(device)
+
+
+def inception_network(weights, device, who, fid_form, numbers='numbers are MEANINGLESS'):
+    """the network of a metric object, on ``device`` in eval mode.  ``weights``: the path of a ``state_dict`` file
+    (``load_inception``), an instance (moved to ``device``), or None for the module attribute ``DEFAULT_WEIGHTS`` (read here, at call
+    time) and, when that is None too, a random network under a fixed seed -- the FID form when ``fid_form`` -- and a loud warning
+    that names ``who`` and says what its ``numbers`` are then worth."""
+    weights = weights if weights is not None else DEFAULT_WEIGHTS
+    if weights is not None:
+        net = load_inception(weights, device) if isinstance(weights, str) else weights.to(device)
+    else:
+        print('WARNING: %s is built WITHOUT pretrained weights (weights=None): a seeded random initialisation. Its %s; pass the path '
+              'of %s.' % (who, numbers, 'pt_inception-2015-12-05-*.pth' if fid_form else 'inception_v3_google-*.pth'), file=sys.stderr)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(0)
+            net = InceptionV3(num_classes=FID_CLASSES, aux_logits=False, fid_variant=True) if fid_form else InceptionV3()
+            net = net.to(device)
+    return net.eval()
+
+
+def _chunks(imgs, batch_size, device):
+    imgs = imgs.detach().to(device, torch.float32)
+    for a in range(0, imgs.size(0), batch_size):
+        yield imgs[a:a + batch_size]
+
+
+def _chunk_features(net, x, resize):
+    if resize and tuple(x.shape[2:]) != (299, 299):
+        x = ops.resize_bilinear(x, (299, 299))
+    return net.features(x)
+
+
+def pooled_features(net, imgs, batch_size, resize, device):
+    """the pooled features [n <= batch_size, dim] of ``imgs`` [N, 3, H, W], chunk by chunk (resized to 299 x 299 on the device first
+    when ``resize``); no synchronisation"""
+    for x in _chunks(imgs, batch_size, device):
+        yield _chunk_features(net, x, resize)
 
 
 class InceptionScore(nn.Module):
@@ -408,16 +437,8 @@ class InceptionScore(nn.Module):
                 raise RuntimeError('InceptionScore: the HIP path has no CPU fallback (cuda=False)')
             device = 'cuda'
         self.resize, self.batch_size, self.device = resize, batch_size, torch.device(device)
-        weights = weights if weights is not None else DEFAULT_WEIGHTS
-        if weights is not None:
-            self.inception_model = load_inception(weights, self.device) if isinstance(weights, str) else weights.to(self.device)
-        else:
-            print('WARNING: InceptionScore is built WITHOUT pretrained weights (weights=None): a seeded random initialisation. '
-                  'Its scores are MEANINGLESS as Inception scores; pass the path of inception_v3_google-*.pth.', file=sys.stderr)
-            with torch.random.fork_rng(devices=[]):
-                torch.manual_seed(0)
-                self.inception_model = InceptionV3().to(self.device)
-        self.inception_model.eval()
+        self.inception_model = inception_network(weights, self.device, 'InceptionScore', False,
+                                                 'scores are MEANINGLESS as Inception scores')
         self.classes = self.inception_model.fc.out_features
         self.probs, self.count = None, 0
         self.clean()
@@ -425,35 +446,20 @@ class InceptionScore(nn.Module):
     def clean(self):
         self.count = 0
 
-    def _reserve(self, rows):
-        need = self.count + rows
-        cap = 0 if self.probs is None else self.probs.size(0)
-        if need <= cap:
-            return
-        new_cap = max(cap, 4 * self.batch_size)
-        while new_cap < need:
-            new_cap *= 2
-        buf = torch.empty(new_cap, self.classes, dtype=torch.float32, device=self.device)
-        if self.count:
-            buf[:self.count].copy_(self.probs[:self.count])
-        self.probs = buf
-
     def get_pred(self, x):
-        """logits of one chunk (resized first when ``resize``)"""
-        if self.resize and tuple(x.shape[2:]) != (299, 299):
-            x = ops.resize_bilinear(x, (299, 299))
-        if self.fid is None:
-            return self.inception_model(x)
-        f = self.inception_model.features(x)                # one forward for both numbers: forward() is fc(features(x))
-        self.fid.add_features(f)
+        """logits of one chunk (resized first when ``resize``): ``InceptionV3.forward`` is fc(features(x)) under ``no_grad``, so the
+        features ``fid`` takes on the way cost no second forward and leave the logits as they are"""
+        f = _chunk_features(self.inception_model, x, self.resize)
+        if self.fid is not None:
+            self.fid.add_features(f)
         with torch.no_grad():
             return self.inception_model.fc(f)
 
     def forward(self, imgs):
-        imgs = imgs.detach().to(self.device, torch.float32)
-        for a in range(0, imgs.size(0), self.batch_size):
-            logits = self.get_pred(imgs[a:a + self.batch_size])
-            self._reserve(logits.size(0))
+        for x in _chunks(imgs, self.batch_size, self.device):
+            logits = self.get_pred(x)
+            self.probs = grow_rows(self.probs, self.count, logits.size(0), 4 * self.batch_size, (self.classes,), torch.float32,
+                                   self.device)
             ops.softmax_rows(logits, self.probs, self.count)
             self.count += logits.size(0)
 
@@ -468,26 +474,6 @@ class InceptionScore(nn.Module):
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------------
-_EXT = ('.png', '.jpg', '.jpeg', '.bmp', '.ppm', '.webp')
-
-
-def find_images(root):
-    """every image file under ``root``, recursively, in sorted order"""
-    out = []
-    for d, _, files in sorted(os.walk(root)):
-        out += [os.path.join(d, f) for f in sorted(files) if f.lower().endswith(_EXT)]
-    return out
-
-
-def read_image(path):
-    """[3, H, W] float32 in [-1, 1]: ToTensor + Normalize(0.5, 0.5) of the reference's ``__main__``"""
-    import numpy as np
-    from PIL import Image
-    with Image.open(path) as im:
-        a = np.asarray(im.convert('RGB'), dtype=np.float32)
-    return (torch.from_numpy(a).permute(2, 0, 1) / 255.0 - 0.5) / 0.5
-
-
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m scene_generation_amd.inception',
                                 description='Inception score of the images under --dir (resized to 299 x 299 on the device)')
@@ -496,31 +482,16 @@ def build_parser():
     p.add_argument('--splits', default=5, type=int)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    from .imageprep import add_arguments
     return add_arguments(p)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    paths = find_images(args.dir)
-    if not paths:
+    if not find_images(args.dir):               # said before a network is built
         raise SystemExit('no images under %s' % args.dir)
     scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=args.weights, device=args.device)
     print('Calculating Inception Score...')
-    group, shape = [], None
-    if args.image_size is not None:             # every file through the loader's resize on the device: full batches of one size
-        from .imageprep import ImageDirFeeder
-        for batch in ImageDirFeeder(args.dir, args.batch_size, args.image_size, args.resize_filter, scorer.device):
-            scorer(batch)
-        paths = []
-    for path in (paths + [None] if paths else []):
-        img = read_image(path) if path is not None else None
-        if group and (img is None or tuple(img.shape) != shape or len(group) == args.batch_size):      # one chunk per image size
-            scorer(torch.stack(group))
-            group = []
-        if img is not None:
-            group.append(img)
-            shape = tuple(img.shape)
+    _feed_dir(scorer, args.dir, args.batch_size, image_size=args.image_size, resize_filter=args.resize_filter, device=scorer.device)
     mean, std = scorer.compute_score(splits=args.splits)
     print('Inception {} {}'.format(mean, std))
     return mean, std

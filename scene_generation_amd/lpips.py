@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .accuracy import _strip_module_prefix
-from .inception import find_images, read_image
+from .evalkit import find_images, grow_rows, state_dict_of, stored_size_chunks
+from .imageprep import ImageDirFeeder, add_arguments
 
 __all__ = ['AlexFeatures', 'Vgg16Features', 'LPIPS', 'Diversity', 'load_lin_weights', 'backbone_state_dict', 'pair_files', 'main']
 
@@ -35,19 +35,12 @@ CHANNELS = {'alex': (64, 192, 384, 256, 256), 'vgg': (64, 128, 256, 512, 512)}
 
 
 # ---- weights ----------------------------------------------------------------------------------------------------------------------------
-def _state_dict(src):
-    """a state_dict from a path (``torch.load``) or a mapping, a DataParallel ``module.`` prefix stripped"""
-    if isinstance(src, str):
-        src = torch.load(src, map_location='cpu')
-    return _strip_module_prefix(dict(src))
-
-
 def backbone_state_dict(src):
     """the ``features.<i>.weight|bias`` entries of a backbone file: a torchvision ``alexnet`` / ``vgg16`` state_dict (its
     ``classifier.*`` entries are dropped) or a whole LPIPS module's, where the backbone sits under ``net.slice<j>.<i>.*`` with
     torchvision's index ``i`` kept.  -> dict, or None when ``src`` holds no backbone entry"""
     out = {}
-    for k, v in _state_dict(src).items():
+    for k, v in state_dict_of(src).items():
         m = re.match(r'(?:features|net\.slice\d+)\.(\d+)\.(weight|bias)$', k)
         if m:
             out['features.%s.%s' % (m.group(1), m.group(2))] = v
@@ -58,7 +51,7 @@ def load_lin_weights(src, channels):
     """the five learned "lin" weight vectors of an LPIPS file as float32 tensors [C_k]: ``lin<k>.model.1.weight`` (the package's
     weights/v0.1/<net>.pth) or ``lins.<k>.model.1.weight`` (a whole module's state_dict), each [1, C_k, 1, 1].  A negative weight
     is refused: the distance is a weighted sum of squares and the package clamps its weights at zero during training."""
-    sd = _state_dict(src)
+    sd = state_dict_of(src)
     out = []
     for k, C in enumerate(channels):
         w = sd.get('lin%d.model.1.weight' % k, sd.get('lins.%d.model.1.weight' % k))
@@ -165,7 +158,7 @@ class LPIPS(nn.Module):
             raise ValueError("LPIPS: net must be 'alex' or 'vgg', got %r (the SqueezeNet variant is not built)" % (net,))
         self.net_name = net
         self.net = AlexFeatures() if net == 'alex' else Vgg16Features()
-        lin_sd = _state_dict(lin_weights) if lin_weights is not None else None
+        lin_sd = state_dict_of(lin_weights) if lin_weights is not None else None
         if backbone_weights is None and lin_sd is not None and backbone_state_dict(lin_sd) is not None:
             backbone_weights = lin_sd
         if backbone_weights is not None:
@@ -217,24 +210,11 @@ class Diversity(object):
     def clean(self):
         self.count = 0
 
-    def _reserve(self, rows, device):
-        need = self.count + rows
-        cap = 0 if self.dist is None else self.dist.numel()
-        if need <= cap:
-            return
-        new_cap = max(cap, 4 * self.batch_size)
-        while new_cap < need:
-            new_cap *= 2
-        buf = torch.empty(new_cap, dtype=torch.float64, device=device)
-        if self.count:
-            buf[:self.count].copy_(self.dist[:self.count])
-        self.dist = buf
-
     def __call__(self, imgs0, imgs1):
         channels_last = imgs0.dim() == 4 and imgs0.dtype == torch.uint8 and imgs0.size(3) == 3 and imgs0.size(1) != 3
         for a in range(0, imgs0.size(0), self.batch_size):
             d = self.lpips(imgs0[a:a + self.batch_size], imgs1[a:a + self.batch_size], channels_last=channels_last)
-            self._reserve(d.numel(), d.device)
+            self.dist = grow_rows(self.dist, self.count, d.numel(), 4 * self.batch_size, (), torch.float64, d.device)
             self.dist[self.count:self.count + d.numel()].copy_(d)
             self.count += d.numel()
 
@@ -251,7 +231,7 @@ class Diversity(object):
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
 def pair_files(dir0, dir1):
-    """[(path in dir0, path in dir1)]: the image files of both directories (``inception.find_images``: recursive, sorted), the i-th
+    """[(path in dir0, path in dir1)]: the image files of both directories (``evalkit.find_images``: recursive, sorted), the i-th
     of one with the i-th of the other"""
     a, b = find_images(dir0), find_images(dir1)
     if not a:
@@ -272,7 +252,6 @@ def build_parser():
     p.add_argument('--dir1', required=True, type=str)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
-    from .imageprep import add_arguments
     return add_arguments(p)
 
 
@@ -280,25 +259,12 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     pairs = pair_files(args.dir0, args.dir1)
     scorer = Diversity(LPIPS(args.net, backbone_weights=args.backbone, lin_weights=args.lin, device=args.device), args.batch_size)
-    g0, g1, shape = [], [], None
     if args.image_size is not None:             # both directories through the loader's resize on the device: full chunks of one size
-        from .imageprep import ImageDirFeeder
-        feeds = [ImageDirFeeder(d, args.batch_size, args.image_size, args.resize_filter, args.device) for d in (args.dir0, args.dir1)]
-        for a, b in zip(*feeds):
-            scorer(a, b)
-        pairs = []
-    for pa, pb in (pairs + [(None, None)] if pairs else []):
-        a = read_image(pa) if pa is not None else None
-        if g0 and (a is None or tuple(a.shape) != shape or len(g0) == args.batch_size):      # one chunk per image size
-            scorer(torch.stack(g0), torch.stack(g1))
-            g0, g1 = [], []
-        if a is not None:
-            b = read_image(pb)
-            if b.shape != a.shape:
-                raise SystemExit('%s and %s differ in size' % (pa, pb))
-            g0.append(a)
-            g1.append(b)
-            shape = tuple(a.shape)
+        chunks = zip(*[ImageDirFeeder(d, args.batch_size, args.image_size, args.resize_filter, args.device) for d in (args.dir0, args.dir1)])
+    else:                                       # the files at their stored sizes: a pair must agree, a chunk holds one size
+        chunks = stored_size_chunks([list(column) for column in zip(*pairs)], args.batch_size)
+    for a, b in chunks:
+        scorer(a, b)
     r = scorer.compute()
     print('Diversity {} {}'.format(r['mean'], r['std']))
     return r['mean'], r['std']
