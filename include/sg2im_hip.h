@@ -780,6 +780,40 @@ int sg_pil_resize_plan(const int64_t* desc_host, int N, int64_t packed_bytes, in
 int sg_pil_resize(const void* packed, int64_t packed_bytes, const int64_t* table, int N, int OH, int OW, int filter, int64_t coef_ints,
                   int64_t inter_bytes, int64_t hblocks, const float* lut, void* y8, float* y, void* ws, size_t ws_bytes, int phases,
                   sgStream stream);
+/* ---- FID-infinity: every subset's FID from two Gram matrices (fidinf.hip; scene_generation_amd/fidinf.py) --------------------------------
+ * For n < D fake rows the Frechet distance of a subset S to fixed real statistics (mu, sigma) needs no D x D matrix: with
+ * Z = X - 1 mu^T, P = Z Z^T and G = Z sigma Z^T (both n x n), |mean_S - mu|^2 and tr Sigma_S are sums over P_SS, and the non-zero
+ * eigenvalues of sigma Sigma_S are those of H G_SS H / (n_S - 1), H = I - 1 1^T / n_S.  Neither call synchronises or allocates; no
+ * atomics: every sum has one owner and a fixed order, so the same call gives bit-identical output.  A null pointer, a size outside the
+ * ranges below, ldx < D, a misaligned pointer (fp64 operands and ws 8-byte, x and the int tables 4-byte) or a workspace below the
+ * matching _ws_bytes returns a negative code (sg_last_error_string) and launches nothing.
+ *
+ * sg_fidinf_grams: x fp32 [n, D] of row stride ldx >= D elements (any 4-byte aligned base), n >= 2, D >= 1; mu fp64 [D]; sigma fp64
+ * [D, D], read as given (no symmetry is assumed); P, G fp64 [n, n], written completely.
+ *   Z[i][k] = fl64((double)x[i][k] - mu[k])            (one rounding; kept in ws)
+ *   Y[i][c] = sum_l Z[i][l] sigma[l][c]                (kept in ws)
+ *   P[i][j] = sum_k Z[i][k] Z[j][k],   G[i][j] = sum_k Y[i][k] Z[j][k]
+ * Every sum is fp64 on the f64 matrix cores (v_mfma_f64_16x16x4_f64) in ascending k from 0.0.  P and G are computed for the 64 x 64
+ * tile pairs ti <= tj only -- inside a diagonal tile for i <= j only -- and each value is stored at (i, j) and (j, i): both equal
+ * their transposes bit for bit.  ws >= sg_fidinf_grams_ws_bytes(n, D) = 16 n D bytes.
+ *
+ * sg_fidinf_subset_terms: P, G fp64 [n, n] as above (G symmetric bit for bit), n >= 2; idx int32 [S, smax] (device): row q holds
+ * sizes[q] row numbers in [0, n), the rest of the row is not read; sizes int32 [S] (device), each in 2 .. smax; smax >= 2; S >= 0
+ * (S == 0 returns 0 without looking at the pointers).  With t_i = idx[q][i], n_q = sizes[q] and all sums over i, j < n_q:
+ *   sums[q] = ( sum_i P[t_i][t_i],  sum_ij P[t_i][t_j] )                                        fp64 [S, 2]
+ *   r_i = sum_j G[t_i][t_j],   t = sum_i r_i
+ *   M[q][i][j] = ((G[t_i][t_j] - (r_i + r_j) / n_q) + t / (n_q n_q)) / (n_q - 1)                fp64 [S, smax, smax], row stride smax
+ * A row sum is taken by one wave (lane l adds j = l, l + 64, ... in ascending order, then a butterfly over the lanes), a total by one
+ * workgroup in the same manner: fixed orders.  M[q]'s leading n_q x n_q block equals its transpose bit for bit; no entry outside that
+ * block is written (subsets are ragged: a tile that straddles n_q writes its inside part only).  The wrapper validates the tables on the
+ * host; the kernels form no address from an entry outside [0, n) (it reads as a zero row and column) and clamp a size to [0, smax]
+ * (below 2: sums[q] is NaN and M[q] is not written).  ws >= sg_fidinf_subset_terms_ws_bytes(S, smax) = 8 (3 S smax + S) bytes. */
+size_t sg_fidinf_grams_ws_bytes(int n, int D);
+int sg_fidinf_grams(const float* x, int n, int D, int ldx, const double* mu, const double* sigma, double* P, double* G, void* ws,
+                    size_t ws_bytes, sgStream stream);
+size_t sg_fidinf_subset_terms_ws_bytes(int S, int smax);
+int sg_fidinf_subset_terms(const double* P, const double* G, int n, const int* idx, const int* sizes, int S, int smax, double* M,
+                           double* sums, void* ws, size_t ws_bytes, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

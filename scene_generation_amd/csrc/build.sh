@@ -5,13 +5,13 @@
 # it includes, the compiler flags) differs from the stamp written next to it -- not on mtimes, which do not survive a copy.
 set -e
 cd "$(dirname "$0")"
-UNITS="runtime igemm igemm_kn0 igemm_kn1 igemm_nk skinny smallm norm graph layout loss conv3x3r_bf16 sample kmeans scenegraph classifier inception fid lpips featsets imageprep"
+UNITS="runtime igemm igemm_kn0 igemm_kn1 igemm_nk skinny smallm norm graph layout loss conv3x3r_bf16 sample kmeans scenegraph classifier inception fid lpips featsets imageprep fidinf"
 if [ "$1" == "--clean" ]; then
   shift
   rm -f *.o *.stamp libsg2im_hip.so
 fi
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value $*"
-HDRS="common.h igemm_core.h rect_gather.h ../../include/sg2im_hip.h"
+HDRS="common.h igemm_core.h rect_gather.h f64_tile.h ../../include/sg2im_hip.h"
 OBJS=()
 built=0
 for f in $UNITS; do

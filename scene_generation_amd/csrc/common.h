@@ -129,6 +129,8 @@ enum {
   SG_K_FEAT_POLY, SG_K_FEAT_MANIFOLD,
   // the Pillow-exact resize of a ragged uint8 batch (imageprep.hip): coefficients + horizontal + vertical pass of one call
   SG_K_PIL_RESIZE,
+  // the extrapolated FID (fidinf.hip): the two Gram matrices of the shifted feature rows (f64 MFMA), the per-subset terms
+  SG_K_FIDINF_GRAMS, SG_K_FIDINF_TERMS,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

@@ -13,76 +13,43 @@
 // top-k lists likewise; the membership counts are integer atomics and the minima are unsigned-integer atomic minima of the bit
 // patterns of non-negative doubles (the same order as the values) -- all order-independent, so a call repeats bit for bit.
 //
-// The f64 MFMA's C/D lane map is NOT the f32 one: col = lane & 15, row = (lane >> 4) + 4 * reg (the f32 16x16 forms have
-// row = 4 * (lane >> 4) + reg).  A and B are one f64 per lane: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15].
-#include "common.h"
+// The tile, its lane map and the step from the LDS stage to the accumulators are f64_tile.h's, shared with fid.hip and fidinf.hip.
+#include "f64_tile.h"
 
 namespace {
 
 constexpr int TPB = 256;
-constexpr int FT = 64;           // tile of the product per workgroup
-constexpr int KB = 32;           // feature columns staged per pass
-constexpr int LDK = KB + 2;      // LDS row stride in doubles: the 32 lanes of a half wave (16 rows x 2 k) read 32 distinct bank pairs
 constexpr int KMAX = 8;          // longest neighbour list
 constexpr int QL = 4;            // threads (column quarters) per row in the neighbour scan
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 struct Tile {
-  double ab[2 * FT * LDK];       // ab[i][k] = row i of the A side, columns k0 .. k0 + 31; from FT * LDK on, the B side
-  const float* pa[FT];           // the 64 rows of each side (nullptr: a zero row)
-  const float* pb[FT];
+  double ab[2 * SG_F64_FT * SG_F64_LDK];   // ab[i][k] = row i of the A side, columns k0 .. k0 + 31; the B side from row SG_F64_FT on
+  const float* pa[SG_F64_FT];              // the 64 rows of each side (nullptr: a zero row)
+  const float* pb[SG_F64_FT];
 };
-
-// tile pair (ti <= tj) number b of the block upper triangle of an nt x nt grid, row by row (wave-uniform scalar loop)
-__device__ __forceinline__ void tile_pair(int b, int nt, int& ti, int& tj) {
-  int i = 0, len = nt;
-  while (b >= len) { b -= len; ++i; --len; }
-  ti = i; tj = i + b;
-}
 
 // acc[m][n] = sum_k A[i][k] B[j][k] for the rows T.pa / T.pb name (set, and synchronised, by the caller).  Element reg of acc[m][n] is
 // row (wave >> 1) * 32 + m * 16 + (lane >> 4) + 4 * reg, column (wave & 1) * 32 + n * 16 + (lane & 15) of the tile.
 __device__ __forceinline__ void tile_product(Tile& T, int D, f64x4 (&acc)[2][2]) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wj = wave & 1, fr = lane & 15, fk = lane >> 4;
-  const int lk = tid & (KB - 1), lr = tid >> 5;           // loader: column lk of rows lr, lr + 8, ...
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < D; k0 += KB) {
-    const int kc = D - k0 < KB ? D - k0 : KB;
+  const int tid = threadIdx.x;
+  const int lk = tid & (SG_F64_KB - 1), lr = tid >> 5;    // loader: column lk of rows lr, lr + 8, ...
+  sg_f64_tile_zero(acc);
+  for (int k0 = 0; k0 < D; k0 += SG_F64_KB) {
+    const int kc = D - k0 < SG_F64_KB ? D - k0 : SG_F64_KB;
     const int kp = (kc + 3) & ~3;                         // D tail: the columns up to the next multiple of 4 are staged as zeros
     const bool okk = lk < kc;
     __syncthreads();
 #pragma unroll
-    for (int p = 0; p < FT / (TPB / KB); ++p) {
-      const int r = lr + p * (TPB / KB);
+    for (int p = 0; p < SG_F64_FT / (TPB / SG_F64_KB); ++p) {
+      const int r = lr + p * (TPB / SG_F64_KB);
       const float* ra = T.pa[r];
       const float* rb = T.pb[r];
-      T.ab[r * LDK + lk] = (okk && ra) ? (double)ra[k0 + lk] : 0.0;
-      T.ab[(FT + r) * LDK + lk] = (okk && rb) ? (double)rb[k0 + lk] : 0.0;
+      T.ab[r * SG_F64_LDK + lk] = (okk && ra) ? (double)ra[k0 + lk] : 0.0;
+      T.ab[(SG_F64_FT + r) * SG_F64_LDK + lk] = (okk && rb) ? (double)rb[k0 + lk] : 0.0;
     }
     __syncthreads();
-    for (int ks = 0; ks < kp; ks += 4) {
-      double a[2], b[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) a[m] = T.ab[(wi * 32 + m * 16 + fr) * LDK + ks + fk];
-#pragma unroll
-      for (int n = 0; n < 2; ++n) b[n] = T.ab[(FT + wj * 32 + n * 16 + fr) * LDK + ks + fk];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0);
-    }
+    sg_f64_tile_mma(T.ab, kp, acc);
   }
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // ---- the KID sums ---------------------------------------------------------------------------------------------------------------------
@@ -98,16 +65,16 @@ __global__ void __launch_bounds__(TPB) feat_poly_kernel(const float* __restrict_
   int which, ti, tj;
   if (b < 2 * ntri) {
     which = b >= ntri;
-    tile_pair(b - which * ntri, nt, ti, tj);
+    sg_f64_tile_pair(b - which * ntri, nt, ti, tj);
   } else {
     which = 2;
     ti = (b - 2 * ntri) / nt;
     tj = (b - 2 * ntri) - ti * nt;
   }
   const int tid = threadIdx.x;
-  if (tid < 2 * FT) {                                     // the gather: one table entry per tile row, checked before it forms an address
-    const bool sideb = tid >= FT;
-    const int pos = (sideb ? tj : ti) * FT + (tid & (FT - 1));
+  if (tid < 2 * SG_F64_FT) {                              // the gather: one table entry per tile row, checked before it forms an address
+    const bool sideb = tid >= SG_F64_FT;
+    const int pos = (sideb ? tj : ti) * SG_F64_FT + (tid & (SG_F64_FT - 1));
     const bool fromy = which == 1 || (which == 2 && sideb);
     const int* tab = fromy ? iy : ix;
     const float* base = fromy ? y : x;
@@ -118,7 +85,7 @@ __global__ void __launch_bounds__(TPB) feat_poly_kernel(const float* __restrict_
       const int r = tab[(size_t)q * s + pos];
       if (r >= 0 && r < lim) p = base + (size_t)r * ld;   // an index outside the set reads as a zero row
     }
-    (sideb ? tile.pb : tile.pa)[tid & (FT - 1)] = p;
+    (sideb ? tile.pb : tile.pa)[tid & (SG_F64_FT - 1)] = p;
   }
   f64x4 acc[2][2];
   tile_product(tile, D, acc);                             // (its first barrier publishes the row pointers)
@@ -130,14 +97,14 @@ __global__ void __launch_bounds__(TPB) feat_poly_kernel(const float* __restrict_
     for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
-        const int pi = ti * FT + wi * 32 + mm * 16 + fk + 4 * reg;
-        const int pj = tj * FT + wj * 32 + nn * 16 + fr;
+        const int pi = ti * SG_F64_FT + wi * 32 + mm * 16 + fk + 4 * reg;
+        const int pj = tj * SG_F64_FT + wj * 32 + nn * 16 + fr;
         const double t = gamma * acc[mm][nn][reg] + coef0;
         double v = t;
         for (int e = 1; e < degree; ++e) v *= t;          // repeated multiplication, never pow
         if (pi < s && pj < s && (which == 2 || pi != pj)) sum += v;      // i != j by position
       }
-  sum = wave_sum_f64(sum);
+  sum = sg_wave_sum_f64(sum);
   if (lane == 0) red[wave] = sum;
   __syncthreads();
   if (tid == 0) {
@@ -169,7 +136,7 @@ __global__ void __launch_bounds__(TPB) feat_norms_kernel(const float* __restrict
     const double t = (double)p[k];
     v += t * t;
   }
-  v = wave_sum_f64(v);
+  v = sg_wave_sum_f64(v);
   if (lane == 0) nrm[r] = v;
 }
 
@@ -198,21 +165,21 @@ __device__ __forceinline__ void topk_insert(double (&best)[KMAX], double v) {
 __global__ void __launch_bounds__(TPB) feat_knn_kernel(const float* __restrict__ x, int n, int D, size_t ldx, const double* __restrict__ nrm,
                                                       int ntc, int CS, double* __restrict__ part) {
   __shared__ Tile tile;
-  static_assert(sizeof(double) * FT * (FT + 1) <= sizeof(double) * 2 * FT * LDK, "the distance tile lies over the operand stage");
-  double* dt = tile.ab;                                   // dt[row][col], row stride FT + 1
+  static_assert(sizeof(double) * SG_F64_FT * (SG_F64_FT + 1) <= sizeof(double) * 2 * SG_F64_FT * SG_F64_LDK, "the distance tile lies over the operand stage");
+  double* dt = tile.ab;                                   // dt[row][col], row stride SG_F64_FT + 1
   const int bi = blockIdx.x, z = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave >> 1, wj = wave & 1, fr = lane & 15, fk = lane >> 4;
   const int srow = tid >> 2, sq = tid & 3;                // the scan: row srow of the block, columns sq * 16 .. sq * 16 + 15
-  const int grow = bi * FT + srow;
+  const int grow = bi * SG_F64_FT + srow;
   double best[KMAX];
 #pragma unroll
   for (int e = 0; e < KMAX; ++e) best[e] = __builtin_inf();
   for (int tj = z; tj < ntc; tj += CS) {
     __syncthreads();                                      // the previous tile's scan is over: the stage may be overwritten
-    if (tid < 2 * FT) {
-      const bool sideb = tid >= FT;
-      const int r = (sideb ? tj : bi) * FT + (tid & (FT - 1));
-      (sideb ? tile.pb : tile.pa)[tid & (FT - 1)] = r < n ? x + (size_t)r * ldx : nullptr;
+    if (tid < 2 * SG_F64_FT) {
+      const bool sideb = tid >= SG_F64_FT;
+      const int r = (sideb ? tj : bi) * SG_F64_FT + (tid & (SG_F64_FT - 1));
+      (sideb ? tile.pb : tile.pa)[tid & (SG_F64_FT - 1)] = r < n ? x + (size_t)r * ldx : nullptr;
     }
     f64x4 acc[2][2];
     tile_product(tile, D, acc);
@@ -224,14 +191,14 @@ __global__ void __launch_bounds__(TPB) feat_knn_kernel(const float* __restrict__
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
           const int row = wi * 32 + mm * 16 + fk + 4 * reg, col = wj * 32 + nn * 16 + fr;
-          const int gi = bi * FT + row, gj = tj * FT + col;
+          const int gi = bi * SG_F64_FT + row, gj = tj * SG_F64_FT + col;
           double d = __builtin_inf();                     // outside the set, or the row itself (by index): never a neighbour
           if (gi < n && gj < n && gi != gj) d = dist2(nrm[gi], nrm[gj], acc[mm][nn][reg]);
-          dt[row * (FT + 1) + col] = d;
+          dt[row * (SG_F64_FT + 1) + col] = d;
         }
     __syncthreads();
 #pragma unroll 4
-    for (int c = 0; c < FT / QL; ++c) topk_insert(best, dt[srow * (FT + 1) + sq * (FT / QL) + c]);
+    for (int c = 0; c < SG_F64_FT / QL; ++c) topk_insert(best, dt[srow * (SG_F64_FT + 1) + sq * (SG_F64_FT / QL) + c]);
   }
   if (grow < n) {
 #pragma unroll
@@ -270,11 +237,11 @@ __global__ void __launch_bounds__(TPB) feat_counts_kernel(const float* __restric
   __shared__ Tile tile;
   const int ti = blockIdx.x, tj = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave >> 1, wj = wave & 1, fr = lane & 15, fk = lane >> 4;
-  if (tid < 2 * FT) {
-    const bool sideb = tid >= FT;
-    const int r = (sideb ? tj : ti) * FT + (tid & (FT - 1));
-    if (sideb) tile.pb[tid & (FT - 1)] = r < m ? b + (size_t)r * ldb : nullptr;
-    else tile.pa[tid & (FT - 1)] = r < n ? a + (size_t)r * lda : nullptr;
+  if (tid < 2 * SG_F64_FT) {
+    const bool sideb = tid >= SG_F64_FT;
+    const int r = (sideb ? tj : ti) * SG_F64_FT + (tid & (SG_F64_FT - 1));
+    if (sideb) tile.pb[tid & (SG_F64_FT - 1)] = r < m ? b + (size_t)r * ldb : nullptr;
+    else tile.pa[tid & (SG_F64_FT - 1)] = r < n ? a + (size_t)r * lda : nullptr;
   }
   f64x4 acc[2][2];
   tile_product(tile, D, acc);
@@ -283,13 +250,13 @@ __global__ void __launch_bounds__(TPB) feat_counts_kernel(const float* __restric
   for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-      const int gi = ti * FT + wi * 32 + mm * 16 + fk + 4 * reg;
+      const int gi = ti * SG_F64_FT + wi * 32 + mm * 16 + fk + 4 * reg;
       const bool oki = gi < n;
       const double ni = oki ? na[gi] : 0.0, ri = oki ? r2[gi] : 0.0;
       double rmin = __builtin_inf();
 #pragma unroll
       for (int nn = 0; nn < 2; ++nn) {
-        const int gj = tj * FT + wj * 32 + nn * 16 + fr;
+        const int gj = tj * SG_F64_FT + wj * 32 + nn * 16 + fr;
         if (oki && gj < m) {
           const double d = dist2(ni, nb[gj], acc[mm][nn][reg]);
           cnt[nn] += d <= ri ? 1 : 0;
@@ -309,7 +276,7 @@ __global__ void __launch_bounds__(TPB) feat_counts_kernel(const float* __restric
     int c = cnt[nn];
     c += __shfl_xor(c, 16, 64);                           // over the 4 lane groups that share the column
     c += __shfl_xor(c, 32, 64);
-    const int gj = tj * FT + wj * 32 + nn * 16 + fr;
+    const int gj = tj * SG_F64_FT + wj * 32 + nn * 16 + fr;
     if (fk == 0 && gj < m && c) atomicAdd(count + gj, c);
   }
 }
@@ -319,7 +286,7 @@ inline size_t up8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 // column splits of the neighbour sweep: enough workgroups to fill the chip at small n, never more than there are column tiles
 inline int knn_splits(int n) {
-  const int nb = (n + FT - 1) / FT;
+  const int nb = (n + SG_F64_FT - 1) / SG_F64_FT;
   int cs = (512 + nb - 1) / nb;
   return cs < 1 ? 1 : (cs > nb ? nb : cs);
 }
@@ -328,7 +295,7 @@ inline int knn_splits(int n) {
 
 extern "C" size_t sg_feat_poly_sums_ws_bytes(int S, int s) {
   if (S < 1 || s < 1) return 0;
-  const size_t nt = ((size_t)s + FT - 1) / FT;
+  const size_t nt = ((size_t)s + SG_F64_FT - 1) / SG_F64_FT;
   return (size_t)S * (nt * (nt + 1) + nt * nt) * sizeof(double);
 }
 
@@ -340,7 +307,7 @@ extern "C" int sg_feat_poly_sums(const float* x, int n, int ldx, const float* y,
                ldx, ldy, S, s);
   SG_ARG_CHECK(degree >= 1 && degree <= 4, "sg_feat_poly_sums: degree=%d is outside 1..4", degree);
   if (S == 0) return 0;
-  const long nt = ((long)s + FT - 1) / FT, ntri = nt * (nt + 1) / 2, T = 2 * ntri + nt * nt;
+  const long nt = ((long)s + SG_F64_FT - 1) / SG_F64_FT, ntri = nt * (nt + 1) / 2, T = 2 * ntri + nt * nt;
   SG_ARG_CHECK((double)S * (double)T <= 2147483647.0, "sg_feat_poly_sums: S=%d subsets of s=%d are beyond the launch grid", S, s);
   SG_ARG_CHECK(x && y && ix && iy && out && ws, "sg_feat_poly_sums: null operand");
   SG_ARG_CHECK(aligned(x, 4) && aligned(y, 4) && aligned(ix, 4) && aligned(iy, 4), "sg_feat_poly_sums: x, y, ix and iy must be 4-byte aligned");
@@ -349,8 +316,8 @@ extern "C" int sg_feat_poly_sums(const float* x, int n, int ldx, const float* y,
                sg_feat_poly_sums_ws_bytes(S, s));
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)ws;
-  const double pairs = (double)S * (double)T * FT * FT;
-  SgProfScope prof(SG_K_FEAT_POLY, st, 2.0 * pairs * D, 4.0 * (double)S * T * 2.0 * FT * D);
+  const double pairs = (double)S * (double)T * SG_F64_FT * SG_F64_FT;
+  SgProfScope prof(SG_K_FEAT_POLY, st, 2.0 * pairs * D, 4.0 * (double)S * T * 2.0 * SG_F64_FT * D);
   hipLaunchKernelGGL(feat_poly_kernel, dim3((unsigned)(S * T)), dim3(TPB), 0, st, x, n, (size_t)ldx, y, m, (size_t)ldy, D, ix, iy, s, (int)nt,
                      (int)ntri, (int)T, gamma, coef0, degree, part);
   hipLaunchKernelGGL(feat_poly_final_kernel, dim3((unsigned)((3 * (long)S + 255) / 256)), dim3(256), 0, st, part, S, (int)ntri, (int)T, out);
@@ -373,11 +340,11 @@ extern "C" int sg_feat_knn_radius(const float* x, int n, int D, int ldx, int k, 
   SG_ARG_CHECK(ws_bytes >= sg_feat_knn_radius_ws_bytes(n), "sg_feat_knn_radius: workspace of %zu bytes, %zu needed", ws_bytes,
                sg_feat_knn_radius_ws_bytes(n));
   hipStream_t st = (hipStream_t)stream;
-  const int nb = (n + FT - 1) / FT, CS = knn_splits(n);
+  const int nb = (n + SG_F64_FT - 1) / SG_F64_FT, CS = knn_splits(n);
   double* nrm = (double*)ws;
   double* part = nrm + n;
-  const double pairs = (double)nb * nb * FT * FT;
-  SgProfScope prof(SG_K_FEAT_MANIFOLD, st, 2.0 * pairs * D, 4.0 * (double)nb * nb * 2.0 * FT * D);
+  const double pairs = (double)nb * nb * SG_F64_FT * SG_F64_FT;
+  SgProfScope prof(SG_K_FEAT_MANIFOLD, st, 2.0 * pairs * D, 4.0 * (double)nb * nb * 2.0 * SG_F64_FT * D);
   hipLaunchKernelGGL(feat_norms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(TPB), 0, st, x, n, D, (size_t)ldx, nrm);
   hipLaunchKernelGGL(feat_knn_kernel, dim3((unsigned)nb, (unsigned)CS), dim3(TPB), 0, st, x, n, D, (size_t)ldx, (const double*)nrm, nb, CS, part);
   hipLaunchKernelGGL(feat_knn_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)part, n, CS * QL, k, r2);
@@ -395,7 +362,7 @@ extern "C" int sg_feat_manifold_counts(const float* a, int n, int lda, const dou
   SG_ARG_CHECK(n >= 0 && m >= 0 && D >= 1 && lda >= D && ldb >= D,
                "sg_feat_manifold_counts: bad sizes (n=%d m=%d D=%d lda=%d ldb=%d; n, m >= 0, D >= 1, lda and ldb >= D)", n, m, D, lda, ldb);
   if (n == 0 || m == 0) return 0;
-  const int nta = (n + FT - 1) / FT, ntb = (m + FT - 1) / FT;
+  const int nta = (n + SG_F64_FT - 1) / SG_F64_FT, ntb = (m + SG_F64_FT - 1) / SG_F64_FT;
   SG_ARG_CHECK(ntb <= 65535, "sg_feat_manifold_counts: m=%d is beyond the launch grid", m);
   SG_ARG_CHECK(a && r2 && b && count && mind2 && ws, "sg_feat_manifold_counts: null operand");
   SG_ARG_CHECK(aligned(a, 4) && aligned(b, 4) && aligned(count, 4), "sg_feat_manifold_counts: a, b and count must be 4-byte aligned");
@@ -405,8 +372,8 @@ extern "C" int sg_feat_manifold_counts(const float* a, int n, int lda, const dou
   hipStream_t st = (hipStream_t)stream;
   double* na = (double*)ws;
   double* nb = na + n;
-  const double pairs = (double)nta * ntb * FT * FT;
-  SgProfScope prof(SG_K_FEAT_MANIFOLD, st, 2.0 * pairs * D, 4.0 * (double)nta * ntb * 2.0 * FT * D);
+  const double pairs = (double)nta * ntb * SG_F64_FT * SG_F64_FT;
+  SgProfScope prof(SG_K_FEAT_MANIFOLD, st, 2.0 * pairs * D, 4.0 * (double)nta * ntb * 2.0 * SG_F64_FT * D);
   const int big = n > m ? n : m;
   hipLaunchKernelGGL(feat_counts_init_kernel, dim3((unsigned)((big + 255) / 256)), dim3(256), 0, st, count, m, (unsigned long long*)mind2, n);
   hipLaunchKernelGGL(feat_norms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(TPB), 0, st, a, n, D, (size_t)lda, na);

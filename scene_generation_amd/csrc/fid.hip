@@ -9,38 +9,28 @@
 // triangle: it reads that tile of ``outer``, adds its products and writes the tile back.  No atomics, k in ascending order: the same
 // call sequence gives bit-identical moments.  Raw (unshifted) moments, so two accumulators merge by plain addition.
 //
-// The f64 MFMA's C/D lane map is NOT the f32 one: col = lane & 15, row = (lane >> 4) + 4 * reg (the f32 16x16 forms have
-// row = 4 * (lane >> 4) + reg).  A and B are one f64 per lane: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15].
-#include "common.h"
+// The 64 x 64 tile (SG_F64_FT: four waves, 2 x 2, each 32 x 32 = 2 x 2 MFMA tiles), the f64 MFMA's lane map and the tile-pair enumeration
+// are f64_tile.h's; the stage here is k-major, so the product loop is this file's own.
+#include "f64_tile.h"
 
 namespace {
 
 constexpr int TPB = 256;
-constexpr int FT = 64;           // tile of outer per workgroup: four waves, 2 x 2, each 32 x 32 = 2 x 2 MFMA tiles
 constexpr int FKB = 32;          // rows of x staged per pass (the evaluation's batch)
-constexpr int FLD = FT + 16;     // LDS row stride in doubles: 640 B, so the two rows a 32-lane half reads (k, k + 1) sit on opposite
-                                 // halves of the 64 banks
+constexpr int FLD = SG_F64_FT + 16;  // LDS row stride in doubles: 640 B, so the two rows a 32-lane half reads (k, k + 1) sit on
+                                 // opposite halves of the 64 banks
 constexpr int ST = 32;           // tile of the finalize kernel
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// tile pair (ti <= tj) number b of the block upper triangle of an nt x nt grid, row by row (wave-uniform scalar loop)
-__device__ __forceinline__ void tile_pair(int b, int nt, int& ti, int& tj) {
-  int i = 0, len = nt;
-  while (b >= len) { b -= len; ++i; --len; }
-  ti = i; tj = i + b;
-}
 
 __global__ void __launch_bounds__(TPB) fid_moments_kernel(const float* __restrict__ x, int rows, int D, size_t ldx, double* sum,
                                                          double* outer, int nt) {
-  __shared__ double sA[FKB * FLD];          // sA[k][i] = x[k0 + k][ti * FT + i]  (A of the MFMA is its transpose)
-  __shared__ double sB[FKB * FLD];          // sB[k][j] = x[k0 + k][tj * FT + j]
+  __shared__ double sA[FKB * FLD];          // sA[k][i] = x[k0 + k][ti * SG_F64_FT + i]  (A of the MFMA is its transpose)
+  __shared__ double sB[FKB * FLD];          // sB[k][j] = x[k0 + k][tj * SG_F64_FT + j]
   int ti, tj;
-  tile_pair(blockIdx.x, nt, ti, tj);
+  sg_f64_tile_pair(blockIdx.x, nt, ti, tj);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wi = wave >> 1, wj = wave & 1;
-  const int c = tid & (FT - 1), r0 = tid >> 6;          // loader: column c of rows r0, r0 + 4, ...
-  const int ca = ti * FT + c, cb = tj * FT + c;
+  const int c = tid & (SG_F64_FT - 1), r0 = tid >> 6;   // loader: column c of rows r0, r0 + 4, ...
+  const int ca = ti * SG_F64_FT + c, cb = tj * SG_F64_FT + c;
   const bool oka = ca < D, okb = cb < D;                // D tail: columns past D are staged as zeros
   const int fr = lane & 15, fk = lane >> 4;
   f64x4 acc[2][2];
@@ -53,7 +43,7 @@ __global__ void __launch_bounds__(TPB) fid_moments_kernel(const float* __restric
     const int kc = rows - k0 < FKB ? rows - k0 : FKB;
     const int kp = (kc + 3) & ~3;                       // k tail: the rows up to the next multiple of 4 are staged as zeros
     __syncthreads();
-    for (int r = r0; r < kp; r += TPB / FT) {
+    for (int r = r0; r < kp; r += TPB / SG_F64_FT) {
       const bool okr = r < kc;
       const float* xr = x + (size_t)(k0 + (okr ? r : 0)) * ldx;
       sA[r * FLD + c] = (okr && oka) ? (double)xr[ca] : 0.0;
@@ -81,14 +71,14 @@ __global__ void __launch_bounds__(TPB) fid_moments_kernel(const float* __restric
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
-        const int row = ti * FT + wi * 32 + m * 16 + fk + 4 * reg;
-        const int col = tj * FT + wj * 32 + n * 16 + fr;
+        const int row = ti * SG_F64_FT + wi * 32 + m * 16 + fk + 4 * reg;
+        const int col = tj * SG_F64_FT + wj * 32 + n * 16 + fr;
         if (row < D && col < D) {
           double* p = outer + (size_t)row * D + col;
           *p = *p + acc[m][n][reg];
         }
       }
-  if (ti == tj && wave == 0 && ti * FT + lane < D) sum[ti * FT + lane] += colsum;
+  if (ti == tj && wave == 0 && ti * SG_F64_FT + lane < D) sum[ti * SG_F64_FT + lane] += colsum;
 }
 
 // mu and the full symmetric sigma from the upper triangle of outer.  One workgroup per 32 x 32 tile pair (ti <= tj): it writes the
@@ -98,7 +88,7 @@ __global__ void __launch_bounds__(TPB) fid_finalize_kernel(const double* __restr
                                                           int D, double* __restrict__ mu, double* __restrict__ sigma, int nt) {
   __shared__ double tile[ST][ST + 1];
   int ti, tj;
-  tile_pair(blockIdx.x, nt, ti, tj);
+  sg_f64_tile_pair(blockIdx.x, nt, ti, tj);
   const int cx = threadIdx.x & (ST - 1), ry = threadIdx.x >> 5;
   const int j = tj * ST + cx;
   for (int r = ry; r < ST; r += TPB / ST) {
@@ -129,7 +119,7 @@ inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7
 
 extern "C" int sg_fid_moments_update(const float* x, int rows, int D, int ldx, double* sum, double* outer, sgStream stream) {
   SG_ARG_CHECK(rows >= 0 && D >= 1 && ldx >= D, "sg_fid_moments_update: bad sizes (rows=%d D=%d ldx=%d; D >= 1, ldx >= D)", rows, D, ldx);
-  const long nt = (D + FT - 1) / FT;
+  const long nt = (D + SG_F64_FT - 1) / SG_F64_FT;
   SG_ARG_CHECK(nt * (nt + 1) / 2 <= 2147483647L, "sg_fid_moments_update: D=%d is beyond the launch grid", D);
   SG_ARG_CHECK(sum && outer && (rows == 0 || x), "sg_fid_moments_update: null operand");
   SG_ARG_CHECK(aligned8(sum) && aligned8(outer), "sg_fid_moments_update: sum and outer must be 8-byte aligned");

@@ -24,6 +24,8 @@ scene_generation/data/utils.py it needs).
 * ``sets`` (a ``featsets.FeatureSetMetrics``, off by default): KID and precision / recall / density / coverage of the generated images
   against the real feature rows the object holds, fed from the same Inception forward as ``fid`` / ``inception`` when one of them
   carries it, read once by ``featsets_summary``; ``--real_features`` on the command line.
+* ``--fid_infinity 1`` (with ``--fid_stats``) puts a ``fidinf.FIDInfinity`` in the ``sets`` slot of ``fid``, the ``FeatureSetMetrics``
+  behind it (``then``): the FID extrapolated to an infinite number of images, from the same forward.
 * ``diversity`` (an ``lpips.Diversity``, off by default): the mean LPIPS distance between two pictures of the same scene graph with
   different appearance draws.  ``sample_pair`` runs ``sample_batch`` and then a second forward of the same batch with fresh bank
   draws that feeds this scorer ONLY; read once by ``diversity_summary``; ``--diversity_backbone`` / ``--diversity_lin`` /
@@ -235,7 +237,12 @@ class Sampler(object):
 
     def _sets_shared(self):
         """``sets`` is fed by the forward of ``fid`` (attached as its ``sets``) or of the scorer (in the place of its ``fid``)"""
-        return (self.fid is not None and getattr(self.fid, 'sets', None) is self.sets) or getattr(self.inception, 'fid', None) is self.sets
+        for tap in (getattr(self.fid, 'sets', None), getattr(self.inception, 'fid', None)):
+            while tap is not None:                          # a tap may forward to the next one (fidinf.FIDInfinity(then=...))
+                if tap is self.sets:
+                    return True
+                tap = getattr(tap, 'then', None)
+        return False
 
     def featsets_summary(self):
         """``FeatureSetMetrics.compute()`` over everything sampled since its ``clean()``: KID mean / std, precision, recall, density,
@@ -376,6 +383,12 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     (+ images_gt, layouts), print and return the IoU summary and the paths written."""
     if getattr(args, 'real_features', None) is not None and getattr(args, 'inception_weights', None) is None:      # before any work
         raise ValueError('--real_features needs --inception_weights (the network whose features the rows are)')
+    want_inf = bool(getattr(args, 'fid_infinity', False))
+    if want_inf and getattr(args, 'fid_stats', None) is None:
+        raise ValueError('--fid_infinity needs --fid_stats (the real statistics the extrapolated distance is measured to)')
+    if want_inf and loader is None and not getattr(args, 'scene_graphs', None) and not getattr(args, 'layouts', None):
+        from .fidinf import check_count
+        check_count(args.num_samples)       # the synthetic generator makes exactly this many: too few or too many are refused here
     model = build_model(args, checkpoint, device)
     graphs = getattr(args, 'scene_graphs', None)
     layouts = getattr(args, 'layouts', None)
@@ -397,7 +410,7 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     inc_path = getattr(args, 'inception_weights', None)
     if inc_path is not None:
         from .inception import InceptionScore
-    fid, fid_stats = None, getattr(args, 'fid_stats', None)
+    fid, fid_inf, fid_stats = None, None, getattr(args, 'fid_stats', None)
     sets, real_features = None, getattr(args, 'real_features', None)
     if fid_stats is not None or real_features is not None:
         if inc_path is None:
@@ -409,8 +422,12 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
             sets = FeatureSetMetrics(weights=net, real_features=real_features, resize=True, batch_size=args.batch_size, device=device)
         if fid_stats is not None:
             from .fid import FrechetInceptionDistance
+            attached = sets
+            if want_inf:                                    # in the sets slot, the FeatureSetMetrics (if any) behind it: still one forward
+                from .fidinf import FIDInfinity
+                attached = fid_inf = FIDInfinity(real_stats=fid_stats, dim=net.fc.in_features, device=device, then=sets)
             fid = FrechetInceptionDistance(weights=net, real_stats=fid_stats, resize=True, batch_size=args.batch_size, device=device,
-                                           sets=sets)
+                                           sets=attached)
         # (without --fid_stats the feature rows go straight from the scorer's forward to the sets object: the same add_features)
         scorer = InceptionScore(batch_size=args.batch_size, resize=True, weights=net, device=device, fid=fid if fid is not None else sets)
     elif inc_path is not None:
@@ -452,6 +469,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         if getattr(args, 'bank', None):
             model.features, model.features_one = load_bank(args.bank)
         sgs = load_scene_graphs(graphs) if graphs else load_layouts(layouts)
+        if want_inf:                        # (the count is known only now: still before the first picture)
+            from .fidinf import check_count
+            check_count(len(sgs))
         for a in range(0, len(sgs), args.batch_size):
             save(sampler.sample_json(sgs[a:a + args.batch_size], want_layout_rgb=args.save_layout), None)
     else:
@@ -485,6 +505,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if fid is not None:
         result['fid'] = sampler.fid_summary()
         print('FID {}'.format(result['fid']['fid']))
+    if fid_inf is not None:
+        result['fid_inf'] = fid_inf.compute()
+        print('FID_inf {}'.format(result['fid_inf']['fid_inf']))
     if sets is not None:
         from .featsets import format_lines
         result['featsets'] = sampler.featsets_summary()
@@ -540,6 +563,9 @@ def make_parser():
     p.add_argument('--real_features', default=None, help='.npy with the pooled Inception features of the real images (python -m '
                    'scene_generation_amd.fid --save_features, or python -m scene_generation_amd.featsets --save_real): prints "KID mean '
                    'std", "Precision p Recall r" and "Density d Coverage c" lines; needs --inception_weights; with or without --fid_stats')
+    p.add_argument('--fid_infinity', default=False, type=bool_flag, help='with --fid_stats: also print one "FID_inf x" line after the '
+                   'FID line, the distance extrapolated to an infinite number of sampled images (python -m scene_generation_amd.fidinf; '
+                   'at most 4096 images)')
     p.add_argument('--diversity_backbone', default=None, help='torchvision alexnet / vgg16 state_dict file (never downloaded): every '
                    'batch is sampled twice with different appearance draws and one "Diversity MEAN STD" line (mean LPIPS distance '
                    'of the pairs) is printed; python -m scene_generation_amd.lpips scores two directories of pictures')
