@@ -895,6 +895,38 @@ int sg_adam_step_ema(float* p, const float* g, float* m, float* v, float* e, int
                      float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, float ema_w, sgStream stream);
 /* the same EMA expression alone, for parameter runs the Adam step skips: e = ema_w == 1 ? p : fmaf(ema_w, p - e, e) */
 int sg_ema_update(float* e, const float* p, int64_t n, float ema_w, sgStream stream);
+/* Gradient control of the fused Adam step: global-norm clipping and a skip-on-non-finite guard that never leave the device.
+ * The record lives in caller-owned DEVICE memory, 8-byte aligned, 32 bytes, zeroed once by the caller; only the kernels below
+ * write it afterwards.  Byte offsets:
+ *    0 sumsq   (double)  sum of squares of the raw buffer g
+ *    8 norm    (float)   |grad_scale| * sqrt(sumsq), computed in double, rounded once
+ *   12 coef    (float)   the factor the _ctl Adam launches multiply grad_scale by
+ *   16 skip    (int32)   1 when norm is not finite (NaN / inf in g, or a norm beyond fp32), else 0
+ *   20 skipped (int32)   calls that set skip  (only ever incremented)
+ *   24 steps   (int32)   calls                (only ever incremented)
+ *   28 reserved */
+typedef struct sgGradCtl {
+  double sumsq;
+  float norm, coef;
+  int32_t skip, skipped, steps, reserved;
+} sgGradCtl;
+/* One streaming read of g (4 B per element, profile kind SG_K_GRAD_NORM) fills the record: squares and sums in float64 (an fp32
+ * square is exact there) in a FIXED order -- per-workgroup partials in ws, one finishing launch, no floating-point atomics: the
+ * same bits on every call and every stream.  coef = (float)min(1, max_norm / (norm_double + 1e-6)), the expression of
+ * torch.nn.utils.clip_grad_norm_; max_norm <= 0 or +inf: no clipping, coef = 1.  A non-finite norm sets skip = 1, coef = 1 and
+ * increments skipped.  g may start at any 4-byte aligned element.  ws: sg_grad_norm_ws_bytes(n) bytes, 8-byte aligned. */
+size_t sg_grad_norm_ws_bytes(int64_t n);
+int sg_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, void* ctl, void* ws, size_t ws_bytes,
+                 sgStream stream);
+/* sg_adam_step / sg_adam_step_ema under a record sg_grad_norm filled earlier on the same stream (or one ordered before it): the
+ * gradient enters as g * (grad_scale * ctl->coef), the product rounded to fp32 once, so coef == 1 gives the bits of sg_adam_step.
+ * With ctl->skip set the Adam part writes nothing (p, m, v keep their bits); the EMA part still moves e toward the unchanged p,
+ * as sg_ema_update does for parameters the Adam step skips.  Same traffic as the plain launches (28 / 36 B per parameter). */
+int sg_adam_step_ctl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                     float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, const void* ctl, sgStream stream);
+int sg_adam_step_ema_ctl(float* p, const float* g, float* m, float* v, float* e, int64_t n, float lr, float beta1, float beta2,
+                         float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, float ema_w, const void* ctl,
+                         sgStream stream);
 int sg_fill(float* p, float value, int64_t n, sgStream stream);
 int sg_scale(float* p, float alpha, int64_t n, sgStream stream);
 /* dst (device) <- src (PAGE-LOCKED host memory, read through its device mapping) by a kernel on ``stream``: how a collated host

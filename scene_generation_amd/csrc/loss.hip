@@ -275,6 +275,105 @@ __global__ void ema_kernel(float* __restrict__ e, const float* __restrict__ p, s
   if (i < n) e[i] = ema_one(e[i], p[i], ema_w);
 }
 
+// ---- gradient control: global-norm clipping and the non-finite guard of the Adam step ---------------------------------------------
+// Stage 1: one streaming read.  Workgroup b adds the squares of its float4s b*256+t, (b+G)*256+t, ... in float64 (an fp32 square is
+// exact there; four loads in flight), folds its lanes with the wave butterfly and its waves in index order, and stores ONE double.
+// The up to three elements before the first 16-byte boundary and after the last whole float4 go to the first lanes of workgroup 0.
+// Nothing depends on timing: the same pointer and n give the same bits.
+// Measured on the generator's 765 MB buffer: 5.7-5.8 TB/s (131-134 us) where sg_adam_step reaches 6.2-6.3 in the same run -- 7 % short
+// of it.  Nontemporal loads (nothing reads the buffer twice) and 1 024 workgroups (four per CU) measured the same as plain loads
+// from 2 048.  A stand-alone copy of this loop whose four loads the compiler had SERIALISED -- each waited for before the next is
+// issued -- ran at 6.6-6.7 TB/s (114 us) on the same box, and eight loads in flight lost to four: this stream wants fewer requests
+// in flight per wave, not more.  Not followed up here.
+constexpr int GN_BLOCKS = 1024;
+typedef float gn_f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// 256 threads; `red`: 4 doubles of LDS.  Valid in every thread.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ double sq_f64(float x) { const double d = (double)x; return d * d; }
+
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, size_t n, size_t head, size_t n4,
+                                                        double* __restrict__ part) {
+  __shared__ double red[4];
+  const gn_f32x4* __restrict__ g4 = reinterpret_cast<const gn_f32x4*>(g + head);
+  const size_t stride = (size_t)gridDim.x * 256;
+  double s = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += 4 * stride) {
+    gn_f32x4 x[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const size_t j = i + e * stride;
+      x[e] = j < n4 ? __builtin_nontemporal_load(&g4[j]) : gn_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += ((sq_f64(x[e].x) + sq_f64(x[e].y)) + sq_f64(x[e].z)) + sq_f64(x[e].w);
+  }
+  if (blockIdx.x == 0) {
+    const size_t t = threadIdx.x, tail0 = head + 4 * n4;
+    if (t < head) s += sq_f64(g[t]);
+    if (tail0 + t < n) s += sq_f64(g[tail0 + t]);       // (n - tail0 <= 3)
+  }
+  s = block_sum_f64(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Stage 2: one workgroup adds the partials (thread t: t, t + 256, ... ascending) and writes the record.  The products and sums of
+// the norm are explicit single roundings (no contraction into an fma): the host can restate them bit for bit.
+__global__ void __launch_bounds__(256) grad_ctl_kernel(const double* __restrict__ part, int nb, float grad_scale, float max_norm,
+                                                      sgGradCtl* __restrict__ ctl) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
+  s = block_sum_f64(s, red);
+  if (threadIdx.x != 0) return;
+  const double norm_d = __dmul_rn(fabs((double)grad_scale), sqrt(s));
+  const float norm = (float)norm_d;
+  const bool bad = !isfinite(norm);
+  float coef = 1.f;
+  if (!bad && max_norm > 0.f && isfinite(max_norm)) coef = (float)fmin(1.0, (double)max_norm / __dadd_rn(norm_d, 1e-6));
+  ctl->sumsq = s;
+  ctl->norm = norm;
+  ctl->coef = coef;
+  ctl->skip = bad ? 1 : 0;
+  if (bad) ctl->skipped = ctl->skipped + 1;
+  ctl->steps = ctl->steps + 1;
+}
+
+// adam_kernel / adam_ema_kernel under a control record: the scale is gscale * coef (one fp32 rounding; coef == 1 leaves gscale's
+// bits), and a set skip flag turns the Adam part into a no-op -- no store to p / m / v -- while the EMA still moves toward p.
+// The record costs every wave two dependent scalar loads before its first vector load: +0.5-0.7 % on the generator's buffer with the
+// loads of adam_kernel (852 against 846 us).  The gradient is read here for the last time before the next backward overwrites it,
+// so its load is nontemporal: 839 against 865 us, 846 against 854 (the same bits; nontemporal loads of p / m / v gain nothing).
+template <bool EMA>
+__global__ void adam_ctl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ e, size_t n, float gscale, float step_size, float beta1, float beta2, float eps,
+                                float bc2_sqrt, float ema_w, const sgGradCtl* __restrict__ ctl) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float scale = gscale * ctl->coef;
+  if (ctl->skip) {
+    if (EMA) e[i] = ema_one(e[i], p[i], ema_w);
+    return;
+  }
+  float pi = p[i], mi = m[i], vi = v[i];
+  float ei = 0.f;
+  if (EMA) ei = e[i];
+  adam_one(pi, __builtin_nontemporal_load(&g[i]), mi, vi, scale, step_size, beta1, beta2, eps, bc2_sqrt);
+  m[i] = mi; v[i] = vi; p[i] = pi;
+  if (EMA) e[i] = ema_one(ei, pi, ema_w);
+}
+
 __global__ void fill_kernel(float* __restrict__ p, float value, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = value;
@@ -472,6 +571,54 @@ extern "C" int sg_ema_update(float* e, const float* p, int64_t n, float ema_w, s
   SG_ARG_CHECK(e && p && n > 0 && ema_w >= 0.f && ema_w <= 1.f, "sg_ema_update: bad arguments");
   hipLaunchKernelGGL(ema_kernel, dim3(sg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, e, p, (size_t)n, ema_w);
   SG_LAUNCH_CHECK("sg_ema_update");
+  return 0;
+}
+
+extern "C" size_t sg_grad_norm_ws_bytes(int64_t n) { (void)n; return GN_BLOCKS * sizeof(double); }
+
+extern "C" int sg_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, void* ctl, void* ws, size_t ws_bytes,
+                            sgStream stream) {
+  SG_ARG_CHECK(g && ctl && ws && n > 0, "sg_grad_norm: bad arguments");
+  SG_ARG_CHECK(((uintptr_t)g & 3) == 0 && ((uintptr_t)ctl & 7) == 0 && ((uintptr_t)ws & 7) == 0,
+               "sg_grad_norm: g must be 4-byte aligned, ctl and ws 8-byte aligned");
+  SG_ARG_CHECK(ws_bytes >= GN_BLOCKS * sizeof(double), "sg_grad_norm: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  // elements before the first 16-byte boundary (at most 3, at most n), whole float4s after them; the rest (at most 3) is the tail
+  size_t head = (size_t)((16 - ((uintptr_t)g & 15)) & 15) / 4;
+  if (head > (size_t)n) head = (size_t)n;
+  const size_t n4 = ((size_t)n - head) / 4;
+  int nb = sg_cdiv((int64_t)n4, 256 * 4);
+  nb = nb < 1 ? 1 : (nb > GN_BLOCKS ? GN_BLOCKS : nb);
+  SgProfScope prof(SG_K_GRAD_NORM, s, 0, 4.0 * (double)n);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nb), dim3(256), 0, s, g, (size_t)n, head, n4, (double*)ws);
+  hipLaunchKernelGGL(grad_ctl_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nb, grad_scale, max_norm, (sgGradCtl*)ctl);
+  SG_LAUNCH_CHECK("sg_grad_norm");
+  return 0;
+}
+
+extern "C" int sg_adam_step_ctl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, const void* ctl,
+                                sgStream stream) {
+  SG_ARG_CHECK(p && g && m && v && ctl && n > 0 && bias_corr1 > 0.f && bias_corr2_sqrt > 0.f && ((uintptr_t)ctl & 7) == 0,
+               "sg_adam_step_ctl: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  SgProfScope prof(SG_K_ADAM, s, 0, 28.0 * (double)n);
+  hipLaunchKernelGGL(adam_ctl_kernel<false>, dim3(sg_cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, (float*)nullptr, (size_t)n,
+                     grad_scale, lr / bias_corr1, beta1, beta2, eps, bias_corr2_sqrt, 1.f, (const sgGradCtl*)ctl);
+  SG_LAUNCH_CHECK("sg_adam_step_ctl");
+  return 0;
+}
+
+extern "C" int sg_adam_step_ema_ctl(float* p, const float* g, float* m, float* v, float* e, int64_t n, float lr, float beta1,
+                                    float beta2, float eps, float bias_corr1, float bias_corr2_sqrt, float grad_scale, float ema_w,
+                                    const void* ctl, sgStream stream) {
+  SG_ARG_CHECK(p && g && m && v && e && ctl && n > 0 && bias_corr1 > 0.f && bias_corr2_sqrt > 0.f && ema_w >= 0.f &&
+               ema_w <= 1.f && ((uintptr_t)ctl & 7) == 0, "sg_adam_step_ema_ctl: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  SgProfScope prof(SG_K_ADAM, s, 0, 36.0 * (double)n);
+  hipLaunchKernelGGL(adam_ctl_kernel<true>, dim3(sg_cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, e, (size_t)n, grad_scale,
+                     lr / bias_corr1, beta1, beta2, eps, bias_corr2_sqrt, ema_w, (const sgGradCtl*)ctl);
+  SG_LAUNCH_CHECK("sg_adam_step_ema_ctl");
   return 0;
 }
 

@@ -11,6 +11,7 @@ switches, layout hints, flat-buffer updates and the profiler front end: everythi
 import contextlib
 import os
 import ctypes
+import struct
 
 import torch
 from torch.autograd import Function
@@ -394,6 +395,52 @@ def ema_update(e, p, w):
     assert e.numel() == p.numel()
     _call('sg_ema_update', _p(e), _p(p), e.numel(), float(w), _stream())
     return e
+
+
+GRAD_CTL_BYTES = 32              # sizeof(sgGradCtl), include/sg2im_hip.h
+
+
+def grad_ctl_alloc(device):
+    """-> (ctl, ws): a zeroed control record (sgGradCtl, as 4 int64) and the partials buffer of grad_norm, owned by the caller.
+    Not ``workspace()``: the record lives across launches and streams, and both are baked into captured graphs by address."""
+    ctl = torch.zeros(GRAD_CTL_BYTES // 8, dtype=torch.int64, device=device)
+    ws = torch.empty(int(_L().sg_grad_norm_ws_bytes(1)) // 8, dtype=torch.float64, device=device)
+    return ctl, ws
+
+
+def grad_norm(g, ctl, ws, grad_scale=1.0, max_norm=0.0):
+    """Fills ``ctl`` from the flat gradient ``g``: the float64 sum of squares, norm = |grad_scale| * sqrt(sumsq),
+    coef = min(1, max_norm / (norm + 1e-6)) (max_norm <= 0 or inf: 1) and the skip flag of a non-finite norm.  One read of ``g``,
+    fixed summation order, nothing returns to the host (grad_ctl_read)."""
+    _f32(g, 'gradient')
+    assert g.is_contiguous() and ctl.numel() * ctl.element_size() >= GRAD_CTL_BYTES
+    _call('sg_grad_norm', _p(g), g.numel(), float(grad_scale), float(max_norm), _p(ctl), _p(ws), ws.numel() * ws.element_size(),
+          _stream())
+    return ctl
+
+
+def grad_ctl_read(ctl):
+    """the record as a dict (one small device-to-host copy, which waits for the launches that write it)"""
+    raw = ctl.cpu().numpy().tobytes()[:GRAD_CTL_BYTES]
+    sumsq, norm, coef, skip, skipped, steps, _ = struct.unpack('<dffiiii', raw)
+    return {'sumsq': sumsq, 'norm': norm, 'coef': coef, 'skip': skip, 'skipped': skipped, 'steps': steps}
+
+
+def adam_step_ctl(p, g, m, v, ctl, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    """adam_step with the gradient scaled by grad_scale * ctl.coef; a no-op when ctl.skip is set (grad_norm)"""
+    bc1 = 1.0 - beta1 ** step
+    bc2_sqrt = (1.0 - beta2 ** step) ** 0.5
+    _call('sg_adam_step_ctl', _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, bc1, bc2_sqrt, float(grad_scale),
+          _p(ctl), _stream())
+
+
+def adam_step_ema_ctl(p, g, m, v, e, ctl, lr, beta1, beta2, eps, step, grad_scale=1.0, ema_w=1.0):
+    """adam_step_ema under a control record: with ctl.skip set p / m / v are left alone and e still moves toward p"""
+    assert e.numel() == p.numel()
+    bc1 = 1.0 - beta1 ** step
+    bc2_sqrt = (1.0 - beta2 ** step) ** 0.5
+    _call('sg_adam_step_ema_ctl', _p(p), _p(g), _p(m), _p(v), _p(e), p.numel(), lr, beta1, beta2, eps, bc1, bc2_sqrt,
+          float(grad_scale), float(ema_w), _p(ctl), _stream())
 
 
 def fill_(t, value):

@@ -12,6 +12,10 @@ checkpoints round-trip.
 Optional: an exponential moving average of the parameters (``ParamEMA``, ``FusedAdam.attach_ema``) in a shadow buffer with the
 flat buffer's layout, updated inside the same launch (sg_adam_step_ema: 36 instead of 28 B/param, no second pass).
 
+Optional: global-norm clipping and a skip-on-non-finite guard (``FusedAdam.set_grad_control``, SG_GRAD_CLIP / SG_GRAD_NORMS): one
+more read of the flat gradient (sg_grad_norm, 4 B/param) leaves norm, clip coefficient and skip flag in a device record the Adam
+launch reads (sg_adam_step_ctl) -- no host synchronisation, no pass over parameters or moments.
+
 ``FusedSGD`` (at the end) is the same idea for torch.optim.SGD with momentum, the optimiser of the accuracy network.
 """
 import os
@@ -98,6 +102,67 @@ def check_ema_decay(value, what='ema_decay'):
     if not 0.0 < d < 1.0:              # (also rejects nan)
         raise ValueError('%s: expected a float in (0, 1), got %r' % (what, d))
     return d
+
+
+GRAD_CLIP_NAMES = ('g', 'd_obj', 'd_mask', 'd_img')       # the Trainer's four optimisers, as SG_GRAD_CLIP and grad_clip= name them
+
+
+def check_max_norm(value, what='max_norm'):
+    try:
+        m = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s: expected a positive finite float' % what)
+    if not 0.0 < m < float('inf'):      # (also rejects nan)
+        raise ValueError('%s: expected a positive finite float, got %r' % (what, m))
+    return m
+
+
+def check_grad_clip(value, what='grad_clip'):
+    """-> {name: max_norm} over (a subset of) GRAD_CLIP_NAMES.  ``value``: a number (all four optimisers), a dict over the names,
+    or the spelling of SG_GRAD_CLIP: ``'10'`` or ``'g=10,d_img=5'``.  Unknown names, values that are not positive and finite,
+    and anything else raise ValueError."""
+    if isinstance(value, str):
+        parts = [s.strip() for s in value.split(',')]
+        if len(parts) == 1 and '=' not in parts[0]:
+            value = parts[0]
+        else:
+            d = {}
+            for s in parts:
+                name, eq, v = s.partition('=')
+                if not eq or name.strip() in d:
+                    raise ValueError('%s: expected a float or name=float[,name=float...], got %r' % (what, value))
+                d[name.strip()] = v.strip()
+            value = d
+    if isinstance(value, dict):
+        out = {}
+        for name, v in value.items():
+            if name not in GRAD_CLIP_NAMES:
+                raise ValueError('%s: unknown optimiser %r (expected one of %s)' % (what, name, ', '.join(GRAD_CLIP_NAMES)))
+            out[name] = check_max_norm(v, '%s[%s]' % (what, name))
+        if not out:
+            raise ValueError('%s: empty' % what)
+        return out
+    m = check_max_norm(value, what)
+    return {name: m for name in GRAD_CLIP_NAMES}
+
+
+def grad_clip_from_env(environ=None):
+    """SG_GRAD_CLIP: the clipping thresholds when a Trainer is built without ``grad_clip``.  Unset or empty: None (no clipping);
+    ``10``: every optimiser; ``g=10,d_img=5``: the named ones; anything else raises ValueError (check_grad_clip)."""
+    v = (os.environ if environ is None else environ).get('SG_GRAD_CLIP', '')
+    if v.strip() == '':
+        return None
+    return check_grad_clip(v, 'SG_GRAD_CLIP=%r' % v)
+
+
+def grad_norms_from_env(environ=None):
+    """SG_GRAD_NORMS=1: gradient norms and the non-finite guard on every optimiser, without clipping.  Unset, empty or 0: off."""
+    v = (os.environ if environ is None else environ).get('SG_GRAD_NORMS', '').strip()
+    if v in ('', '0'):
+        return False
+    if v == '1':
+        return True
+    raise ValueError('SG_GRAD_NORMS=%r: expected 0 or 1' % v)
 
 
 class ParamEMA:
@@ -189,6 +254,7 @@ class FusedAdam:
         # step() (the Trainer's discriminator optimisers: ('front',) -- the generator's object front runs beside their steps)
         self.join_exclude = ()
         self.ema = None                   # ParamEMA updated by every step() (attach_ema)
+        self.max_norm, self._gctl, self._gctl_ws = None, None, None      # gradient control (set_grad_control)
         self.pre_step_hooks = []          # e.g. GradReducer.wait
         self.zero_grad_hooks = []         # e.g. GradReducer.begin_step
         self.grad_listeners = []          # callables(i): parameter i just received (a contribution to) its gradient
@@ -302,6 +368,44 @@ class FusedAdam:
             raise ValueError('attach_ema: the EMA must be built over this optimiser\'s FlatParams')
         self.ema = ema
 
+    def set_grad_control(self, max_norm=None, monitor=True):
+        """Global-norm clipping and a skip-on-non-finite guard for every step() that follows, decided on the device.
+
+        With the control on, step() reads the flat gradient once more (sg_grad_norm, 4 B per parameter, after the spill fold, the
+        lazy-zero finalisation and every pre_step hook, so it sees the reduced gradient and the deferred 1 / world in
+        ``grad_scale``) and leaves norm = |grad_scale| * ||grad||_2, coef = min(1, max_norm / (norm + 1e-6)) -- the factor of
+        torch.nn.utils.clip_grad_norm_ -- and a skip flag in a 32-byte device record; the Adam launches take the gradient as
+        grad * (grad_scale * coef) and write nothing when the norm is not finite (an attached EMA still moves toward the unchanged
+        weights).  No host synchronisation, no pass over parameters or moments, no temporary.  ``max_norm=None``: norms and the
+        guard only (coef = 1: the bits of a step without the control, as long as no step is skipped).
+        ``set_grad_control(None, False)`` switches it off: step() issues the plain launches again.
+
+        Unlike torch's in-place clip ``p.grad`` is left as the backward wrote it (``scaled_grad()`` too).  Unlike a
+        GradScaler-style skip the HOST step counts advance on a skipped step (the decision never reaches the host): the bias
+        corrections of later steps are those of one step more, nothing else changes.
+
+        The record and the partials buffer are allocated here, once, on the optimiser's device -- not from ``ops.workspace()``,
+        which is per stream and hands out temporaries inside captures."""
+        if max_norm is None and not monitor:
+            self.max_norm, self._gctl, self._gctl_ws = None, None, None
+            return
+        self.max_norm = None if max_norm is None else check_max_norm(max_norm)
+        if self._gctl is None:
+            self._gctl, self._gctl_ws = ops.grad_ctl_alloc(self.fp.flat.device)
+
+    @property
+    def grad_control(self):
+        return self._gctl is not None
+
+    def grad_stats(self):
+        """{'norm', 'coef', 'skip', 'skipped', 'steps'} of the last step() under set_grad_control (``skipped`` / ``steps``: counts
+        since it was switched on); None with the control off.  One 32-byte device-to-host copy on the current stream: the only
+        call of the gradient control that synchronises."""
+        if self._gctl is None:
+            return None
+        rec = ops.grad_ctl_read(self._gctl)
+        return {k: rec[k] for k in ('norm', 'coef', 'skip', 'skipped', 'steps')}
+
     @property
     def step_count(self):
         return max(self.steps) if self.steps else 0
@@ -357,6 +461,10 @@ class FusedAdam:
             self.fp.attach_grads()
             fp, ema = self.fp, self.ema
             w = ema.weight() if ema is not None else None
+            ctl = self._gctl
+            if ctl is not None:
+                # the whole flat buffer: untouched slices and alignment gaps are zero here (finalize_grads; FlatParams)
+                ops.grad_norm(fp.grad, ctl, self._gctl_ws, self.grad_scale, self.max_norm or 0.0)
             for i, j, active in step_runs(self._touched, self.steps):
                 lo, hi = fp.offsets[i], fp.offsets[j] + fp.params[j].numel()
                 if not active:
@@ -364,7 +472,15 @@ class FusedAdam:
                         ops.ema_update(ema.flat[lo:hi], fp.flat[lo:hi], w)
                     continue
                 st = self.steps[i]
-                if ema is not None:
+                if ctl is not None:            # (the host counts advance also when the device skips the step: set_grad_control)
+                    if ema is not None:
+                        ops.adam_step_ema_ctl(fp.flat[lo:hi], fp.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                              ema.flat[lo:hi], ctl, self.lr, self.betas[0], self.betas[1], self.eps, st + 1,
+                                              self.grad_scale, w)
+                    else:
+                        ops.adam_step_ctl(fp.flat[lo:hi], fp.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], ctl,
+                                          self.lr, self.betas[0], self.betas[1], self.eps, st + 1, self.grad_scale)
+                elif ema is not None:
                     ops.adam_step_ema(fp.flat[lo:hi], fp.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], ema.flat[lo:hi],
                                       self.lr, self.betas[0], self.betas[1], self.eps, st + 1, self.grad_scale, w)
                 else:

@@ -14,6 +14,8 @@ Same attributes and step functions as the reference Trainer; differences in HOW 
   * optional host-side flow control (``max_lead_steps`` / SG_LEAD_STEPS, default off): see ``_lead_point``
   * optional EMA of the generator's weights (``ema_decay`` / SG_G_EMA_DECAY, default off): fused into its Adam launch,
     ``ema_model()`` for sampling, extra checkpoint keys next to the reference's
+  * optional gradient control (``grad_clip`` / ``grad_norms``, SG_GRAD_CLIP / SG_GRAD_NORMS, default off): global-norm clipping and
+    a skip-on-non-finite guard decided on the device, norms in ``write_losses``
 TensorBoard / image logging of the reference (trainer.py:342-397) is glue outside the hot path: ``write_losses``
 prints; checkpoints keep the reference schema (trainer.py:136-203, train.py:132-162).
 """
@@ -86,7 +88,7 @@ def _frozen(*modules):
 
 class Trainer:
     def __init__(self, args, vocab, checkpoint=None, device=None, distributed=False, model_extra=None, trunk_precision=None,
-                 ema_decay=None, ema_start=0):
+                 ema_decay=None, ema_start=0, grad_clip=None, grad_norms=None):
         self.vocab = vocab
         self.args = args
         respect_cpu_quota()          # host threads <= the container's CPU quota: an OpenMP burst must not freeze the launch thread
@@ -106,6 +108,11 @@ class Trainer:
         # run-time choice and not a flag: the flag surface stays the reference's
         self._ema_decay = optim.ema_decay_from_env() if ema_decay is None else optim.check_ema_decay(ema_decay)
         self._ema_start = int(ema_start)
+        # gradient control of the four optimisers (FusedAdam.set_grad_control): None = SG_GRAD_CLIP / SG_GRAD_NORMS (unset: off).
+        # ``grad_clip``: one threshold for all of them or a dict over optim.GRAD_CLIP_NAMES; ``grad_norms``: norms and the
+        # non-finite guard on all of them, without clipping.  A run-time choice like the EMA: no flag is added
+        self._grad_clip = (optim.grad_clip_from_env() if grad_clip is None else optim.check_grad_clip(grad_clip)) or {}
+        self._grad_norms = optim.grad_norms_from_env() if grad_norms is None else bool(grad_norms)
         self.init_generator(args, checkpoint)
         self.init_image_discriminator(args, checkpoint)
         self.init_obj_discriminator(args, checkpoint)
@@ -143,6 +150,19 @@ class Trainer:
         if self._ema_decay is not None:
             self.ema = optim.ParamEMA(self.optimizer.fp, self._ema_decay, self._ema_start)
             self.optimizer.attach_ema(self.ema)
+        for name, opt in self.named_optimizers():
+            if self._grad_norms or name in self._grad_clip:
+                opt.set_grad_control(self._grad_clip.get(name), monitor=True)
+
+    def named_optimizers(self):
+        """(name, optimiser) under the names of optim.GRAD_CLIP_NAMES, for the networks that exist"""
+        opts = (self.optimizer, self.optimizer_d_obj, self.optimizer_d_mask, self.optimizer_d_img)
+        return [(n, o) for n, o in zip(optim.GRAD_CLIP_NAMES, opts) if o is not None]
+
+    def grad_stats(self):
+        """{name: FusedAdam.grad_stats()} of the optimisers under gradient control (empty when it is off); one small host read
+        each.  Read it after Trainer.step returns: the generator's record is written on the step's Adam side stream."""
+        return {n: o.grad_stats() for n, o in self.named_optimizers() if o.grad_control}
 
     def _lead_point(self, k):
         """Host-side flow control (opt-in), called at fixed places of an iteration: wait until the GPU has passed THIS place of
@@ -356,6 +376,11 @@ class Trainer:
         if self.ema is not None:              # EMA on only: the reference's keys above are unchanged
             checkpoint['model_ema_state'] = self.ema_model().state_dict()
             checkpoint['ema_state'] = self.ema.state_dict()
+        stats = self.grad_stats()
+        if stats:                             # gradient control on only
+            checkpoint['grad_control'] = {'max_norm': {n: o.max_norm for n, o in self.named_optimizers() if o.grad_control},
+                                          'skipped': {n: st['skipped'] for n, st in stats.items()},
+                                          'steps': {n: st['steps'] for n, st in stats.items()}}
         if val_inception_mean is not None:
             history = checkpoint.setdefault('val_inception', [])
             history.append(val_inception_mean)
@@ -674,6 +699,19 @@ class Trainer:
                         hist[name] = []
                     hist[name].append(val)
                 self.writer.add_scalar('%s/%s' % (scope, name), val, index)
+        stats = self.grad_stats()
+        if stats:                             # gradient control on only: the reference's norm_g / norm_d lists (train.py:147-148)
+            for name, st in stats.items():
+                print(' %s [grad_norm]: %.4f (coef %.4f)' % (name, st['norm'], st['coef']))
+                if st['skipped']:
+                    print(' %s [skipped]: %d of %d steps (non-finite gradient)' % (name, st['skipped'], st['steps']))
+                self.writer.add_scalar('grad_norm/%s' % name, st['norm'], index)
+            if checkpoint is not None:
+                if 'g' in stats:
+                    checkpoint.setdefault('norm_g', []).append(stats['g']['norm'])
+                norm_d = {n: st['norm'] for n, st in stats.items() if n != 'g'}
+                if norm_d:
+                    checkpoint.setdefault('norm_d', []).append(norm_d)
         if checkpoint is not None:
             checkpoint.setdefault('losses_ts', []).append(t)
 
