@@ -216,6 +216,40 @@ class GradOut(object):
         return None
 
 
+def param_grads(weight, bias, need_w, need_b, wgrad, bias_sum, fused=True):
+    """The parameter-gradient tail of a conv / dense backward -> (gw, gb) as backward returns them.  ``wgrad(gw, gb)`` issues the
+    weight-gradient launch into ``gw``.  ``fused``: its kernel writes the bias gradient too (``gb`` None: not wanted); otherwise
+    it gets ``gb`` None and ``bias_sum(gb)`` follows it.  ``bias_sum(gb)`` alone when only the bias gradient is wanted (the weight
+    under skip_param_grads).  Both sinks exist before the first launch; the weight is finished first, then the bias: the order
+    the data-parallel reducer's listeners see."""
+    gw = gb = None
+    if need_w or need_b:
+        ow = GradOut(weight) if need_w else None
+        ob = GradOut(bias) if need_b else None
+        if need_w:
+            wgrad(ow.buf, ob.buf if need_b and fused else None)
+        if need_b and not (need_w and fused):
+            bias_sum(ob.buf)
+        gw = ow.finish() if need_w else None
+        gb = ob.finish() if need_b else None
+    return gw, gb
+
+
+def conv_bias_grad(gy, gb, d):
+    """gb = the sum of gy over images and pixels: the bias gradient of the conv ``d`` as a launch of its own"""
+    wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
+    _call('sg_channel_sum', _p(gy), _p(gb), d.N, d.Cout, d.OH * d.OW, _p(workspace(wsb, gy.device)), wsb, _stream())
+
+
+def act_bwd(y, gy, act, slope, stream):
+    """``gy`` taken through the activation ``act`` whose output is ``y`` (ACT_NONE: ``gy`` itself)"""
+    if act == ACT_NONE:
+        return gy
+    g = torch.empty_like(gy)
+    _call('sg_act_bwd', _p(y), _p(gy), _p(g), gy.numel(), act, slope, stream)
+    return g
+
+
 # =============================================================================================
 # convolution family
 # =============================================================================================
@@ -238,6 +272,11 @@ def _conv_desc(N, C1, C2, H, W, Cout, KS, stride, pad, reflect, upsample, OH, OW
         d._memo = {}
         _desc_cache[key] = d
     return d
+
+
+def reflect3x3_desc(N, C, H, W, Cout):
+    """the desc of ReflectionPad2d(1) + Conv2d(3, stride 1): a ResnetBlock conv"""
+    return _conv_desc(N, C, 0, H, W, Cout, 3, 1, 1, True, 1, H, W, 0, 0)
 
 
 def _q(d, name, *extra):
@@ -344,11 +383,6 @@ def carry_hints(src, dst, grad_from=False):
     if h:
         set_hints(dst, **{k: v for k, v in h.items() if k != 'pending' and (k != 'grad_from' or grad_from)})
     return dst
-
-
-def detach_keep(t):
-    """``t.detach()``: the hints follow the storage (kept for callers of the round-1 API)"""
-    return t.detach()
 
 
 def ensure_dense(t):

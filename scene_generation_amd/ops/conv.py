@@ -1,14 +1,58 @@
 """Convolution family: nn.Conv2d / nn.ConvTranspose2d / the sub-pixel form of Interpolate(x2)+Conv3x3 / nn.Linear as autograd
 Functions over the implicit-GEMM, Winograd, head and skinny kernels.
+
+Which kernels a Conv2dFn runs is one value, conv_route(): generic implicit GEMM, channel-sparse, or one of four special kernels
+(Winograd F(.,3x3), Winograd F(2x2,4x4), the one-channel head, the small-M 7x7) whose shape predicates are disjoint.  The forward
+stores it and the forward, the data gradient and the weight gradient dispatch on it.  The parameter-gradient tail of a backward
+(gradient sinks, weight-gradient launch, fused or separate bias gradient, finish) is _core.param_grads; ConvInstNormFn alone
+keeps its own, because its bias gradient comes out of the data-gradient launch.
 (Part of scene_generation_amd.ops: see ops/__init__.py.)"""
 
 import torch
 from torch.autograd import Function
 
+from .. import _hip
 from . import _core
-from ._core import (ACT_NONE, GradOut, _L, _al16, _call, _conv_desc, _f32, _p, _q, _stream, _wants_grad, conv_out_size,
-    ensure_dense, hints_of, scale_, workspace)
+from ._core import (ACT_NONE, GradOut, _L, _al16, _call, _conv_desc, _f32, _p, _q, _stream, _wants_grad, act_bwd, conv_bias_grad,
+    conv_out_size, ensure_dense, hints_of, param_grads, reflect3x3_desc, scale_, workspace)
 from .layout import (factored_layout_conv)
+
+# the kernel route of a Conv2dFn (conv_route)
+ROUTE_GENERIC, ROUTE_SPARSE, ROUTE_WINO, ROUTE_WINO24, ROUTE_HEAD, ROUTE_SMALLM = range(6)
+# the special routes: (its switch in _core, the library's shape predicate, weight-gradient entry point, workspace query).  No order
+# among them: the four predicates are disjoint by construction (k7 reflect 3 with Cout <= 4 / k3 / one output channel with k 1, 3
+# or 4 and zero pad / k4, the Winograd ones with C1 and Cout multiples of 128), which
+# tests/test_conv_route_cpu.py::test_special_route_predicates_are_disjoint sweeps.  None of the weight-gradient kernels writes the
+# bias gradient: a separate sg_channel_sum in the same workspace does.
+_SPECIAL = {
+    ROUTE_SMALLM: (None, 'sg_conv2d_smallm_supported', 'sg_conv2d_smallm_wgrad', 'sg_conv2d_smallm_ws_bytes'),
+    ROUTE_WINO: ('WINOGRAD', 'sg_conv2d_wino_supported', 'sg_conv2d_wino_wgrad', 'sg_conv2d_wino_ws_bytes'),
+    ROUTE_HEAD: ('HEADCONV', 'sg_conv2d_head_supported', 'sg_conv2d_head_wgrad', 'sg_conv2d_head_ws_bytes'),
+    ROUTE_WINO24: ('WINOGRAD24', 'sg_conv2d_wino24_supported', 'sg_conv2d_wino24_wgrad', 'sg_conv2d_wino24_ws_bytes')}
+
+
+def conv_route(d, two_source, sparse):
+    """The kernel route of the conv ``d``: a function of the desc, of whether it has a second source / a sparse channel list, and
+    of the switches WINOGRAD, WINOGRAD24 and HEADCONV.  Memoised on the desc; the switches and the library's option generation
+    are part of the key (the predicates depend on run-time options)."""
+    key = ('route', _hip.OPTION_GENERATION, _core.WINOGRAD, _core.WINOGRAD24, _core.HEADCONV, two_source, sparse)
+    route = d._memo.get(key)
+    if route is None:
+        route = ROUTE_SPARSE if sparse else ROUTE_GENERIC
+        if not (two_source or sparse):
+            for r, (switch, supported, _, _) in _SPECIAL.items():
+                if (switch is None or getattr(_core, switch)) and _q(d, supported):
+                    route = r
+                    break
+        d._memo[key] = route
+    return route
+
+
+def _kept(d, floats_query, keep, dev):
+    """the buffer of a Winograd operand that a launch saves for a later one: ``floats_query`` floats, None when the operand is not
+    wanted (``keep``) or the desc's plan saves none (the query answers 0)"""
+    n = _q(d, floats_query) if keep else 0
+    return torch.empty(n, dtype=torch.float32, device=dev) if n else None
 
 
 class Conv2dFn(Function):
@@ -29,37 +73,30 @@ class Conv2dFn(Function):
         bcast = 1 if (x2 is not None and x2.dim() == 2) else 0      # [N, C2] broadcast over H x W
         d = _conv_desc(N, C1, C2, H, W, Cout, KS, stride, pad, reflect, upsample, OH, OW, 0, bcast)
         y = torch.empty(N, Cout, OH, OW, dtype=torch.float32, device=x1.device)
-        ctx.smallm = x2 is None and sparse is None and bool(_q(d, 'sg_conv2d_smallm_supported'))
-        ctx.wino = (x2 is None and sparse is None and _core.WINOGRAD and bool(_q(d, 'sg_conv2d_wino_supported')))
-        if ctx.wino:                  # (float4 operand loads: a view that starts mid-vector is copied, see _al16)
-            x1, weight = _al16(x1), _al16(weight)
-        ctx.head = (x2 is None and sparse is None and _core.HEADCONV and not ctx.wino and not ctx.smallm
-                    and bool(_q(d, 'sg_conv2d_head_supported')))
-        ctx.wino24 = (x2 is None and sparse is None and _core.WINOGRAD24 and not ctx.head and not ctx.smallm
-                      and bool(_q(d, 'sg_conv2d_wino24_supported')))
-        if ctx.wino24:              # stride-1 4x4 convs of the PatchGANs: Winograd F(2x2,4x4), 25 batched dense GEMMs
+        route = ctx.route = conv_route(d, x2 is not None, sparse is not None)
+        ctx.kept_ut = ctx.kept_v = None      # the Winograd operands this forward saves for its backward (ROUTE_WINO)
+        if route == ROUTE_WINO24:     # stride-1 4x4 convs of the PatchGANs: Winograd F(2x2,4x4), 25 batched dense GEMMs
             wsb = _q(d, 'sg_conv2d_wino24_ws_bytes')
             _call('sg_conv2d_wino24_fwd', d._ref, _p(x1), _p(weight), _p(bias), _p(y), act, slope,
                   _p(workspace(wsb, x1.device)), wsb, _stream())
-        elif ctx.head:                # one output channel (PatchGAN score maps, mask_net's 1x1 head): vector-ALU reduction
+        elif route == ROUTE_HEAD:     # one output channel (PatchGAN score maps, mask_net's 1x1 head): vector-ALU reduction
             wsb = _q(d, 'sg_conv2d_head_ws_bytes')
             _call('sg_conv2d_head_fwd', d._ref, _p(x1), _p(weight), _p(bias), _p(y), act, slope,
                   _p(workspace(wsb, x1.device)), wsb, _stream())
-        elif ctx.wino:              # ResnetBlock convs: Winograd F(2x2,3x3), 16 batched dense GEMMs
+        elif route == ROUTE_WINO:     # ResnetBlock convs: Winograd F(2x2,3x3), 16 batched dense GEMMs
+            x1, weight = _al16(x1), _al16(weight)   # (float4 operand loads: a view that starts mid-vector is copied, see _al16)
             wsb = _q(d, 'sg_conv2d_wino_ws_bytes')
             # the data gradient of the same conv multiplies with the transposed filter transform: build it now, in the same
             # pass over the weights (they do not change between this forward and its backward)
-            utn = _q(d, 'sg_conv2d_wino_ut_floats') if ctx.needs_input_grad[0] else 0
-            ctx.wino_ut = torch.empty(utn, dtype=torch.float32, device=x1.device) if utn else None
+            ctx.kept_ut = _kept(d, 'sg_conv2d_wino_ut_floats', ctx.needs_input_grad[0], x1.device)
             # ... and the weight gradient multiplies with the input transform this forward builds anyway: keep it (33.5 MB per
             # ResnetBlock conv at the benchmark shape) instead of transforming x a second time in the backward
-            vn = _q(d, 'sg_conv2d_wino_v_floats') if (ctx.needs_input_grad[0] and ctx.needs_input_grad[2]) else 0
-            ctx.wino_v = torch.empty(vn, dtype=torch.float32, device=x1.device) if vn else None
-            _call('sg_conv2d_wino_fwd', d._ref, _p(x1), _p(weight), _p(bias), _p(y), act, slope, _p(ctx.wino_ut),
-                  _p(ctx.wino_v), _p(workspace(wsb, x1.device)), wsb, _stream())
-        elif ctx.smallm:              # <= 4 output channels (the RGB head): direct vector-ALU kernel, no MFMA tile waste
+            ctx.kept_v = _kept(d, 'sg_conv2d_wino_v_floats', ctx.needs_input_grad[0] and ctx.needs_input_grad[2], x1.device)
+            _call('sg_conv2d_wino_fwd', d._ref, _p(x1), _p(weight), _p(bias), _p(y), act, slope, _p(ctx.kept_ut),
+                  _p(ctx.kept_v), _p(workspace(wsb, x1.device)), wsb, _stream())
+        elif route == ROUTE_SMALLM:   # <= 4 output channels (the RGB head): direct vector-ALU kernel, no MFMA tile waste
             _call('sg_conv2d_smallm_fwd', d._ref, _p(x1), _p(weight), _p(bias), _p(y), act, slope, _stream())
-        elif sparse is not None:    # (chan_list [N, L] int32, chan_cnt [N] int32): see sg_conv2d_fwd_sparse
+        elif route == ROUTE_SPARSE:   # (chan_list [N, L] int32, chan_cnt [N] int32): see sg_conv2d_fwd_sparse
             clist, ccnt = sparse
             assert clist.dtype == torch.int32 and ccnt.dtype == torch.int32 and clist.size(0) == N == ccnt.numel()
             L = int(clist.size(1))
@@ -88,19 +125,17 @@ class Conv2dFn(Function):
         d = ctx.desc
         act, slope, has_bias, grad_from = ctx.cfg
         gy = _f32(gy)
-        if ctx.wino:
+        route = ctx.route
+        if route == ROUTE_WINO:
             gy = _al16(gy)
         s = _stream()
-        if act != ACT_NONE:
-            g2 = torch.empty_like(gy)
-            _call('sg_act_bwd', _p(y), _p(gy), _p(g2), gy.numel(), act, slope, s)
-            gy = g2
+        gy = act_bwd(y, gy, act, slope, s)
         need_x1, need_x2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and x2 is not None
         need_w = ctx.needs_input_grad[2] and _wants_grad(weight)
         need_b = has_bias and ctx.needs_input_grad[3] and _wants_grad(ctx.bias_ref)
-        gx1 = gx2 = gw = gb = None
+        gx1 = gx2 = None
         dev = gy.device
-        wino_keep = {'ytp': None}
+        ytp = None       # ROUTE_WINO: the gradient transform its data gradient keeps for its weight gradient
         if need_x1 or need_x2:
             wsb = _q(d, 'sg_conv2d_ws_bytes', 1)
             ws = workspace(wsb, dev)
@@ -111,23 +146,21 @@ class Conv2dFn(Function):
             folded = x2 is None and _q(d, 'sg_conv2d_dgrad_folded_supported')
 
             def dgrad(c0, c1):
-                if ctx.head and c0 == 0 and c1 == d.C1:
+                nonlocal ytp
+                # a special route's own data gradient covers the full channel range only (under a grad_from hint: the generic ones)
+                if route in (ROUTE_HEAD, ROUTE_WINO24, ROUTE_WINO) and c0 == 0 and c1 == d.C1:
                     out = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev)
-                    _call('sg_conv2d_head_dgrad', d._ref, _p(gy), _p(weight), _p(out), s)
-                    return out
-                if ctx.wino24 and c0 == 0 and c1 == d.C1:   # Winograd F(2x2,4x4) on gy with the rotated, transposed filter
-                    out = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev)
-                    fb = _q(d, 'sg_conv2d_wino24_ws_bytes')
-                    _call('sg_conv2d_wino24_dgrad', d._ref, _p(gy), _p(weight), _p(out), _p(workspace(fb, dev)), fb, s)
-                    return out
-                if ctx.wino and c0 == 0 and c1 == d.C1:     # Winograd on the padded gradient grid + reflection fold
-                    out = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev)
-                    fb = _q(d, 'sg_conv2d_wino_ws_bytes')
-                    # the gradient transform is the other operand of this conv's weight gradient: keep it when that follows
-                    yn = _q(d, 'sg_conv2d_wino_ytp_floats') if (need_w and getattr(ctx, 'wino_v', None) is not None) else 0
-                    wino_keep['ytp'] = torch.empty(yn, dtype=torch.float32, device=dev) if yn else None
-                    _call('sg_conv2d_wino_dgrad', d._ref, _p(gy), _p(weight), _p(out), _p(getattr(ctx, 'wino_ut', None)),
-                          _p(wino_keep['ytp']), _p(workspace(fb, dev)), fb, s)
+                    if route == ROUTE_HEAD:
+                        _call('sg_conv2d_head_dgrad', d._ref, _p(gy), _p(weight), _p(out), s)
+                    elif route == ROUTE_WINO24:         # Winograd F(2x2,4x4) on gy with the rotated, transposed filter
+                        fb = _q(d, 'sg_conv2d_wino24_ws_bytes')
+                        _call('sg_conv2d_wino24_dgrad', d._ref, _p(gy), _p(weight), _p(out), _p(workspace(fb, dev)), fb, s)
+                    else:                               # Winograd on the padded gradient grid + reflection fold
+                        fb = _q(d, 'sg_conv2d_wino_ws_bytes')
+                        # the gradient transform is the other operand of this conv's weight gradient: keep it when that follows
+                        ytp = _kept(d, 'sg_conv2d_wino_ytp_floats', need_w and ctx.kept_v is not None, dev)
+                        _call('sg_conv2d_wino_dgrad', d._ref, _p(gy), _p(weight), _p(out), _p(ctx.kept_ut), _p(ytp),
+                              _p(workspace(fb, dev)), fb, s)
                     return out
                 if folded:       # ReflectionPad(1)+3x3: gradient straight on the H x W grid (no padded grid, no fold pass)
                     out = torch.empty(d.N, c1 - c0, d.H, d.W, dtype=torch.float32, device=dev)
@@ -155,56 +188,36 @@ class Conv2dFn(Function):
                     red = torch.empty(d.N, d.C2, dtype=torch.float32, device=dev)
                     _call('sg_gap_fwd', _p(gx2), _p(red), d.N * d.C2, d.H * d.W, s)
                     gx2 = scale_(red, float(d.H * d.W))
+        gw = gb = None
         if need_w or need_b:
-            ow = GradOut(weight) if need_w else None
-            ob = GradOut(ctx.bias_ref) if need_b else None
-            if need_w:
-                gw = ow.buf
-                gb = ob.buf if need_b else None
-                if ctx.wino24:
-                    wsb = max(_q(d, 'sg_conv2d_wino24_ws_bytes'), _L().sg_channel_sum_ws_bytes(d.Cout))
-                    ws = workspace(wsb, dev)
-                    _call('sg_conv2d_wino24_wgrad', d._ref, _p(gy), _p(x1), _p(gw), _p(ws), wsb, s)
-                    if gb is not None:
-                        _call('sg_channel_sum', _p(gy), _p(gb), d.N, d.Cout, d.OH * d.OW, _p(ws), wsb, s)
-                elif ctx.head:
-                    wsb = max(_q(d, 'sg_conv2d_head_ws_bytes'), _L().sg_channel_sum_ws_bytes(d.Cout))
-                    ws = workspace(wsb, dev)
-                    _call('sg_conv2d_head_wgrad', d._ref, _p(gy), _p(x1), _p(gw), _p(ws), wsb, s)
-                    if gb is not None:
-                        _call('sg_channel_sum', _p(gy), _p(gb), d.N, d.Cout, d.OH * d.OW, _p(ws), wsb, s)
-                elif ctx.wino:
-                    wsb = max(_q(d, 'sg_conv2d_wino_ws_bytes'), _L().sg_channel_sum_ws_bytes(d.Cout))
-                    ws = workspace(wsb, dev)
-                    ytp = wino_keep['ytp']
+            special = _SPECIAL.get(route)
+            if not need_w:
+                wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
+            elif special:                   # one workspace request for the weight gradient and the channel sum after it
+                wsb = max(_q(d, special[3]), _L().sg_channel_sum_ws_bytes(d.Cout))
+            elif route == ROUTE_SPARSE:
+                clist, ccnt = ctx.sparse
+                L = int(clist.size(1))
+                wsb = _q(d, 'sg_conv2d_sparse_ws_bytes', L, 2)
+            else:
+                wsb = _q(d, 'sg_conv2d_ws_bytes', 2)
+            ws = workspace(wsb, dev)
+
+            def wgrad(gw, gb):
+                if route == ROUTE_WINO:     # the saved input transform is passed only next to the kept gradient transform
                     _call('sg_conv2d_wino_wgrad', d._ref, _p(gy), _p(x1), _p(gw),
-                          _p(ctx.wino_v) if ytp is not None else None, _p(ytp), _p(ws), wsb, s)
-                    if gb is not None:
-                        _call('sg_channel_sum', _p(gy), _p(gb), d.N, d.Cout, d.OH * d.OW, _p(ws), wsb, s)
-                elif ctx.smallm:
-                    wsb = max(_q(d, 'sg_conv2d_smallm_ws_bytes'), _L().sg_channel_sum_ws_bytes(d.Cout))
-                    ws = workspace(wsb, dev)
-                    _call('sg_conv2d_smallm_wgrad', d._ref, _p(gy), _p(x1), _p(gw), _p(ws), wsb, s)
-                    if gb is not None:
-                        _call('sg_channel_sum', _p(gy), _p(gb), d.N, d.Cout, d.OH * d.OW, _p(ws), wsb, s)
-                elif ctx.sparse is not None:
-                    clist, ccnt = ctx.sparse
-                    L = int(clist.size(1))
-                    wsb = _q(d, 'sg_conv2d_sparse_ws_bytes', L, 2)
-                    ws = workspace(wsb, dev)
+                          _p(ctx.kept_v) if ytp is not None else None, _p(ytp), _p(ws), wsb, s)
+                elif special:
+                    _call(special[2], d._ref, _p(gy), _p(x1), _p(gw), _p(ws), wsb, s)
+                elif route == ROUTE_SPARSE:
                     _call('sg_conv2d_wgrad_sparse', d._ref, _p(gy), _p(x1), _p(x2), _p(clist), _p(ccnt), L,
                           _p(gw), _p(gb), _p(ws), wsb, s)
                 else:
-                    wsb = _q(d, 'sg_conv2d_ws_bytes', 2)
-                    ws = workspace(wsb, dev)
                     _call('sg_conv2d_wgrad', d._ref, _p(gy), _p(x1), _p(x2), _p(gw), _p(gb), _p(ws), wsb, s)
-            else:
-                gb = ob.buf
-                wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
-                ws = workspace(wsb, dev)
+
+            def bias_sum(gb):
                 _call('sg_channel_sum', _p(gy), _p(gb), d.N, d.Cout, d.OH * d.OW, _p(ws), wsb, s)
-            gw = ow.finish() if need_w else None
-            gb = ob.finish() if need_b else None
+            gw, gb = param_grads(weight, ctx.bias_ref, need_w, need_b, wgrad, bias_sum, fused=special is None)
         return gx1, gx2, gw, gb, None, None, None, None, None, None, None, None
 
 
@@ -221,24 +234,21 @@ class ConvInstNormFn(Function):
         skip = None if skip is None else _al16(_f32(skip))
         N, C, H, W = x.shape
         Cout = weight.size(0)
-        d = _conv_desc(N, C, 0, H, W, Cout, 3, 1, 1, True, 1, H, W, 0, 0)
+        d = reflect3x3_desc(N, C, H, W, Cout)
         dev = x.device
         ypre = torch.empty(N, Cout, H, W, dtype=torch.float32, device=dev)
         out = torch.empty_like(ypre)
         mean = torch.empty(N * Cout, dtype=torch.float32, device=dev)
         rstd = torch.empty_like(mean)
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        utn = _q(d, 'sg_conv2d_wino_ut_floats') if need_x else 0
-        ut = torch.empty(utn, dtype=torch.float32, device=dev) if utn else None
-        vn = _q(d, 'sg_conv2d_wino_v_floats') if need_w else 0
-        v = torch.empty(vn, dtype=torch.float32, device=dev) if vn else None
+        ut = _kept(d, 'sg_conv2d_wino_ut_floats', ctx.needs_input_grad[0], dev)
+        v = _kept(d, 'sg_conv2d_wino_v_floats', ctx.needs_input_grad[1], dev)
         wsb = _q(d, 'sg_conv2d_wino_ws_bytes')
         _call('sg_conv2d_wino_fwd_instnorm', d._ref, _p(x), _p(weight), _p(bias), _p(skip), _p(ypre), _p(out), _p(mean), _p(rstd),
               eps, act, slope, _p(ut), _p(v), _p(workspace(wsb, dev)), wsb, _stream())
         ctx.desc = d
         ctx.bias_ref = bias
         ctx.cfg = (act, slope, bias is not None, skip is not None)
-        ctx.wino_ut, ctx.wino_v = ut, v
+        ctx.kept_ut, ctx.kept_v = ut, v
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, weight, ypre, mean, rstd)
         return out
@@ -258,20 +268,19 @@ class ConvInstNormFn(Function):
         need_b = has_bias and ctx.needs_input_grad[2] and _wants_grad(ctx.bias_ref)
         gconv = torch.empty_like(ypre)
         gx = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev) if need_x else None
-        yn = _q(d, 'sg_conv2d_wino_ytp_floats') if (need_w and ctx.wino_v is not None) else 0
-        ytp = torch.empty(yn, dtype=torch.float32, device=dev) if yn else None
+        ytp = _kept(d, 'sg_conv2d_wino_ytp_floats', need_w and ctx.kept_v is not None, dev)
         wsb = _q(d, 'sg_conv2d_wino_ws_bytes')
         # the bias gradient comes out of the same launch (per-image plane sums of the conv's gy + one small launch over the images)
         ob = GradOut(ctx.bias_ref) if need_b else None
         _call('sg_conv2d_wino_dgrad_instnorm', d._ref, _p(gout), _p(ypre), _p(mean), _p(rstd), act, slope, _p(weight), _p(gconv),
-              _p(gx), _p(ob.buf) if need_b else None, _p(ctx.wino_ut), _p(ytp), _p(workspace(wsb, dev)), wsb, s)
+              _p(gx), _p(ob.buf) if need_b else None, _p(ctx.kept_ut), _p(ytp), _p(workspace(wsb, dev)), wsb, s)
         gw = gb = None
         if need_w or need_b:
             ow = GradOut(weight) if need_w else None
             wsb2 = max(wsb, _L().sg_channel_sum_ws_bytes(d.Cout))
             ws = workspace(wsb2, dev)
             if need_w:
-                _call('sg_conv2d_wino_wgrad', d._ref, _p(gconv), _p(x), _p(ow.buf), _p(ctx.wino_v) if ytp is not None else None,
+                _call('sg_conv2d_wino_wgrad', d._ref, _p(gconv), _p(x), _p(ow.buf), _p(ctx.kept_v) if ytp is not None else None,
                       _p(ytp), _p(ws), wsb2, s)
             gw = ow.finish() if need_w else None
             gb = ob.finish() if need_b else None
@@ -284,8 +293,7 @@ def conv_instnorm_fusable(x, weight, reflect_pad, stride, pad):
             and weight.size(2) == 3 and weight.size(3) == 3 and weight.size(1) == x.size(1)):
         return False
     N, C, H, W = x.shape
-    d = _conv_desc(N, C, 0, H, W, weight.size(0), 3, 1, 1, True, 1, H, W, 0, 0)
-    return bool(_q(d, 'sg_conv2d_wino_in_supported'))
+    return bool(_q(reflect3x3_desc(N, C, H, W, weight.size(0)), 'sg_conv2d_wino_in_supported'))
 
 
 def conv2d_instnorm(x, weight, bias, skip=None, eps=1e-5, act=ACT_NONE, slope=0.0):
@@ -302,7 +310,7 @@ class Conv3x3ReflectBf16Fn(Function):
         x = _f32(x, 'conv input')
         weight = _f32(weight, 'conv weight')
         N, C, H, W = x.shape
-        d = _conv_desc(N, C, 0, H, W, weight.size(0), 3, 1, 1, True, 1, H, W, 0, 0)
+        d = reflect3x3_desc(N, C, H, W, weight.size(0))
         if not _q(d, 'sg_conv3x3r_bf16_supported'):
             raise ValueError('bf16 trunk conv: unsupported shape x %s, weight %s' % (tuple(x.shape), tuple(weight.shape)))
         y = torch.empty(N, d.Cout, H, W, dtype=torch.float32, device=x.device)
@@ -327,22 +335,14 @@ class Conv3x3ReflectBf16Fn(Function):
         wsb = _q(d, 'sg_conv3x3r_bf16_ws_bytes')
         need_w = ctx.needs_input_grad[1] and _wants_grad(weight)
         need_b = ctx.bias_ref is not None and ctx.needs_input_grad[2] and _wants_grad(ctx.bias_ref)
-        gx = gw = gb = None
+        gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev)
             _call('sg_conv3x3r_bf16_dgrad', d._ref, _p(gy), _p(weight), _p(gx), _p(workspace(wsb, dev)), wsb, s)
-        if need_w:
-            ow = GradOut(weight)
-            ob = GradOut(ctx.bias_ref) if need_b else None
-            _call('sg_conv3x3r_bf16_wgrad', d._ref, _p(gy), _p(x), _p(ow.buf), _p(ob.buf) if need_b else None,
-                  _p(workspace(wsb, dev)), wsb, s)
-            gw = ow.finish()
-            gb = ob.finish() if need_b else None
-        elif need_b:
-            ob = GradOut(ctx.bias_ref)
-            csb = _L().sg_channel_sum_ws_bytes(d.Cout)
-            _call('sg_channel_sum', _p(gy), _p(ob.buf), d.N, d.Cout, d.H * d.W, _p(workspace(csb, dev)), csb, s)
-            gb = ob.finish()
+
+        def wgrad(gw, gb):
+            _call('sg_conv3x3r_bf16_wgrad', d._ref, _p(gy), _p(x), _p(gw), _p(gb), _p(workspace(wsb, dev)), wsb, s)
+        gw, gb = param_grads(weight, ctx.bias_ref, need_w, need_b, wgrad, lambda gb: conv_bias_grad(gy, gb, d))
         return gx, gw, gb
 
 
@@ -352,8 +352,7 @@ def conv3x3_reflect_bf16_supported(x, weight):
             and weight.size(1) == x.size(1)):
         return False
     N, C, H, W = x.shape
-    d = _conv_desc(N, C, 0, H, W, weight.size(0), 3, 1, 1, True, 1, H, W, 0, 0)
-    return bool(_q(d, 'sg_conv3x3r_bf16_supported'))
+    return bool(_q(reflect3x3_desc(N, C, H, W, weight.size(0)), 'sg_conv3x3r_bf16_supported'))
 
 
 def conv3x3_reflect_bf16(x, weight, bias=None):
@@ -410,14 +409,11 @@ class CondConv2dFn(Function):
         act, slope, has_bias = ctx.cfg
         gy = _f32(gy)
         dev, s = gy.device, _stream()
-        if act != ACT_NONE:
-            g2 = torch.empty_like(gy)
-            _call('sg_act_bwd', _p(y), _p(gy), _p(g2), gy.numel(), act, slope, s)
-            gy = g2
+        gy = act_bwd(y, gy, act, slope, s)
         need_x1, need_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_w = ctx.needs_input_grad[2] and _wants_grad(ctx.weight_ref)
         need_b = has_bias and ctx.needs_input_grad[3] and _wants_grad(ctx.bias_ref)
-        gx1 = gc = gw = gb = None
+        gx1 = gc = None
         if need_x1:
             gx1 = torch.empty(d.N, d.C1, d.H, d.W, dtype=torch.float32, device=dev)
             wsb = _q(d, 'sg_conv2d_ws_bytes', 1)
@@ -429,21 +425,14 @@ class CondConv2dFn(Function):
         if need_c:
             gc = torch.empty_like(cond)
             _call('sg_linear_bwd_data', _p(gproj), _p(w2r), _p(gc), d.N, C2, d.Cout * R, s)
-        if need_w or need_b:
-            ow = GradOut(ctx.weight_ref) if need_w else None
-            ob = GradOut(ctx.bias_ref) if need_b else None
-            if need_w:
-                gw1, gw2r = torch.empty_like(w1), torch.empty_like(w2r)
-                wsb = _q(d, 'sg_conv2d_ws_bytes', 2)
-                _call('sg_conv2d_wgrad', d._ref, _p(gy), _p(x1), None, _p(gw1), _p(ob.buf) if need_b else None,
-                      _p(workspace(wsb, dev)), wsb, s)
-                _call('sg_linear_bwd_weight', _p(gproj), _p(cond), _p(gw2r), None, d.N, C2, d.Cout * R, s)
-                _call('sg_cond_conv_merge_w', _p(gw1), _p(gw2r), _p(ow.buf), d.Cout, d.C1, C2, R, s)
-            else:
-                wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
-                _call('sg_channel_sum', _p(gy), _p(ob.buf), d.N, d.Cout, d.OH * d.OW, _p(workspace(wsb, dev)), wsb, s)
-            gw = ow.finish() if need_w else None
-            gb = ob.finish() if need_b else None
+
+        def wgrad(gw, gb):          # dW1 (with the bias gradient) and dW2, interleaved into the parameter's gradient
+            gw1, gw2r = torch.empty_like(w1), torch.empty_like(w2r)
+            wsb = _q(d, 'sg_conv2d_ws_bytes', 2)
+            _call('sg_conv2d_wgrad', d._ref, _p(gy), _p(x1), None, _p(gw1), _p(gb), _p(workspace(wsb, dev)), wsb, s)
+            _call('sg_linear_bwd_weight', _p(gproj), _p(cond), _p(gw2r), None, d.N, C2, d.Cout * R, s)
+            _call('sg_cond_conv_merge_w', _p(gw1), _p(gw2r), _p(gw), d.Cout, d.C1, C2, R, s)
+        gw, gb = param_grads(ctx.weight_ref, ctx.bias_ref, need_w, need_b, wgrad, lambda gb: conv_bias_grad(gy, gb, d))
         return gx1, gc, gw, gb, None, None, None, None
 
 
@@ -532,7 +521,7 @@ class ConvTranspose2dFn(Function):
         d = ctx.desc
         gy = _f32(gy)
         s = _stream()
-        gx = gw = gb = None
+        gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             wsb = _q(d, 'sg_conv2d_ws_bytes', 1)
@@ -540,18 +529,11 @@ class ConvTranspose2dFn(Function):
             _call('sg_convT2d_dgrad', d._ref, _p(gy), _p(weight), _p(gx), _p(ws), wsb, s)
         need_w = ctx.needs_input_grad[1] and _wants_grad(weight)
         need_b = ctx.bias_ref is not None and ctx.needs_input_grad[2] and _wants_grad(ctx.bias_ref)
-        ow = GradOut(weight) if need_w else None
-        ob = GradOut(ctx.bias_ref) if need_b else None
-        if need_w:
+
+        def wgrad(gw, gb):
             wsb = _q(d, 'sg_conv2d_ws_bytes', 2)
-            ws = workspace(wsb, gy.device)
-            _call('sg_convT2d_wgrad', d._ref, _p(gy), _p(x), _p(ow.buf), _p(ob.buf) if need_b else None, _p(ws), wsb, s)
-        elif need_b:
-            wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
-            ws = workspace(wsb, gy.device)
-            _call('sg_channel_sum', _p(gy), _p(ob.buf), d.N, d.Cout, d.OH * d.OW, _p(ws), wsb, s)
-        gw = ow.finish() if need_w else None
-        gb = ob.finish() if need_b else None
+            _call('sg_convT2d_wgrad', d._ref, _p(gy), _p(x), _p(gw), _p(gb), _p(workspace(wsb, gy.device)), wsb, s)
+        gw, gb = param_grads(weight, ctx.bias_ref, need_w, need_b, wgrad, lambda gb: conv_bias_grad(gy, gb, d))
         return gx, gw, gb, None, None, None
 
 
@@ -598,26 +580,20 @@ class UpConv3Fn(Function):
         d, weight = ctx.desc, ctx.weight_ref
         gy = _f32(gy)
         s, dev = _stream(), gy.device
-        gx = gw = gb = None
+        gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             wsb = _q(d, 'sg_conv2d_ws_bytes', 1)
             _call('sg_convT2d_dgrad', d._ref, _p(gy), _p(wt), _p(gx), _p(workspace(wsb, dev)), wsb, s)
         need_w = ctx.needs_input_grad[1] and _wants_grad(weight)
         need_b = ctx.bias_ref is not None and ctx.needs_input_grad[2] and _wants_grad(ctx.bias_ref)
-        ow = GradOut(weight) if need_w else None
-        ob = GradOut(ctx.bias_ref) if need_b else None
-        if need_w:
+
+        def wgrad(gw, gb):          # the transposed conv's weight gradient, then the adjoint of the fold
             gwt = torch.empty_like(wt)
             wsb = _q(d, 'sg_conv2d_ws_bytes', 2)
-            _call('sg_convT2d_wgrad', d._ref, _p(gy), _p(x), _p(gwt), _p(ob.buf) if need_b else None,
-                  _p(workspace(wsb, dev)), wsb, s)
-            _call('sg_upconv3_unfold_wgrad', _p(gwt), _p(ow.buf), d.Cout, d.C1, s)
-        elif need_b:
-            wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
-            _call('sg_channel_sum', _p(gy), _p(ob.buf), d.N, d.Cout, d.OH * d.OW, _p(workspace(wsb, dev)), wsb, s)
-        gw = ow.finish() if need_w else None
-        gb = ob.finish() if need_b else None
+            _call('sg_convT2d_wgrad', d._ref, _p(gy), _p(x), _p(gwt), _p(gb), _p(workspace(wsb, dev)), wsb, s)
+            _call('sg_upconv3_unfold_wgrad', _p(gwt), _p(gw), d.Cout, d.C1, s)
+        gw, gb = param_grads(weight, ctx.bias_ref, need_w, need_b, wgrad, lambda gb: conv_bias_grad(gy, gb, d))
         return gx, gw, gb
 
 
@@ -657,24 +633,17 @@ class LinearFn(Function):
         if rows == 0:
             return (torch.zeros_like(x), torch.zeros_like(weight),
                     torch.zeros(out_f, device=x.device) if has_bias else None, None, None)
-        if act != ACT_NONE:
-            g2 = torch.empty_like(gy)
-            _call('sg_act_bwd', _p(y), _p(gy), _p(g2), gy.numel(), act, slope, s)
-            gy = g2
-        gx = gw = gb = None
+        gy = act_bwd(y, gy, act, slope, s)
+        gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             _call('sg_linear_bwd_data', _p(gy), _p(weight), _p(gx), rows, in_f, out_f, s)
         need_w = ctx.needs_input_grad[1] and _wants_grad(weight)
         need_b = has_bias and ctx.needs_input_grad[2] and _wants_grad(ctx.bias_ref)
-        ow = GradOut(weight) if need_w else None
-        ob = GradOut(ctx.bias_ref) if need_b else None
-        if need_w:
-            _call('sg_linear_bwd_weight', _p(gy), _p(x), _p(ow.buf), _p(ob.buf) if need_b else None, rows, in_f, out_f, s)
-        elif need_b:
-            _call('sg_channel_sum', _p(gy), _p(ob.buf), rows, out_f, 1, None, 0, s)
-        gw = ow.finish() if need_w else None
-        gb = ob.finish() if need_b else None
+        gw, gb = param_grads(
+            weight, ctx.bias_ref, need_w, need_b,
+            lambda gw, gb: _call('sg_linear_bwd_weight', _p(gy), _p(x), _p(gw), _p(gb), rows, in_f, out_f, s),
+            lambda gb: _call('sg_channel_sum', _p(gy), _p(gb), rows, out_f, 1, None, 0, s))    # (rows of one pixel: no workspace)
         return gx, gw, gb, None, None
 
 

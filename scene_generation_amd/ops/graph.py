@@ -5,7 +5,7 @@ import torch
 from torch.autograd import Function
 
 from . import _core
-from ._core import (ACT_NONE, GradOut, _L, _call, _f32, _i64, _p, _stream, _wants_grad, workspace)
+from ._core import (ACT_NONE, GradOut, _L, _call, _f32, _i64, _p, _stream, _wants_grad, act_bwd, workspace)
 
 
 # =============================================================================================
@@ -100,10 +100,7 @@ class GatherLinearFn(Function):
         if T == 0:
             return (torch.zeros_like(obj), torch.zeros_like(pred), None, None, None, torch.zeros_like(weight),
                     torch.zeros(out_f, device=dev) if has_bias else None, None, None)
-        if act != ACT_NONE:
-            g2 = torch.empty_like(gy)
-            _call('sg_act_bwd', _p(y), _p(gy), _p(g2), gy.numel(), act, slope, s)
-            gy = g2
+        gy = act_bwd(y, gy, act, slope, s)
         need_w = ctx.needs_input_grad[5] and _wants_grad(weight)
         need_b = has_bias and ctx.needs_input_grad[6] and _wants_grad(ctx.bias_ref)
         ow = GradOut(weight) if need_w else None

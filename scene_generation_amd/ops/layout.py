@@ -6,8 +6,8 @@ import torch
 from torch.autograd import Function
 
 from . import _core
-from ._core import (ACT_NONE, GradOut, _L, _call, _conv_desc, _dev, _f32, _i64, _p, _q, _stream, _wants_grad,
-    conv_out_size, set_hints, workspace)
+from ._core import (ACT_NONE, GradOut, _L, _call, _conv_desc, _dev, _f32, _i64, _p, _q, _stream, _wants_grad, act_bwd,
+    conv_bias_grad, conv_out_size, set_hints, workspace)
 from .graph import (one_hot)
 
 
@@ -301,10 +301,7 @@ class PerImageConvFn(Function):
         act, slope, has_bias, cfull, C2, stride, pad, reflect = ctx.cfg
         gy = _f32(gy)
         s, dev = _stream(), gy.device
-        if act != ACT_NONE:
-            g2 = torch.empty_like(gy)
-            _call('sg_act_bwd', _p(y), _p(gy), _p(g2), gy.numel(), act, slope, s)
-            gy = g2
+        gy = act_bwd(y, gy, act, slope, s)
         gx2 = gwimg = gb = None
         # skip_param_grads (the discriminators inside the generator step): the per-image weights only carry parameter
         # gradients when the appearance vectors are detached, which is the case for every discriminator input
@@ -316,8 +313,7 @@ class PerImageConvFn(Function):
                   _p(workspace(wsb, dev)), wsb, s)
         if has_bias and ctx.needs_input_grad[3] and _wants_grad(ctx.bias_ref):
             ob = GradOut(ctx.bias_ref)
-            wsb = _L().sg_channel_sum_ws_bytes(d.Cout)
-            _call('sg_channel_sum', _p(gy), _p(ob.buf), d.N, d.Cout, d.OH * d.OW, _p(workspace(wsb, dev)), wsb, s)
+            conv_bias_grad(gy, ob.buf, d)
             gb = ob.finish()
         if C2 and ctx.needs_input_grad[1]:
             # same conv seen with its full channel layout [layout channels | x2]: only the x2 slice is differentiated
