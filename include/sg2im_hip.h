@@ -290,6 +290,37 @@ typedef struct sgTGatherPlan {
 } sgTGatherPlan;
 int sg_conv2d_tgather_plan(const sgConvDesc* d, int entry, int c_begin, int c_end, int ws_mod16, size_t ws_bytes,
                            sgTGatherPlan* plan);
+/* host-only query of THE launch plan of a weight-gradient GEMM (csrc/igemm_nk.hip: the launcher runs from the same function,
+ * nk_launch_plan in csrc/igemm_core.h): what sg_conv2d_wgrad, sg_conv2d_wgrad_sparse, sg_conv2d_wgrad_perimage or sg_convT2d_wgrad
+ * launches for this desc under the current options (wgrad_xcd, wgrad_rowsum, wgrad_padded).  Never touches the device.
+ *   entry    SG_WG_*: the entry point;  L: length of the channel lists (SG_WG_SPARSE / SG_WG_PERIMAGE; ignored otherwise)
+ *   a_mod16  address modulo 16 of the GEMM's A operand (gy; x for SG_WG_CONVT): 0, 4, 8 or 12
+ *   ws_bytes the workspace offered (a short one can shrink the split, drop the XCD padding, the fused bias gradient or the
+ *            padded planes).  Returns non-zero where the entry point itself would (bad desc, workspace too small, ...).
+ *   form     SG_WG_TAP: tap-major columns [tap][cpad channels] (LoadTapNK);  SG_WG_GATHER: (channel, tap) columns of a few-channel
+ *            input (LoadGatherNK);  SG_WG_PADDED: the same columns gathered from reflect-padded planes (LoadPaddedNK)
+ *   bm x bn  the tile;  cpad: channels padded to whole column tiles (0 unless SG_WG_TAP)
+ *   a_vec    1: A is read as float4 (LoadPixKVec), 0: scalar (LoadPixK)
+ *   two      1: the tap loader reads two sources;  nomask: 1: the mask-free tap loader runs
+ *   kchunk   k range (image x pixel) of one chunk;  chunks: chunks that hold pixels;  grid_z: chunks launched (after padding
+ *            with empty chunks to a multiple of 8 for XCD pinning; N x S for per-image chunks)
+ *   xcd      0: off, 1: the chunks are pinned to XCDs, 2: per-image chunks pinned to XCDs
+ *   reduce   SG_WR_*: what runs behind the GEMM: nothing (it stored the result), slab_reduce, slab_reduce_wide, the un-permuting
+ *            reduce of the tap-major slabs, the scatter of the per-image slabs through the inverse channel lists, the per-image
+ *            copy, or the reduce over the chunks of each image
+ *   rowsum_fused  1: a bias gradient asked for (gb != NULL) comes from the A loader's row sums, 0: from sg_channel_sum
+ *   ws_needed     workspace bytes the GEMM and its reduce read or write (slabs, row sums, inverse lists, padded planes) */
+enum { SG_WG_CONV = 0, SG_WG_SPARSE = 1, SG_WG_PERIMAGE = 2, SG_WG_CONVT = 3 };
+enum { SG_WG_TAP = 0, SG_WG_GATHER = 1, SG_WG_PADDED = 2 };
+enum { SG_WR_NONE = 0, SG_WR_SLAB = 1, SG_WR_WIDE = 2, SG_WR_UNPERMUTE = 3, SG_WR_SPARSE = 4, SG_WR_PERIMAGE = 5, SG_WR_GROUP = 6 };
+typedef struct sgWgradPlan {
+  int32_t form, bm, bn, cpad;
+  int32_t a_vec, two, nomask;
+  int32_t kchunk, chunks, grid_z, xcd;
+  int32_t reduce, rowsum_fused, reserved;
+  int64_t ws_needed;
+} sgWgradPlan;
+int sg_conv2d_wgrad_plan(const sgConvDesc* d, int entry, int L, int a_mod16, size_t ws_bytes, sgWgradPlan* plan);
 /* Interpolate(x2, nearest) + Conv2d(C, Cout, 3, padding=1) (mask_net, reference generators.py:20-21, layers.py:304-314) as a
  * SUB-PIXEL transposed convolution: every output pixel (2i+a, 2j+b) only sees a 2x2 neighbourhood of the stored input, with
  * the 3x3 taps that land on the same source pixel summed -- conv3x3(up2(x); w) == convT(k4, s2, p1)(x; wt) with

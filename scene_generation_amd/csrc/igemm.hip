@@ -46,6 +46,15 @@ inline size_t wgrad_ws(int M, int C, int KS2, int Kpix, bool two) {
   return (size_t)pl.splits * ((size_t)M * KS2 * (pl.tap ? pl.cpad : C) + (size_t)M) * sizeof(float);
 }
 
+// the gather a weight-gradient entry point (SG_WG_*) hands to nk_run, shared with sg_conv2d_wgrad_plan.  SG_WG_CONVT runs the GEMM
+// with the roles swapped: A = x, the gathered operand = gy, the pixel grid = the input's
+inline Gather wgrad_gather(const sgConvDesc* d, int entry, const float* s1, const float* s2) {
+  if (entry == SG_WG_CONVT) return make_gather(s1, nullptr, d->Cout, 0, d->OH, d->OW, 1, d->H, d->W, d->stride, d->pad, 0);
+  Gather g = make_gather(s1, s2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
+  g.bcast2 = d->x2_broadcast;
+  return g;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -168,8 +177,7 @@ extern "C" int sg_conv2d_wgrad(const sgConvDesc* d, const float* gy, const float
   SG_ARG_CHECK(gy && x1 && gw, "sg_conv2d_wgrad: null pointer");
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_wgrad: C2>0 but x2 null");
   hipStream_t s = (hipStream_t)stream;
-  Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
-  g.bcast2 = d->x2_broadcast;
+  const Gather g = wgrad_gather(d, SG_WG_CONV, x1, x2);
   const double flops = 2.0 * d->Cout * (double)(d->C1 + d->C2) * d->KS * d->KS * d->N * d->OH * d->OW;
   bool gb_done = false;      // the weight-gradient GEMM reads all of gy anyway: its loaders also produce the bias gradient
   if (int rc = sgk::nk_run(d->KS, gy, d->Cout, d->Cout, g, d->N, gw, ws, ws ? ws_bytes : 0, flops, s, nullptr, gb, &gb_done)) return rc;
@@ -181,10 +189,13 @@ extern "C" int sg_conv2d_wgrad(const sgConvDesc* d, const float* gy, const float
 // ConvTranspose2d: y[n,co,oh,ow] = b + sum_{ci,kh,kw} w[ci,co,kh,kw] x[n,ci,(oh+p-kh)/s,(ow+p-kw)/s]
 
 // ---- channel-sparse variants (layers fed by a masks_to_layout() layout) ---------------------------
-static int check_sparse(const sgConvDesc* d, const int32_t* list, const int32_t* cnt, int L, const char* who) {
-  SG_ARG_CHECK(list && cnt, "%s: null channel list", who);
+static int check_sparse_len(const sgConvDesc* d, int L, const char* who) {
   SG_ARG_CHECK(L > 0 && L <= d->C1 + d->C2, "%s: L=%d outside (0, %d]", who, L, d->C1 + d->C2);
   return 0;
+}
+static int check_sparse(const sgConvDesc* d, const int32_t* list, const int32_t* cnt, int L, const char* who) {
+  SG_ARG_CHECK(list && cnt, "%s: null channel list", who);
+  return check_sparse_len(d, L, who);
 }
 // what the gather routes of the sparse / per-image weight gradients need (and all they needed before the padded planes)
 static size_t sparse_wgrad_base_ws(const sgConvDesc* d, int L) {
@@ -229,8 +240,7 @@ extern "C" int sg_conv2d_wgrad_sparse(const sgConvDesc* d, const float* gy, cons
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_wgrad_sparse: C2>0 but x2 null");
   SG_ARG_CHECK(ws_bytes >= sparse_wgrad_base_ws(d, L), "sg_conv2d_wgrad_sparse: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
-  g.bcast2 = d->x2_broadcast;
+  const Gather g = wgrad_gather(d, SG_WG_SPARSE, x1, x2);
   const Sparse sp{chan_list, chan_cnt, L, nullptr, nullptr};
   if (int rc = sgk::nk_run(d->KS, gy, d->Cout, d->Cout, g, d->N, gw, ws, ws_bytes, 0.0, s, &sp)) return rc;
   SG_LAUNCH_CHECK("sg_conv2d_wgrad_sparse");
@@ -266,10 +276,9 @@ extern "C" int sg_conv2d_wgrad_perimage(const sgConvDesc* d, const float* gy, co
   const size_t base = sparse_wgrad_base_ws(d, L), pb = sparse_wgrad_padded_bytes(d, L);
   SG_ARG_CHECK(ws_bytes >= base, "sg_conv2d_wgrad_perimage: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
-  g.bcast2 = d->x2_broadcast;
+  const Gather g = wgrad_gather(d, SG_WG_PERIMAGE, x1, x2);
   Sparse sp{chan_list, chan_cnt, L, nullptr, gwimg};
-  if (pb && ws_bytes >= nk_padded_offset(base) + pb) sp.pad_off = nk_padded_offset(base);
+  sp.pad_off = nk_perimage_pad_off(base, pb, ws_bytes);
   if (int rc = sgk::nk_run(d->KS, gy, d->Cout, d->Cout, g, d->N, nullptr, ws, ws_bytes, 0.0, s, &sp)) return rc;
   SG_LAUNCH_CHECK("sg_conv2d_wgrad_perimage");
   return 0;
@@ -329,12 +338,36 @@ extern "C" int sg_convT2d_wgrad(const sgConvDesc* d, const float* gy, const floa
   SG_ARG_CHECK(gy && x && gw, "sg_convT2d_wgrad: null pointer");
   SG_ARG_CHECK(d->C2 == 0 && d->upsample == 1 && !d->pad_reflect, "sg_convT2d_wgrad: unsupported desc");
   hipStream_t s = (hipStream_t)stream;
-  Gather g = make_gather(gy, nullptr, d->Cout, 0, d->OH, d->OW, 1, d->H, d->W, d->stride, d->pad, 0);
+  const Gather g = wgrad_gather(d, SG_WG_CONVT, gy, nullptr);
   if (int rc = sgk::nk_run(d->KS, x, d->C1, d->C1, g, d->N, gw, ws, ws ? ws_bytes : 0,
                          2.0 * d->Cout * (double)d->C1 * d->KS * d->KS * d->N * d->H * d->W, s, nullptr))
     return rc;
   SG_LAUNCH_CHECK("sg_convT2d_wgrad");
   if (gb) return sg_channel_sum(gy, gb, d->N, d->Cout, d->OH * d->OW, ws, ws ? ws_bytes : 0, stream);
+  return 0;
+}
+
+// host-only: the plan nk_run launches for an entry point's call (nk_launch_plan, the function the launcher runs from)
+extern "C" int sg_conv2d_wgrad_plan(const sgConvDesc* d, int entry, int L, int a_mod16, size_t ws_bytes, sgWgradPlan* plan) {
+  SG_ARG_CHECK(d && plan && entry >= SG_WG_CONV && entry <= SG_WG_CONVT, "sg_conv2d_wgrad_plan: bad arguments");
+  SG_ARG_CHECK(a_mod16 == 0 || a_mod16 == 4 || a_mod16 == 8 || a_mod16 == 12, "sg_conv2d_wgrad_plan: a_mod16 is 0, 4, 8 or 12");
+  if (check_desc(d, "sg_conv2d_wgrad_plan")) return -1;
+  const bool sparse = entry == SG_WG_SPARSE || entry == SG_WG_PERIMAGE;
+  SG_ARG_CHECK(entry != SG_WG_CONVT || (d->C2 == 0 && d->upsample == 1 && !d->pad_reflect), "sg_conv2d_wgrad_plan: unsupported desc");
+  size_t pad_off = 0;
+  if (sparse) {
+    if (check_sparse_len(d, L, "sg_conv2d_wgrad_plan")) return -1;
+    const size_t base = sparse_wgrad_base_ws(d, L);
+    SG_ARG_CHECK(ws_bytes >= base, "sg_conv2d_wgrad_plan: workspace too small");
+    if (entry == SG_WG_PERIMAGE) pad_off = nk_perimage_pad_off(base, sparse_wgrad_padded_bytes(d, L), ws_bytes);
+  }
+  const Gather g = wgrad_gather(d, entry, nullptr, nullptr);
+  const int M = entry == SG_WG_CONVT ? d->C1 : d->Cout;
+  // (only sg_conv2d_wgrad hands its bias gradient to the GEMM)
+  const NkLaunch nl = nk_launch_plan(nk_shape(d->KS, M, M, g, d->N), sparse, sparse ? L : 0, entry == SG_WG_PERIMAGE, a_mod16 == 0,
+                                     entry == SG_WG_CONV, ws_bytes, pad_off);
+  SG_ARG_CHECK(nl.err == nullptr, "sg_conv2d_wgrad_plan: %s", nl.err);
+  *plan = nl.p;
   return 0;
 }
 

@@ -1703,7 +1703,6 @@ constexpr int NSW = SG_NSW;
 using CfgW128 = TileCfg<128, 128, 2, NSW>;
 using CfgW64 = TileCfg<64, 64, 2, NSW>;
 using CfgW32 = TileCfg<32, 128, 1, NSW>;
-using CfgW64W = TileCfg<64, 128, 2, NSW>;
 using CfgDP128 = TileCfg<128, 128, 2, 2, 1>; // ... software-pipelined fragment reads, barrier before the last phase
 using CfgDI128 = TileCfg<128, 128, 2, 2, 2>; // ... and the LDS stores of the next tile interleaved with the MFMAs of phase 0
 
@@ -1733,16 +1732,34 @@ thread_local int t_fixed_kchunk = 0;        // >0: grid.z = ceil(K / chunk) with
 thread_local int t_xcd_z = 0;               // 1: pin the k-chunks of a plain split-K launch to XCDs (weight gradients)
 thread_local int t_min_z = 0;               // >0: at least this many k-chunks (trailing ones may be empty: zero slabs)
 
+// k-chunk, grid.z and XCD pinning of a split-K launch as functions of the launch modifiers above (launch_cfg launches exactly
+// this; nk_launch_plan reports it for the weight-gradient GEMMs).  bkt: the k-tile depth of the tile configuration
+inline int splitk_chunk(int K, int splits, int bkt, int fixed_kchunk) {
+  int kchunk = K;
+  if (splits > 1) kchunk = sg_cdiv(sg_cdiv(K, splits), bkt) * bkt;
+  if (fixed_kchunk > 0) kchunk = fixed_kchunk;
+  return kchunk;
+}
+inline int splitk_grid_z(int K, int splits, int kchunk, int grid_z, int fixed_kchunk, int min_z) {
+  int z = grid_z > 0 ? grid_z : ((splits > 1 || fixed_kchunk > 0) ? sg_cdiv(K, kchunk) : 1);
+  if (min_z > 0 && z < min_z && grid_z == 0) z = min_z;
+  return z;
+}
+// xcd_mode: t_xcd_z.  plain split-K launches, and the per-image k-chunks (ksplit) of the factored stem's weight gradient
+// (grid.z = images x chunks: its column tiles re-read the same gy chunk from seven L2s -- 6.5x the algorithmic bytes in round 4)
+inline bool splitk_xcd(int xcd_mode, int grid_z, int fixed_kchunk, int ksplit, int cols_per_batch, int ncls, int z) {
+  const bool plain_z = grid_z == 0 && fixed_kchunk == 0 && ksplit == 0;
+  const bool image_z = grid_z > 0 && ksplit > 0 && xcd_mode == 2;
+  return xcd_mode && (plain_z || image_z) && cols_per_batch == 0 && ncls == 0 && z >= 8 && z % 8 == 0;
+}
+
 template <class CFG, class AL, class BL, class EP>
 int launch_cfg(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, int splits, hipStream_t s) {
   int tiles = sg_cdiv(M, CFG::BM) * sg_cdiv(N, CFG::BN);
   if (t_batch.cols_per_batch > 0) tiles = sg_cdiv(M, CFG::BM) * t_batch.nbatch * sg_cdiv(t_batch.cols_per_batch, CFG::BN);
   if (t_batch.par.ncls > 0) tiles = sg_cdiv(M, CFG::BM) * t_batch.par.tile0[t_batch.par.ncls];
-  int kchunk = K;
-  if (splits > 1) kchunk = sg_cdiv(sg_cdiv(K, splits), CFG::BKT) * CFG::BKT;
-  if (t_fixed_kchunk > 0) kchunk = t_fixed_kchunk;
-  dim3 grid(tiles, 1, t_grid_z > 0 ? t_grid_z : ((splits > 1 || t_fixed_kchunk > 0) ? sg_cdiv(K, kchunk) : 1));
-  if (t_min_z > 0 && (int)grid.z < t_min_z && t_grid_z == 0) grid.z = t_min_z;
+  const int kchunk = splitk_chunk(K, splits, CFG::BKT, t_fixed_kchunk);
+  dim3 grid(tiles, 1, splitk_grid_z(K, splits, kchunk, t_grid_z, t_fixed_kchunk, t_min_z));
   BatchInfo bi = t_batch;
   bi.prio = sg_opt(SG_OPT_WAVE_PRIO) ? 1 : 0;
   bi.par_chunk = 0;
@@ -1750,11 +1767,7 @@ int launch_cfg(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, in
     const int g = sg_opt(SG_OPT_PAR_XCD_CHUNK);
     if (bi.par.ncls > 0 && g > 0 && (g & (g - 1)) == 0) bi.par_chunk = g;
   }
-  // k-chunks pinned to XCDs: plain split-K launches, and the per-image k-chunks (ksplit) of the factored stem's weight gradient
-  // (grid.z = images x chunks: its column tiles re-read the same gy chunk from seven L2s -- 6.5x the algorithmic bytes in round 4)
-  const bool plain_z = t_grid_z == 0 && t_fixed_kchunk == 0 && bi.ksplit == 0;
-  const bool image_z = t_grid_z > 0 && bi.ksplit > 0 && t_xcd_z == 2;
-  bi.xcd_z = (t_xcd_z && (plain_z || image_z) && bi.cols_per_batch == 0 && bi.par.ncls == 0 && grid.z >= 8 && grid.z % 8 == 0) ? 1 : 0;
+  bi.xcd_z = splitk_xcd(t_xcd_z, t_grid_z, t_fixed_kchunk, bi.ksplit, bi.cols_per_batch, bi.par.ncls, (int)grid.z) ? 1 : 0;   // k-chunks pinned to XCDs
   bi.tail_sx = 0; bi.tail_slab = nullptr; bi.tail_cnt = nullptr; bi.tail_n = 0; bi.tail_s = 0; bi.tail_first = 0;
   for (int c = 0; c < 4; ++c) { bi.par.split[c] = 1; bi.par.slot0[c] = 0; }
   bi.par.nslots = 0;
@@ -2196,6 +2209,134 @@ inline NkPlan nk_plan(int M, int C, int KS2, int Kpix, bool two) {
   }
   p.splits = s < 1 ? 1 : s;
   return p;
+}
+
+// THE launch plan of a weight-gradient GEMM (run_nk_ks launches exactly this; sg_conv2d_wgrad_plan reports ``p``).  Inputs: the
+// shape (M rows of A, Mtot its row pitch; the gather's geometry), sparse / L / perimage = Sparse non-null / Sparse::L /
+// Sparse::gwimg non-null, a16 = A is 16-byte aligned, want_gb = a bias gradient is asked for, and the workspace offered: ws_bytes
+// (0 when there is none) and Sparse::pad_off.  err: nullptr, or why the launch is refused.
+struct NkShape { int KS, M, Mtot, C1, C2, NB, PH, PW, SH, SW, ups, stride, pad, reflect, pstep; };
+inline NkShape nk_shape(int KS, int M, int Mtot, const Gather& g, int NB) {
+  return NkShape{KS, M, Mtot, g.C1, g.C2, NB, g.PH, g.PW, g.SH, g.SW, g.ushift ? 2 : 1, g.stride, g.pad, g.reflect, g.pstep};
+}
+struct NkLaunch {
+  sgWgradPlan p;
+  const char* err;
+  bool few;            // the few-channel per-image form: (channel, tap) columns, S chunks of kcs pixels inside each image
+  int tile;            // 0: 128x128, 1: 64x64, 2: 32x128
+  int S, kcs;
+  int splits;          // what launch_cfg is handed
+  int zpad;            // t_min_z
+  size_t mn;           // floats of one slab
+  size_t rowsum_off;   // floats from the workspace to the row sums [grid_z][M] (p.rowsum_fused)
+};
+inline NkLaunch nk_launch_plan(const NkShape& h, bool sparse, int L, bool perimage, bool a16, bool want_gb, size_t ws_bytes,
+                               size_t pad_off) {
+  NkLaunch n = {};
+  sgWgradPlan& p = n.p;
+  const int KS = h.KS, M = h.M, NB = h.NB;
+  const int PQ = h.PH * h.PW, KS2 = KS * KS;
+  const int Kpix = NB * PQ;
+  const int C = h.C1 + h.C2;
+  // channel-sparse input (see run_kn_sparse): one k-chunk per image, compact columns, per-image slabs that
+  // sparse_wgrad_reduce_kernel scatters back to the dense gradient in a fixed order
+  const int Ccols = sparse ? L : C;
+  const int Ncols = Ccols * KS2;
+  const bool vec_ok = (PQ % 4 == 0) && a16;
+  NkPlan pl = nk_plan(M, Ccols, KS2, Kpix, h.C2 > 0);
+  if (sparse && perimage && h.C2 == 0 && sg_cdiv(Ccols, 64) * 64 >= 3 * Ccols) {
+    // a handful of channels per image (factored layout convs): the tap-major layout would pad every tap to a 64-column
+    // tile; use the (channel, tap)-ordered gather instead, L*KS2 columns, k-chunks inside each image for occupancy
+    n.few = true;
+    n.tile = M <= 32 ? 2 : 1;
+    const long tiles = (long)sg_cdiv(M, n.tile == 2 ? 32 : 64) * sg_cdiv(Ncols, n.tile == 2 ? 128 : 64) * NB;
+    int S = (int)((1024 + tiles - 1) / tiles);
+    if (S > 128 / Ccols) S = 128 / Ccols;           // slabs fit the workspace sized for the tap-major path
+    if (S > PQ / 256) S = PQ / 256;
+    if (S < 1) S = 1;
+    n.kcs = sg_cdiv(sg_cdiv(PQ, S), BK) * BK;
+    n.S = S = sg_cdiv(PQ, n.kcs);
+    n.mn = (size_t)M * Ncols;
+    const size_t slabs = n.mn * sizeof(float) * (size_t)S * NB;
+    if (ws_bytes < slabs) { n.err = "wgrad: workspace too small"; return n; }
+    // Reflection-padded 7x7 stem: the gather decodes every one of the L*49 columns' elements with reflection arithmetic --
+    // vector-ALU work the f32 MFMA cannot overlap (the launch ran at 45 TFLOP/s, every other weight gradient of the step at
+    // 90-105).  When the workspace has room (Sparse::pad_off) the listed planes are reflect-padded once, behind the slabs, and the
+    // same GEMM -- same tiles, k-chunks, k order, epilogue -- gathers from them with one add per element: bit-identical.
+    const size_t pbytes = nk_padded_bytes(KS, NB, Ccols, h.C2, h.SH, h.SW, h.ups, h.PH, h.PW, h.stride, h.pad, h.reflect);
+    const bool padded = sg_opt(SG_OPT_WGRAD_PADDED) && pbytes > 0 && pad_off >= slabs && h.pstep == 1 && NB <= 65535 &&
+                        ws_bytes >= pad_off + pbytes;
+    p.form = padded ? SG_WG_PADDED : SG_WG_GATHER;
+    p.bm = n.tile == 2 ? 32 : 64; p.bn = n.tile == 2 ? 128 : 64;
+    // (the gather form reads the output gradient with 16-byte loads only on the 7x7 stem: one vector-memory instruction per thread
+    // and k-tile instead of four next to the four gathered elements of B)
+    p.a_vec = (n.tile != 2 && (padded || KS == 7) && vec_ok) ? 1 : 0;
+    p.kchunk = n.kcs; p.chunks = p.grid_z = NB * S;
+    // (image, chunk) slices pinned to XCDs when grid.z % 8 == 0
+    p.xcd = splitk_xcd(sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0, p.grid_z, 0, S, 0, 0, p.grid_z) ? 2 : 0;
+    p.reduce = S > 1 ? SG_WR_GROUP : SG_WR_NONE;
+    p.ws_needed = (int64_t)(padded ? pad_off + pbytes : (S > 1 ? slabs : 0));
+    n.splits = 1;
+    return n;
+  }
+  if (sparse) pl.tap = true;
+  if (sparse && pl.cpad == 0) pl.cpad = sg_cdiv(Ccols, pl.tile == 1 ? 64 : 128) * (pl.tile == 1 ? 64 : 128);
+  n.tile = pl.tile;
+  int splits = sparse ? NB : pl.splits;
+  // slab size: the tap-major path keeps whole padded channel tiles, [m][t][cpad]
+  const size_t mn = n.mn = pl.tap ? (size_t)M * KS2 * pl.cpad : (size_t)M * Ncols;
+  if (!sparse && splits > 1 && ws_bytes < mn * sizeof(float) * (size_t)splits) splits = (int)(ws_bytes / (mn * sizeof(float)));
+  if (!sparse && splits < 2) splits = 1;
+  if (pl.tap && ws_bytes < mn * sizeof(float) * (size_t)splits) { n.err = "wgrad: workspace too small"; return n; }
+  if (!pl.tap && KS != 1 && KS != 3 && KS != 4 && KS != 7) { n.err = "wgrad: kernel size unsupported"; return n; }
+  const int kchunk = sparse ? PQ : sg_cdiv(sg_cdiv(Kpix, splits), 64) * 64;      // multiple of every BKT
+  splits = sg_cdiv(Kpix, kchunk);
+  // XCD-pinned k-chunks (igemm_kernel: xcd_z) need grid.z % 8 == 0: pad with empty chunks (kbeg >= Kpix: they store zero slabs)
+  // when the workspace has room for them
+  if (sg_opt(SG_OPT_WGRAD_XCD) && !sparse && splits >= 6) {
+    const int z8 = (splits + 7) / 8 * 8;
+    if (ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)z8) { n.zpad = z8; splits = z8; }
+  }
+  // bias gradient from the A loader's row sums: tap-major dense launches whose workspace has room for [splits][M] behind the slabs
+  if (sg_opt(SG_OPT_WGRAD_ROWSUM) && want_gb && pl.tap && !sparse && M == h.Mtot &&
+      ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)splits) {
+    p.rowsum_fused = 1;
+    n.rowsum_off = mn * (size_t)splits;
+  }
+  n.splits = splits;
+  const int fixed = sparse ? PQ : 0;
+  p.form = pl.tap ? SG_WG_TAP : SG_WG_GATHER;
+  p.bm = pl.tile == 0 ? 128 : (pl.tile == 1 ? 64 : 32); p.bn = pl.tile == 1 ? 64 : 128;
+  p.cpad = pl.tap ? pl.cpad : 0;
+  p.a_vec = (pl.tap && vec_ok) ? 1 : 0;                  // (the dense (channel, tap) form reads A with scalar loads)
+  p.two = (pl.tap && h.C2 > 0) ? 1 : 0;
+  p.kchunk = splitk_chunk(Kpix, splits, BK * NSW, fixed);
+  p.chunks = (splits > 1 || fixed > 0) ? sg_cdiv(Kpix, p.kchunk) : 1;
+  p.grid_z = splitk_grid_z(Kpix, splits, p.kchunk, 0, fixed, n.zpad);
+  // mask-free gather: reflection padding and whole 16-pixel k-tiles (split chunks are multiples of 16); one source only.  Never
+  // with an empty XCD-padding chunk: its first k-tile is loaded like any other, and LoadTapNK<MASK = false> would read the
+  // table's "no pixel" entry (-1) as an offset -- element 2^32 - 1 of the first channel plane
+  p.nomask = (pl.tap && !p.two && h.reflect && (Kpix % (BK * NSW) == 0) && (!sparse || PQ % (BK * NSW) == 0) &&
+              p.chunks == p.grid_z) ? 1 : 0;
+  p.xcd = splitk_xcd(n.zpad > 0 ? 1 : 0, 0, fixed, 0, 0, 0, p.grid_z) ? 1 : 0;
+  size_t need = 0;
+  if (sparse) {
+    p.reduce = perimage ? SG_WR_PERIMAGE : SG_WR_SPARSE;
+    need = (size_t)NB * mn * sizeof(float) + (perimage ? 0 : (size_t)NB * C * sizeof(int));
+  } else if (pl.tap) {
+    p.reduce = SG_WR_UNPERMUTE;
+    need = (mn + (p.rowsum_fused ? (size_t)M : 0)) * sizeof(float) * (size_t)splits;
+  } else {
+    p.reduce = splits >= 32 ? SG_WR_WIDE : (splits > 1 ? SG_WR_SLAB : SG_WR_NONE);
+    need = splits > 1 ? mn * sizeof(float) * (size_t)splits : 0;
+  }
+  p.ws_needed = (int64_t)need;
+  return n;
+}
+// Sparse::pad_off of sg_conv2d_wgrad_perimage for a workspace of ws_bytes: the padded planes sit behind the gather route's bytes
+// (base), when the conv has them (pb = nk_padded_bytes) and the workspace holds both
+inline size_t nk_perimage_pad_off(size_t base, size_t pb, size_t ws_bytes) {
+  return (pb && ws_bytes >= nk_padded_offset(base) + pb) ? nk_padded_offset(base) : 0;
 }
 
 }  // namespace

@@ -85,8 +85,8 @@ __global__ void reflect_pad_planes_kernel(const float* __restrict__ x, const int
   pp[((size_t)b * L + j) * PP + e] = x[((size_t)b * C + c) * ((size_t)H * W) + (unsigned)(ih * W + iw)];
 }
 // the per-image weight gradient of the factored 7x7 stem over padded planes: launch_nk_general's three forms with LoadPaddedNK
-void launch_nk_padded(int tile, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep, int Kpix,
-                      hipStream_t s, const Sparse& sp, const float* pp) {
+void launch_nk_padded(int tile, bool vecA, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep,
+                      int Kpix, hipStream_t s, const Sparse& sp, const float* pp) {
   float* const rowsum = nullptr;
   const FastDiv dPQ((unsigned)PQ), dPW((unsigned)g.PW);
   const int PWp = g.SW + 2 * g.pad, PP = (g.SH + 2 * g.pad) * PWp;
@@ -94,7 +94,7 @@ void launch_nk_padded(int tile, const float* A, int M, int Mtot, int PQ, const G
 #define SG_PAD_B(BNv) LoadPaddedNK<BNv, 7, NSW>{pp, bytes, PQ, g.PW, PWp, PP, sp.L, sp.cnt, dPQ, dPW}
   if (tile == 2)
     launch_cfg<CfgW32>(LoadPixK<32>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(128), ep, M, Ncols, Kpix, 1, s);
-  else if ((PQ % 4 == 0) && aligned16(A))
+  else if (vecA)
     launch_cfg<CfgW64>(LoadPixKVec<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s);
   else
     launch_cfg<CfgW64>(LoadPixK<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s);
@@ -102,7 +102,7 @@ void launch_nk_padded(int tile, const float* A, int M, int Mtot, int PQ, const G
 }
 // general (c, tap)-ordered loader: only for few-channel inputs (RGB crops / images)
 template <int KS>
-void launch_nk_general(int tile, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep,
+void launch_nk_general(int tile, bool vecA, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep,
                        int Kpix, int splits, hipStream_t s, const Sparse* sp = nullptr, int zdiv = 1) {
   float* const rowsum = nullptr;
   const FastDiv dPQ((unsigned)PQ);
@@ -110,7 +110,8 @@ void launch_nk_general(int tile, const float* A, int M, int Mtot, int PQ, const 
   if (tile == 2)
     launch_cfg<CfgW32>(LoadPixK<32>{A, M, Mtot, PQ, dPQ, rowsum}, LoadGatherNK<128, KS, false, true, NSW>{g, Ncols, sl, sc, L, zdiv}, ep,
                        M, Ncols, Kpix, splits, s);
-  else if (KS == 7 && sp && (PQ % 4 == 0) && aligned16(A))
+  else if (KS == 7 && vecA)
+    // (nk_launch_plan: vecA only with KS == 7, per-image lists, PQ % 4 == 0, A 16-byte aligned)
     // the per-image weight gradient of the factored 7x7 stem (64 x 9*49 x 16 384 per image: the slowest GEMM launch of the step,
     // 45 TFLOP/s): the output gradient is read with 16-byte loads -- one vector-memory instruction per thread and k-tile instead of
     // four next to the four gathered elements of B (same-box A/B, two pairs: 31.24 vs 31.31 ms/step, +0.2 %)
@@ -153,103 +154,72 @@ int run_nk_ks(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, 
   // sparse_wgrad_reduce_kernel scatters back to the dense gradient in a fixed order
   const int Ccols = sp ? sp->L : C;
   const int Ncols = Ccols * KS2;
-  NkPlan pl = nk_plan(M, Ccols, KS2, Kpix, g.C2 > 0);
-  if (sp && sp->gwimg && g.C2 == 0 && sg_cdiv(Ccols, 64) * 64 >= 3 * Ccols) {
-    // a handful of channels per image (factored layout convs): the tap-major layout would pad every tap to a 64-column
-    // tile; use the (channel, tap)-ordered gather instead, L*KS2 columns, k-chunks inside each image for occupancy
-    const int tile = M <= 32 ? 2 : 1;
-    const long tiles = (long)sg_cdiv(M, tile == 2 ? 32 : 64) * sg_cdiv(Ncols, tile == 2 ? 128 : 64) * NB;
-    int S = (int)((1024 + tiles - 1) / tiles);
-    if (S > 128 / Ccols) S = 128 / Ccols;           // slabs fit the workspace sized for the tap-major path
-    if (S > PQ / 256) S = PQ / 256;
-    if (S < 1) S = 1;
-    const int kcs = sg_cdiv(sg_cdiv(PQ, S), BK) * BK;
-    S = sg_cdiv(PQ, kcs);
-    const size_t mnc = (size_t)M * Ncols;
-    SG_ARG_CHECK(ws && ws_bytes >= mnc * sizeof(float) * (size_t)S * NB, "wgrad: workspace too small");
+  // every decision below is nk_launch_plan's (igemm_core.h), which sg_conv2d_wgrad_plan reports
+  const NkLaunch nl = nk_launch_plan(nk_shape(KS, M, Mtot, g, NB), sp != nullptr, sp ? sp->L : 0, sp && sp->gwimg, aligned16(A), gb != nullptr,
+                                     ws ? ws_bytes : 0, sp ? sp->pad_off : 0);
+  SG_ARG_CHECK(nl.err == nullptr, "%s", nl.err);
+  const sgWgradPlan& pl = nl.p;
+  const bool vecA = pl.a_vec != 0;
+  if (nl.few) {
+    // a handful of channels per image (factored layout convs): the (channel, tap)-ordered gather, L*KS2 columns, k-chunks inside
+    // each image for occupancy
+    const int tile = nl.tile, S = nl.S;
+    const size_t mnc = nl.mn;
     float* dstp = S > 1 ? reinterpret_cast<float*>(ws) : sp->gwimg;
     const EpRowMajor ep{dstp, nullptr, M, Ncols, Ncols, SG_ACT_NONE, 0.f, mnc};
-    t_batch = BatchInfo{}; t_batch.kimg = PQ; t_batch.ksplit = S; t_batch.kcs = kcs;
+    t_batch = BatchInfo{}; t_batch.kimg = PQ; t_batch.ksplit = S; t_batch.kcs = nl.kcs;
     t_grid_z = NB * S;
     t_xcd_z = sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0;      // (image, chunk) slices pinned to XCDs when grid.z % 8 == 0 (launch_cfg)
-    // Reflection-padded 7x7 stem: the gather below decodes every one of the L*49 columns' elements with reflection arithmetic --
-    // vector-ALU work the f32 MFMA cannot overlap (the launch ran at 45 TFLOP/s, every other weight gradient of the step at
-    // 90-105).  When the workspace has room (Sparse::pad_off) the listed planes are reflect-padded once, behind the slabs, and the
-    // same GEMM -- same tiles, k-chunks, k order, epilogue -- gathers from them with one add per element: bit-identical.
-    const size_t pbytes = nk_padded_bytes(KS, NB, Ccols, g.C2, g.SH, g.SW, g.ushift ? 2 : 1, g.PH, g.PW, g.stride, g.pad, g.reflect);
-    const bool padded = sg_opt(SG_OPT_WGRAD_PADDED) && pbytes > 0 && sp->pad_off >= mnc * sizeof(float) * (size_t)S * NB &&
-                        g.pstep == 1 && NB <= 65535 && ws_bytes >= sp->pad_off + pbytes;
-    if (padded) {
+    if (pl.form == SG_WG_PADDED) {                   // the listed planes reflect-padded once, behind the slabs (nk_launch_plan)
       float* pp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + sp->pad_off);
       const int PWp = g.SW + 2 * g.pad, PP = (g.SH + 2 * g.pad) * PWp;
       hipLaunchKernelGGL(reflect_pad_planes_kernel, dim3(sg_cdiv(PP, 256), Ccols, NB), dim3(256), 0, s, g.src1, sp->list, sp->cnt, pp,
                          g.C1, Ccols, g.SH, g.SW, g.pad, PWp, PP, FastDiv((unsigned)PWp));
       SgProfScope prof(sg_igemm_kind(2, KS, tile), s, 2.0 * M * (double)Ncols * Kpix, 0);
-      launch_nk_padded(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, s, *sp, pp);
+      launch_nk_padded(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, s, *sp, pp);
     } else {
       SgProfScope prof(sg_igemm_kind(2, KS, tile), s, 2.0 * M * (double)Ncols * Kpix, 0);
       switch (KS) {
-        case 1: launch_nk_general<1>(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
-        case 3: launch_nk_general<3>(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
-        case 4: launch_nk_general<4>(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
-        case 7: launch_nk_general<7>(tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
+        case 1: launch_nk_general<1>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
+        case 3: launch_nk_general<3>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
+        case 4: launch_nk_general<4>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
+        case 7: launch_nk_general<7>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
       }
     }
     t_batch = BatchInfo{};
     t_grid_z = 0;
     t_xcd_z = 0;
-    if (S > 1)
+    if (pl.reduce == SG_WR_GROUP)
       hipLaunchKernelGGL(slab_group_reduce_kernel, dim3(sg_cdiv(mnc * NB, 256)), dim3(256), 0, s, (const float*)ws, sp->gwimg,
                          mnc, S, NB);
     return 0;
   }
-  if (sp) pl.tap = true;
-  if (sp && pl.cpad == 0) pl.cpad = sg_cdiv(Ccols, pl.tile == 1 ? 64 : 128) * (pl.tile == 1 ? 64 : 128);
-  int splits = sp ? NB : pl.splits;
-  // slab size: the tap-major path keeps whole padded channel tiles, [m][t][cpad]
-  const size_t mn = pl.tap ? (size_t)M * KS2 * pl.cpad : (size_t)M * Ncols;
-  if (!sp && splits > 1 && ws_bytes < mn * sizeof(float) * (size_t)splits) splits = (int)(ws_bytes / (mn * sizeof(float)));
-  if (!sp && splits < 2) splits = 1;
-  SG_ARG_CHECK(!pl.tap || (ws && ws_bytes >= mn * sizeof(float) * (size_t)splits), "wgrad: workspace too small");
-  const int kchunk = sp ? PQ : sg_cdiv(sg_cdiv(Kpix, splits), 64) * 64;      // multiple of every BKT
-  splits = sg_cdiv(Kpix, kchunk);
-  // XCD-pinned k-chunks (igemm_kernel: xcd_z) need grid.z % 8 == 0: pad with empty chunks (kbeg >= Kpix: they store zero slabs)
-  // when the workspace has room for them
-  int zpad = 0;
-  if (sg_opt(SG_OPT_WGRAD_XCD) && !sp && splits >= 6) {
-    const int z8 = (splits + 7) / 8 * 8;
-    if (ws && ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)z8) { zpad = z8; splits = z8; }
-  }
-  // bias gradient from the A loader's row sums: tap-major dense launches whose workspace has room for [splits][M] behind the slabs
-  const int fuse_gb = sg_opt(SG_OPT_WGRAD_ROWSUM);
-  float* rowsum = nullptr;
-  if (fuse_gb && gb && pl.tap && !sp && M == Mtot && ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)splits)
-    rowsum = reinterpret_cast<float*>(ws) + mn * (size_t)splits;
+  const bool tap = pl.form == SG_WG_TAP;
+  const int splits = nl.splits;
+  const size_t mn = nl.mn;
+  float* const rowsum = pl.rowsum_fused ? reinterpret_cast<float*>(ws) + nl.rowsum_off : nullptr;
   if (sp) { t_fixed_kchunk = PQ; flops = 2.0 * M * (double)Ncols * Kpix; }
-  t_xcd_z = zpad > 0 ? 1 : 0;
-  t_min_z = zpad;
-  float* dst = (splits > 1 || sp || pl.tap) ? reinterpret_cast<float*>(ws) : out;
+  t_xcd_z = nl.zpad > 0 ? 1 : 0;
+  t_min_z = nl.zpad;
+  float* dst = (splits > 1 || sp || tap) ? reinterpret_cast<float*>(ws) : out;
   {
-    SgProfScope prof(sg_igemm_kind(2, KS, pl.tile), s, flops, 0);
-    if (pl.tap) {
+    SgProfScope prof(sg_igemm_kind(2, KS, nl.tile), s, flops, 0);
+    if (tap) {
       const EpWgrad ep{dst, M, pl.cpad, KS2, mn};
-      const bool vecA = (PQ % 4 == 0) && aligned16(A);
-      // mask-free gather: reflection padding and whole 16-pixel k-tiles (split chunks are multiples of 64)
-      const bool nomask = g.reflect && (Kpix % (BK * NSW) == 0) && (!sp || PQ % (BK * NSW) == 0);
-      switch (pl.tile) {
+      // (nomask is passed as planned for one source; launch_nk_tap ignores it for two)
+      const bool nomask = pl.nomask != 0;
+      switch (nl.tile) {
         case 0: launch_nk_tap<CfgW128, 128, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
         case 1: launch_nk_tap<CfgW64, 64, 64>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
-        case 3: launch_nk_tap<CfgW64W, 64, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
         default: launch_nk_tap<CfgW32, 32, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
       }
     } else {
       const EpRowMajor ep{dst, nullptr, M, Ncols, Ncols, SG_ACT_NONE, 0.f, mn};
       switch (KS) {
-        case 1: launch_nk_general<1>(pl.tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        case 3: launch_nk_general<3>(pl.tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        case 4: launch_nk_general<4>(pl.tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        case 7: launch_nk_general<7>(pl.tile, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        default: t_fixed_kchunk = 0; t_xcd_z = 0; t_min_z = 0; return -1;
+        case 1: launch_nk_general<1>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
+        case 3: launch_nk_general<3>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
+        case 4: launch_nk_general<4>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
+        case 7: launch_nk_general<7>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
       }
     }
   }
@@ -257,29 +227,33 @@ int run_nk_ks(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, 
   t_xcd_z = 0;
   t_min_z = 0;
   const size_t nout = (size_t)M * C * KS2;
-  if (sp && sp->gwimg) {
-    const size_t n = (size_t)NB * M * sp->L * KS2;
-    hipLaunchKernelGGL(sparse_wgrad_perimage_kernel, dim3(sg_cdiv(n, 256)), dim3(256), 0, s, (const float*)ws, sp->cnt,
-                       sp->gwimg, M, sp->L, KS2, pl.cpad, NB);
-    return 0;
+  switch (pl.reduce) {
+    case SG_WR_PERIMAGE: {
+      const size_t n = (size_t)NB * M * sp->L * KS2;
+      hipLaunchKernelGGL(sparse_wgrad_perimage_kernel, dim3(sg_cdiv(n, 256)), dim3(256), 0, s, (const float*)ws, sp->cnt,
+                         sp->gwimg, M, sp->L, KS2, pl.cpad, NB);
+      break;
+    }
+    case SG_WR_SPARSE: {
+      int* inv = reinterpret_cast<int*>(reinterpret_cast<float*>(ws) + (size_t)NB * mn);
+      hipLaunchKernelGGL(sparse_inv_kernel, dim3(sg_cdiv(C, 256), NB), dim3(256), 0, s, sp->list, sp->cnt, sp->L, C, inv);
+      hipLaunchKernelGGL(sparse_wgrad_reduce_kernel, dim3(sg_cdiv(nout, 256)), dim3(256), 0, s, (const float*)ws,
+                         (const int*)inv, out, M, C, KS2, pl.cpad, NB);
+      break;
+    }
+    case SG_WR_UNPERMUTE:
+      hipLaunchKernelGGL(wgrad_unpermute_reduce_kernel, dim3(sg_cdiv((size_t)C * KS2, 256), M), dim3(256), 0, s, (const float*)ws, out,
+                         M, C, KS2, pl.cpad, splits, (const float*)rowsum, rowsum ? gb : nullptr);
+      if (rowsum && gb_done) *gb_done = true;
+      break;
+    case SG_WR_WIDE:
+      hipLaunchKernelGGL(slab_reduce_wide_kernel, dim3(sg_cdiv(mn, 16)), dim3(256), 0, s, (const float*)ws, out, mn, splits);
+      break;
+    case SG_WR_SLAB:
+      hipLaunchKernelGGL(slab_reduce_kernel, dim3(sg_cdiv(mn, 256)), dim3(256), 0, s, (const float*)ws, out, mn, splits);
+      break;
+    default: break;
   }
-  if (sp) {
-    int* inv = reinterpret_cast<int*>(reinterpret_cast<float*>(ws) + (size_t)NB * mn);
-    hipLaunchKernelGGL(sparse_inv_kernel, dim3(sg_cdiv(C, 256), NB), dim3(256), 0, s, sp->list, sp->cnt, sp->L, C, inv);
-    hipLaunchKernelGGL(sparse_wgrad_reduce_kernel, dim3(sg_cdiv(nout, 256)), dim3(256), 0, s, (const float*)ws,
-                       (const int*)inv, out, M, C, KS2, pl.cpad, NB);
-    return 0;
-  }
-  if (pl.tap)
-  {
-    hipLaunchKernelGGL(wgrad_unpermute_reduce_kernel, dim3(sg_cdiv((size_t)C * KS2, 256), M), dim3(256), 0, s, (const float*)ws, out,
-                       M, C, KS2, pl.cpad, splits, (const float*)rowsum, rowsum ? gb : nullptr);
-    if (rowsum && gb_done) *gb_done = true;
-  }
-  else if (splits >= 32)
-    hipLaunchKernelGGL(slab_reduce_wide_kernel, dim3(sg_cdiv(mn, 16)), dim3(256), 0, s, (const float*)ws, out, mn, splits);
-  else if (splits > 1)
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(sg_cdiv(mn, 256)), dim3(256), 0, s, (const float*)ws, out, mn, splits);
   return 0;
 }
 

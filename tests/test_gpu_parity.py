@@ -165,6 +165,8 @@ CONV_CASES = [
     (8, 128, 0, 17, 17, 128, 4, 1, 2, False, 1, 2),    # Winograd F(2x2,4x4): PatchGAN k4 s1 p2 (17 -> 18), fused LeakyReLU
     (8, 128, 0, 20, 14, 256, 4, 1, 1, False, 1, 0),    # F(2x2,4x4): pad 1, odd 19x13 output (clipped edge tiles), Cin != Cout
     (8, 256, 0, 19, 19, 128, 4, 1, 0, False, 1, 1),    # F(2x2,4x4): valid conv, data gradient with padding 3, k-chunked wgrad
+    # (the chunking of the weight gradient -- chunk counts, the cap, XCD padding -- is asserted plan by plan against float64 in
+    #  tests/wgrad_cases.py: row g_64x3_k4s2_32x32 is the next shape at the C ABI)
     (6, 3, 0, 64, 64, 64, 4, 2, 1, False, 1, 2),       # crop-D first conv: few-channel wgrad in 48 k-chunks (wide slab reduce)
     (40, 3, 0, 64, 64, 64, 4, 2, 1, False, 1, 2),      # the same at ~200 crops: the 256-chunk cap, XCD-padded chunk count
     (16, 128, 0, 8, 8, 128, 3, 1, 1, True, 1, 0),      # Winograd F(4x4,3x3): 16 * 2 * 2 = 64 tiles of 4x4 outputs (one 64-column GEMM tile)

@@ -5,8 +5,8 @@ Both go through the C ABI.  The references are float64 on the CPU, built from ``
 them runs the code under test.
 
 Weight gradient: the padded-plane route changes where the gathered element comes from, not which products meet in which order,
-so it must equal the gather route (option off) bit for bit; against float64 it is held to twice the gather route's own maximum
-error on the same case.  A workspace of the size the query returned before the padded planes were added must select the gather
+so it must equal the gather route (option off) bit for bit; against float64 every element is held to the derived bound of
+tests/wgrad_cases.py, with the chunk count of the plan the library reports.  A workspace of the size the query returned before the padded planes were added must select the gather
 route -- no fault, no error.
 
 Fold: interior elements have one source; the others add up to nine values in a fixed order (row candidates outer, column
@@ -122,8 +122,20 @@ def test_stem_wgrad_padded_planes(L, case):
           % (case, err_on, err_off, float(ref.abs().max())))
     assert torch.equal(on, off), 'the padded-plane route differs from the gather route'
     assert on.view(torch.int32).equal(off.view(torch.int32)), 'the two routes differ in a sign of zero'
-    assert err_on <= 2.0 * err_off, (err_on, err_off)
-    cnt = _wgrad_case(case)[3]
+    # every element within its own rounding bound of float64 (tests/wgrad_cases.py): gamma(n + S) sum|gy||x|, n the terms of the
+    # element, S the k-chunks of an image that the plan reports for this launch
+    import wgrad_cases as WG
+    N, Lc, M, H, W, KS, pad = case
+    x, gy, lst, cnt = _wgrad_case(case)[:4]
+    d = WG.make_desc(N, x.size(1), H, W, M, KS, 1, pad, True, 1, H, W)
+    plan = WG.wgrad_plan(L, d, WG.WG_PERIMAGE, Lc, 0, L.sg_conv2d_sparse_ws_bytes(ctypes.byref(d), Lc, 2))
+    assert plan['form'] == WG.WG_PADDED and plan['grid_z'] % N == 0, plan
+    per = lambda g, v: WG.perimage_wgrad(WG.wgrad_images(g, v, KS, 1, pad, True, 1), lst.numpy(), cnt.numpy())
+    g64, x64 = gy.double().numpy(), x.double().numpy()
+    bound = WG.bound(per(np.ones_like(g64), np.ones_like(x64)), plan['grid_z'] // N, per(np.abs(g64), np.abs(x64)))
+    err = (on.double() - ref).abs().numpy()
+    print('wgrad_perimage %s: worst error / bound %.3f' % (case, float((err / np.maximum(bound, 1e-300)).max())))
+    assert bool((err <= bound).all()), float((err / np.maximum(bound, 1e-300)).max())
     for b in range(case[0]):
         assert not bool(on[b, :, int(cnt[b]):].any()), 'columns beyond the image\'s channel list must be zero'
 

@@ -105,7 +105,19 @@ def convT_wgrad(L, d, gd, xd, want_gb):
     ws, n = conv_ws(L, d, 2)
     o, ob = outbuf(d.C1 * d.Cout * d.KS * d.KS), (outbuf(d.Cout) if want_gb else None)
     call(L, 'sg_convT2d_wgrad', dref(d), ptr(gd), ptr(xd), ptr(o), ptr(ob), ptr(ws), n, stream())
+    # the plan the library reports for this launch (sg_conv2d_wgrad_plan; tests/wgrad_cases.py restates it): the GEMM runs with the
+    # roles swapped -- rows = the input channels, the gathered operand = gy over the input grid -- and hands no bias gradient over
+    import wgrad_cases as WG
+    got = WG.wgrad_plan(L, d, WG.WG_CONVT, 0, xd.data_ptr() % 16, n)
+    want = WG.py_plan(WG.WG_CONVT, d.N, d.Cout, 0, d.OH, d.OW, d.C1, d.KS, d.stride, d.pad, 0, 1, d.H, d.W, a_mod16=xd.data_ptr() % 16,
+                      ws_bytes=n, xcd=_hip_option('wgrad_xcd'))
+    assert got == want and got['rowsum_fused'] == 0 and got['ws_needed'] <= n, (got, want, n)
     return take(o, (d.C1, d.Cout, d.KS, d.KS)), (take(ob, (d.Cout,)) if want_gb else None)
+
+
+def _hip_option(name):
+    from scene_generation_amd import _hip
+    return _hip.get_option(name)
 
 
 def logical_grid(d):

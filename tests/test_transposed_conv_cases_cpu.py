@@ -350,7 +350,9 @@ def test_restated_constants_match_the_sources():
     assert core.count('splits <= 1') >= 2
     assert T.C_GATHER == (8 - 1) + 1
     # c_wgrad: k-chunks are multiples of 64
-    assert re.search(r'kchunk = sp \? PQ : sg_cdiv\(sg_cdiv\(Kpix, splits\), %d\) \* %d;' % (T.WGRAD_CHUNK, T.WGRAD_CHUNK), nk)
+    # (the launcher's decisions live in nk_launch_plan of igemm_core.h, which run_nk_ks of igemm_nk.hip runs from)
+    assert re.search(r'kchunk = sparse \? PQ : sg_cdiv\(sg_cdiv\(Kpix, splits\), %d\) \* %d;' % (T.WGRAD_CHUNK, T.WGRAD_CHUNK), core)
+    assert 'nk_launch_plan(' in nk
     assert T.c_wgrad(64) == 1 and T.c_wgrad(65) == 2
     # C_VARIANT: a pre-folded value is v00 plus three conditional adds
     body = core[core.index('__global__ void reflect_variants_kernel'):core.index('// Wt[b][a][r] = W[a][b][r]')]
