@@ -61,6 +61,12 @@ int sg_plan_cache_clear(void);
  * Replaces nn.Conv2d / nn.ConvTranspose2d (+ the nn.ReflectionPad2d, Interpolate(x2, nearest) and
  * torch.cat((layout, img), 1) feeding them) at generators.py:20-27,68-89, layers.py:160-180,251-270,
  * discriminators.py:137-158,215-234 and trainer.py:246,250,328.
+ * Every GEMM family of the convolutions runs from one host-side plan function that a host-only query reports (tile, loaders,
+ * mask, split, reduce -- under the current options, launching nothing): sg_conv2d_fwd_plan (forward gathers: sg_conv2d_fwd,
+ * _fwd_sparse, _fwd_perimage), sg_conv2d_tgather_plan (transposed gathers), sg_conv2d_wgrad_plan (weight gradients) and
+ * sg_conv2d_wino_plan (Winograd).
+ * A desc with reflection padding must satisfy pad < H*upsample, pad < W*upsample and (OH-1)*stride + KS <= H*upsample + 2*pad
+ * (the same for the width): the gathers mirror a coordinate once.  Every entry point refuses any other (as torch refuses it).
  * ------------------------------------------------------------------------------------------- */
 typedef struct sgConvDesc {
   int32_t N;            /* images */
@@ -113,7 +119,9 @@ int sg_conv2d_wgrad(const sgConvDesc* d, const float* gy, const float* x1, const
    layout.py:64-93: per image only the one-hot planes of the classes present and the dense representation block are
    non-zero).  chan_list [N, L] int32: ascending concat-channel ids (over x1|x2) that may be non-zero in image n, the
    first chan_cnt[n] (<= L) entries are used; every other channel of that image MUST be all-zero or the result
-   differs from sg_conv2d_fwd / sg_conv2d_wgrad.  Same outputs as the dense calls (different summation order). */
+   differs from sg_conv2d_fwd / sg_conv2d_wgrad.  Same outputs as the dense calls (different summation order).
+   The workspace of sg_conv2d_fwd_sparse and sg_conv2d_fwd_perimage must be 16-byte aligned (they build compact per-image weight
+   rows in it and read them as float4); a misaligned one is refused before anything is launched. */
 size_t sg_conv2d_sparse_ws_bytes(const sgConvDesc* d, int L, int kind /* 0 fwd, 2 wgrad */);
 int sg_conv2d_fwd_sparse(const sgConvDesc* d, const float* x1, const float* x2, const float* w, const float* bias,
                          const int32_t* chan_list, const int32_t* chan_cnt, int L, float* y, int act, float slope,
@@ -321,6 +329,37 @@ typedef struct sgWgradPlan {
   int64_t ws_needed;
 } sgWgradPlan;
 int sg_conv2d_wgrad_plan(const sgConvDesc* d, int entry, int L, int a_mod16, size_t ws_bytes, sgWgradPlan* plan);
+/* host-only query of THE launch plan of a forward gather (csrc/igemm_kn0.hip: the launchers run from the same functions, kn_plan
+ * and kn_sparse_plan in csrc/igemm_core.h): what sg_conv2d_fwd, sg_conv2d_fwd_sparse or sg_conv2d_fwd_perimage launches for this
+ * desc under the current options (tile, t128_min, tile3, tile3_min, split_target, split_kmin, splits, fixedtap).  Never touches
+ * the device.  Returns non-zero exactly where the entry point itself would for the same desc, L and workspace (the checks are one
+ * function): bad desc, L outside (0, C1 + C2] for the list entries, a workspace below the entry's minimum or, for the list entries,
+ * not 16-byte aligned -- and for a null plan, an unknown entry or a mod16 argument that is not 0, 4, 8 or 12.
+ *   entry    SG_FW_*: the entry point;  L: length of the channel lists (SG_FW_SPARSE / SG_FW_PERIMAGE; ignored otherwise)
+ *   w_mod16, y_mod16, ws_mod16  addresses modulo 16 of the weights, the result and the workspace (w_mod16 is ignored for the list
+ *            entries: their weights are copied into compact rows first)
+ *   ws_bytes the workspace offered (one that holds only the k-table switches split-K off)
+ *   bm x bn  the tile;  a_vec 1: the weight rows are read as float4 (always, for the compact rows of the list entries), 0: scalar
+ *   loader   SG_FW_TABLE: taps from the k-table (LoadGatherKN);  SG_FW_FIXED: taps fixed per thread (LoadFixedKN)
+ *   two      1: the gather reads two sources;  bcast: 1: the second is a row per sample;  nomask: 1: the mask-free table loader runs
+ *   K        the reduced extent: Cin * KS * KS, or the padded compact K of the list entries (L * KS * KS rounded up to 16)
+ *   splits   split-K slabs (1 = none);  kchunk: k range of one slab (K when unsplit)
+ *   reduce   SG_FR_*: what adds the slabs: nothing, the float4 reduce, or the scalar one (result or workspace misaligned, or
+ *            OH * OW not a multiple of 4)
+ *   batched  1: one GEMM per image over its own compact weights and k extent (the list entries: tiles never straddle images)
+ *   ws_needed  workspace bytes the entry point requires for this plan (k-table area + slabs, or the list entries' tables)
+ * Not reported (it depends on the CU count): the tail split (options w43_tail_split, tail_smax, tail_ktmin), which runs the
+ * tiles of a ragged last round of an unsplit launch as k-pieces. */
+enum { SG_FW_CONV = 0, SG_FW_SPARSE = 1, SG_FW_PERIMAGE = 2 };
+enum { SG_FW_TABLE = 0, SG_FW_FIXED = 1 };          /* LoadGatherKN / LoadFixedKN */
+enum { SG_FR_NONE = 0, SG_FR_VEC = 1, SG_FR_SCALAR = 2 };
+typedef struct sgFwdPlan {
+  int32_t bm, bn, a_vec, loader, two, bcast, nomask;
+  int32_t K, splits, kchunk, reduce, batched;       /* K: Cin*KS*KS, or the padded compact K of the sparse forms */
+  int64_t ws_needed;
+} sgFwdPlan;
+int sg_conv2d_fwd_plan(const sgConvDesc* d, int entry, int L, int w_mod16, int y_mod16, int ws_mod16, size_t ws_bytes,
+                       sgFwdPlan* plan);
 /* Interpolate(x2, nearest) + Conv2d(C, Cout, 3, padding=1) (mask_net, reference generators.py:20-21, layers.py:304-314) as a
  * SUB-PIXEL transposed convolution: every output pixel (2i+a, 2j+b) only sees a 2x2 neighbourhood of the stored input, with
  * the 3x3 taps that land on the same source pixel summed -- conv3x3(up2(x); w) == convT(k4, s2, p1)(x; wt) with

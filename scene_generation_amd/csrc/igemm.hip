@@ -28,7 +28,15 @@ int check_desc(const sgConvDesc* d, const char* who) {
   SG_ARG_CHECK(d->upsample == 1 || d->upsample == 2, "%s: upsample %d unsupported", who, d->upsample);
   SG_ARG_CHECK(d->N > 0 && d->C1 > 0 && d->C2 >= 0 && d->Cout > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0,
                "%s: non-positive dimension", who);
-  SG_ARG_CHECK(!d->pad_reflect || d->pad < d->H * d->upsample, "%s: reflect pad too large", who);
+  // reflection mirrors ONCE (tap_offset): the pad must stay below the logical size on BOTH axes and the output grid inside the
+  // padded one, or a tap lands at a negative offset -- which the masked kernels read as the wrong element and the mask-free ones
+  // as an address (torch refuses the same: ReflectionPad2d needs pad < dim on each axis)
+  SG_ARG_CHECK(!d->pad_reflect || (d->pad >= 0 && d->pad < d->H * d->upsample && d->pad < d->W * d->upsample),
+               "%s: reflect pad %d too large for a %d x %d plane", who, d->pad, d->H * d->upsample, d->W * d->upsample);
+  SG_ARG_CHECK(!d->pad_reflect || ((long)(d->OH - 1) * d->stride + d->KS <= (long)d->H * d->upsample + 2L * d->pad &&
+                                   (long)(d->OW - 1) * d->stride + d->KS <= (long)d->W * d->upsample + 2L * d->pad),
+               "%s: output %d x %d reaches beyond the reflect-padded %d x %d plane", who, d->OH, d->OW,
+               d->H * d->upsample + 2 * d->pad, d->W * d->upsample + 2 * d->pad);
   const double lim = SG_MAX_ELEMS;     // 32-bit offsets; 2^29 elements with buffer-load masking (see SG_MAX_ELEMS)
   SG_ARG_CHECK((double)d->N * (d->C1 + d->C2) * d->H * d->W <= lim && (double)d->N * d->Cout * d->OH * d->OW <= lim &&
                    (double)d->N * (d->C1 + d->C2) * (d->H * d->upsample + 2.0 * d->pad) *
@@ -83,12 +91,28 @@ extern "C" size_t sg_conv2d_ws_bytes(const sgConvDesc* d, int kind) {
   return a > cs ? a : cs;
 }
 
+// The argument checks of the forward-gather entry points (SG_FW_*) that do not need the pointers themselves: shared by
+// sg_conv2d_fwd, sg_conv2d_fwd_sparse, sg_conv2d_fwd_perimage and sg_conv2d_fwd_plan.  ws_mod16: the workspace address modulo 16
+static int check_sparse_len(const sgConvDesc* d, int L, const char* who);
+static int check_fwd_args(const sgConvDesc* d, int entry, int L, int ws_mod16, size_t ws_bytes, const char* who) {
+  if (check_desc(d, who)) return -1;
+  if (entry == SG_FW_CONV) {
+    SG_ARG_CHECK(ws_bytes >= ktab_bytes((d->C1 + d->C2) * d->KS * d->KS), "%s: workspace too small", who);
+    return 0;
+  }
+  if (check_sparse_len(d, L, who)) return -1;
+  SG_ARG_CHECK(ws_bytes >= sparse_fwd_ws(d->N, d->Cout, L, d->KS * d->KS), "%s: workspace too small", who);
+  // (the compact weights Wc sit a multiple of 16 bytes behind the workspace pointer and are read as float4)
+  SG_ARG_CHECK(ws_mod16 == 0, "%s: the workspace must be 16-byte aligned (the compact weights are read as float4)", who);
+  return 0;
+}
+static int ptr_mod16(const void* p) { return (int)(reinterpret_cast<uintptr_t>(p) & 15); }
+
 extern "C" int sg_conv2d_fwd(const sgConvDesc* d, const float* x1, const float* x2, const float* w, const float* bias,
                              float* y, int act, float slope, void* ws, size_t ws_bytes, sgStream stream) {
-  if (check_desc(d, "sg_conv2d_fwd")) return -1;
+  if (check_fwd_args(d, SG_FW_CONV, 0, ptr_mod16(ws), ws_bytes, "sg_conv2d_fwd")) return -1;
   sgk::t_alg_bytes = 4.0 * ((double)d->N * (d->C1 + d->C2) * d->H * d->W + (double)d->Cout * (d->C1 + d->C2) * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(x1 && w && y && ws, "sg_conv2d_fwd: null pointer");
-  SG_ARG_CHECK(ws_bytes >= ktab_bytes((d->C1 + d->C2) * d->KS * d->KS), "sg_conv2d_fwd: workspace too small");
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_fwd: C2>0 but x2 null");
   hipStream_t s = (hipStream_t)stream;
   const int Cin = d->C1 + d->C2, K = Cin * d->KS * d->KS;
@@ -217,11 +241,11 @@ extern "C" size_t sg_conv2d_sparse_ws_bytes(const sgConvDesc* d, int L, int kind
 extern "C" int sg_conv2d_fwd_sparse(const sgConvDesc* d, const float* x1, const float* x2, const float* w,
                                     const float* bias, const int32_t* chan_list, const int32_t* chan_cnt, int L, float* y,
                                     int act, float slope, void* ws, size_t ws_bytes, sgStream stream) {
-  if (check_desc(d, "sg_conv2d_fwd_sparse") || check_sparse(d, chan_list, chan_cnt, L, "sg_conv2d_fwd_sparse")) return -1;
+  if (check_fwd_args(d, SG_FW_SPARSE, L, ptr_mod16(ws), ws_bytes, "sg_conv2d_fwd_sparse")) return -1;
+  SG_ARG_CHECK(chan_list && chan_cnt, "sg_conv2d_fwd_sparse: null channel list");
   sgk::t_alg_bytes = 4.0 * ((double)d->N * L * d->H * d->W + (double)d->N * d->Cout * L * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(x1 && w && y && ws, "sg_conv2d_fwd_sparse: null pointer");
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_fwd_sparse: C2>0 but x2 null");
-  SG_ARG_CHECK(ws_bytes >= sg_conv2d_sparse_ws_bytes(d, L, 0), "sg_conv2d_fwd_sparse: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int K = (d->C1 + d->C2) * d->KS * d->KS;
   Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
@@ -251,11 +275,11 @@ extern "C" int sg_conv2d_wgrad_sparse(const sgConvDesc* d, const float* gy, cons
 extern "C" int sg_conv2d_fwd_perimage(const sgConvDesc* d, const float* x1, const float* x2, const float* wimg,
                                       const float* bias, const int32_t* chan_list, const int32_t* chan_cnt, int L, float* y,
                                       int act, float slope, void* ws, size_t ws_bytes, sgStream stream) {
-  if (check_desc(d, "sg_conv2d_fwd_perimage") || check_sparse(d, chan_list, chan_cnt, L, "sg_conv2d_fwd_perimage")) return -1;
+  if (check_fwd_args(d, SG_FW_PERIMAGE, L, ptr_mod16(ws), ws_bytes, "sg_conv2d_fwd_perimage")) return -1;
+  SG_ARG_CHECK(chan_list && chan_cnt, "sg_conv2d_fwd_perimage: null channel list");
   sgk::t_alg_bytes = 4.0 * ((double)d->N * L * d->H * d->W + (double)d->N * d->Cout * L * d->KS * d->KS + (double)d->N * d->Cout * d->OH * d->OW);
   SG_ARG_CHECK(x1 && wimg && y && ws, "sg_conv2d_fwd_perimage: null pointer");
   SG_ARG_CHECK(d->C2 == 0 || x2, "sg_conv2d_fwd_perimage: C2>0 but x2 null");
-  SG_ARG_CHECK(ws_bytes >= sg_conv2d_sparse_ws_bytes(d, L, 0), "sg_conv2d_fwd_perimage: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int K = (d->C1 + d->C2) * d->KS * d->KS;
   Gather g = make_gather(x1, x2, d->C1, d->C2, d->H, d->W, d->upsample, d->OH, d->OW, d->stride, d->pad, d->pad_reflect);
@@ -368,6 +392,44 @@ extern "C" int sg_conv2d_wgrad_plan(const sgConvDesc* d, int entry, int L, int a
                                      entry == SG_WG_CONV, ws_bytes, pad_off);
   SG_ARG_CHECK(nl.err == nullptr, "sg_conv2d_wgrad_plan: %s", nl.err);
   *plan = nl.p;
+  return 0;
+}
+
+// host-only: the plan kn0_run / kn_sparse_run launch for an entry point's call (kn_plan / kn_sparse_plan, the functions the
+// launchers run from; check_fwd_args, the checks the entry points make)
+extern "C" int sg_conv2d_fwd_plan(const sgConvDesc* d, int entry, int L, int w_mod16, int y_mod16, int ws_mod16, size_t ws_bytes,
+                                  sgFwdPlan* plan) {
+  SG_ARG_CHECK(d && plan && entry >= SG_FW_CONV && entry <= SG_FW_PERIMAGE, "sg_conv2d_fwd_plan: bad arguments");
+  for (const int m : {w_mod16, y_mod16, ws_mod16})
+    SG_ARG_CHECK(m == 0 || m == 4 || m == 8 || m == 12, "sg_conv2d_fwd_plan: a mod16 argument is 0, 4, 8 or 12");
+  if (check_fwd_args(d, entry, L, ws_mod16, ws_bytes, "sg_conv2d_fwd_plan")) return -1;
+  const int KS2 = d->KS * d->KS, M = d->Cout, PHW = d->OH * d->OW, Npix = d->N * PHW;
+  sgFwdPlan p = {};
+  p.two = d->C2 > 0 ? 1 : 0;
+  p.bcast = (d->C2 > 0 && d->x2_broadcast) ? 1 : 0;
+  int tile;
+  if (entry == SG_FW_CONV) {
+    const int K = (d->C1 + d->C2) * KS2;
+    const KnPlan pl = kn_plan(d->KS, 0, M, K, Npix, true, w_mod16 == 0, d->C2 > 0, d->pad_reflect != 0, 0u, ws_bytes, PHW, y_mod16 == 0,
+                              ws_mod16 == 0);
+    tile = pl.tile;
+    p.a_vec = pl.vec ? 1 : 0;
+    p.loader = pl.fixed ? SG_FW_FIXED : SG_FW_TABLE;
+    p.nomask = (pl.nomask && !pl.fixed) ? 1 : 0;          // (the fixed-tap loader has one form: launch_ab ignores nomask for it)
+    p.K = K; p.splits = pl.splits;
+    p.kchunk = splitk_chunk(K, pl.splits, BK * SG_NSUB, 0);
+    p.reduce = pl.reduce; p.batched = 0;
+    p.ws_needed = (int64_t)(ktab_bytes(K) + (pl.splits > 1 ? (size_t)pl.splits * M * Npix * sizeof(float) : 0));
+  } else {
+    const KnSparsePlan pl = kn_sparse_plan(KS2, M, L, d->N, PHW, d->pad_reflect != 0);
+    tile = pl.tile;
+    p.a_vec = 1; p.loader = SG_FW_TABLE; p.nomask = pl.nomask ? 1 : 0;
+    p.K = pl.Kc; p.splits = 1; p.kchunk = pl.Kc; p.reduce = SG_FR_NONE; p.batched = 1;
+    p.ws_needed = (int64_t)sparse_fwd_ws(d->N, M, L, KS2);
+  }
+  p.bm = tile == 0 ? 128 : (tile == 2 ? 32 : 64);
+  p.bn = tile == 1 ? 64 : 128;
+  *plan = p;
   return 0;
 }
 

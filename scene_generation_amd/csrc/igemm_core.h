@@ -2044,9 +2044,11 @@ inline size_t ktab_bytes(int K) { return (size_t)(sg_cdiv(K, 64) * 64 + 128) * s
 // gathers).  full_m: the launch writes every row of the result (Mtot == M: split-K allowed); a16: A is 16-byte aligned;
 // two / reflect: the gather's second source / reflection padding; vstride: per-tap source copies (kn1_run); ws_avail: bytes behind
 // the k-table workspace pointer (table + split-K slabs)
-struct KnPlan { bool vec; int tile; bool nomask; int splits; bool fixed; };
+// PHW / out16 / ws16: pixels per image, and whether the result and the workspace are 16-byte aligned -- they choose the kernel
+// that adds the split-K slabs (reduce: SG_FR_*; the slabs start ktab_bytes(K), a multiple of 16, behind the workspace pointer)
+struct KnPlan { bool vec; int tile; bool nomask; int splits; bool fixed; int reduce; };
 inline KnPlan kn_plan(int KS, int MODE, int M, int K, int Npix, bool full_m, bool a16, bool two, bool reflect, unsigned vstride,
-                      size_t ws_avail) {
+                      size_t ws_avail, int PHW = 0, bool out16 = false, bool ws16 = false) {
   KnPlan p;
   p.vec = (K % 4 == 0) && a16;
   p.tile = pick_tile(M, Npix);
@@ -2066,6 +2068,24 @@ inline KnPlan kn_plan(int KS, int MODE, int M, int K, int Npix, bool full_m, boo
   }
   // 4x4 and 1x1 kernels on one source with whole channels per k-tile: fixed taps per thread (LoadFixedKN)
   p.fixed = fixed_taps_enabled() && (KS == 4 || KS == 1) && p.vec && !two && K % BK == 0 && vstride == 0;
+  // the float4 slab reduce needs the four lanes of a vector in one channel plane and aligned slabs / result
+  const size_t nout = (size_t)M * Npix;
+  p.reduce = p.splits <= 1 ? SG_FR_NONE : ((nout % 4 == 0 && PHW % 4 == 0 && PHW > 0 && ws16 && out16) ? SG_FR_VEC : SG_FR_SCALAR);
+  return p;
+}
+
+// THE launch plan of the channel-sparse / per-image forward (run_kn_sparse launches exactly this; sg_conv2d_fwd_plan reports it).
+// The compact weights Wc are always read as float4 (the workspace is 16-byte aligned, Kc % 16 == 0); tiles never straddle images,
+// so the mask-free kernels need full pixel tiles PER IMAGE; the k extent of an image comes from kcnt, so no split-K
+inline int sparse_kc(int L, int KS2);
+inline int sparse_kpad(int L, int KS2);
+struct KnSparsePlan { int tile; bool nomask; int Kc, Kpad; };
+inline KnSparsePlan kn_sparse_plan(int KS2, int M, int L, int NB, int PHW, bool reflect) {
+  KnSparsePlan p;
+  p.Kc = sparse_kc(L, KS2); p.Kpad = sparse_kpad(L, KS2);
+  p.tile = pick_tile(M, NB * PHW);
+  const int tBM = p.tile == 0 ? 128 : (p.tile == 2 ? 32 : 64), tBN = p.tile == 1 ? 64 : 128;
+  p.nomask = reflect && (PHW % tBN == 0) && (M % tBM == 0);
   return p;
 }
 
@@ -2073,7 +2093,8 @@ template <int KS, int MODE>
 int run_kn(const float* A, int M, int K, const Gather& g, int NB, const float* bias, float* out, int Mtot, int act,
            float slope, double flops, void* ktab_ws, size_t ws_avail, hipStream_t s) {
   const int Npix = NB * g.PH * g.PW;
-  const KnPlan pl = kn_plan(KS, MODE, M, K, Npix, Mtot == M, aligned16(A), g.C2 > 0, g.reflect != 0, t_variant_stride, ws_avail);
+  const KnPlan pl = kn_plan(KS, MODE, M, K, Npix, Mtot == M, aligned16(A), g.C2 > 0, g.reflect != 0, t_variant_stride, ws_avail,
+                            g.PH * g.PW, aligned16(out), aligned16(ktab_ws));
   const bool vec = pl.vec, nomask = pl.nomask;
   const int tile = pl.tile, splits = pl.splits;
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ktab_ws) + ktab_bytes(K));
@@ -2100,10 +2121,9 @@ int run_kn(const float* A, int M, int K, const Gather& g, int NB, const float* b
       default: launch_ab<typename CfgFor<KS>::C32, 32, 128, KS, MODE>(A, K, M, vec, g, Npix, ktab, ep, splits, nomask, s, fx); break;
     }
   }
-  if (splits > 1)
-  {
+  if (pl.reduce != SG_FR_NONE) {
     const int PHWo = g.PH * g.PW;
-    if (nout % 4 == 0 && PHWo % 4 == 0 && aligned16(slabs) && aligned16(out))
+    if (pl.reduce == SG_FR_VEC)
       hipLaunchKernelGGL(slab_reduce_nchw_vec_kernel, dim3(sg_cdiv(nout / 4, 256)), dim3(256), 0, s, (const float4*)slabs,
                          (float4*)out, nout / 4, splits, bias, PHWo / 4, Mtot, act, slope);
     else

@@ -1,4 +1,6 @@
-// conv-style gathers: conv forward, transposed-conv data gradient, channel-sparse / per-image forward (see igemm_core.h / igemm.hip)
+// conv-style gathers: conv forward, transposed-conv data gradient, channel-sparse / per-image forward (see igemm_core.h / igemm.hip).
+// Both launchers run from a plan struct -- run_kn<KS, 0> from kn_plan, run_kn_sparse from kn_sparse_plan (igemm_core.h) -- which
+// sg_conv2d_fwd_plan (igemm.hip) reports without touching the device; tests/forward_conv_cases.py names one row per plan class.
 #include "igemm_core.h"
 
 namespace {
@@ -44,13 +46,13 @@ int run_kn_sparse(const float* W, int M, int K, const Gather& g, int NB, const f
                   float slope, const Sparse& sp, void* ws, hipStream_t s) {
   constexpr int KS2 = KS * KS;
   const int PHW = g.PH * g.PW, Npix = NB * PHW;
-  const int Kc = sparse_kc(sp.L, KS2), Kpad = sparse_kpad(sp.L, KS2);
+  // every decision below is kn_sparse_plan's (igemm_core.h), which sg_conv2d_fwd_plan reports
+  const KnSparsePlan pl = kn_sparse_plan(KS2, M, sp.L, NB, PHW, g.reflect != 0);
+  const int Kc = pl.Kc, Kpad = pl.Kpad, tile = pl.tile;
+  const bool nomask = pl.nomask;
   KEntry* ktab = reinterpret_cast<KEntry*>(ws);
   float* Wc = reinterpret_cast<float*>(ktab + (size_t)NB * Kpad);
   int* kcnt = reinterpret_cast<int*>(Wc + (size_t)NB * M * Kc);
-  int tile = pick_tile(M, Npix);
-  const int tBM = tile == 0 ? 128 : (tile == 2 ? 32 : 64), tBN = tile == 1 ? 64 : 128;
-  const bool nomask = g.reflect && (PHW % tBN == 0) && (M % tBM == 0);
   {
     const int work = M * Kc > Kpad ? M * Kc : Kpad;
     hipLaunchKernelGGL(build_sparse_fwd_kernel, dim3(sg_cdiv(work, 256), NB), dim3(256), 0, s, W, M, K, KS2, g.C1, g.C2,

@@ -461,6 +461,10 @@ def conv2d(x, weight, bias=None, stride=1, pad=0, reflect=False, upsample=1, act
     then only computed for channels >= c, the rest is returned as zeros); 'sparse' = (chan_list, chan_cnt) promises that,
     per image, every channel outside the list is all-zero (forward and weight gradient then only visit the listed
     channels, sg_conv2d_*_sparse); 'factored' = the layout as planes x per-object vectors (factored_layout_conv)."""
+    if reflect and not (0 <= pad < min(x.size(2), x.size(3)) * upsample):
+        # what nn.ReflectionPad2d raises; the kernels mirror a coordinate once, so the library's desc check refuses it as well
+        raise RuntimeError('conv2d: reflection padding %d must be less than the (upsampled) input size %d x %d on both axes'
+                           % (pad, x.size(2) * upsample, x.size(3) * upsample))
     h = hints_of(x)
     if (_core.UPCONV and upsample == 2 and stride == 1 and pad == 1 and not reflect and x2 is None and h is None
             and act == ACT_NONE and weight.size(2) == 3 and weight.size(3) == 3 and not _upconv_prefers_winograd(x, weight)):

@@ -125,6 +125,24 @@ def test_install_as_runs_reference_train_py_imports_and_trainer_construction(tmp
     assert r.returncode == 0 and 'DROPIN_OK' in r.stdout, textwrap.shorten(r.stdout + r.stderr, 4000)
 
 
+def test_conv2d_rejects_the_reflection_pad_torch_refuses():
+    """a reflection pad that reaches the plane's size on EITHER axis: torch refuses it, and so does the drop-in conv -- before any
+    device call (the kernels mirror a coordinate once; the library's desc check is the second line)"""
+    import pytest
+    import torch
+    import torch.nn.functional as F
+    from scene_generation_amd import ops
+    w = torch.zeros(4, 2, 7, 7)
+    for shape, ups in (((1, 2, 8, 3), 1), ((1, 2, 3, 8), 1), ((1, 2, 3, 3), 1), ((1, 2, 4, 1), 2)):
+        x = torch.zeros(shape)
+        with pytest.raises(RuntimeError):
+            ops.conv2d(x, w, None, stride=1, pad=3, reflect=True, upsample=ups)
+        with pytest.raises(RuntimeError):
+            F.pad(F.interpolate(x, scale_factor=ups, mode='nearest'), (3,) * 4, mode='reflect')
+    with pytest.raises(RuntimeError):
+        ops.conv2d(torch.zeros(1, 2, 5, 5), w, None, stride=1, pad=-1, reflect=True)
+
+
 def test_install_as_without_host_checkout_only_overlays_hot_path(tmp_path):
     """On a box without the reference (the GPU box): the alias resolves the hot-path modules and leaves
     ``scene_generation.data`` absent instead of breaking them."""

@@ -129,6 +129,8 @@ def _linear_case(hip, rows, inf, outf, act):
 
 
 CONV_CASES = [
+    # (operator-level parity in fp32.  Which tile, loader, mask or split a shape runs on the forward gather -- and a float64 bound for
+    #  each such plan, through the C ABI -- is the table of tests/forward_conv_cases.py, run by tests/test_gpu_forward_conv.py)
     # N, C1, C2, H, W, Cout, KS, stride, pad, reflect, ups, act
     (2, 5, 0, 12, 12, 8, 3, 1, 1, False, 1, 0),
     (2, 12, 0, 16, 16, 8, 7, 1, 3, True, 1, 1),        # ReflectionPad(3)+Conv7 (generators.py:68)
