@@ -648,6 +648,48 @@ int sg_triple_agreement(const int64_t* triples, const float* boxes, const float*
  * counts[1, :] likewise for the location block and loc_idx.  Rows without a set bit count for nothing. */
 int sg_attribute_agreement(const float* attrs, const int32_t* size_idx, const int32_t* loc_idx, int64_t* counts, int O, int S,
                            int g, sgStream stream);
+/* ---- size and location attributes from class statistics (attributes.hip; scene_generation_amd/attributes.py) --------------------
+ * The two ends of the reference's attribute sampler: the per-class counts of scripts/create_attributes_file.py and the draw of
+ * --sample_attributes (data/coco_panoptic.py:336-340,389-391,432-449,468-521).  All integers.  S = size_len, g = grid side (cell =
+ * col + g * row), A = S + g * g; predicates as above, opposites 1<->2, 3<->4, 5<->6; class image_class is the __image__ object.
+ *
+ * Statistics: counts [C, A] int64.  A row of attrs [O, A] fp32 contributes its FIRST set bit (> 0.5f) of the size block and of the
+ * location block, independently; a block without a bit contributes nothing.  Rows of class image_class
+ * (create_attributes_file.py:127) and of classes outside [0, C) are skipped.  The call ADDS (integer atomics: exact whatever the
+ * order), so a dataset is accumulated batch by batch. */
+int sg_attribute_histogram(const int64_t* objs, const float* attrs, int64_t* counts, int O, int C, int S, int g, int image_class,
+                           sgStream stream);
+/* draw(w, allowed, u) over int64 weights w_c = hist_c * allowed_c: if their sum is 0 (a class never seen, or never seen in the
+ * allowed cells; a class outside [0, C) counts as never seen) w_c = allowed_c; with t = double(u) * double(sum) the result is the
+ * smallest c whose inclusive prefix sum, converted to double, is > t.  Exact and independent of evaluation order.  u [O, 2] fp32 in
+ * [0, 1) (clamped to [0, 1 - 2^-24]): column 0 is object o's size draw, column 1 its location draw, each used at most once, so an
+ * image's result does not depend on its place in the batch.  Image n owns the objects with obj_to_img == n and the triples with
+ * triple_to_img == n (both vectors sorted ascending; the ranges are found by binary search).  Per image, in this order:
+ *  1. a real object whose size block of ``given`` [O, A] (may be null) holds a bit keeps its first one, else
+ *     size = draw(size_hist[class], all, u[o, 0]); a given location bit counts as set from the start.  Given bits never change.
+ *  2. the __image__ object gets size S - 1 and the cell c + g * c, c = rint(0.5 * (g - 1)) (ties to even), unless given.
+ *  3. the image's triples (s, p, o) in stored order; skipped when p is outside 1..6, s == o, either end is an __image__ object or
+ *     lies outside the image.  For each kept one step(s, p, o), then step(o, opposite(p), s).
+ *  4. step(a, q, b): loc[a] set: nothing.  loc[b] unset: loc[a] = draw(loc_hist[class a], all, u[a, 1]).  loc[b] set and q inside /
+ *     surrounding: loc[a] = loc[b] and, unless a's size was given, the size rule below.  loc[b] set and q in 1..4:
+ *     loc[a] = draw(loc_hist[class a], allowed(q, loc[b]), u[a, 1]) with (col_b, row_b) of loc[b]:
+ *       left of: col <= max(col_b - 1, 0)       right of: col >= min(col_b + 1, g - 1)
+ *       above:   row <= max(row_b - 1, 0)       below:    row >= min(row_b + 1, g - 1)
+ *  5. real objects that still have no location draw one unrestricted.
+ * Size rule SG_ATTR_RULE_REFERENCE (coco_panoptic.py:478-489 as written; the surrounding object becomes the smaller one):
+ *     surrounding: size_b <= size_a -> size_a = max(0, size_b - 1);   inside: size_b >= size_a -> size_a = min(S - 1, size_b + 1)
+ * SG_ATTR_RULE_GEOMETRIC (the evident intent):
+ *     surrounding: size_a <= size_b -> size_a = min(S - 1, size_b + 1);   inside: size_a >= size_b -> size_a = max(0, size_b - 1)
+ * One wavefront per image, one lane per cell: 1 <= S <= 64 and g * g <= 64 (else an error before any launch).  Every element of
+ * size_idx [O] / loc_idx [O] int32 and attrs [O, A] fp32 (the one-hot block) is written: -1 and no bit where nothing was assigned
+ * (objects of no image in [0, N), and the objects past the first SG_ATTR_MAX_OBJS of an image, whose triples are skipped).
+ * SG_ATTR_MAX_OBJS: 13 bytes of LDS per object, 13 KB per wavefront, which leaves twelve images resident per CU. */
+#define SG_ATTR_MAX_OBJS 1024
+#define SG_ATTR_RULE_REFERENCE 0
+#define SG_ATTR_RULE_GEOMETRIC 1
+int sg_sample_attributes(const int64_t* objs, const int64_t* obj_to_img, const int64_t* triples, const int64_t* triple_to_img,
+                         const int64_t* counts, const float* u, const float* given, int32_t* size_idx, int32_t* loc_idx, float* attrs,
+                         int N, int O, int T, int C, int S, int g, int image_class, int size_rule, sgStream stream);
 /* ---- the object-accuracy classifier (classifier.hip; scene_generation_amd/accuracy.py) ------------------------------------------
  * What a torchvision ResNet (scripts/train_accuracy_net.py:62-101) needs beyond the entry points above.  No float atomics: every
  * result is bit-identical from run to run.  Base pointers may be unaligned (16-byte loads are used only where they allow it).

@@ -133,6 +133,8 @@ enum {
   SG_K_FIDINF_GRAMS, SG_K_FIDINF_TERMS,
   // the gradient control of the fused Adam step (loss.hip): the float64 sum of squares of a flat gradient buffer (4 B per element)
   SG_K_GRAD_NORM,
+  // size and location attributes from class statistics (attributes.hip): the per-class counts, the constrained draw
+  SG_K_ATTRIBUTES_HIST, SG_K_ATTRIBUTES_SAMPLE,
   SG_K_COUNT
 };
 static inline int sg_igemm_kind(int family, int KS, int tile) {

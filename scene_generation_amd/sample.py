@@ -3,6 +3,7 @@ scene_generation/data/utils.py it needs).
 
     python -m scene_generation_amd.sample --checkpoint CKPT.pt --output_dir OUT [--weights ema] [--scene_graphs FILE.json [--bank DIR]]
                                           [--layouts FILE.json] [--consistent_graphs 1] [--graph_metrics 1]
+                                          [--sample_attributes 1 --attributes_file F.pickle [--attribute_size_rule geometric]]
 
 * ``Sampler``: one test-mode forward per collated batch (``sample_batch``, the flags of sample_images.py:203-221) or per list of
   scene graphs written by a person (``sample_json`` -> Model.forward_json), then the device-side ``imagenet_deprocess_batch``
@@ -13,6 +14,9 @@ scene_generation/data/utils.py it needs).
 * the box IoU bookkeeping of sample_images.py:241-255 as tensor operations (``iou_totals``), read once at the end.
 * ``graph_metrics`` (off by default): how many of the call's triples and attribute bits the predicted boxes and masks honour
   (scene_generation_amd.scenegraph), accumulated on the device next to the IoU totals and read once by ``graph_summary``.
+* ``sample_attributes`` (off by default; needs ``attribute_stats``, an ``attributes.AttributeStats``): the size and location blocks a
+  batch or a scene graph does not give are drawn from the class statistics under the graph's relations (one launch,
+  scene_generation_amd.attributes), the reference's ``--sample_attributes 1``; bits that are given are kept.
 * ``accuracy`` (an ``accuracy.AccuracyMeter``, off by default): the object classifier's verdict on the crops of the generated images
   (sample_images.py:224-239), accumulated on the device and read once; ``--accuracy_model_path`` on the command line.
 * ``inception`` (an ``inception.InceptionScore``, off by default): the Inception score of the generated images (train.py:177-225
@@ -91,10 +95,23 @@ class Sampler(object):
     sampled without ground-truth textures (features_clustered_001.npy of the reference).  ``colors``: [num_objs, 3] table of the
     label-map picture (default: torch.randint(0, 256), sample_images.py:197).  ``factored``: run the generator's stem on the
     factored test-mode layout (Model.factored_test_layout).  ON by default: measured on MI355X at N = 32 / 128 x 128, 6.82 against
-    7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline."""
+    7.98 ms per batch with a spread of 0.17 ms between blocks; ``factored=False`` is the dense baseline.
+    ``sample_attributes`` (with ``attribute_stats``): attribute blocks without a bit are drawn from the class statistics
+    (attributes.sample_attributes, size rule ``attribute_size_rule``); call k of this sampler draws with seed ``attribute_seed + k``,
+    so successive batches differ and a run is reproducible.  Off: nothing new is launched."""
 
     def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None,
-                 fid=None, diversity=None, sets=None):
+                 fid=None, diversity=None, sets=None, attribute_stats=None, sample_attributes=False, attribute_seed=0,
+                 attribute_size_rule='reference'):
+        self.sample_attributes = bool(sample_attributes)
+        if self.sample_attributes:
+            from .attributes import SIZE_RULES
+            if attribute_stats is None:
+                raise ValueError('sample_attributes needs the class statistics (Sampler(attribute_stats=...) / --attributes_file)')
+            if attribute_size_rule not in SIZE_RULES:
+                raise ValueError('attribute_size_rule %r: expected one of %s' % (attribute_size_rule, ', '.join(SIZE_RULES)))
+        self.attribute_stats, self.attribute_size_rule = attribute_stats, attribute_size_rule
+        self.attribute_seed = int(attribute_seed)      # the seed of the NEXT call's table of uniforms
         self.diversity = diversity           # lpips.Diversity fed by sample_pair, or None
         self.sets = sets                     # featsets.FeatureSetMetrics whose fake side every forward feeds, or None
         self.model, self.features, self.factored = model, features, bool(factored)
@@ -149,7 +166,7 @@ class Sampler(object):
         sample_images.py:203-221.  Without ground-truth textures every object takes a random row of its class's bank, drawn with
         ``random.randint`` in object order like the reference (``random.seed`` reproduces it).  (``_scored=False``, the second
         forward of ``sample_pair``: the same forward with no scorer fed and no counter touched.)"""
-        imgs, objs, boxes, masks, triples, obj_to_img, _, attributes = [t.to(self.device) for t in batch]
+        imgs, objs, boxes, masks, triples, obj_to_img, triple_to_img, attributes = [t.to(self.device) for t in batch]
         objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()        # the call's one host synchronisation
         features = None
         if not use_gt_textures:
@@ -163,6 +180,10 @@ class Sampler(object):
         given_attributes = attributes        # what the batch specified: the graph metrics score these
         if not use_gt_attr:
             attributes = torch.zeros_like(attributes)
+        if self.sample_attributes and _scored:                          # blocks without a bit are drawn; the metrics score the result
+            attributes = given_attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, triple_to_img)
+        elif self.sample_attributes:                                    # the second forward of a pair: the first one's draw again
+            attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, triple_to_img, advance=-1)
         m = self.model
         score = None
         if _scored and self.accuracy is not None:        # sample_images.py:224-239: crops at the ground-truth boxes when they drive the layout
@@ -202,10 +223,23 @@ class Sampler(object):
             scene_graphs = [scene_graphs]
         objs, triples, obj_to_img, attributes, features = m.encode_scene_graphs(scene_graphs)
         objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()
+        if self.sample_attributes:
+            attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h)
         out = self._forward(lambda: m(None, objs, triples, obj_to_img, attributes=attributes, test_mode=True, use_gt_box=False,
                                       features=features), objs_h, o2i_h, want_layout_rgb, want_layout, objs)
         self._graph_metrics(out, triples, attributes)
         return out
+
+    def _fill_attributes(self, objs, triples, obj_to_img, attributes, o2i_h, triple_to_img=None, advance=0):
+        """with ``sample_attributes``: one launch that draws the size / location blocks ``attributes`` leaves empty (given bits are
+        kept) with the seed of this call, then moves the seed on; no host synchronisation (the host list is the call's own).
+        ``advance=-1``: the previous call's seed again, and the seed stays."""
+        from .attributes import sample_attributes
+        seed = self.attribute_seed + advance
+        block, _, _ = sample_attributes(objs, triples, obj_to_img, self.attribute_stats, given=attributes, seed=seed,
+                                        triple_to_img=triple_to_img, obj_to_img_host=o2i_h, size_rule=self.attribute_size_rule)
+        self.attribute_seed = seed + 1
+        return block
 
     def _graph_metrics(self, out, triples, attributes):
         """with ``graph_metrics``: four launches that add to the counters (centroids of the predicted masks, triple agreement, the
@@ -383,6 +417,10 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     (+ images_gt, layouts), print and return the IoU summary and the paths written."""
     if getattr(args, 'real_features', None) is not None and getattr(args, 'inception_weights', None) is None:      # before any work
         raise ValueError('--real_features needs --inception_weights (the network whose features the rows are)')
+    want_attr = bool(getattr(args, 'sample_attributes', False))
+    if want_attr and not getattr(args, 'attributes_file', None):
+        raise ValueError('--sample_attributes 1 needs --attributes_file (python -m scene_generation_amd.attributes build, or the '
+                         'reference\'s attributes_10_25.pickle)')
     want_inf = bool(getattr(args, 'fid_infinity', False))
     if want_inf and getattr(args, 'fid_stats', None) is None:
         raise ValueError('--fid_infinity needs --fid_stats (the real statistics the extrapolated distance is measured to)')
@@ -395,6 +433,10 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if graphs and layouts:
         raise ValueError('--scene_graphs and --layouts: give one of them')
     metrics = bool(getattr(args, 'graph_metrics', False))
+    stats = None
+    if want_attr:
+        from .attributes import AttributeStats
+        stats = AttributeStats.load(args.attributes_file, model.vocab, device=device, num_classes=model.num_objs)
     if getattr(args, 'consistent_graphs', False) and model.num_preds < 7:
         raise ValueError('--consistent_graphs derives the six geometric predicates; the checkpoint knows %d' % model.num_preds)
     features = None
@@ -441,7 +483,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         diversity = Diversity(LPIPS(getattr(args, 'diversity_net', 'alex'), backbone_weights=div_backbone, lin_weights=div_lin,
                                     device=device), batch_size=args.batch_size)
     sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter,
-                      inception=scorer, fid=fid, diversity=diversity, sets=sets)
+                      inception=scorer, fid=fid, diversity=diversity, sets=sets, attribute_stats=stats, sample_attributes=want_attr,
+                      attribute_seed=getattr(args, 'attribute_seed', 0),
+                      attribute_size_rule=getattr(args, 'attribute_size_rule', 'reference'))
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -550,6 +594,13 @@ def make_parser():
                    'from the batch\'s own boxes and masks instead of drawn at random')
     p.add_argument('--graph_metrics', default=False, type=bool_flag, help='report how many of the requested relations and size / '
                    'location attributes the predicted layout honours')
+    p.add_argument('--sample_attributes', default=False, type=bool_flag, help='draw the size / location attributes a batch or a scene '
+                   'graph does not give from the class statistics of --attributes_file, under the graph\'s relations')
+    p.add_argument('--attributes_file', default=None, help='.pickle in the reference\'s format (attributes_10_25.pickle) or .npz, as '
+                   'python -m scene_generation_amd.attributes build writes them')
+    p.add_argument('--attribute_size_rule', default='reference', choices=['reference', 'geometric'], help='how "inside" / '
+                   '"surrounding" adjust a sampled size: as the reference does, or so that the surrounding object is the larger one')
+    p.add_argument('--attribute_seed', default=0, type=int, help='seed of the first batch\'s attribute draws; batch k uses seed + k')
     p.add_argument('--accuracy_model_path', default=None, help='the object classifier (python -m scene_generation_amd.accuracy '
                    'train, or the reference\'s resnet101_172_classes.pth): prints the Accuracy line of sample_images.py')
     p.add_argument('--accuracy_model_name', default='resnet101', help='its architecture: resnet18 / 34 / 50 / 101 / 152')
