@@ -34,13 +34,14 @@ __device__ __forceinline__ bool is_nan(float v) { return v != v; }
 // 64 x 64); 64 x 64 otherwise.  vec: 16-byte loads of the weight rows (K % 4 == 0 and an aligned base).  splits: the reduction cut
 // into k-chunks of whole k-tiles, at least 256 deep, when the tiles alone leave compute units idle (the 8 x 8 blocks: K = 1280 / 2048
 // over 64 pixels per image); the chunks are written as slabs and added in order by rect_reduce_kernel.
-inline RectPlan rect_plan(int M, int K, long Npix, bool w16) {
+inline RectPlan rect_plan(const sgRectDesc* d, bool w16) {
+  const RectDims n(d);
   RectPlan p;
-  p.vec = (K % 4 == 0 && w16) ? 1 : 0;
-  if (M <= 32) { p.tile = SG_RECT_TILE_32X128; p.bm = 32; p.bn = 128; }
-  else if ((long)sg_cdiv(M, 64) * sg_cdiv(Npix, 128) >= 768) { p.tile = SG_RECT_TILE_64X128; p.bm = 64; p.bn = 128; }
+  p.vec = (n.K % 4 == 0 && w16) ? 1 : 0;
+  if (n.M <= 32) { p.tile = SG_RECT_TILE_32X128; p.bm = 32; p.bn = 128; }
+  else if ((long)sg_cdiv(n.M, 64) * sg_cdiv(n.Npix, 128) >= 768) { p.tile = SG_RECT_TILE_64X128; p.bm = 64; p.bn = 128; }
   else { p.tile = SG_RECT_TILE_64X64; p.bm = 64; p.bn = 64; }
-  rect_plan_splits(p, M, K, Npix);
+  rect_plan_splits(p, n.M, n.K, n.Npix);
   return p;
 }
 
@@ -269,78 +270,37 @@ __global__ void __launch_bounds__(TPB) score_final_kernel(const double* __restri
 extern "C" int sg_conv2d_rect_plan(const sgRectDesc* d, int w_aligned16, sgRectPlan* plan) {
   SG_ARG_CHECK(rect_desc_ok(d), "sg_conv2d_rect_plan: bad desc");
   SG_ARG_CHECK(plan != nullptr, "sg_conv2d_rect_plan: null plan");
-  const RectPlan p = rect_plan(d->Cout, d->C * d->KH * d->KW, (long)d->N * d->OH * d->OW, w_aligned16 != 0);
-  plan->tile = p.tile; plan->bm = p.bm; plan->bn = p.bn; plan->vec = p.vec; plan->splits = p.splits; plan->kchunk = p.kchunk;
+  rect_plan_copy(rect_plan(d, w_aligned16 != 0), plan);
   return 0;
 }
 
-extern "C" size_t sg_conv2d_rect_ws_bytes(const sgRectDesc* d) {
-  if (!rect_desc_ok(d)) return 0;
-  const long Npix = (long)d->N * d->OH * d->OW;
-  const RectPlan p = rect_plan(d->Cout, d->C * d->KH * d->KW, Npix, true);
-  return p.splits > 1 ? (size_t)p.splits * d->Cout * Npix * sizeof(float) : 0;
-}
+extern "C" size_t sg_conv2d_rect_ws_bytes(const sgRectDesc* d) { return rect_desc_ok(d) ? rect_ws_bytes(rect_plan(d, true), d) : 0; }
 
 extern "C" int sg_conv2d_rect_fwd(const sgRectDesc* d, const float* x, const float* w, const float* bias, float* y, int act, void* ws,
                                   size_t ws_bytes, sgStream stream) {
   SG_ARG_CHECK(rect_desc_ok(d), "sg_conv2d_rect_fwd: bad desc (KH * KW <= %d, stride 1 or 2, 0 <= pad < kernel, OH / OW of the "
                "zero-padded conv, out_c0 + Cout <= out_ctot, tensors below 2^29 elements)", RECT_MAX_TAPS);
-  SG_ARG_CHECK(act == SG_ACT_NONE || act == SG_ACT_RELU, "sg_conv2d_rect_fwd: act must be SG_ACT_NONE or SG_ACT_RELU");
-  if (d->N == 0) return 0;
-  SG_ARG_CHECK(x && w && y, "sg_conv2d_rect_fwd: null operand");
   hipStream_t s = (hipStream_t)stream;
-  const int M = d->Cout, K = d->C * d->KH * d->KW, PHW = d->OH * d->OW, Npix = d->N * PHW;
-  const RectPlan pl = rect_plan(M, K, Npix, aligned16(w));
-  const size_t nout = (size_t)M * Npix;
-  SG_ARG_CHECK(pl.splits == 1 || (ws && ws_bytes >= (size_t)pl.splits * nout * sizeof(float)),
-               "sg_conv2d_rect_fwd: workspace of %zu bytes, sg_conv2d_rect_ws_bytes asks for %zu", ws_bytes,
-               (size_t)pl.splits * nout * sizeof(float));
-  const int KS2 = d->KH * d->KW, Kpad = sg_cdiv(K, 64) * 64 + 128;      // the k-loop prefetches entries up to two tiles past the end
-  const unsigned shw = (unsigned)(d->H * d->W);
-  // the same table (and cache key) as the square gathers': it depends on (K, taps per channel, C, plane size) only
-  const KEntry* ktab = reinterpret_cast<const KEntry*>(cached_table(
-      TabKey{0, K, Kpad, KS2, d->C, 0, shw, 0, 0, 0, 0, 0}, (size_t)Kpad * sizeof(KEntry), s, [&](void* dst) {
-        hipLaunchKernelGGL(build_ktab_kernel, dim3(sg_cdiv(Kpad, 256)), dim3(256), 0, s, reinterpret_cast<KEntry*>(dst), K, Kpad, KS2,
-                           d->C, 0, shw, 0, 0, 0u);
-      }));
-  SG_ARG_CHECK(ktab != nullptr, "sg_conv2d_rect_fwd: device allocation of the k-split table failed");
-  const Gather g = make_gather(x, nullptr, d->C, 0, d->H, d->W, 1, d->OH, d->OW, d->stride, 0, 0);
-  float* slabs = reinterpret_cast<float*>(ws);
-  EpNCHW ep{y + (size_t)d->out_c0 * PHW, bias, PHW, d->out_ctot, M, Npix, act, 0.f, 0, 0, 1, 0, 0, 0, 0};
-  if (pl.splits > 1) ep = EpNCHW{slabs, nullptr, PHW, M, M, Npix, SG_ACT_NONE, 0.f, nout, 0, 1, 0, 0, 0, 0};
-  const double flops = 2.0 * M * (double)K * Npix;
-  sgk::t_alg_bytes = 4.0 * ((double)d->N * d->C * shw + (double)M * K + (double)nout);
-  {
-    const bool vec = pl.vec != 0;
+  const RectPlan pl = rect_plan(d, aligned16(w));
+  const bool vec = pl.vec != 0;
+  const int kind = pl.tile == SG_RECT_TILE_32X128 ? SG_K_RECT_CONV_T32 : pl.tile == SG_RECT_TILE_64X128 ? SG_K_RECT_CONV_T64W : SG_K_RECT_CONV_T64;
+  return rect_fwd("sg_conv2d_rect", kind, pl, d, x, w, bias, y, act, ws, ws_bytes, s,
+                  [&](const Gather& g, const KEntry* ktab, const EpNCHW& ep, int M, int K, int Npix) {
     switch (pl.tile) {
-      case SG_RECT_TILE_32X128: {
-        SgProfScope prof(SG_K_RECT_CONV_T32, s, flops, sgk::t_alg_bytes);
+      case SG_RECT_TILE_32X128:
         rect_launch<CfgFor<3>::C32, 32, 128>(w, K, M, vec, RectGather<128>{g, Npix, ktab, d->KH, d->KW, d->padH, d->padW}, ep, Npix,
                                              pl.splits, s);
         break;
-      }
-      case SG_RECT_TILE_64X128: {
-        SgProfScope prof(SG_K_RECT_CONV_T64W, s, flops, sgk::t_alg_bytes);
+      case SG_RECT_TILE_64X128:
         rect_launch<CfgFor<3>::C64W, 64, 128>(w, K, M, vec, RectGather<128>{g, Npix, ktab, d->KH, d->KW, d->padH, d->padW}, ep, Npix,
                                               pl.splits, s);
         break;
-      }
-      default: {
-        SgProfScope prof(SG_K_RECT_CONV_T64, s, flops, sgk::t_alg_bytes);
+      default:
         rect_launch<CfgFor<3>::C64, 64, 64>(w, K, M, vec, RectGather<64>{g, Npix, ktab, d->KH, d->KW, d->padH, d->padW}, ep, Npix,
                                             pl.splits, s);
         break;
-      }
     }
-  }
-  SG_LAUNCH_CHECK("sg_conv2d_rect_fwd");
-  if (pl.splits > 1) {
-    SgProfScope prof(SG_K_RECT_REDUCE, s, 0.0, 4.0 * (double)nout * (pl.splits + 1));
-    hipLaunchKernelGGL(rect_reduce_kernel, dim3(sg_cdiv(nout, TPB)), dim3(TPB), 0, s, (const float*)slabs, y, (unsigned)nout, pl.splits,
-                       bias, PHW, M, d->out_c0, d->out_ctot, act, FastDiv((unsigned)PHW), FastDiv((unsigned)M));
-    SG_LAUNCH_CHECK("sg_conv2d_rect_fwd (slab reduction)");
-  }
-  return 0;
+  });
 }
 
 extern "C" int sg_maxpool3s2v_fwd(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, int out_c0, int out_ctot,

@@ -1,8 +1,10 @@
 // The rectangular gather of the forward convolutions with separate kernel extents and paddings: sg_conv2d_rect_fwd (inception.hip,
-// at most 25 taps) and sg_conv2d_wide_fwd (lpips.hip, up to 11 x 11) instantiate it with their own tap-table size.  Included after
-// igemm_core.h by those two units; everything has internal linkage.
+// at most 25 taps) and sg_conv2d_wide_fwd (lpips.hip, up to 11 x 11) instantiate it with their own tap-table size, and run the one
+// host body below (rect_fwd) behind their own limits, tile choice and tile dispatch.  Included after igemm_core.h by those two units;
+// everything has internal linkage.
 #pragma once
 #include "igemm_core.h"
+#include <string>
 
 namespace {
 
@@ -131,6 +133,64 @@ int rect_launch(const float* w, int K, int M, bool vec, const LoadGatherRect<BN,
                 hipStream_t s) {
   if (vec) return launch_cfg<CFG>(LoadKContig<BM, true>{w, K, M}, bl, ep, M, Npix, K, splits, s);
   return launch_cfg<CFG>(LoadKContig<BM, false>{w, K, M}, bl, ep, M, Npix, K, splits, s);
+}
+
+// ---- the host side both families share: a unit keeps its limits, its tile choice (a RectPlan from the desc) and its tile dispatch ---
+struct RectDims {
+  int M, K; long Npix;
+  explicit RectDims(const sgRectDesc* d) : M(d->Cout), K(d->C * d->KH * d->KW), Npix((long)d->N * d->OH * d->OW) {}
+};
+
+inline void rect_plan_copy(const RectPlan& p, sgRectPlan* plan) {
+  plan->tile = p.tile; plan->bm = p.bm; plan->bn = p.bn; plan->vec = p.vec; plan->splits = p.splits; plan->kchunk = p.kchunk;
+}
+
+// the slabs of a split plan
+inline size_t rect_ws_bytes(const RectPlan& p, const sgRectDesc* d) {
+  const RectDims n(d);
+  return p.splits > 1 ? (size_t)p.splits * n.M * n.Npix * sizeof(float) : 0;
+}
+
+// sg_<stem>_fwd behind the unit's desc check: the remaining argument checks, the k-split table, the gather and the epilogue, the GEMM
+// through launch(g, ktab, ep, M, K, Npix) -- the unit's rect_launch dispatch on pl.tile -- under profile kind ``kind``, then the slab reduction.
+template <class Launch>
+int rect_fwd(const char* stem, int kind, const RectPlan& pl, const sgRectDesc* d, const float* x, const float* w, const float* bias,
+             float* y, int act, void* ws, size_t ws_bytes, hipStream_t s, Launch launch) {
+  SG_ARG_CHECK(act == SG_ACT_NONE || act == SG_ACT_RELU, "%s_fwd: act must be SG_ACT_NONE or SG_ACT_RELU", stem);
+  if (d->N == 0) return 0;
+  SG_ARG_CHECK(x && w && y, "%s_fwd: null operand", stem);
+  const RectDims n(d);
+  const int M = n.M, K = n.K, PHW = d->OH * d->OW, Npix = (int)n.Npix;
+  const size_t nout = (size_t)M * Npix;
+  SG_ARG_CHECK(pl.splits == 1 || (ws && ws_bytes >= rect_ws_bytes(pl, d)), "%s_fwd: workspace of %zu bytes, %s_ws_bytes asks for %zu",
+               stem, ws_bytes, stem, rect_ws_bytes(pl, d));
+  const int KS2 = d->KH * d->KW, Kpad = sg_cdiv(K, 64) * 64 + 128;      // the k-loop prefetches entries up to two tiles past the end
+  const unsigned shw = (unsigned)(d->H * d->W);
+  // the k-split table (and cache key) of the square and rectangular gathers: it depends on (K, taps per channel, C, plane size) only
+  const KEntry* ktab = reinterpret_cast<const KEntry*>(cached_table(
+      TabKey{0, K, Kpad, KS2, d->C, 0, shw, 0, 0, 0, 0, 0}, (size_t)Kpad * sizeof(KEntry), s, [&](void* dst) {
+        hipLaunchKernelGGL(build_ktab_kernel, dim3(sg_cdiv(Kpad, 256)), dim3(256), 0, s, reinterpret_cast<KEntry*>(dst), K, Kpad, KS2,
+                           d->C, 0, shw, 0, 0, 0u);
+      }));
+  SG_ARG_CHECK(ktab != nullptr, "%s_fwd: device allocation of the k-split table failed", stem);
+  const Gather g = make_gather(x, nullptr, d->C, 0, d->H, d->W, 1, d->OH, d->OW, d->stride, 0, 0);
+  float* slabs = reinterpret_cast<float*>(ws);
+  EpNCHW ep{y + (size_t)d->out_c0 * PHW, bias, PHW, d->out_ctot, M, Npix, act, 0.f, 0, 0, 1, 0, 0, 0, 0};
+  if (pl.splits > 1) ep = EpNCHW{slabs, nullptr, PHW, M, M, Npix, SG_ACT_NONE, 0.f, nout, 0, 1, 0, 0, 0, 0};
+  const double flops = 2.0 * M * (double)K * Npix;
+  sgk::t_alg_bytes = 4.0 * ((double)d->N * d->C * shw + (double)M * K + (double)nout);
+  {
+    SgProfScope prof(kind, s, flops, sgk::t_alg_bytes);
+    launch(g, ktab, ep, M, K, Npix);
+  }
+  SG_LAUNCH_CHECK((std::string(stem) + "_fwd").c_str());
+  if (pl.splits > 1) {
+    SgProfScope prof(SG_K_RECT_REDUCE, s, 0.0, 4.0 * (double)nout * (pl.splits + 1));
+    hipLaunchKernelGGL(rect_reduce_kernel, dim3(sg_cdiv(nout, RECT_TPB)), dim3(RECT_TPB), 0, s, (const float*)slabs, y, (unsigned)nout,
+                       pl.splits, bias, PHW, M, d->out_c0, d->out_ctot, act, FastDiv((unsigned)PHW), FastDiv((unsigned)M));
+    SG_LAUNCH_CHECK((std::string(stem) + "_fwd (slab reduction)").c_str());
+  }
+  return 0;
 }
 
 }  // namespace

@@ -11,7 +11,6 @@ switches, layout hints, flat-buffer updates and the profiler front end: everythi
 import contextlib
 import os
 import ctypes
-import struct
 
 import torch
 from torch.autograd import Function
@@ -19,10 +18,12 @@ from torch.autograd import Function
 from .. import _hip
 from .._hip import sgConvDesc
 
-ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
-LOSS_MSE_CONST, LOSS_MSE, LOSS_L1, LOSS_BCE_CONST, LOSS_MEAN, LOSS_MSE_SIGMOID_CONST, LOSS_BCE_PROB_CONST = range(7)
-
-WSUM_MAX = 32
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH, ACT_SIGMOID = (
+    _hip.CONST['SG_ACT_' + n] for n in ('NONE', 'RELU', 'LEAKY', 'TANH', 'SIGMOID'))
+LOSS_MSE_CONST, LOSS_MSE, LOSS_L1, LOSS_BCE_CONST, LOSS_MEAN, LOSS_MSE_SIGMOID_CONST, LOSS_BCE_PROB_CONST = (
+    _hip.CONST['SG_LOSS_' + n] for n in ('MSE_CONST', 'MSE', 'L1', 'BCE_LOGITS_CONST', 'MEAN', 'MSE_SIGMOID_CONST', 'BCE_PROB_CONST'))
+WSUM_MAX = _hip.CONST['SG_WSUM_MAX']
+SG_ERR_INDEX = _hip.CONST['SG_ERR_INDEX']
 
 _ws_cache = {}
 
@@ -112,9 +113,6 @@ def _call(name, *args):
         if rc == SG_ERR_INDEX:          # an index operand outside its range: what the reference's indexing raises
             raise IndexError('%s: %s' % (name, _hip.last_error()))
         raise RuntimeError('%s failed (rc=%d): %s' % (name, rc, _hip.last_error()))
-
-
-SG_ERR_INDEX = -2
 
 
 def check_indices(idx, lo, hi, what):
@@ -431,7 +429,7 @@ def ema_update(e, p, w):
     return e
 
 
-GRAD_CTL_BYTES = 32              # sizeof(sgGradCtl), include/sg2im_hip.h
+GRAD_CTL_BYTES = ctypes.sizeof(_hip.sgGradCtl)
 
 
 def grad_ctl_alloc(device):
@@ -455,9 +453,7 @@ def grad_norm(g, ctl, ws, grad_scale=1.0, max_norm=0.0):
 
 def grad_ctl_read(ctl):
     """the record as a dict (one small device-to-host copy, which waits for the launches that write it)"""
-    raw = ctl.cpu().numpy().tobytes()[:GRAD_CTL_BYTES]
-    sumsq, norm, coef, skip, skipped, steps, _ = struct.unpack('<dffiiii', raw)
-    return {'sumsq': sumsq, 'norm': norm, 'coef': coef, 'skip': skip, 'skipped': skipped, 'steps': steps}
+    return _hip.plan_dict(_hip.sgGradCtl.from_buffer_copy(ctl.cpu().numpy().tobytes()[:GRAD_CTL_BYTES]))
 
 
 def adam_step_ctl(p, g, m, v, ctl, lr, beta1, beta2, eps, step, grad_scale=1.0):

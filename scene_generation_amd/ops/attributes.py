@@ -3,11 +3,12 @@ sg_sample_attributes.  No wrapper synchronises; outputs are fresh device tensors
 scene_generation_amd.ops: see ops/__init__.py.)"""
 import torch
 
+from .._hip import CONST
 from ._core import _call, _dev, _f32, _i64, _p, _stream
 from .scenegraph import _sg_counts
 
-ATTR_MAX_OBJS, ATTR_MAX_CELLS = 1024, 64           # SG_ATTR_MAX_OBJS of include/sg2im_hip.h; one lane of a wavefront per cell
-ATTR_SIZE_RULES = {'reference': 0, 'geometric': 1}  # SG_ATTR_RULE_*
+ATTR_MAX_OBJS, ATTR_MAX_CELLS = CONST['SG_ATTR_MAX_OBJS'], 64           # cells: one lane of a wavefront per cell
+ATTR_SIZE_RULES = {'reference': CONST['SG_ATTR_RULE_REFERENCE'], 'geometric': CONST['SG_ATTR_RULE_GEOMETRIC']}
 
 
 def _attr_block(t, O, A, name):

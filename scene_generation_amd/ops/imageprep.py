@@ -4,12 +4,13 @@ see ops/__init__.py.)"""
 import numpy as np
 import torch
 
+from .._hip import CONST
 from ._core import _L, _call, _p, _stream, workspace
 
-PIL_FILTERS = {'bilinear': 0, 'bicubic': 1}
-PIL_COEF, PIL_HORIZONTAL, PIL_VERTICAL, PIL_ALL = 1, 2, 4, 7       # the launches of one call (SG_PIL_COEF ... of the header)
-# the limits of include/sg2im_hip.h (SG_PIL_MAX_IN, SG_PIL_MAX_OUT, SG_PIL_MAX_IMAGES, SG_PIL_TABLE_COLS)
-PIL_MAX_IN, PIL_MAX_OUT, PIL_MAX_IMAGES, _TABLE_COLS = 16384, 4096, 65536, 9
+PIL_FILTERS = {'bilinear': CONST['SG_PIL_BILINEAR'], 'bicubic': CONST['SG_PIL_BICUBIC']}
+# the launches of one call
+PIL_COEF, PIL_HORIZONTAL, PIL_VERTICAL, PIL_ALL = (CONST['SG_PIL_' + n] for n in ('COEF', 'HORIZONTAL', 'VERTICAL', 'ALL'))
+PIL_MAX_IN, PIL_MAX_OUT, PIL_MAX_IMAGES, _TABLE_COLS = (CONST['SG_PIL_' + n] for n in ('MAX_IN', 'MAX_OUT', 'MAX_IMAGES', 'TABLE_COLS'))
 
 _lut_cache = {}
 

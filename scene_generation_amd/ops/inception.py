@@ -5,20 +5,11 @@ import ctypes
 
 import torch
 
+from .._hip import CONST, last_error, plan_dict, sgRectDesc, sgRectPlan      # noqa: F401  (the structs are re-exported)
 from ._core import ACT_NONE, ACT_RELU, _L, _call, _f32, _p, _stream, workspace
 
-RECT_TILE_64X64, RECT_TILE_32X128, RECT_TILE_64X128 = 1, 2, 3
+RECT_TILE_64X64, RECT_TILE_32X128, RECT_TILE_64X128 = (CONST['SG_RECT_TILE_' + n] for n in ('64X64', '32X128', '64X128'))
 RECT_TILES = {RECT_TILE_64X64: '64x64', RECT_TILE_32X128: '32x128', RECT_TILE_64X128: '64x128'}
-
-
-class sgRectDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in
-                ('N', 'C', 'H', 'W', 'Cout', 'KH', 'KW', 'stride', 'padH', 'padW', 'OH', 'OW', 'out_c0', 'out_ctot')]
-
-
-class sgRectPlan(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ('tile', 'bm', 'bn', 'vec', 'splits', 'kchunk')]
-
 
 _rect_cache = {}
 
@@ -28,55 +19,65 @@ def conv_out_size(size, k, stride, pad):
 
 
 def rect_desc(N, C, H, W, Cout, KH, KW, stride=1, padH=0, padW=0, out_c0=0, out_ctot=None):
-    """sgRectDesc for these sizes (one instance per shape: the ctypes reference and the workspace size are kept on it)"""
+    """sgRectDesc for these sizes (one instance per shape: the ctypes reference and the workspace sizes are kept on it)"""
     OH, OW = conv_out_size(H, KH, stride, padH), conv_out_size(W, KW, stride, padW)
     key = (N, C, H, W, Cout, KH, KW, stride, padH, padW, OH, OW, out_c0, Cout if out_ctot is None else out_ctot)
     d = _rect_cache.get(key)
     if d is None:
         d = sgRectDesc(*key)
         d._ref = ctypes.byref(d)
-        d._ws = None
+        d._ws = {}                      # stem of the entry point -> its workspace bytes
         _rect_cache[key] = d
     return d
 
 
+def _rect_plan(name, d, w_aligned16):
+    """the body of conv2d_rect_plan / conv2d_wide_plan (``name``: the stem of the entry point sg_<name>_plan)"""
+    plan = sgRectPlan()
+    if getattr(_L(), 'sg_%s_plan' % name)(d._ref, 1 if w_aligned16 else 0, ctypes.byref(plan)) != 0:
+        raise RuntimeError('sg_%s_plan failed: %s' % (name, last_error()))
+    return plan_dict(plan)
+
+
+def _rect_fwd(name, x, w, bias, stride, pad, act, out, out_c0, clamp=False):
+    """the body of conv2d_rect / conv2d_wide (``name``: the stem of the entry points sg_<name>_ws_bytes / _fwd).  ``clamp``: the
+    fresh result of a kernel larger than the padded plane is allocated empty, for the entry point to refuse it."""
+    x, w = _f32(x, 'conv input'), _f32(w, 'conv weight')
+    if x.dim() != 4 or w.dim() != 4 or w.size(1) != x.size(1):
+        raise ValueError('%s: x [N, C, H, W] and w [Cout, C, KH, KW], got %s and %s' % (name, tuple(x.shape), tuple(w.shape)))
+    if act not in (ACT_NONE, ACT_RELU):
+        raise ValueError('%s: act must be ACT_NONE or ACT_RELU' % name)
+    N, C, H, W = x.shape
+    Cout, _, KH, KW = w.shape
+    OH, OW = conv_out_size(H, KH, stride, pad[0]), conv_out_size(W, KW, stride, pad[1])
+    if out is None:
+        out = torch.empty(N, Cout, max(OH, 0) if clamp else OH, max(OW, 0) if clamp else OW, dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 4 or out.size(0) != N
+          or tuple(out.shape[2:]) != (OH, OW) or out_c0 < 0 or out_c0 + Cout > out.size(1)):
+        raise ValueError('%s: out must be a contiguous float32 device tensor [%d, >= %d, %d, %d], got %s'
+                         % (name, N, out_c0 + Cout, OH, OW, tuple(out.shape)))
+    if bias is not None:
+        bias = _f32(bias, 'conv bias')
+        if bias.numel() != Cout:
+            raise ValueError('%s: bias of %d elements for %d output channels' % (name, bias.numel(), Cout))
+    d = rect_desc(N, C, H, W, Cout, KH, KW, stride, pad[0], pad[1], out_c0, out.size(1))
+    ws_bytes = d._ws.get(name)
+    if ws_bytes is None:
+        ws_bytes = d._ws[name] = int(getattr(_L(), 'sg_%s_ws_bytes' % name)(d._ref))
+    ws = workspace(ws_bytes, x.device) if ws_bytes else None
+    _call('sg_%s_fwd' % name, d._ref, _p(x), _p(w), _p(bias), _p(out), act, _p(ws), ws_bytes, _stream())
+    return out
+
+
 def conv2d_rect_plan(d, w_aligned16=True):
     """-> dict(tile, bm, bn, vec, splits, kchunk): the launch sg_conv2d_rect_fwd issues for desc ``d`` (a host-only query)"""
-    plan = sgRectPlan()
-    rc = _L().sg_conv2d_rect_plan(d._ref, 1 if w_aligned16 else 0, ctypes.byref(plan))
-    if rc != 0:
-        from .. import _hip
-        raise RuntimeError('sg_conv2d_rect_plan failed: %s' % _hip.last_error())
-    return {n: int(getattr(plan, n)) for n, _ in sgRectPlan._fields_}
+    return _rect_plan('conv2d_rect', d, w_aligned16)
 
 
 def conv2d_rect(x, w, bias=None, stride=1, pad=(0, 0), act=ACT_NONE, out=None, out_c0=0):
     """act(conv2d(x, w [Cout, C, KH, KW], bias, stride, padding=pad)) written to channels [out_c0, out_c0 + Cout) of ``out``
     [N, Ctot, OH, OW] (a fresh [N, Cout, OH, OW] when None); the other channels of ``out`` are left alone.  -> out"""
-    x, w = _f32(x, 'conv input'), _f32(w, 'conv weight')
-    if x.dim() != 4 or w.dim() != 4 or w.size(1) != x.size(1):
-        raise ValueError('conv2d_rect: x [N, C, H, W] and w [Cout, C, KH, KW], got %s and %s' % (tuple(x.shape), tuple(w.shape)))
-    if act not in (ACT_NONE, ACT_RELU):
-        raise ValueError('conv2d_rect: act must be ACT_NONE or ACT_RELU')
-    N, C, H, W = x.shape
-    Cout, _, KH, KW = w.shape
-    OH, OW = conv_out_size(H, KH, stride, pad[0]), conv_out_size(W, KW, stride, pad[1])
-    if out is None:
-        out = torch.empty(N, Cout, OH, OW, dtype=torch.float32, device=x.device)
-    elif (out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 4 or out.size(0) != N
-          or tuple(out.shape[2:]) != (OH, OW) or out_c0 < 0 or out_c0 + Cout > out.size(1)):
-        raise ValueError('conv2d_rect: out must be a contiguous float32 device tensor [%d, >= %d, %d, %d], got %s'
-                         % (N, out_c0 + Cout, OH, OW, tuple(out.shape)))
-    if bias is not None:
-        bias = _f32(bias, 'conv bias')
-        if bias.numel() != Cout:
-            raise ValueError('conv2d_rect: bias of %d elements for %d output channels' % (bias.numel(), Cout))
-    d = rect_desc(N, C, H, W, Cout, KH, KW, stride, pad[0], pad[1], out_c0, out.size(1))
-    if d._ws is None:
-        d._ws = int(_L().sg_conv2d_rect_ws_bytes(d._ref))
-    ws = workspace(d._ws, x.device) if d._ws else None
-    _call('sg_conv2d_rect_fwd', d._ref, _p(x), _p(w), _p(bias), _p(out), act, _p(ws), d._ws, _stream())
-    return out
+    return _rect_fwd('conv2d_rect', x, w, bias, stride, pad, act, out, out_c0)
 
 
 def maxpool3s2v(x, out=None, out_c0=0):

@@ -4,9 +4,10 @@ x [P, D] whose rows are grouped by class (offsets [C + 1] int32).  Every per-pro
 import numpy as np
 import torch
 
+from .._hip import CONST
 from ._core import _L, _call, _dev, _f32, _p, _stream, workspace
 
-KMEANS_TILE, KMEANS_MAX_K, KMEANS_MAX_D = 1024, 256, 128       # SG_KMEANS_TILE / _MAX_K / _MAX_D of include/sg2im_hip.h
+KMEANS_TILE, KMEANS_MAX_K, KMEANS_MAX_D = CONST['SG_KMEANS_TILE'], CONST['SG_KMEANS_MAX_K'], CONST['SG_KMEANS_MAX_D']
 
 
 def _i32(t, name):

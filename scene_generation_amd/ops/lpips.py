@@ -1,13 +1,11 @@
 """The diversity score's own operators (csrc/lpips.hip): the wide forward convolution (kernels up to 11 x 11, stride up to 4: AlexNet's
 stem), the scaling layer of LPIPS and one tap of its distance.  Forward only (inference); no wrapper synchronises.  (Part of
 scene_generation_amd.ops: see ops/__init__.py.)"""
-import ctypes
-
 import torch
 
-from ._core import ACT_NONE, ACT_RELU, _L, _call, _dev, _f32, _p, _stream, workspace
+from ._core import ACT_NONE, _L, _call, _dev, _f32, _p, _stream, workspace
 from .fid import _pd
-from .inception import conv_out_size, rect_desc, sgRectPlan
+from .inception import _rect_fwd, _rect_plan
 
 LPIPS_EPS = 1e-10
 
@@ -15,42 +13,13 @@ LPIPS_EPS = 1e-10
 def conv2d_wide_plan(d, w_aligned16=True):
     """-> dict(tile, bm, bn, vec, splits, kchunk): the launch sg_conv2d_wide_fwd issues for desc ``d`` (``rect_desc``; a host-only
     query).  Raises for a desc the entry point rejects (more than 11 taps a side, stride above 4, pad >= kernel, wrong OH / OW)."""
-    plan = sgRectPlan()
-    rc = _L().sg_conv2d_wide_plan(d._ref, 1 if w_aligned16 else 0, ctypes.byref(plan))
-    if rc != 0:
-        from .. import _hip
-        raise RuntimeError('sg_conv2d_wide_plan failed: %s' % _hip.last_error())
-    return {n: int(getattr(plan, n)) for n, _ in sgRectPlan._fields_}
+    return _rect_plan('conv2d_wide', d, w_aligned16)
 
 
 def conv2d_wide(x, w, bias=None, stride=1, pad=(0, 0), act=ACT_NONE, out=None, out_c0=0):
     """``conv2d_rect`` for kernels up to 11 x 11 and strides 1..4: act(conv2d(x, w [Cout, C, KH, KW], bias, stride, padding=pad))
     written to channels [out_c0, out_c0 + Cout) of ``out`` [N, Ctot, OH, OW] (a fresh [N, Cout, OH, OW] when None).  -> out"""
-    x, w = _f32(x, 'conv input'), _f32(w, 'conv weight')
-    if x.dim() != 4 or w.dim() != 4 or w.size(1) != x.size(1):
-        raise ValueError('conv2d_wide: x [N, C, H, W] and w [Cout, C, KH, KW], got %s and %s' % (tuple(x.shape), tuple(w.shape)))
-    if act not in (ACT_NONE, ACT_RELU):
-        raise ValueError('conv2d_wide: act must be ACT_NONE or ACT_RELU')
-    N, C, H, W = x.shape
-    Cout, _, KH, KW = w.shape
-    OH, OW = conv_out_size(H, KH, stride, pad[0]), conv_out_size(W, KW, stride, pad[1])
-    if out is None:
-        out = torch.empty(N, Cout, max(OH, 0), max(OW, 0), dtype=torch.float32, device=x.device)
-    elif (out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 4 or out.size(0) != N
-          or tuple(out.shape[2:]) != (OH, OW) or out_c0 < 0 or out_c0 + Cout > out.size(1)):
-        raise ValueError('conv2d_wide: out must be a contiguous float32 device tensor [%d, >= %d, %d, %d], got %s'
-                         % (N, out_c0 + Cout, OH, OW, tuple(out.shape)))
-    if bias is not None:
-        bias = _f32(bias, 'conv bias')
-        if bias.numel() != Cout:
-            raise ValueError('conv2d_wide: bias of %d elements for %d output channels' % (bias.numel(), Cout))
-    d = rect_desc(N, C, H, W, Cout, KH, KW, stride, pad[0], pad[1], out_c0, out.size(1))
-    ws_bytes = getattr(d, '_wide_ws', None)
-    if ws_bytes is None:
-        ws_bytes = d._wide_ws = int(_L().sg_conv2d_wide_ws_bytes(d._ref))
-    ws = workspace(ws_bytes, x.device) if ws_bytes else None
-    _call('sg_conv2d_wide_fwd', d._ref, _p(x), _p(w), _p(bias), _p(out), act, _p(ws), ws_bytes, _stream())
-    return out
+    return _rect_fwd('conv2d_wide', x, w, bias, stride, pad, act, out, out_c0, clamp=True)
 
 
 def lpips_input(x, channels_last=False):

@@ -3,9 +3,10 @@ sg_draw_pairs / sg_triple_agreement / sg_attribute_agreement.  No wrapper synchr
 caller hands in an accumulator.  (Part of scene_generation_amd.ops: see ops/__init__.py.)"""
 import torch
 
+from .._hip import CONST
 from ._core import _call, _dev, _f32, _i64, _p, _stream
 
-SCENEGRAPH_MAX_M, SCENEGRAPH_MAX_P = 256, 64       # SG_SCENEGRAPH_MAX_M / _MAX_P of include/sg2im_hip.h
+SCENEGRAPH_MAX_M, SCENEGRAPH_MAX_P = CONST['SG_SCENEGRAPH_MAX_M'], CONST['SG_SCENEGRAPH_MAX_P']
 
 
 def _sg_i32(t, name):

@@ -11,6 +11,8 @@ import zlib
 
 import numpy as np
 
+from scene_generation_amd._hip import CONST
+
 from norm_cases import option  # noqa: F401  (re-exported: the option context manager)
 
 # ---- kernel constants the tables are built around (tests/test_dense_pointwise_cases_cpu.py reads them back from the sources)
@@ -23,12 +25,12 @@ GRID_Y_MAX = 65535      # sg_pad_upsample_bwd: planes per launch
 PLANES_PER_BLOCK = 4    # gap_fwd_kernel / cond_window_sums_kernel: one wave per plane, 256 threads
 U = 2.0 ** -24          # unit roundoff of fp32
 
-# include/sg2im_hip.h
-LINEAR_FWD, LINEAR_BWD_DATA, LINEAR_BWD_WEIGHT = 0, 1, 2
+# include/sg2im_hip.h, under the short names the tables use
+LINEAR_FWD, LINEAR_BWD_DATA, LINEAR_BWD_WEIGHT = (CONST['SG_LINEAR_' + n] for n in ('FWD', 'BWD_DATA', 'BWD_WEIGHT'))
 ENTRY_NAMES = {LINEAR_FWD: 'fwd', LINEAR_BWD_DATA: 'bwd_data', LINEAR_BWD_WEIGHT: 'bwd_weight'}
-LIN_SKINNY, LIN_TILED = 0, 1
-LIN_ROWMAJOR, LIN_KSCALAR, LIN_KVEC = 0, 1, 4
-ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH, ACT_SIGMOID = range(5)
+LIN_SKINNY, LIN_TILED = CONST['SG_LIN_SKINNY'], CONST['SG_LIN_TILED']
+LIN_ROWMAJOR, LIN_KSCALAR, LIN_KVEC = (CONST['SG_LIN_' + n] for n in ('ROWMAJOR', 'KSCALAR', 'KVEC'))
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH, ACT_SIGMOID = (CONST['SG_ACT_' + n] for n in ('NONE', 'RELU', 'LEAKY', 'TANH', 'SIGMOID'))
 ACTS = (ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH, ACT_SIGMOID)
 ACT_LIPSCHITZ = {ACT_NONE: 1.0, ACT_RELU: 1.0, ACT_LEAKY: 1.0, ACT_TANH: 1.0, ACT_SIGMOID: 0.25}
 

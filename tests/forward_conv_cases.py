@@ -25,6 +25,8 @@ import ctypes
 
 import numpy as np
 
+from scene_generation_amd._hip import CONST, plan_dict, sgFwdPlan
+
 from dense_pointwise_cases import gamma, rng_of, f32, act_ref, ACT_LIPSCHITZ, ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH  # noqa: F401
 from transposed_conv_cases import option, make_desc, conv_out_size  # noqa: F401  (re-exported)
 from wgrad_cases import _reflect, _axis, sources  # noqa: F401
@@ -39,19 +41,15 @@ OPTION_DEFAULTS = dict(tile=-1, t128_min=384, tile3=1, tile3_min=768, split_targ
 TAIL_DEFAULTS = dict(w43_tail_split=2, tail_smax=4, tail_ktmin=8)
 SLOPE = 0.2
 
-# include/sg2im_hip.h
-FW_CONV, FW_SPARSE, FW_PERIMAGE = 0, 1, 2
-FW_TABLE, FW_FIXED = 0, 1
-FR_NONE, FR_VEC, FR_SCALAR = 0, 1, 2
+# include/sg2im_hip.h, under the short names the tables use
+FW_CONV, FW_SPARSE, FW_PERIMAGE = (CONST['SG_FW_' + n] for n in ('CONV', 'SPARSE', 'PERIMAGE'))
+FW_TABLE, FW_FIXED = CONST['SG_FW_TABLE'], CONST['SG_FW_FIXED']
+FR_NONE, FR_VEC, FR_SCALAR = (CONST['SG_FR_' + n] for n in ('NONE', 'VEC', 'SCALAR'))
 ENTRY_OF = {'dense': FW_CONV, 'sparse': FW_SPARSE, 'perimage': FW_PERIMAGE}
 ENTRY_FN = {'dense': 'sg_conv2d_fwd', 'sparse': 'sg_conv2d_fwd_sparse', 'perimage': 'sg_conv2d_fwd_perimage'}
-PLAN_FIELDS = ('bm', 'bn', 'a_vec', 'loader', 'two', 'bcast', 'nomask', 'K', 'splits', 'kchunk', 'reduce', 'batched')
+PLAN_FIELDS = tuple(n for n, t in sgFwdPlan._fields_ if t is ctypes.c_int32)
 AMPLE = 8 << 20         # bytes: more workspace than any row's plan needs
 TILES = {0: (128, 128), 1: (64, 64), 2: (32, 128), 3: (64, 128)}
-
-
-class sgFwdPlan(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in PLAN_FIELDS] + [('ws_needed', ctypes.c_int64)]
 
 
 def fwd_plan(lib, desc, entry, L=0, w_mod16=0, y_mod16=0, ws_mod16=0, ws_bytes=AMPLE):
@@ -59,11 +57,7 @@ def fwd_plan(lib, desc, entry, L=0, w_mod16=0, y_mod16=0, ws_mod16=0, ws_bytes=A
     p = sgFwdPlan()
     rc = lib.sg_conv2d_fwd_plan(ctypes.byref(desc), int(entry), int(L), int(w_mod16), int(y_mod16), int(ws_mod16), int(ws_bytes),
                                 ctypes.byref(p))
-    if rc != 0:
-        return None
-    out = dict((n, getattr(p, n)) for n in PLAN_FIELDS)
-    out['ws_needed'] = p.ws_needed
-    return out
+    return None if rc else plan_dict(p)
 
 
 # =============================================================================================

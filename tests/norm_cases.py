@@ -8,8 +8,11 @@ shape alone and cannot drift from the dispatch.
 import contextlib
 import ctypes
 
+from scene_generation_amd._hip import CONST
+
 # include/sg2im_hip.h: SG_IN_*
-IN_THREE_PASS_WAVE, IN_THREE_PASS_BLOCK, IN_REG, IN_VEC, IN_BIG = range(5)
+IN_THREE_PASS_WAVE, IN_THREE_PASS_BLOCK, IN_REG, IN_VEC, IN_BIG = (
+    CONST['SG_IN_' + n] for n in ('THREE_PASS_WAVE', 'THREE_PASS_BLOCK', 'REG', 'VEC', 'BIG'))
 IN_KIND_NAMES = {IN_THREE_PASS_WAVE: 'three_pass_wave', IN_THREE_PASS_BLOCK: 'three_pass_block', IN_REG: 'reg', IN_VEC: 'vec',
                  IN_BIG: 'big'}
 INSTNORM_REG_VALUES = (0, 1, 2)          # the option instnorm_reg: three-pass kernels only / + register-resident / + float4 forms

@@ -56,8 +56,7 @@ def run(arrays, size, filt, want='both', packed_table=None):
 # =====================================================================================================================================
 def lds_chunk():
     """SG_PIL_LDS_CHUNK (include/sg2im_hip.h): the bytes of a source row the horizontal kernel stages in LDS at once"""
-    import re
-    return int(re.search(r'#define\s+SG_PIL_LDS_CHUNK\s+(\d+)', open(_hip.HEADER).read()).group(1))
+    return _hip.CONST['SG_PIL_LDS_CHUNK']
 
 
 def ragged_batch(size):

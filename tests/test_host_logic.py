@@ -32,6 +32,129 @@ def test_library_exports_every_declared_symbol():
     assert isinstance(lib.sg_last_error_string(), bytes)
 
 
+def test_every_struct_and_constant_of_the_header_is_bound():
+    """_hip.STRUCTS / _hip.CONST hold what a plain scan of the raw header finds, and nothing else"""
+    src = re.sub(r'/\*.*?\*/', ' ', open(_hip.HEADER).read(), flags=re.S)        # (a comment speaks of SG_CHECK_INDICES=1)
+    assert set(re.findall(r'typedef struct (\w+)', src)) == set(_hip.STRUCTS) and len(_hip.STRUCTS) >= 8
+    names = set(re.findall(r'\b(SG_\w+)\s*=\s*\(?-?\d', src)) | set(re.findall(r'#define\s+(SG_\w+)\s+\(?-?\d', src))
+    assert names == set(_hip.CONST), names ^ set(_hip.CONST)
+    for name, cls in _hip.STRUCTS.items():
+        assert getattr(_hip, name) is cls and issubclass(cls, ctypes.Structure) and cls.__name__ == name
+    assert (_hip.CONST['SG_ERR_INDEX'], _hip.CONST['SG_WSUM_MAX'], _hip.CONST['SG_LIN_KVEC'], _hip.CONST['SG_WA_ALL']) == (-2, 32, 4, 63)
+    d = _hip.sgConvDesc(1, 3, 0, 8, 8)
+    d._ref, d._memo, d._ws = ctypes.byref(d), {}, None           # the launch path keeps these on the instances
+    assert (d.N, d.C1, d.W, d.x2_broadcast) == (1, 3, 8, 0)
+
+
+def test_struct_layouts_equal_the_c_compilers(tmp_path):
+    """sizeof and every field's offset and size as the host C compiler of oracle/Makefile lays the header's structs out"""
+    import shutil
+    import subprocess
+    cc = os.environ.get('CC') or re.search(r'^CC \?= (\S+)', open(os.path.join(ROOT, 'oracle', 'Makefile')).read(), re.M).group(1)
+    if shutil.which(cc) is None:
+        pytest.skip('no host C compiler (%s)' % cc)
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sg2im_hip.h"', 'int main(void) {']
+    for name, cls in _hip.STRUCTS.items():
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        for f, _ in cls._fields_:
+            lines.append('  printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (name, f, name, f, name, f))
+    lines += ['  return 0;', '}']
+    (tmp_path / 'layout.c').write_text('\n'.join(lines) + '\n')
+    subprocess.check_call([cc, '-std=c99', '-Wall', '-Werror', '-I', os.path.dirname(_hip.HEADER), str(tmp_path / 'layout.c'), '-o',
+                           str(tmp_path / 'layout')])
+    got = dict((ln.split()[0], tuple(int(v) for v in ln.split()[1:]))
+               for ln in subprocess.check_output([str(tmp_path / 'layout')], text=True).splitlines())
+    want = {}
+    for name, cls in _hip.STRUCTS.items():
+        want[name] = (ctypes.sizeof(cls),)
+        for f, _ in cls._fields_:
+            want['%s.%s' % (name, f)] = (getattr(cls, f).offset, getattr(cls, f).size)
+    assert got == want
+    assert want['sgGradCtl'] == (32,) and want['sgTGatherPlan.K'] == (88, 16) and want['sgWgradPlan.ws_needed'] == (56, 8)
+
+
+@pytest.mark.parametrize('text,named', [
+    ('typedef struct sgBad { int32_t a; uint16_t x; } sgBad;', 'sgBad'),                 # an unknown field type
+    ('typedef struct sgBits { int32_t a : 3; } sgBits;', 'sgBits'),                       # a bit-field
+    ('typedef struct sgPtr { int32_t a; float* p; } sgPtr;', 'sgPtr'),
+    ('typedef struct sgTag { int32_t a; } sgOther;', 'sgTag'),
+    ('enum { SG_FIRST = 0, SG_IMPLICIT };', 'SG_IMPLICIT'),                               # an enumerator without an initialiser
+    ('enum { SG_FIRST = 0, SG_EXPR = 1 << 3 };', 'SG_EXPR'),
+    ('enum { SG_TWICE = 1 };\n#define SG_TWICE 2\n', 'SG_TWICE'),                         # a constant redefined to another value
+    ('#define SG_RATE 0.5f\n', 'SG_RATE'),
+])
+def test_header_parser_refuses_what_it_does_not_understand(text, named):
+    with pytest.raises(ValueError, match=named):
+        _hip.parse_types(text)
+
+
+def test_header_parser_forms():
+    structs, const = _hip.parse_types('typedef struct sgT {\n  int32_t a, b[2];  /* two */\n  int64_t n;  // one\n  float f; double d[3];\n} sgT;\n'
+                                      'enum { SG_A = 1, SG_B = -3, };\nenum { SG_A2 = 1 };\n#define SG_C (-2)\n#define SG_D 0x10\n#define SG_A 1\n')
+    t = structs['sgT']
+    assert [(n, ty._length_ if issubclass(ty, ctypes.Array) else 0) for n, ty in t._fields_] == [('a', 0), ('b', 2), ('n', 0), ('f', 0), ('d', 3)]
+    assert t._fields_[2][1] is ctypes.c_int64 and t._fields_[4][1]._type_ is ctypes.c_double
+    assert const == {'SG_A': 1, 'SG_B': -3, 'SG_A2': 1, 'SG_C': -2, 'SG_D': 16}
+    s = t(1, (2, 3), 4, 0.5, (1.0, 2.0, 3.0))
+    assert _hip.plan_dict(s) == {'a': 1, 'b': (2, 3), 'n': 4, 'f': 0.5, 'd': (1.0, 2.0, 3.0)} and isinstance(_hip.plan_dict(s)['b'], tuple)
+
+
+def test_grad_ctl_record_is_read_through_the_header_struct():
+    import struct
+    from scene_generation_amd import ops
+    assert ops.GRAD_CTL_BYTES == 32 == ctypes.sizeof(_hip.sgGradCtl)
+    raw = struct.pack('<dffiiii', 1.5e300, 0.25, 3.0, 1, 7, 9, 12345)
+    ctl = torch.from_numpy(np.frombuffer(raw, dtype=np.int64).copy())
+    assert ops.grad_ctl_read(ctl) == {'sumsq': 1.5e300, 'norm': 0.25, 'coef': 3.0, 'skip': 1, 'skipped': 7, 'steps': 9}
+
+
+def test_no_struct_is_declared_by_hand_in_python():
+    """the header is the only declaration of an ABI struct: no ctypes.Structure subclass outside _hip.py"""
+    found = []
+    for top in ('scene_generation_amd', 'tests', 'tools'):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                path = os.path.join(dirpath, f)
+                if f.endswith('.py') and os.path.abspath(path) not in (os.path.abspath(_hip.__file__), os.path.abspath(__file__)):
+                    text = open(path).read()
+                    if 'ctypes.Structure' in text or re.search(r'import[^\n]*\bStructure\b', text):
+                        found.append(os.path.relpath(path, ROOT))
+    assert found == []
+
+
+def test_plan_helpers_return_what_they_returned_before_the_structs_were_bound_from_the_header():
+    """tests/golden/plan_queries.json: the outputs of the four plan helpers of the tests and of the rect / wide plan queries, recorded
+    when their structs were still declared by hand (host-only queries under the default options): accepted and refused descs of each"""
+    import forward_conv_cases as FC
+    import transposed_conv_cases as TC
+    import wgrad_cases as WG
+    import winograd_cases as WC
+    from scene_generation_amd import ops
+    helpers = dict(wino=WC.wino_plan, tgather=TC.tgather_plan, wgrad=WG.wgrad_plan, fwd=FC.fwd_plan)
+    cases = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'plan_queries.json')))
+    seen = set()
+    for c in cases:
+        want = c['result']
+        if c['query'] in helpers:
+            def run():
+                return helpers[c['query']](_hip.lib(), TC.make_desc(*c['desc']), **c['args'])
+        else:
+            def run():
+                return (ops.conv2d_rect_plan if c['query'] == 'rect' else ops.conv2d_wide_plan)(ops.rect_desc(*c['desc']), **c['args'])
+        if isinstance(want, str):
+            with pytest.raises({'raises AssertionError': AssertionError, 'raises RuntimeError': RuntimeError}[want]):
+                run()
+        else:
+            got = run()
+            if want is not None:
+                want = {k: tuple(v) if isinstance(v, list) else v for k, v in want.items()}
+                assert all(type(v) is type(want[k]) for k, v in got.items()), (c, got)
+                assert list(got) != [] and 'reserved' not in got
+            assert got == want, (c, got)
+        seen.add((c['query'], 'refused' if want is None or isinstance(want, str) else 'accepted'))
+    assert seen == {(q, r) for q in ('wino', 'tgather', 'wgrad', 'fwd', 'rect', 'wide') for r in ('accepted', 'refused')}
+
+
 def test_argument_errors_are_reported_not_thrown():
     lib = _hip.lib()
     rc = lib.sg_linear_fwd(None, None, None, None, 4, 4, 4, 0, 0.0, None)

@@ -32,6 +32,8 @@ import ctypes
 
 import numpy as np
 
+from scene_generation_amd._hip import CONST, plan_dict, sgTGatherPlan
+
 from dense_pointwise_cases import gamma, rng_of, f32, option  # noqa: F401  (re-exported)
 
 BK = 16                 # igemm_core.h: sub-tile depth; the fixed-tap loaders need K % BK == 0 in every class
@@ -46,19 +48,13 @@ def c_wgrad(kpix):
     return -(-kpix // WGRAD_CHUNK)
 
 
-# include/sg2im_hip.h
-TG_CONVT_FWD, TG_CONV_DGRAD, TG_DGRAD_FOLDED = 0, 1, 2
-TG_PLAIN, TG_PARITY = 0, 1
-TG_TABLE, TG_FIXED = 0, 1
+# include/sg2im_hip.h, under the short names the tables use
+TG_CONVT_FWD, TG_CONV_DGRAD, TG_DGRAD_FOLDED = (CONST['SG_TG_' + n] for n in ('CONVT_FWD', 'CONV_DGRAD', 'DGRAD_FOLDED'))
+TG_PLAIN, TG_PARITY = CONST['SG_TG_PLAIN'], CONST['SG_TG_PARITY']
+TG_TABLE, TG_FIXED = CONST['SG_TG_TABLE'], CONST['SG_TG_FIXED']
 ENTRY_NAMES = {TG_CONVT_FWD: 'convT_fwd', TG_CONV_DGRAD: 'conv_dgrad', TG_DGRAD_FOLDED: 'dgrad_folded'}
 PAR_SPLIT_VALUES = (1, 0)        # option par_split: every parity case runs under both
 TAIL_SPLIT_VALUES = (0, 2)       # option w43_tail_split: every stride-1 case runs under both
-
-
-class sgTGatherPlan(ctypes.Structure):
-    _fields_ = ([('route', ctypes.c_int32), ('ncls', ctypes.c_int32)] +
-                [(n, ctypes.c_int32 * 4) for n in ('taps', 'PH', 'PW', 'ph0', 'pw0', 'K')] +
-                [(n, ctypes.c_int32) for n in ('loader', 'a_vec', 'bm', 'bn', 'splits', 'M')])
 
 
 def make_desc(N, C1, H, W, Cout, KS, stride, pad, reflect, ups, OH, OW, out_pad=0, C2=0):
@@ -72,9 +68,10 @@ def tgather_plan(lib, desc, entry, c0, c1, ws_mod16=0, ws_bytes=0):
     p = sgTGatherPlan()
     rc = lib.sg_conv2d_tgather_plan(ctypes.byref(desc), int(entry), int(c0), int(c1), int(ws_mod16), int(ws_bytes), ctypes.byref(p))
     assert rc == 0, lib.sg_last_error_string().decode()
-    out = dict(route=p.route, ncls=p.ncls, loader=p.loader, a_vec=p.a_vec, tile=(p.bm, p.bn), splits=p.splits, M=p.M)
+    out = plan_dict(p)
+    out['tile'] = (out.pop('bm'), out.pop('bn'))
     for n in ('taps', 'PH', 'PW', 'ph0', 'pw0', 'K'):
-        out[n] = tuple(getattr(p, n)[:p.ncls])
+        out[n] = out[n][:p.ncls]
     return out
 
 

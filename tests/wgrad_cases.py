@@ -28,6 +28,8 @@ import ctypes
 
 import numpy as np
 
+from scene_generation_amd._hip import CONST, plan_dict, sgWgradPlan
+
 from dense_pointwise_cases import gamma, rng_of, f32, option  # noqa: F401  (re-exported)
 from transposed_conv_cases import make_desc, conv_out_size, bound  # noqa: F401
 
@@ -40,30 +42,22 @@ TARGET_128, TARGET = 768, 1024      # nk_plan: workgroups aimed at with 128x128 
 FEW_TARGET, FEW_COLS, FEW_PIX = 1024, 128, 256     # nk_launch_plan, few-channel per-image form: S <= 128 / L, S <= PQ / 256
 PAD_MAX_BYTES = 1 << 30
 
-# include/sg2im_hip.h
-WG_CONV, WG_SPARSE, WG_PERIMAGE, WG_CONVT = 0, 1, 2, 3
-WG_TAP, WG_GATHER, WG_PADDED = 0, 1, 2
-WR_NONE, WR_SLAB, WR_WIDE, WR_UNPERMUTE, WR_SPARSE, WR_PERIMAGE, WR_GROUP = range(7)
+# include/sg2im_hip.h, under the short names the tables use
+WG_CONV, WG_SPARSE, WG_PERIMAGE, WG_CONVT = (CONST['SG_WG_' + n] for n in ('CONV', 'SPARSE', 'PERIMAGE', 'CONVT'))
+WG_TAP, WG_GATHER, WG_PADDED = (CONST['SG_WG_' + n] for n in ('TAP', 'GATHER', 'PADDED'))
+WR_NONE, WR_SLAB, WR_WIDE, WR_UNPERMUTE, WR_SPARSE, WR_PERIMAGE, WR_GROUP = (
+    CONST['SG_WR_' + n] for n in ('NONE', 'SLAB', 'WIDE', 'UNPERMUTE', 'SPARSE', 'PERIMAGE', 'GROUP'))
 ENTRY_OF = {'dense': WG_CONV, 'sparse': WG_SPARSE, 'perimage': WG_PERIMAGE}
-PLAN_FIELDS = ('form', 'bm', 'bn', 'cpad', 'a_vec', 'two', 'nomask', 'kchunk', 'chunks', 'grid_z', 'xcd', 'reduce', 'rowsum_fused',
-               'reserved')
+PLAN_FIELDS = tuple(n for n, t in sgWgradPlan._fields_ if t is ctypes.c_int32)      # the int32 fields, ``reserved`` among them
 OPTIONS = ('wgrad_xcd', 'wgrad_rowsum', 'wgrad_padded')
 AMPLE = 4 << 20         # bytes: more workspace than any row's plan needs
-
-
-class sgWgradPlan(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in PLAN_FIELDS] + [('ws_needed', ctypes.c_int64)]
 
 
 def wgrad_plan(lib, desc, entry, L=0, a_mod16=0, ws_bytes=AMPLE):
     """sg_conv2d_wgrad_plan under the current options -> dict, or None when the query returns non-zero"""
     p = sgWgradPlan()
     rc = lib.sg_conv2d_wgrad_plan(ctypes.byref(desc), int(entry), int(L), int(a_mod16), int(ws_bytes), ctypes.byref(p))
-    if rc != 0:
-        return None
-    out = dict((n, getattr(p, n)) for n in PLAN_FIELDS if n != 'reserved')
-    out['ws_needed'] = p.ws_needed
-    return out
+    return None if rc else plan_dict(p)
 
 
 # =============================================================================================

@@ -45,6 +45,8 @@ import re
 
 import numpy as np
 
+from scene_generation_amd._hip import CONST, plan_dict, sgWinoPlan
+
 from dense_pointwise_cases import gamma, rng_of, f32, option  # noqa: F401  (re-exported)
 from transposed_conv_cases import (conv_fwd, conv_dgrad_logical, fold_pad_upsample, nearest_up2, bias_grad, make_desc,  # noqa: F401
                                    probe_sites, onehot, _pairs, _reflect)
@@ -53,32 +55,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RMS_FACTOR = 2.0
 C_JOIN = 8
 
-# include/sg2im_hip.h
-WINO_FWD, WINO_DGRAD, WINO_WGRAD, WINO_FWD_INSTNORM, WINO_DGRAD_INSTNORM, WINO24_FWD, WINO24_DGRAD, WINO24_WGRAD = range(8)
+# include/sg2im_hip.h, under the short names the tables use
+(WINO_FWD, WINO_DGRAD, WINO_WGRAD, WINO_FWD_INSTNORM, WINO_DGRAD_INSTNORM, WINO24_FWD, WINO24_DGRAD, WINO24_WGRAD) = (
+    CONST['SG_' + n] for n in ('WINO_FWD', 'WINO_DGRAD', 'WINO_WGRAD', 'WINO_FWD_INSTNORM', 'WINO_DGRAD_INSTNORM', 'WINO24_FWD',
+                               'WINO24_DGRAD', 'WINO24_WGRAD'))
 ENTRY_NAMES = ('fwd', 'dgrad', 'wgrad', 'fwd_instnorm', 'dgrad_instnorm', 'w24_fwd', 'w24_dgrad', 'w24_wgrad')
-WA_X, WA_W, WA_Y, WA_GY, WA_GX, WA_GW, WA_ALL = 1, 2, 4, 8, 16, 32, 63
-WS_UT, WS_V, WS_YTP = 1, 2, 4
-WF_UNSUPPORTED, WF_F23_GENERIC, WF_F23_ADJOINT, WF_F43, WF_F24 = range(5)
-WK_NONE, WK_IN_LDS, WK_IN_GENERAL = 0, 1, 2
-WK_WT_LDS, WK_WT_PLAIN = 1, 2
-WK_FOLD_CELLS, WK_FOLD_WALK, WK_FOLD_F43, WK_FOLD_PAD_UPSAMPLE = 1, 2, 3, 4
-WSRC_SAVED, WSRC_REBUILT = 1, 2
-PLAN_FIELDS = ('form', 'P', 'Ps', 'Pd', 'Pds', 'in_kernel', 'wt_kernel', 'fold_kernel', 'bm', 'bn', 'nsub', 'kfold', 'pipe', 'wgrad_src',
-               'norm_tiles', 'TH', 'TW', 'THd', 'TWd', 'S', 'Pc')
+WA_X, WA_W, WA_Y, WA_GY, WA_GX, WA_GW, WA_ALL = (CONST['SG_WA_' + n] for n in ('X', 'W', 'Y', 'GY', 'GX', 'GW', 'ALL'))
+WS_UT, WS_V, WS_YTP = (CONST['SG_WS_' + n] for n in ('UT', 'V', 'YTP'))
+WF_UNSUPPORTED, WF_F23_GENERIC, WF_F23_ADJOINT, WF_F43, WF_F24 = (
+    CONST['SG_WF_' + n] for n in ('UNSUPPORTED', 'F23_GENERIC', 'F23_ADJOINT', 'F43', 'F24'))
+WK_NONE, WK_IN_LDS, WK_IN_GENERAL = (CONST['SG_WK_' + n] for n in ('NONE', 'IN_LDS', 'IN_GENERAL'))
+WK_WT_LDS, WK_WT_PLAIN = CONST['SG_WK_WT_LDS'], CONST['SG_WK_WT_PLAIN']
+WK_FOLD_CELLS, WK_FOLD_WALK, WK_FOLD_F43, WK_FOLD_PAD_UPSAMPLE = (
+    CONST['SG_WK_FOLD_' + n] for n in ('CELLS', 'WALK', 'F43', 'PAD_UPSAMPLE'))
+WSRC_SAVED, WSRC_REBUILT = CONST['SG_WSRC_SAVED'], CONST['SG_WSRC_REBUILT']
+PLAN_FIELDS = tuple(n for n, _ in sgWinoPlan._fields_)
 # the library's defaults of the options the plans depend on (csrc/runtime.hip; the CPU module checks them against the library)
 OPTION_DEFAULTS = dict(wino_wt=1, wino_fold_cells=1, wino_reuse=1, wino_in_fuse=1, wino_pipe=2, wino_gemm_tile=0, wino43=1, wino_adjoint=1,
                        w43_kfold=256, w43_nsub=1, w43_wgrad_tile=0, w24_small=1, w24_s=-1, w24_gemm_tile=2, w24_pmin=256, wino24=1)
-
-
-class sgWinoPlan(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in PLAN_FIELDS]
 
 
 def wino_plan(lib, desc, entry, align_mask=WA_ALL, saved_mask=0):
     """sg_conv2d_wino_plan under the current options -> dict, or None when the query returns non-zero"""
     p = sgWinoPlan()
     rc = lib.sg_conv2d_wino_plan(ctypes.byref(desc), int(entry), int(align_mask), int(saved_mask), ctypes.byref(p))
-    return None if rc else {n: getattr(p, n) for n in PLAN_FIELDS}
+    return None if rc else plan_dict(p)
 
 
 # =============================================================================================
