@@ -64,7 +64,8 @@ int sg_plan_cache_clear(void);
  * Every GEMM family of the convolutions runs from one host-side plan function that a host-only query reports (tile, loaders,
  * mask, split, reduce -- under the current options, launching nothing): sg_conv2d_fwd_plan (forward gathers: sg_conv2d_fwd,
  * _fwd_sparse, _fwd_perimage), sg_conv2d_tgather_plan (transposed gathers), sg_conv2d_wgrad_plan (weight gradients) and
- * sg_conv2d_wino_plan (Winograd).
+ * sg_conv2d_wino_plan (Winograd).  The vector-ALU kernels report theirs the same way: sg_conv2d_head_plan (one output channel) and
+ * sg_conv2d_smallm_plan (ReflectionPad(3) + 7x7 to <= 4 channels).
  * A desc with reflection padding must satisfy pad < H*upsample, pad < W*upsample and (OH-1)*stride + KS <= H*upsample + 2*pad
  * (the same for the width): the gathers mirror a coordinate once.  Every entry point refuses any other (as torch refuses it).
  * ------------------------------------------------------------------------------------------- */
@@ -251,18 +252,54 @@ typedef struct sgWinoPlan {
 } sgWinoPlan;
 int sg_conv2d_wino_plan(const sgConvDesc* d, int entry, int align_mask, int saved_mask, sgWinoPlan* plan);
 /* Direct (vector-ALU) kernels for ReflectionPad2d(3) + Conv2d(C, Cout <= 4, 7) [+ act]: the generator's RGB head
-   (reference generators.py:88-90).  Same results as sg_conv2d_fwd / sg_conv2d_wgrad (gb via sg_channel_sum). */
+   (reference generators.py:88-90).  Same results as sg_conv2d_fwd / sg_conv2d_wgrad (gb via sg_channel_sum).
+   Alignment: the forward stores y, and the weight gradient loads gy, four pixels at a time (W % 4 == 0 keeps every row on the
+   vector grid): y (forward) and gy (weight gradient) must be 16-byte aligned, and both entry points refuse any other address on
+   the host, before a launch.
+   sg_conv2d_smallm_plan (host only, launches nothing; the launchers run from the same function):
+     entry    SG_SMALLM_FWD or SG_SMALLM_WGRAD
+     MO       the instantiation: output rows per thread (3 for Cout == 3, else 4; rows >= Cout repeat row Cout - 1, never stored)
+     grid_x, grid_y, grid_z   forward: 64-column tiles x 16-row tiles x images;  weight gradient: channels x images x 1
+     col_blocks, row_blocks   weight gradient: blocks of 128 columns x 16 rows each workgroup walks (forward: 1 x 1)
+     iters    forward: channel pairs each of the two thread groups walks, (C1 + 1) / 2;  idle_last: 1 when the second group has
+              no channel in the last one (odd C1);  both 0 for the weight gradient */
+enum { SG_SMALLM_FWD = 0, SG_SMALLM_WGRAD = 2 };
+typedef struct sgSmallmPlan {
+  int32_t MO;
+  int32_t grid_x, grid_y, grid_z;
+  int32_t col_blocks, row_blocks;
+  int32_t iters, idle_last;
+} sgSmallmPlan;
 int sg_conv2d_smallm_supported(const sgConvDesc* d);
 size_t sg_conv2d_smallm_ws_bytes(const sgConvDesc* d);
+int sg_conv2d_smallm_plan(const sgConvDesc* d, int entry, sgSmallmPlan* plan);
 int sg_conv2d_smallm_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, int act,
                          float slope, sgStream stream);
 int sg_conv2d_smallm_wgrad(const sgConvDesc* d, const float* gy, const float* x, float* gw, void* ws, size_t ws_bytes,
                            sgStream stream);
 /* Direct (vector-ALU) kernels for SINGLE-output-channel convs with zero padding, stride 1, KS in {1,3,4}: the PatchGAN score
    heads (reference discriminators.py:152-158,232-234) and the 1x1 head of mask_net (generators.py:27).  Memory-bound
-   reductions; channel chunks / images are combined in a fixed order.  ws: sg_conv2d_head_ws_bytes.  gb via sg_channel_sum. */
+   reductions; channel chunks / images are combined in a fixed order.  ws: sg_conv2d_head_ws_bytes.  gb via sg_channel_sum.
+   No alignment is required: the forward's 1x1 stream kernel reads x and writes y as float4 and runs only where both are 16-byte
+   aligned (the LDS-staged kernel takes the call otherwise).
+   sg_conv2d_head_plan (host only, launches nothing; the launchers run from the same function): what sg_conv2d_head_fwd / _dgrad /
+   _wgrad (entry SG_HEAD_*) launches for this desc.  x_mod16, y_mod16: the addresses of x and y modulo 16 (0, 4, 8 or 12; they
+   matter to the forward only).  Returns non-zero for a desc sg_conv2d_head_supported refuses.
+     kind        SG_HEAD_STREAM: the 1x1 stream kernel (forward; KS 1, pad 0, H*W % 4 == 0, x and y aligned);  SG_HEAD_STAGED: the
+                 LDS-staged kernels
+     CH          channels per workgroup (staged; from the LDS budget, at most 16), or the 8 channels a stream thread loads together
+     chunks      workgroups (staged) / load groups (stream) along the channels;  last_chunk: the channels of the last one
+     lds_bytes   dynamic LDS of the entry's launch (0 for the stream kernel)
+     Q_full, Q_last   weight gradient: the pixel parts (1, 2, 4, 8 or 16) a full and the last chunk split the plane into; else 0 */
+enum { SG_HEAD_FWD = 0, SG_HEAD_DGRAD = 1, SG_HEAD_WGRAD = 2 };
+enum { SG_HEAD_STREAM = 1, SG_HEAD_STAGED = 2 };
+typedef struct sgHeadPlan {
+  int32_t kind, CH, chunks, last_chunk;
+  int32_t lds_bytes, Q_full, Q_last;
+} sgHeadPlan;
 int sg_conv2d_head_supported(const sgConvDesc* d);
 size_t sg_conv2d_head_ws_bytes(const sgConvDesc* d);
+int sg_conv2d_head_plan(const sgConvDesc* d, int entry, int x_mod16, int y_mod16, sgHeadPlan* plan);
 int sg_conv2d_head_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, int act,
                        float slope, void* ws, size_t ws_bytes, sgStream stream);
 int sg_conv2d_head_dgrad(const sgConvDesc* d, const float* gy, const float* w, float* gx, sgStream stream);

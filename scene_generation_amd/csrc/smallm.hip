@@ -230,6 +230,24 @@ bool smallm_ok(const sgConvDesc* d) {
          d->pad == 3 && d->W % 4 == 0 && d->H >= 4 && d->W >= 4 && d->OH == d->H && d->OW == d->W;
 }
 
+// THE launch plan of the two entry points (sg_conv2d_smallm_plan reports it, the launchers run from it).  d: smallm_ok.
+sgSmallmPlan smallm_plan(const sgConvDesc* d, int entry) {
+  sgSmallmPlan p;
+  // MO = the real channel count for the RGB head: no instructions for a fourth row (the <7, 4> weight gradient spent a quarter of
+  // its FMAs on it)
+  p.MO = d->Cout == 3 ? 3 : 4;
+  if (entry == SG_SMALLM_FWD) {
+    p.grid_x = sg_cdiv(d->W, 64); p.grid_y = sg_cdiv(d->H, 16); p.grid_z = d->N;
+    p.col_blocks = p.row_blocks = 1;
+    p.iters = (d->C1 + 1) / 2; p.idle_last = d->C1 & 1;
+  } else {
+    p.grid_x = d->C1; p.grid_y = d->N; p.grid_z = 1;
+    p.col_blocks = sg_cdiv(d->W, 128); p.row_blocks = sg_cdiv(d->H, 16);
+    p.iters = p.idle_last = 0;
+  }
+  return p;
+}
+
 }  // namespace
 
 extern "C" int sg_conv2d_smallm_supported(const sgConvDesc* d) { return smallm_ok(d) ? 1 : 0; }
@@ -238,14 +256,23 @@ extern "C" size_t sg_conv2d_smallm_ws_bytes(const sgConvDesc* d) {
   return smallm_ok(d) ? (size_t)d->N * d->Cout * d->C1 * 49 * sizeof(float) : 0;
 }
 
+extern "C" int sg_conv2d_smallm_plan(const sgConvDesc* d, int entry, sgSmallmPlan* plan) {
+  SG_ARG_CHECK(smallm_ok(d), "sg_conv2d_smallm_plan: unsupported desc");
+  SG_ARG_CHECK(plan && (entry == SG_SMALLM_FWD || entry == SG_SMALLM_WGRAD), "sg_conv2d_smallm_plan: bad arguments");
+  *plan = smallm_plan(d, entry);
+  return 0;
+}
+
 extern "C" int sg_conv2d_smallm_fwd(const sgConvDesc* d, const float* x, const float* w, const float* bias, float* y, int act,
                                     float slope, sgStream stream) {
   SG_ARG_CHECK(smallm_ok(d), "sg_conv2d_smallm_fwd: unsupported desc (needs ReflectionPad(3)+7x7, stride 1, Cout <= 4, W %% 4 == 0)");
   SG_ARG_CHECK(x && w && y, "sg_conv2d_smallm_fwd: null pointer");
+  SG_ARG_CHECK((reinterpret_cast<uintptr_t>(y) & 15) == 0, "sg_conv2d_smallm_fwd: y must be 16-byte aligned (float4 stores)");
   hipStream_t s = (hipStream_t)stream;
   SgProfScope prof(sg_igemm_kind(0, 7, 2), s, 2.0 * d->Cout * d->C1 * 49.0 * d->N * d->H * d->W, 0);
-  const dim3 grid(sg_cdiv(d->W, 64), sg_cdiv(d->H, 16), d->N);
-  if (d->Cout == 3)        // (the RGB head: no instructions for the fourth row)
+  const sgSmallmPlan p = smallm_plan(d, SG_SMALLM_FWD);
+  const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+  if (p.MO == 3)
     hipLaunchKernelGGL((smallm_fwd_kernel<7, 3>), grid, dim3(512), 0, s, x, w, bias, y, d->C1, d->H, d->W, d->Cout, act, slope);
   else
     hipLaunchKernelGGL((smallm_fwd_kernel<7, 4>), grid, dim3(512), 0, s, x, w, bias, y, d->C1, d->H, d->W, d->Cout, act, slope);
@@ -257,16 +284,18 @@ extern "C" int sg_conv2d_smallm_wgrad(const sgConvDesc* d, const float* gy, cons
                                       size_t ws_bytes, sgStream stream) {
   SG_ARG_CHECK(smallm_ok(d), "sg_conv2d_smallm_wgrad: unsupported desc");
   SG_ARG_CHECK(gy && x && gw && ws && ws_bytes >= sg_conv2d_smallm_ws_bytes(d), "sg_conv2d_smallm_wgrad: bad arguments");
+  SG_ARG_CHECK((reinterpret_cast<uintptr_t>(gy) & 15) == 0, "sg_conv2d_smallm_wgrad: gy must be 16-byte aligned (float4 loads)");
   hipStream_t s = (hipStream_t)stream;
   float* part = reinterpret_cast<float*>(ws);
   const size_t nw = (size_t)d->Cout * d->C1 * 49;
   {
     SgProfScope prof(sg_igemm_kind(2, 7, 2), s, 2.0 * d->Cout * d->C1 * 49.0 * d->N * d->H * d->W, 0);
-    // (MO = the real channel count: the <7, 4> instantiation spent a quarter of its FMAs on the zero row of the RGB head)
-    if (d->Cout == 3)
-      hipLaunchKernelGGL((smallm_wgrad_kernel<7, 3>), dim3(d->C1, d->N), dim3(256), 0, s, gy, x, part, d->C1, d->H, d->W, d->Cout);
+    const sgSmallmPlan p = smallm_plan(d, SG_SMALLM_WGRAD);
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    if (p.MO == 3)
+      hipLaunchKernelGGL((smallm_wgrad_kernel<7, 3>), grid, dim3(256), 0, s, gy, x, part, d->C1, d->H, d->W, d->Cout);
     else
-      hipLaunchKernelGGL((smallm_wgrad_kernel<7, 4>), dim3(d->C1, d->N), dim3(256), 0, s, gy, x, part, d->C1, d->H, d->W, d->Cout);
+      hipLaunchKernelGGL((smallm_wgrad_kernel<7, 4>), grid, dim3(256), 0, s, gy, x, part, d->C1, d->H, d->W, d->Cout);
   }
   hipLaunchKernelGGL(smallm_reduce_kernel, dim3(sg_cdiv(nw, 256)), dim3(256), 0, s, (const float*)part, gw, nw, d->N);
   SG_LAUNCH_CHECK("sg_conv2d_smallm_wgrad");
@@ -318,6 +347,40 @@ bool head_ok(const sgConvDesc* d) {
   const int PP = (d->H + 2 * d->pad) * (d->W + 2 * d->pad), OP = d->OH * d->OW;
   return PP + 4 * OP <= HEAD_LDS_FLOATS && d->C1 >= 16 &&
          (d->OH + 2 * (d->KS - 1)) * (d->OW + 2 * (d->KS - 1)) + 16 * d->KS * d->KS <= HEAD_LDS_FLOATS;
+}
+
+// pixel parts of the weight gradient: the (channel, tap) pairs of a chunk times the parts fill the 256 threads.  (A macro, shared by
+// the kernel and the plan: the kernel must see the select chain itself -- behind a function call the compiler no longer proves Q a
+// power of two and divides by it where it used to shift)
+#define HEAD_WGRAD_PARTS(pairs) ((pairs) >= 128 ? 1 : ((pairs) >= 64 ? 2 : ((pairs) >= 32 ? 4 : ((pairs) >= 16 ? 8 : 16))))
+
+// THE launch plan of the three entry points (sg_conv2d_head_plan reports it, the launchers run from it).  d: head_ok, g its geometry.
+sgHeadPlan head_plan(const sgConvDesc* d, const HeadGeom& g, int entry, int x_mod16, int y_mod16) {
+  sgHeadPlan p;
+  p.kind = SG_HEAD_STAGED; p.CH = g.CH; p.chunks = g.chunks; p.last_chunk = g.C - (g.chunks - 1) * g.CH;
+  p.Q_full = p.Q_last = 0;
+  const size_t PP = (size_t)g.PH * g.PW, OP = (size_t)d->OH * d->OW, KK = (size_t)d->KS * d->KS;
+  size_t floats = 0;
+  if (entry == SG_HEAD_FWD) {
+    // 1x1 with pad 0 is a channel reduction of a stream: float4 loads and stores where the plane and both addresses allow them
+    if (d->KS == 1 && d->pad == 0 && (d->H * d->W) % 4 == 0 && d->N <= 65535 && x_mod16 == 0 && y_mod16 == 0) {
+      p.kind = SG_HEAD_STREAM; p.CH = 8; p.chunks = (g.C + 7) / 8; p.last_chunk = g.C - (p.chunks - 1) * 8;
+    } else {
+      floats = (size_t)g.CH * PP + 4 * OP;                   // planes + per-wave sums
+    }
+  } else if (entry == SG_HEAD_DGRAD) {
+    const size_t E = d->KS - 1;
+    floats = (d->OH + 2 * E) * (d->OW + 2 * E) + (size_t)g.CH * KK;      // extended gy + the chunk's weights
+  } else {
+    // planes + gy + pixel-offset table.  The staged planes are reused as a 256-float reduction buffer at the end of the kernel:
+    // tiny maps (a 1x1 head on a < 16-pixel map, a 3x3 head on a 1x1 map) stage fewer than 256 floats -- never allocate less
+    floats = (size_t)g.CH * PP + 2 * OP;
+    if (floats < 256) floats = 256;
+    p.Q_full = HEAD_WGRAD_PARTS(g.CH * (int)KK);           // (C1 >= 16 >= CH: there always is a full chunk)
+    p.Q_last = HEAD_WGRAD_PARTS(p.last_chunk * (int)KK);
+  }
+  p.lds_bytes = (int)(floats * sizeof(float));
+  return p;
 }
 
 // rows [prow0, prow0 + nrows) of the zero-padded planes of channels [c0, c0+nc) of one image -> LDS [nc][nrows*PW]
@@ -440,7 +503,7 @@ __global__ void __launch_bounds__(256) head_wgrad_kernel(const float* __restrict
   }
   __syncthreads();
   const int pairs = nc * KK;                           // <= 16 * 16 = 256
-  const int Q = pairs >= 128 ? 1 : (pairs >= 64 ? 2 : (pairs >= 32 ? 4 : (pairs >= 16 ? 8 : 16)));   // pixel parts
+  const int Q = HEAD_WGRAD_PARTS(pairs);                  // pixel parts
   const int j = threadIdx.x % (256 / Q), q = threadIdx.x / (256 / Q);
   float acc = 0.f;
   if (j < pairs) {
@@ -468,6 +531,14 @@ template <class K> void head_set_lds(K kernel, size_t bytes) {
 }  // namespace
 
 extern "C" int sg_conv2d_head_supported(const sgConvDesc* d) { return head_ok(d) ? 1 : 0; }
+
+extern "C" int sg_conv2d_head_plan(const sgConvDesc* d, int entry, int x_mod16, int y_mod16, sgHeadPlan* plan) {
+  SG_ARG_CHECK(head_ok(d), "sg_conv2d_head_plan: unsupported desc");
+  SG_ARG_CHECK(plan && (entry == SG_HEAD_FWD || entry == SG_HEAD_DGRAD || entry == SG_HEAD_WGRAD) && (x_mod16 & ~12) == 0 &&
+                   (y_mod16 & ~12) == 0, "sg_conv2d_head_plan: bad arguments");
+  *plan = head_plan(d, head_geom(d), entry, x_mod16, y_mod16);
+  return 0;
+}
 
 extern "C" size_t sg_conv2d_head_ws_bytes(const sgConvDesc* d) {
   if (!head_ok(d)) return 0;
@@ -522,8 +593,9 @@ extern "C" int sg_conv2d_head_fwd(const sgConvDesc* d, const float* x, const flo
   SG_ARG_CHECK(head_ok(d), "sg_conv2d_head_fwd: unsupported desc (needs Cout == 1, stride 1, zero padding, KS in {1,3,4})");
   SG_ARG_CHECK(x && w && y && ws && ws_bytes >= sg_conv2d_head_ws_bytes(d), "sg_conv2d_head_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (d->KS == 1 && d->pad == 0 && (d->H * d->W) % 4 == 0 && d->N <= 65535 &&
-      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
+  const HeadGeom g = head_geom(d);
+  const sgHeadPlan p = head_plan(d, g, SG_HEAD_FWD, (int)(reinterpret_cast<uintptr_t>(x) & 15), (int)(reinterpret_cast<uintptr_t>(y) & 15));
+  if (p.kind == SG_HEAD_STREAM) {
     SgProfScope prof(SG_K_HEAD, s, 2.0 * d->C1 * (double)d->N * d->OH * d->OW, head_bytes(d));
     const int HW4 = d->H * d->W / 4;
     hipLaunchKernelGGL(head1x1_fwd_kernel, dim3(sg_cdiv(HW4, 256), d->N), dim3(256), 0, s, reinterpret_cast<const float4*>(x), w,
@@ -531,10 +603,9 @@ extern "C" int sg_conv2d_head_fwd(const sgConvDesc* d, const float* x, const flo
     SG_LAUNCH_CHECK("sg_conv2d_head_fwd");
     return 0;
   }
-  const HeadGeom g = head_geom(d);
   float* part = reinterpret_cast<float*>(ws);
-  const dim3 grid(g.chunks, d->N);
-  const size_t lds = ((size_t)g.CH * g.PH * g.PW + 4 * (size_t)d->OH * d->OW) * sizeof(float);
+  const dim3 grid(p.chunks, d->N);
+  const size_t lds = (size_t)p.lds_bytes;
   SgProfScope prof(SG_K_HEAD, s, 2.0 * d->C1 * d->KS * d->KS * (double)d->N * d->OH * d->OW, head_bytes(d));
   SG_HEAD_DISPATCH(head_fwd_kernel, x, w, part, g)
   const int tot = d->N * d->OH * d->OW;
@@ -549,9 +620,9 @@ extern "C" int sg_conv2d_head_dgrad(const sgConvDesc* d, const float* gy, const 
   SG_ARG_CHECK(gy && w && gx, "sg_conv2d_head_dgrad: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const HeadGeom g = head_geom(d);
-  const dim3 grid(g.chunks, d->N);
-  const int E = d->KS - 1;
-  const size_t lds = ((size_t)(d->OH + 2 * E) * (d->OW + 2 * E) + (size_t)g.CH * d->KS * d->KS) * sizeof(float);
+  const sgHeadPlan p = head_plan(d, g, SG_HEAD_DGRAD, 0, 0);
+  const dim3 grid(p.chunks, d->N);
+  const size_t lds = (size_t)p.lds_bytes;
   SgProfScope prof(SG_K_HEAD, s, 2.0 * d->C1 * d->KS * d->KS * (double)d->N * d->OH * d->OW, head_bytes(d));
   SG_HEAD_DISPATCH(head_dgrad_kernel, gy, w, gx, g)
   SG_LAUNCH_CHECK("sg_conv2d_head_dgrad");
@@ -565,12 +636,9 @@ extern "C" int sg_conv2d_head_wgrad(const sgConvDesc* d, const float* gy, const 
   hipStream_t s = (hipStream_t)stream;
   const HeadGeom g = head_geom(d);
   float* part = reinterpret_cast<float*>(ws);
-  const dim3 grid(g.chunks, d->N);
-  // the staged planes are reused as a 256-float reduction buffer at the end of the kernel: tiny maps (a 1x1 head on a
-  // < 16-pixel map, a 3x3 head on a 1x1 map) stage fewer than 256 floats -- never allocate less
-  size_t lds_floats = (size_t)g.CH * g.PH * g.PW + 2 * (size_t)d->OH * d->OW;
-  if (lds_floats < 256) lds_floats = 256;
-  const size_t lds = lds_floats * sizeof(float);
+  const sgHeadPlan p = head_plan(d, g, SG_HEAD_WGRAD, 0, 0);
+  const dim3 grid(p.chunks, d->N);
+  const size_t lds = (size_t)p.lds_bytes;
   const size_t nw = (size_t)d->C1 * d->KS * d->KS;
   {
     SgProfScope prof(SG_K_HEAD, s, 2.0 * d->C1 * d->KS * d->KS * (double)d->N * d->OH * d->OW, head_bytes(d));

@@ -8,6 +8,8 @@ stores it and the forward, the data gradient and the weight gradient dispatch on
 keeps its own, because its bias gradient comes out of the data-gradient launch.
 (Part of scene_generation_amd.ops: see ops/__init__.py.)"""
 
+import ctypes
+
 import torch
 from torch.autograd import Function
 
@@ -46,6 +48,29 @@ def conv_route(d, two_source, sparse):
                     break
         d._memo[key] = route
     return route
+
+
+HEAD_FWD, HEAD_DGRAD, HEAD_WGRAD = (_hip.CONST['SG_HEAD_' + n] for n in ('FWD', 'DGRAD', 'WGRAD'))
+HEAD_STREAM, HEAD_STAGED = _hip.CONST['SG_HEAD_STREAM'], _hip.CONST['SG_HEAD_STAGED']
+SMALLM_FWD, SMALLM_WGRAD = _hip.CONST['SG_SMALLM_FWD'], _hip.CONST['SG_SMALLM_WGRAD']
+
+
+def conv2d_head_plan(d, entry=HEAD_FWD, x_mod16=0, y_mod16=0):
+    """-> dict(kind, CH, chunks, last_chunk, lds_bytes, Q_full, Q_last): the launch sg_conv2d_head_fwd / _dgrad / _wgrad (``entry``:
+    HEAD_*) issues for the sgConvDesc ``d`` with x and y at these addresses modulo 16 (a host-only query)"""
+    plan = _hip.sgHeadPlan()
+    if _L().sg_conv2d_head_plan(ctypes.byref(d), int(entry), int(x_mod16), int(y_mod16), ctypes.byref(plan)) != 0:
+        raise RuntimeError('sg_conv2d_head_plan failed: %s' % _hip.last_error())
+    return _hip.plan_dict(plan)
+
+
+def conv2d_smallm_plan(d, entry=SMALLM_FWD):
+    """-> dict(MO, grid_x, grid_y, grid_z, col_blocks, row_blocks, iters, idle_last): the launch sg_conv2d_smallm_fwd / _wgrad
+    (``entry``: SMALLM_*) issues for the sgConvDesc ``d`` (a host-only query)"""
+    plan = _hip.sgSmallmPlan()
+    if _L().sg_conv2d_smallm_plan(ctypes.byref(d), int(entry), ctypes.byref(plan)) != 0:
+        raise RuntimeError('sg_conv2d_smallm_plan failed: %s' % _hip.last_error())
+    return _hip.plan_dict(plan)
 
 
 def _kept(d, floats_query, keep, dev):
@@ -126,7 +151,7 @@ class Conv2dFn(Function):
         act, slope, has_bias, grad_from = ctx.cfg
         gy = _f32(gy)
         route = ctx.route
-        if route == ROUTE_WINO:
+        if route in (ROUTE_WINO, ROUTE_SMALLM):      # (float4 loads of gy: a view that starts mid-vector is copied, see _al16)
             gy = _al16(gy)
         s = _stream()
         gy = act_bwd(y, gy, act, slope, s)

@@ -30,6 +30,25 @@ def test_special_route_predicates_are_disjoint():
         claimed = [c + a for c, a in zip(claimed, ans)]
         swept += 1
     assert swept > 100000
+    # the descs of tests/head_smallm_cases.py (rows, probes, both sides of every inequality of the head and small-M predicates), and
+    # what the square sweep above does not reach: non-square planes, planes at the head's LDS budget, channel counts around its floor
+    import head_smallm_cases as HS
+    extra = [HS.desc_of(f) for f in HS.CASES + HS.PROBES + [e[1] for e in HS.HEAD_EDGES + HS.SMALLM_EDGES]]
+    for (H, W), C1, Cout, KS, pad, reflect in itertools.product(
+            ((4, 4), (5, 8), (8, 5), (17, 68), (17, 132), (2, 256), (2, 257), (40, 38), (49, 49), (49, 50), (50, 50)), (1, 2, 5, 15, 16, 17, 40, 128),
+            (1, 2, 3, 4, 5, 128), (1, 3, 4, 7), range(5), (0, 1)):
+        OH, OW = _core.conv_out_size(H, KS, 1, pad), _core.conv_out_size(W, KS, 1, pad)
+        if (reflect and pad == 0) or pad >= min(H, W) or OH <= 0 or OW <= 0:
+            continue
+        extra.append(sgConvDesc(2, C1, 0, H, W, Cout, KS, 1, pad, reflect, 1, OH, OW, 0, 0))
+    assert len(extra) > 10000
+    before = list(claimed)
+    for d in extra:
+        ans = [bool(f(ctypes.byref(d))) for f in fns]
+        assert sum(ans) <= 1, ('more than one special kernel claims', [getattr(d, f) for f, _ in d._fields_], ans)
+        claimed = [c + a for c, a in zip(claimed, ans)]
+    head, smallm = PREDICATES.index('sg_conv2d_head_supported'), PREDICATES.index('sg_conv2d_smallm_supported')
+    assert claimed[head] > before[head] + 100 and claimed[smallm] > before[smallm] + 100
     assert all(c > 0 for c in claimed), dict(zip(PREDICATES, claimed))     # (a sweep that reaches no desc of a class proves nothing)
 
 

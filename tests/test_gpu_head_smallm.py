@@ -1,0 +1,317 @@
+"""The vector-ALU convolution kernels of csrc/smallm.hip through the C ABI -- sg_conv2d_smallm_fwd / _wgrad and sg_conv2d_head_fwd /
+_dgrad / _wgrad, the 1x1 stream kernel included -- against the float64 restatements of tests/head_smallm_cases.py, row by row of its
+tables.
+
+Every launch: NaN in the four floats before and behind each input (a gather that is off by a few elements reads a NaN, which no zero
+weight hides, and stays inside the buffer); the result pre-filled with a guard value, which no element may keep, and a guard word
+behind it; the workspace NaN over the bytes the ``*_ws_bytes`` query asked for and guard words behind them.  The plan the library
+reports for THIS call (the actual addresses of x and y modulo 16) is the one the row claims and the one head_smallm_cases.py restates;
+every element within its own bound of float64 (c from the reported plan); a second call bit-identical; the generic entry points
+(sg_conv2d_fwd / _dgrad / _wgrad) on the same desc within the sum of both bounds.  One-hot probes -- the index logic -- are held to bit
+equality.  The worst error / bound ratio per reported plan goes to head_smallm_margins.json (profiles/head_smallm_test_margins.md
+holds a run's)."""
+import numpy as np
+import pytest
+import torch
+
+import forward_conv_cases as FC
+import head_smallm_cases as HS
+import test_gpu_dense_pointwise as G
+import test_gpu_parity as P
+import transposed_conv_cases as T
+import wgrad_cases as WG
+from test_gpu_dense_pointwise import outbuf, take, within, same, call, ptr, stream, GUARD
+from test_gpu_forward_conv import place_fenced
+from test_gpu_transposed_conv import twice, dref
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+_MARGINS = {}
+GUARD_WORDS = 256
+
+
+@pytest.fixture(scope='module')
+def L():
+    assert torch.cuda.is_available(), 'gpu tests need a device'
+    from scene_generation_amd import _hip
+    return _hip.lib()      # fails loudly if the extension is missing
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _margins():
+    """after the module: the worst observed error / bound ratio per plan -> head_smallm_margins.json"""
+    yield
+    P._dump('head_smallm_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in sorted(_MARGINS.items())})
+
+
+@pytest.fixture(autouse=True)
+def _release_operands():
+    yield
+    del G._KEEP[:]
+
+
+def held(fam, got, ref, bound, name):
+    """within(), with the worst ratio noted for this module's margins file"""
+    err = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
+    b = np.broadcast_to(np.asarray(bound, dtype=np.float64), err.shape)
+    ratio = np.where(b > 0, err / np.maximum(b, 1e-300), np.where(err > 0, np.inf, 0.0))
+    worst = float(np.nan_to_num(ratio, nan=np.inf).max()) if ratio.size else 0.0
+    if fam not in _MARGINS or worst > _MARGINS[fam][0]:
+        _MARGINS[fam] = (worst, name)
+    within(fam, got, ref, bound, name)
+
+
+def fenced(a, off=0):
+    """place_fenced(), ``off`` floats further from the 16-byte boundary (NaN in the four floats before and the four behind)"""
+    if off == 0:
+        return place_fenced(a)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    base = torch.full((a.size + 8 + off,), float('nan'), dtype=torch.float32, device=DEV)
+    assert base.data_ptr() % 16 == 0
+    v = base[4 + off:4 + off + a.size]
+    v.copy_(torch.from_numpy(a).reshape(-1))
+    G._KEEP.append(v)
+    return v
+
+
+def taken(o, shape, name):
+    y = take(o, shape)
+    assert not (y == GUARD).any(), '%s: %d result elements were never written' % (name, int((y == GUARD).sum()))
+    return y
+
+
+class Workspace:
+    """the bytes the query asked for, NaN, and guard words behind them"""
+
+    def __init__(self, nbytes):
+        self.n, self.words = nbytes, (nbytes + 3) // 4
+        self.buf = torch.full((self.words + GUARD_WORDS,), GUARD, dtype=torch.float32, device=DEV)
+        self.buf[:self.words] = float('nan')
+
+    def intact(self, name):
+        assert bool((self.buf[self.words:].cpu() == GUARD).all()), '%s: the launch wrote behind the workspace bytes the query asked for' % name
+
+
+def family(case, entry, plan):
+    if case['family'] == 'smallm':
+        return 'smallm %s MO=%d' % (entry, plan['MO'])
+    if plan['kind'] == HS.HEAD_STREAM:
+        return 'head fwd 1x1 stream'
+    ch = 'CH=%s' % (plan['CH'] if plan['CH'] in (1, 16) else '2..15')
+    return 'head %s staged k%d %s%s' % (entry, case['KS'], ch, ' Q=%d/%d' % (plan['Q_full'], plan['Q_last']) if entry == 'wgrad' else '')
+
+
+def operands(case, inp, x_off=None):
+    """the row's inputs on the device, fenced: x (at the row's offset), w, gy, bias or None"""
+    x_off = case['x_off'] if x_off is None else x_off
+    return dict(x=fenced(inp['x'], x_off), w=fenced(inp['w']), gy=fenced(inp['gy']), b=None if inp.get('b') is None else fenced(inp['b']))
+
+
+def run_entry(L, case, entry, dev, y_off=None):
+    """one C-ABI call of the row's family -> (result, the plan reported for this call's addresses)"""
+    d = HS.desc_of(case)
+    N, C, M, H, W, OH, OW, KS = (case[k] for k in ('N', 'C1', 'Cout', 'H', 'W', 'OH', 'OW', 'KS'))
+    name = '%s %s' % (case['name'], entry)
+    ws = Workspace(HS.case_ws_bytes(case))
+    head = case['family'] == 'head'
+    assert int(getattr(L, 'sg_conv2d_%s_ws_bytes' % case['family'])(dref(d))) == ws.n
+    if entry == 'fwd':
+        y_off = case['y_off'] if y_off is None else y_off
+        o = outbuf(N * M * OH * OW, y_off)
+        assert (o.data_ptr() - 4 * y_off) % 16 == 0
+        if head:
+            plan = HS.head_plan(L, d, HS.HEAD_FWD, dev['x'].data_ptr() % 16, o.data_ptr() % 16)
+            call(L, 'sg_conv2d_head_fwd', dref(d), ptr(dev['x']), ptr(dev['w']), ptr(dev['b']), ptr(o), case['act'], case['slope'], ptr(ws.buf), ws.n, stream())
+        else:
+            plan = HS.smallm_plan(L, d, HS.SMALLM_FWD)
+            call(L, 'sg_conv2d_smallm_fwd', dref(d), ptr(dev['x']), ptr(dev['w']), ptr(dev['b']), ptr(o), case['act'], case['slope'], stream())
+        shape = (N, M, OH, OW)
+    elif entry == 'dgrad':
+        o = outbuf(N * C * H * W)
+        plan = HS.head_plan(L, d, HS.HEAD_DGRAD, dev['x'].data_ptr() % 16, 0)
+        call(L, 'sg_conv2d_head_dgrad', dref(d), ptr(dev['gy']), ptr(dev['w']), ptr(o), stream())
+        shape = (N, C, H, W)
+    else:
+        o = outbuf(M * C * KS * KS)
+        assert dev['gy'].data_ptr() % 16 == 0
+        if head:
+            plan = HS.head_plan(L, d, HS.HEAD_WGRAD, dev['x'].data_ptr() % 16, 0)
+            call(L, 'sg_conv2d_head_wgrad', dref(d), ptr(dev['gy']), ptr(dev['x']), ptr(o), ptr(ws.buf), ws.n, stream())
+        else:
+            plan = HS.smallm_plan(L, d, HS.SMALLM_WGRAD)
+            call(L, 'sg_conv2d_smallm_wgrad', dref(d), ptr(dev['gy']), ptr(dev['x']), ptr(o), ptr(ws.buf), ws.n, stream())
+        shape = (M, C, KS, KS)
+    torch.cuda.synchronize()
+    ws.intact(name)
+    assert plan is not None, L.sg_last_error_string().decode()
+    return taken(o, shape, name), plan
+
+
+def generic_entry(L, case, entry, dev):
+    """the same desc through sg_conv2d_fwd / _dgrad / _wgrad -> (result, its bound from the plan the library reports for that launch)"""
+    d = HS.desc_of(case)
+    N, C, M, H, W, OH, OW, KS = (case[k] for k in ('N', 'C1', 'Cout', 'H', 'W', 'OH', 'OW', 'KS'))
+    r = HS.case_refs(case)
+    n = int(L.sg_conv2d_ws_bytes(dref(d), {'fwd': 0, 'dgrad': 1, 'wgrad': 2}[entry]))
+    ws = Workspace(n)
+    if entry == 'fwd':
+        o = outbuf(N * M * OH * OW)
+        plan = FC.fwd_plan(L, d, FC.FW_CONV, 0, dev['w'].data_ptr() % 16, o.data_ptr() % 16, ws.buf.data_ptr() % 16, n)
+        call(L, 'sg_conv2d_fwd', dref(d), ptr(dev['x']), None, ptr(dev['w']), ptr(dev['b']), ptr(o), case['act'], case['slope'], ptr(ws.buf), n, stream())
+        got = taken(o, (N, M, OH, OW), case['name'] + ' generic fwd')
+        bound = HS._act_bound(case, HS.gamma(plan['K'] + 1 + FC.joins(case, plan)) * r['y_sabs'], r['y'])
+    elif entry == 'dgrad':
+        o = outbuf(N * C * H * W)
+        call(L, 'sg_conv2d_dgrad', dref(d), ptr(dev['gy']), ptr(dev['w']), ptr(o), 0, C, ptr(ws.buf), n, stream())
+        got = taken(o, (N, C, H, W), case['name'] + ' generic dgrad')
+        bound = T.bound(r['gx_terms'], T.C_GATHER, r['gx_sabs'])
+    else:
+        o = outbuf(M * C * KS * KS)
+        plan = WG.wgrad_plan(L, d, WG.WG_CONV, 0, dev['gy'].data_ptr() % 16, n)
+        call(L, 'sg_conv2d_wgrad', dref(d), ptr(dev['gy']), ptr(dev['x']), None, ptr(o), None, ptr(ws.buf), n, stream())
+        got = taken(o, (M, C, KS, KS), case['name'] + ' generic wgrad')
+        bound = T.bound(r['gw_terms'], plan['grid_z'], r['gw_sabs'])
+    torch.cuda.synchronize()
+    ws.intact(case['name'] + ' generic ' + entry)
+    return got, bound
+
+
+def own_bound(case, entry, plan):
+    return {'fwd': lambda: HS.y_bound(case, plan), 'dgrad': lambda: HS.gx_bound(case), 'wgrad': lambda: HS.gw_bound(case, plan)}[entry]()
+
+
+REF_KEY = {'fwd': 'y', 'dgrad': 'gx', 'wgrad': 'gw'}
+
+
+# =============================================================================================
+# the case table
+# =============================================================================================
+@pytest.mark.parametrize('case', HS.CASES, ids=lambda c: c['name'])
+def test_case(L, case):
+    inp, ref = HS.case_inputs(case), HS.case_refs(case)
+    dev = operands(case, inp)
+    aligned = operands(case, inp, x_off=0) if case['x_off'] else dev
+    for entry in HS.case_entries(case):
+        name = '%s %s' % (case['name'], entry)
+        got, plan = twice(lambda: run_entry(L, case, entry, dev), name)          # (a second call: bit-identical)
+        for k, v in case['claims'].get(entry, {}).items():
+            assert plan[k] == v, '%s: plan field %s is %s, the table claims %s (%s)' % (name, k, plan[k], v, plan)
+        assert plan == HS.case_py_plan(case, entry), name
+        bound = own_bound(case, entry, plan)
+        held(family(case, entry, plan), got, ref[REF_KEY[entry]], bound, name)
+        other, obound = generic_entry(L, case, entry, aligned)
+        held('against the generic %s' % entry, got, other, bound + obound, name + ' against the generic entry point')
+
+
+STREAM_ROWS = [c for c in HS.HEAD_CASES if HS.case_py_plan(c, 'fwd')['kind'] == HS.HEAD_STREAM]
+
+
+@pytest.mark.parametrize('case', STREAM_ROWS, ids=lambda c: c['name'])
+def test_stream_rows_run_staged_when_an_address_is_off(L, case):
+    """x, then y, 4 bytes off a 16-byte boundary: the plan reports the staged kernel for those addresses, and the values stay within
+    the staged bound (another channel order: not bit-equal to the stream kernel)"""
+    inp, ref = HS.case_inputs(case), HS.case_refs(case)
+    for x_off, y_off in ((1, 0), (0, 1), (3, 2)):
+        name = '%s [x + %d, y + %d floats]' % (case['name'], x_off, y_off)
+        got, plan = run_entry(L, case, 'fwd', operands(case, inp, x_off=x_off), y_off=y_off)
+        assert plan['kind'] == HS.HEAD_STAGED and plan == HS.case_py_plan(case, 'fwd', 4 * x_off, 4 * y_off), (name, plan)
+        held(family(case, 'fwd', plan), got, ref['y'], HS.y_bound(case, plan), name)
+
+
+# =============================================================================================
+# one-hot probes: the index logic, bit for bit
+# =============================================================================================
+@pytest.mark.parametrize('case', HS.PROBES, ids=lambda c: c['name'])
+def test_onehot_probes_are_exact(L, case):
+    """a weight that is 1.0 at one (c, kh, kw) per output channel: the forward is a placed (small-M: mirrored) copy of input planes,
+    the head's data gradient a placed copy of gy; a gy that is 1.0 at one pixel: the weight gradient is that pixel's window of x"""
+    inp = HS.case_inputs(case)
+    taps, M = HS.probe_taps(case), case['Cout']
+    for i in range(0, len(taps), M):
+        sel = (taps[i:i + M] + taps[:M])[:M]
+        w = np.zeros((M, case['C1'], case['KS'], case['KS']), dtype=np.float32)
+        for m, (c, kh, kw) in enumerate(sel):
+            w[m, c, kh, kw] = 1.0
+        dev = operands(case, dict(inp, w=w))
+        name = '%s one-hot w at %s' % (case['name'], sel)
+        y, plan = run_entry(L, case, 'fwd', dev)
+        assert plan == HS.case_py_plan(case, 'fwd')
+        same(y, HS.place_fwd(case, inp['x'], sel), name + ' y')
+        if case['family'] == 'head':
+            same(run_entry(L, case, 'dgrad', dev)[0], HS.place_dgrad(case, inp['gy'], *sel[0]), name + ' gx')
+        del G._KEEP[:]
+    for site in HS.probe_sites(case):
+        g1 = np.zeros_like(inp['gy'])
+        g1[site[0], site[1], site[2][0], site[2][1]] = 1.0
+        gw, _ = run_entry(L, case, 'wgrad', operands(case, dict(inp, gy=g1)))
+        same(gw, HS.place_wgrad(case, inp['x'], site), '%s one-hot gy at %s' % (case['name'], site))
+        del G._KEEP[:]
+
+
+# =============================================================================================
+# operator level, coverage
+# =============================================================================================
+@pytest.mark.parametrize('name', HS.OPERATOR_ROWS)
+def test_operator_takes_the_special_route_and_the_generic_one_with_the_switch_off(L, name):
+    """ops.conv2d on the row runs ROUTE_HEAD / ROUTE_SMALLM; with HEADCONV off a head row runs the generic route; both agree with
+    float64 within the bound of the plan they ran, and so do the special route's gradients where the row has no activation"""
+    from scene_generation_amd import ops
+    case = HS.BY_NAME[name]
+    inp, ref = HS.case_inputs(case), HS.case_refs(case)
+    want = ops.ROUTE_HEAD if case['family'] == 'head' else ops.ROUTE_SMALLM
+    saved = ops.HEADCONV
+    try:
+        for headconv in ((True, False) if case['family'] == 'head' else (True,)):
+            ops.HEADCONV = headconv
+            x, w = (torch.from_numpy(inp[k]).to(DEV).requires_grad_() for k in ('x', 'w'))
+            b = None if inp['b'] is None else torch.from_numpy(inp['b']).to(DEV)
+            y = ops.conv2d(x, w, b, stride=1, pad=case['pad'], reflect=bool(case['reflect']), act=case['act'], slope=case['slope'])
+            route = y.grad_fn.route
+            assert route == (want if headconv else ops.ROUTE_GENERIC), (name, headconv, route)
+            assert x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0
+            if route == ops.ROUTE_GENERIC:
+                d = HS.desc_of(case)
+                n = int(L.sg_conv2d_ws_bytes(dref(d), 0))
+                plan = FC.fwd_plan(L, d, FC.FW_CONV, 0, 0, 0, 0, n)
+                bound = HS._act_bound(case, HS.gamma(plan['K'] + 1 + FC.joins(case, plan)) * ref['y_sabs'], ref['y'])
+                held('operator, generic route', y.detach().cpu().numpy(), ref['y'], bound, name + ' y (HEADCONV off)')
+                continue
+            plan = HS.case_py_plan(case, 'fwd', 0, 0)
+            held('operator, ' + family(case, 'fwd', plan), y.detach().cpu().numpy(), ref['y'], HS.y_bound(case, plan), name + ' y')
+            if case['act'] == HS.ACT_NONE:
+                y.backward(torch.from_numpy(inp['gy']).to(DEV))
+                gplan = HS.case_py_plan(case, 'wgrad', 0, 0)
+                held('operator, ' + family(case, 'wgrad', gplan), w.grad.cpu().numpy(), ref['gw'], HS.gw_bound(case, gplan), name + ' gw')
+                if case['family'] == 'head':
+                    held('operator, ' + family(case, 'dgrad', HS.case_py_plan(case, 'dgrad', 0, 0)), x.grad.cpu().numpy(), ref['gx'], HS.gx_bound(case), name + ' gx')
+    finally:
+        ops.HEADCONV = saved
+
+
+def test_smallm_backward_copies_a_gradient_that_starts_mid_vector(L):
+    """Conv2dFn.backward hands gy to sg_conv2d_smallm_wgrad, which refuses an address off a 16-byte boundary: a view that starts
+    mid-vector is copied first (_al16), and the weight gradient is the aligned run's, bit for bit"""
+    from scene_generation_amd import ops
+    case = HS.BY_NAME['sm_17x68_c5_m3']
+    inp = HS.case_inputs(case)
+    grads = []
+    for off in (0, 1):
+        x, w = torch.from_numpy(inp['x']).to(DEV), torch.from_numpy(inp['w']).to(DEV).requires_grad_()
+        y = ops.conv2d(x, w, None, stride=1, pad=3, reflect=True)
+        assert y.grad_fn.route == ops.ROUTE_SMALLM
+        base = torch.zeros(inp['gy'].size + 4, dtype=torch.float32, device=DEV)
+        gy = base[off:off + inp['gy'].size].view(inp['gy'].shape)
+        gy.copy_(torch.from_numpy(inp['gy']))
+        assert gy.data_ptr() % 16 == 4 * off and gy.is_contiguous()
+        y.backward(gy)
+        grads.append(w.grad.cpu().numpy())
+    assert np.array_equal(grads[0], grads[1])
+    held('operator, smallm wgrad MO=3', grads[1], HS.case_refs(case)['gw'], HS.gw_bound(case, None), case['name'] + ' gw from a misaligned gy')
+
+
+def test_table_reaches_every_plan_class(L):
+    seen = set()
+    for c in HS.CASES:
+        seen |= HS.plan_classes(c, {e: HS.case_lib_plan(L, c, e) for e in HS.case_entries(c)})
+    missing = [k for k in HS.REQUIRED_CLASSES if k not in seen]
+    assert not missing, missing
