@@ -963,6 +963,38 @@ int sg_fidinf_grams(const float* x, int n, int D, int ldx, const double* mu, con
 size_t sg_fidinf_subset_terms_ws_bytes(int S, int smax);
 int sg_fidinf_subset_terms(const double* P, const double* G, int n, const int* idx, const int* sizes, int S, int smax, double* M,
                            double* sums, void* ws, size_t ws_bytes, sgStream stream);
+/* ---- IS-infinity: the Inception score of every subset of the stored softmax rows (isinf.hip; scene_generation_amd/isinf.py) ------------
+ * The definition is that of sg_inception_score with one split, so a subset of all rows in identity order reproduces that score up to
+ * the order of the sums.  With p the stored fp32 row, s_i = sum_j (double)p_ij and ph_ij = (double)p_ij / s_i:
+ *   h_i = sum_j ph_ij log ph_ij                         a term whose ph is not > 0 is 0: a row of sum 0 contributes nothing
+ * and for a subset of n_q rows t_i = idx[q][i], all sums over i < n_q:
+ *   q_j = sum_i (double)p[t_i][j],   qh_j = q_j / sum_j q_j,   mh_j = (sum_i ph[t_i][j]) / n_q      (a ph that is not > 0 adds 0)
+ *   log score_q = (sum_i h[t_i]) / n_q - sum_j mh_j log qh_j                                        a term whose mh_j is not > 0 is 0
+ * Every sum is fp64 in a fixed order and there are no floating-point atomics, so the same call gives bit-identical output.  Neither
+ * call synchronises or allocates.  A null pointer, a misaligned one (fp64 operands and ws 8-byte, probs and the int tables 4-byte),
+ * n < 1, classes < 1, ldp < classes, S < 0, smax < 2 or a workspace below sg_isinf_subset_scores_ws_bytes returns a negative code
+ * (sg_last_error_string) and launches nothing.
+ *
+ * sg_isinf_row_terms: probs fp32 [n, classes] of row stride ldp >= classes elements (any 4-byte aligned base); writes rs[i] = s_i and
+ * h[i], fp64 [n], in one pass over the rows: a wave per row, lane l adds the classes l, l + 64, ... in ascending order, then a
+ * butterfly over the lanes.
+ *
+ * sg_isinf_subset_scores: probs, rs, h as above; idx int32 [S, smax] (device): row q holds sizes[q] row numbers, the rest of the row is
+ * not read; sizes int32 [S] (device) -- the layout of fidinf.draw_subsets; smax >= 2; S >= 0 (S == 0 returns 0 without looking at the
+ * pointers).  out fp64 [S, 2] = {log score_q, score_q = exp of it}.  The rows are gathered through the table in the loader (there is
+ * no gathered copy).  A subset's positions are cut into chunks of SG_ISINF_ROWS_PER_WG; one workgroup per (subset, chunk, tile of 1024
+ * classes) adds the chunk's rows in ascending position, a thread per 4 adjacent classes (one 16-byte load per row when probs is
+ * 16-byte aligned and ldp a multiple of 4, 4-byte loads otherwise -- the same sums in the same order either way), and writes the
+ * partial q_j, the partial sum of ph and the chunk's sum of h (lane l adds the positions l, l + 64, ..., then a butterfly) to ws; one
+ * finishing workgroup per subset adds the partials in ascending chunk order and forms the two numbers.  The wrapper validates the
+ * tables on the host; the kernels form no address from an entry outside [0, n) (it reads as a row that contributes nothing) and
+ * clamp a size to [0, smax]; below 2 both outputs are NaN.
+ * ws >= sg_isinf_subset_scores_ws_bytes(S, smax, classes) = 8 S (ceil(smax / SG_ISINF_ROWS_PER_WG) + 1) (2 classes + 1) bytes. */
+#define SG_ISINF_ROWS_PER_WG 64
+int sg_isinf_row_terms(const float* probs, int n, int classes, int ldp, double* rs, double* h, sgStream stream);
+size_t sg_isinf_subset_scores_ws_bytes(int S, int smax, int classes);
+int sg_isinf_subset_scores(const float* probs, int n, int classes, int ldp, const double* rs, const double* h, const int* idx,
+                           const int* sizes, int S, int smax, double* out, void* ws, size_t ws_bytes, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

@@ -131,6 +131,8 @@ enum {
   SG_K_PIL_RESIZE,
   // the extrapolated FID (fidinf.hip): the two Gram matrices of the shifted feature rows (f64 MFMA), the per-subset terms
   SG_K_FIDINF_GRAMS, SG_K_FIDINF_TERMS,
+  // the extrapolated Inception score (isinf.hip): the per-row sums and entropies, the gathered column reduction of every subset
+  SG_K_ISINF_ROWS, SG_K_ISINF_SUBSETS,
   // the gradient control of the fused Adam step (loss.hip): the float64 sum of squares of a flat gradient buffer (4 B per element)
   SG_K_GRAD_NORM,
   // size and location attributes from class statistics (attributes.hip): the per-class counts, the constrained draw

@@ -175,7 +175,8 @@ const char* kTail[SG_K_COUNT - SG_K_IGEMM_COUNT] = {"linear", "layout_fwd", "lay
                                                     "rect_conv_t64", "rect_conv_t32", "rect_conv_t64x128", "rect_reduce", "inception_pool",
                                                     "resize_bilinear", "softmax_rows", "inception_score", "fid_moments", "wide_conv_t64",
                                                     "lpips_input", "lpips_layer", "feat_poly", "feat_manifold", "pil_resize",
-                                                    "fidinf_grams", "fidinf_terms", "grad_norm", "attributes_hist",
+                                                    "fidinf_grams", "fidinf_terms", "isinf_row_terms", "isinf_subset_scores", "grad_norm",
+                                                    "attributes_hist",
                                                     "attributes_sample"};
 char g_names[SG_K_COUNT][32];
 bool g_names_init = false;

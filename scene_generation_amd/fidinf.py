@@ -21,7 +21,8 @@ matrix and two numbers per subset, never a feature row.
 
 * The route is for N <= ``max_rows`` rows (the M blocks grow as N^2); beyond that the bias it removes is small and plain FID
   (fid.py) is the tool.
-* IS-infinity, the paper's companion for the Inception score, is NOT built.
+* IS-infinity, the paper's companion for the Inception score, is ``isinf.py``; it uses ``draw_sizes``, ``draw_subsets`` and
+  ``extrapolate`` of this module.  The paper's Sobol sampling of the generator's input is NOT built.
 * ``FIDInfinity`` speaks the protocol ``FrechetInceptionDistance(sets=...)`` and ``InceptionScore(fid=...)`` drive, and forwards every
   call to an optional ``FeatureSetMetrics`` (``then``), so FID, FID-infinity, KID and precision / recall hang on one Inception forward.
 """

@@ -1,7 +1,7 @@
 """The Inception score: the reference's last evaluation figure (scripts/inception_score.py, train.py:177-225) on this stack.
 
     python -m scene_generation_amd.inception --dir DIR --weights PATH [--splits 5] [--batch_size 32]     -> mean and std
-                                             [--image_size H,W [--resize_filter bilinear|bicubic]]
+                                             [--image_size H,W [--resize_filter bilinear|bicubic]] [--save_probs OUT.npy]
 
 * ``InceptionV3``: torchvision's Inception-v3 (``inception_v3(transform_input=False)``) with its ``state_dict`` keys and shapes, so
   the published ``inception_v3_google-*.pth`` loads with ``strict=True``.  Inference only: every conv + BatchNorm + ReLU is ONE
@@ -10,7 +10,7 @@
   file loads and never runs.
 * ``InceptionScore``: the reference's object -- ``clean()``, ``__call__(imgs)``, ``compute_score(splits) -> (mean, std)`` -- that
   ``evaluate.check_model`` and ``Trainer`` drive.  Softmax rows accumulate in a device buffer that grows by doubling; ``__call__``
-  never synchronises, ``compute_score`` does the one host read.
+  never synchronises, ``compute_score`` does the one host read.  ``rows()`` is the view of the rows ``isinf.ISInfinity`` works on.
 * ``inception_network`` / ``pooled_features``: what the score, ``fid`` and ``featsets`` share -- the network a ``weights`` argument
   stands for, and the chunk / resize / ``features`` loop.  File, image and buffer helpers live in ``evalkit``, directory feeding in
   ``imageprep``.
@@ -463,6 +463,12 @@ class InceptionScore(nn.Module):
             ops.softmax_rows(logits, self.probs, self.count)
             self.count += logits.size(0)
 
+    def rows(self):
+        """the softmax rows added since ``clean()``, float32 [count, classes] on the device (a view of the buffer); no host read"""
+        if self.probs is None:
+            return torch.empty(0, self.classes, dtype=torch.float32, device=self.device)
+        return self.probs[:self.count]
+
     def scores(self, splits=1):
         """float64 device tensor {mean, std, per-split scores}; no host read"""
         probs = self.probs if self.probs is not None else torch.empty(1, self.classes, dtype=torch.float32, device=self.device)
@@ -482,6 +488,8 @@ def build_parser():
     p.add_argument('--splits', default=5, type=int)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--device', default='cuda', type=str)
+    p.add_argument('--save_probs', default=None, type=str, help='write the softmax rows [N, classes] as an .npy (what python -m '
+                   'scene_generation_amd.isinf --probs reads)')
     return add_arguments(p)
 
 
@@ -494,6 +502,10 @@ def main(argv=None):
     _feed_dir(scorer, args.dir, args.batch_size, image_size=args.image_size, resize_filter=args.resize_filter, device=scorer.device)
     mean, std = scorer.compute_score(splits=args.splits)
     print('Inception {} {}'.format(mean, std))
+    if args.save_probs is not None:
+        import numpy as np
+        with open(args.save_probs, 'wb') as f:      # (an open file: numpy.save appends no suffix to it)
+            np.save(f, scorer.rows().cpu().numpy())
     return mean, std
 
 

@@ -30,6 +30,8 @@ scene_generation/data/utils.py it needs).
   carries it, read once by ``featsets_summary``; ``--real_features`` on the command line.
 * ``--fid_infinity 1`` (with ``--fid_stats``) puts a ``fidinf.FIDInfinity`` in the ``sets`` slot of ``fid``, the ``FeatureSetMetrics``
   behind it (``then``): the FID extrapolated to an infinite number of images, from the same forward.
+* ``--is_infinity 1`` (with ``--inception_weights``) reads an ``isinf.ISInfinity`` over the rows the scorer holds after the last batch:
+  the Inception score extrapolated to an infinite number of images, from the same forward.
 * ``diversity`` (an ``lpips.Diversity``, off by default): the mean LPIPS distance between two pictures of the same scene graph with
   different appearance draws.  ``sample_pair`` runs ``sample_batch`` and then a second forward of the same batch with fresh bank
   draws that feeds this scorer ONLY; read once by ``diversity_summary``; ``--diversity_backbone`` / ``--diversity_lin`` /
@@ -427,6 +429,12 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if want_inf and loader is None and not getattr(args, 'scene_graphs', None) and not getattr(args, 'layouts', None):
         from .fidinf import check_count
         check_count(args.num_samples)       # the synthetic generator makes exactly this many: too few or too many are refused here
+    want_isinf = bool(getattr(args, 'is_infinity', False))
+    if want_isinf and getattr(args, 'inception_weights', None) is None:
+        raise ValueError('--is_infinity needs --inception_weights (the network whose softmax rows the score is extrapolated from)')
+    if want_isinf and loader is None and not getattr(args, 'scene_graphs', None) and not getattr(args, 'layouts', None):
+        from .isinf import check_count as check_rows
+        check_rows(args.num_samples)        # likewise: a count that gives no two subset sizes is refused before the first picture
     model = build_model(args, checkpoint, device)
     graphs = getattr(args, 'scene_graphs', None)
     layouts = getattr(args, 'layouts', None)
@@ -516,6 +524,9 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         if want_inf:                        # (the count is known only now: still before the first picture)
             from .fidinf import check_count
             check_count(len(sgs))
+        if want_isinf:
+            from .isinf import check_count as check_rows
+            check_rows(len(sgs))
         for a in range(0, len(sgs), args.batch_size):
             save(sampler.sample_json(sgs[a:a + args.batch_size], want_layout_rgb=args.save_layout), None)
     else:
@@ -546,6 +557,10 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
     if scorer is not None:
         result['inception'] = sampler.inception_summary(getattr(args, 'inception_splits', 5))
         print('Inception {} {}'.format(result['inception']['mean'], result['inception']['std']))
+        if want_isinf:
+            from .isinf import ISInfinity
+            result['is_inf'] = ISInfinity(scorer).compute()
+            print('IS_inf {}'.format(result['is_inf']['is_inf']))
     if fid is not None:
         result['fid'] = sampler.fid_summary()
         print('FID {}'.format(result['fid']['fid']))
@@ -617,6 +632,9 @@ def make_parser():
     p.add_argument('--fid_infinity', default=False, type=bool_flag, help='with --fid_stats: also print one "FID_inf x" line after the '
                    'FID line, the distance extrapolated to an infinite number of sampled images (python -m scene_generation_amd.fidinf; '
                    'at most 4096 images)')
+    p.add_argument('--is_infinity', default=False, type=bool_flag, help='with --inception_weights: also print one "IS_inf x" line after '
+                   'the Inception line, the score extrapolated to an infinite number of sampled images (python -m '
+                   'scene_generation_amd.isinf)')
     p.add_argument('--diversity_backbone', default=None, help='torchvision alexnet / vgg16 state_dict file (never downloaded): every '
                    'batch is sampled twice with different appearance draws and one "Diversity MEAN STD" line (mean LPIPS distance '
                    'of the pairs) is printed; python -m scene_generation_amd.lpips scores two directories of pictures')
