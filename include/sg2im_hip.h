@@ -55,6 +55,20 @@ int sg_set_option(const char* name, int value);
 /* device bytes held by the shape-table cache; drop it (synchronises the tables' build events) */
 size_t sg_plan_cache_bytes(void);
 int sg_plan_cache_clear(void);
+/* What launches SHARE on the current device (a host query for tests; it adds no option, changes no launch and is never called on
+ * the training path).  Launches outside a stream capture draw their ticket counters from a ring of their own (device, stream),
+ * created by the first such launch of that stream; captured launches draw from one region per device that is handed out once.  A
+ * launch leaves every counter it drew at zero.  Before the ring of ``stream`` exists its three fields read 0, and before the
+ * device's first eager request for a counter every counter field does.  ``count_nonzero`` != 0: synchronises the device, copies
+ * every counter of the device (the capture region and the rings of all its streams) to the host and counts those that are not 0. */
+typedef struct sgRuntimeState {
+  int ring_size, ring_at, ring_laps;        /* the eager ring `stream` draws from: size, next index, wraps so far */
+  int captured_size, captured_used;         /* capture region of the current device */
+  int counters_nonzero;                     /* -1 unless asked for */
+  size_t tail_bytes, tail_captured_bytes;   /* scratch of (device, stream); scratch shared by captured launches */
+  int tail_retired;                         /* outgrown scratch buffers still held */
+} sgRuntimeState;
+int sg_runtime_state(sgStream stream, int count_nonzero, sgRuntimeState* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Convolution family = implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32, k-ordered fma chain).

@@ -20,7 +20,8 @@ LIB_PATH = os.environ.get('SG_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libsg2i
 _STRUCT_RE = r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;'
 _ENUM_RE = r'enum\s*(\w*)\s*\{(.*?)\}\s*;'
 _INT = r'-?\s*(?:0[xX][0-9a-fA-F]+|\d+)'
-_FIELD_TYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double}
+_FIELD_TYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double,
+                'int': ctypes.c_int, 'size_t': ctypes.c_size_t}
 
 
 def _strip_comments(src):
@@ -30,7 +31,7 @@ def _strip_comments(src):
 def parse_types(src):
     """header text -> (structs, const): {name: ctypes.Structure subclass} with the header's field order, and {name: int} of the
     enumerators and the integer ``#define SG_*``.  Raises ValueError, naming the struct / enum / define, for anything but
-    ``<int32_t|int64_t|float|double> name[, name[n]...];`` fields, ``NAME = <integer>`` enumerators and integer defines."""
+    ``<int32_t|int64_t|float|double|int|size_t> name[, name[n]...];`` fields, ``NAME = <integer>`` enumerators and integer defines."""
     src = _strip_comments(src)
     structs, const = {}, {}
 

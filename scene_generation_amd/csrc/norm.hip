@@ -490,7 +490,14 @@ constexpr int BN_REG = 40;
 struct BnFinal {
   int* counter; float* save_mean; float* save_rstd; float* rmean; float* rvar; int64_t* nbt; float eps, momentum;
 };
+// bn_combine and bn_write_stats are inlined into bn_final_kernel AND into the last arriver of bn_stats_kernel, and the two must
+// agree bit for bit (common.h).  Left to the compiler, each copy got its own choice of which a * b + c become an fma, and where
+// the partial means cancel (a channel mean near zero) the saved mean of the two forms differed in the last bit
+// (tests/test_gpu_shared_state.py, batchnorm_fwd).  So contraction is OFF in both functions and the one fma is written out: the
+// roundings below are exactly those bn_final_kernel has always been compiled to (unfused everywhere, except that the m2 term of the
+// slices 1..7 of a group of eight is one fma), so the two-kernel form computes what it computed before.
 __device__ __forceinline__ void bn_combine(const float* __restrict__ part, int c, int S, bool coherent, float& n, float& mean, float& m2) {
+#pragma clang fp contract(off)
   n = 0.f; mean = 0.f; m2 = 0.f;
   // (the partials of 8 slices are fetched together: one thread walking S <= 64 dependent round trips took 10 us)
   for (int z0 = 0; z0 < S; z0 += 8) {
@@ -508,13 +515,14 @@ __device__ __forceinline__ void bn_combine(const float* __restrict__ part, int c
       if (nb <= 0.f) continue;
       const float d = pm[e] - mean, nt = n + nb;
       mean += d * (nb / nt);
-      m2 += pq[e] + d * d * (n * nb / nt);
+      m2 += e == 0 ? pq[e] + d * d * (n * nb / nt) : __builtin_fmaf(n * nb / nt, d * d, pq[e]);
       n = nt;
     }
   }
 }
 __device__ __forceinline__ void bn_write_stats(int c, float n, float mean, float m2, float* save_mean, float* save_rstd, float* rmean,
                                                float* rvar, int64_t* nbt, float eps, float momentum) {
+#pragma clang fp contract(off)
   const float var = m2 / n;
   save_mean[c] = mean;
   save_rstd[c] = 1.f / sqrtf(var + eps);

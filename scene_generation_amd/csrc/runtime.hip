@@ -72,16 +72,27 @@ extern "C" int sg_set_option(const char* key, int value) {
 }
 
 // ---- ticket counters of the in-launch finalisation (common.h: sg_arrive_last) ---------------------------------------------------
-// One zero-initialised pool per device.  Launches outside a stream capture take counters from a RING (a counter is busy only
-// while its launch runs and is left at zero by the last arriver: 65536 slots cannot wrap onto a launch still in flight);
-// launches recorded into a hipGraph keep their counter for the life of the graph, so they come from a second region that is
-// only ever handed out once (exhausted -> nullptr -> the caller's two-kernel form).
+// Launches outside a stream capture take counters from a RING of their own (device, stream), zero-initialised when the stream's
+// first such launch asks (a counter is busy only while its launch runs and is left at zero by the last arriver; launches of one
+// stream run in order, so a ring of 65536 slots cannot wrap onto a launch still in flight, whatever other streams do -- until the
+// rings were per stream that held only because Trainer.step joins its side streams once per step).  Launches recorded into a
+// hipGraph keep their counter for the life of the graph, so they come from one region per device that is only ever handed out
+// once (exhausted -> nullptr -> the caller's two-kernel form).  Nothing is allocated or zeroed inside a capture: a capture on a
+// device whose region does not exist yet gets nullptr.  The rings are kept the way g_tail keeps its buffers (a vector under the
+// mutex, never freed); sg_runtime_state reports all of it.
 namespace {
 constexpr int CNT_RING = 65536, CNT_CAPTURED = 262144, CNT_DEVICES = 16;
 std::mutex g_cnt_mu;
-int* g_cnt_pool[CNT_DEVICES] = {};
-unsigned g_cnt_ring[CNT_DEVICES] = {};
+int* g_cnt_pool[CNT_DEVICES] = {};            // the capture region
 int g_cnt_cap[CNT_DEVICES] = {};
+struct CntRing { int dev; hipStream_t s; int* p; unsigned at; int laps; };
+std::vector<CntRing> g_cnt_rings;
+int* cnt_zeroed(size_t n) {                   // g_cnt_mu held; outside captures only
+  int* p = nullptr;
+  if (hipMalloc((void**)&p, n * sizeof(int)) != hipSuccess) return nullptr;
+  if (hipMemset(p, 0, n * sizeof(int)) != hipSuccess) { hipFree(p); return nullptr; }      // synchronous: visible to every later launch
+  return p;
+}
 }  // namespace
 
 int* sg_counter_alloc(hipStream_t s, int n, bool always, int family) {
@@ -93,22 +104,27 @@ int* sg_counter_alloc(hipStream_t s, int n, bool always, int family) {
   std::lock_guard<std::mutex> lk(g_cnt_mu);
   if (!g_cnt_pool[dev]) {
     if (capturing) return nullptr;                        // (no allocation / memset inside a capture)
-    int* p = nullptr;
-    const size_t bytes = (size_t)(CNT_RING + CNT_CAPTURED) * sizeof(int);
-    if (hipMalloc((void**)&p, bytes) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, bytes) != hipSuccess) { hipFree(p); return nullptr; }      // synchronous: visible to every later launch
-    g_cnt_pool[dev] = p;
+    if (!(g_cnt_pool[dev] = cnt_zeroed(CNT_CAPTURED))) return nullptr;
   }
   if (capturing) {
     if (g_cnt_cap[dev] + n > CNT_CAPTURED) return nullptr;
-    int* r = g_cnt_pool[dev] + CNT_RING + g_cnt_cap[dev];
+    int* r = g_cnt_pool[dev] + g_cnt_cap[dev];
     g_cnt_cap[dev] += n;
     return r;
   }
-  unsigned at = g_cnt_ring[dev];
-  if (at + (unsigned)n > (unsigned)CNT_RING) at = 0;
-  g_cnt_ring[dev] = at + (unsigned)n;
-  return g_cnt_pool[dev] + at;
+  CntRing* ring = nullptr;
+  for (auto& r : g_cnt_rings)
+    if (r.dev == dev && r.s == s) { ring = &r; break; }
+  if (!ring) {
+    int* p = cnt_zeroed(CNT_RING);
+    if (!p) return nullptr;
+    g_cnt_rings.push_back(CntRing{dev, s, p, 0u, 0});
+    ring = &g_cnt_rings.back();
+  }
+  unsigned at = ring->at;
+  if (at + (unsigned)n > (unsigned)CNT_RING) { at = 0; ring->laps += 1; }
+  ring->at = at + (unsigned)n;
+  return ring->p + at;
 }
 
 namespace {
@@ -126,11 +142,16 @@ std::vector<TailScratch> g_tail;
 namespace {
 struct TailCap { float* p; size_t bytes; };
 TailCap g_tail_cap[CNT_DEVICES] = {};
+std::vector<float*> g_tail_retired[CNT_DEVICES];        // outgrown buffers (of g_tail and g_tail_cap), held for good
+void tail_retire(int dev, float* p) {
+  if (p && dev >= 0 && dev < CNT_DEVICES) g_tail_retired[dev].push_back(p);
+}
 void tail_cap_reserve(int dev, size_t bytes) {          // g_cnt_mu held; outside captures only
   if (dev < 0 || dev >= CNT_DEVICES || g_tail_cap[dev].bytes >= bytes) return;
   float* q = nullptr;
   if (hipMalloc((void**)&q, bytes) != hipSuccess) return;
-  g_tail_cap[dev].p = q; g_tail_cap[dev].bytes = bytes;   // (the old buffer may be baked into a captured graph: kept)
+  tail_retire(dev, g_tail_cap[dev].p);                    // (the old buffer may be baked into a captured graph: kept)
+  g_tail_cap[dev].p = q; g_tail_cap[dev].bytes = bytes;
 }
 }  // namespace
 
@@ -149,6 +170,7 @@ float* sg_tail_scratch(hipStream_t s, size_t bytes) {
       // a larger request: the old buffer may still be read by a launch in flight -- it is kept (a few MB), a new one takes its place
       float* q = nullptr;
       if (hipMalloc((void**)&q, bytes) != hipSuccess) return nullptr;
+      tail_retire(dev, t.p);
       t.p = q; t.bytes = bytes;
       return q;
     }
@@ -156,6 +178,39 @@ float* sg_tail_scratch(hipStream_t s, size_t bytes) {
   if (hipMalloc((void**)&q, bytes) != hipSuccess) return nullptr;
   g_tail.push_back(TailScratch{dev, s, q, bytes});
   return q;
+}
+
+extern "C" int sg_runtime_state(sgStream stream, int count_nonzero, sgRuntimeState* out) {
+  if (!out) { sg_set_error("sg_runtime_state: out is null"); return -1; }
+  memset(out, 0, sizeof(*out));
+  out->counters_nonzero = -1;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CNT_DEVICES) { sg_set_error("sg_runtime_state: no current device below %d", CNT_DEVICES); return -1; }
+  hipStream_t s = (hipStream_t)stream;
+  if (count_nonzero && hipDeviceSynchronize() != hipSuccess) { sg_set_error("sg_runtime_state: hipDeviceSynchronize failed"); return -1; }
+  std::lock_guard<std::mutex> lk(g_cnt_mu);
+  for (const auto& r : g_cnt_rings)
+    if (r.dev == dev && r.s == s) { out->ring_size = CNT_RING; out->ring_at = (int)r.at; out->ring_laps = r.laps; }
+  if (g_cnt_pool[dev]) { out->captured_size = CNT_CAPTURED; out->captured_used = g_cnt_cap[dev]; }
+  for (const auto& t : g_tail)
+    if (t.dev == dev && t.s == s) out->tail_bytes = t.bytes;
+  out->tail_captured_bytes = g_tail_cap[dev].bytes;
+  out->tail_retired = (int)g_tail_retired[dev].size();
+  if (count_nonzero) {
+    std::vector<int> host(CNT_CAPTURED);
+    int dirty = 0;
+    auto count = [&](const int* p, int n) {
+      if (hipMemcpy(host.data(), p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return false;
+      for (int i = 0; i < n; ++i) dirty += host[i] != 0;
+      return true;
+    };
+    bool ok = !g_cnt_pool[dev] || count(g_cnt_pool[dev], CNT_CAPTURED);
+    for (const auto& r : g_cnt_rings)
+      if (ok && r.dev == dev) ok = count(r.p, CNT_RING);
+    if (!ok) { sg_set_error("sg_runtime_state: copying the counters to the host failed"); return -1; }
+    out->counters_nonzero = dirty;
+  }
+  return 0;
 }
 
 namespace {

@@ -488,6 +488,16 @@ def stage_copy(dst, src_pinned, nbytes):
     return dst
 
 
+def runtime_state(count_nonzero=False, stream=None):
+    """-> dict of sgRuntimeState (include/sg2im_hip.h): what launches on the current device share -- the ticket ring of ``stream``
+    (a raw handle; default: the current stream), the capture region, the tail-split scratch.  ``count_nonzero``: synchronise the
+    device and count the ticket counters that are not zero (else -1).  A host query for tests; not for the training path."""
+    st = _hip.sgRuntimeState()
+    if _L().sg_runtime_state(_stream() if stream is None else stream, 1 if count_nonzero else 0, ctypes.byref(st)) != 0:
+        raise RuntimeError('sg_runtime_state failed: %s' % _hip.last_error())
+    return _hip.plan_dict(st)
+
+
 def add_clear_(y, x):
     """y += x ; x = 0 (optim.FusedAdam._fold_spill)"""
     assert y.numel() == x.numel()

@@ -225,7 +225,13 @@ class DeviceBatchPrefetcher(object):
     def close(self):
         """stop the staging thread and release what it holds (pinned slots, the source iterator).  Call it -- or use the
         prefetcher as a context manager -- when a loop leaves early (``break`` at max iterations): the worker reads up to
-        depth + 1 batches ahead of the consumer, and those batches are consumed from the source."""
+        depth + 1 batches ahead of the consumer, and those batches are consumed from the source.
+
+        The copy kernels read the page-locked slots through their device mapping, which torch's host allocator knows nothing
+        about: a slot freed while its last copy is still queued goes straight back to the allocator's cache, and whoever is handed
+        the block next (the next prefetcher, a DataLoader pin thread) writes into a batch that has not been read yet.  So close()
+        DRAINS: it waits for the event behind every slot's last copy before it lets go of the slot's buffer.  ``__del__`` goes
+        through here too."""
         th = self._thread
         if self.threaded and th is not None:
             self._stop.set()
@@ -237,6 +243,12 @@ class DeviceBatchPrefetcher(object):
             self._thread = None
             if th is not threading_current():
                 th.join(timeout=2.0)
+        self._queue = []
+        for slot in self._slots:                # (after the join: the worker no longer packs into a slot)
+            ev = slot.get('ev')
+            if ev is not None:
+                ev.synchronize()
+            slot.clear()
 
     def __enter__(self):
         return self

@@ -322,12 +322,16 @@ def test_winograd_f43_tail_split_at_the_benchmark_shape(hip):
     assert not torch.equal(res[1][0], res[0][0]) or not torch.equal(res[1][1], res[0][1]), 'the split schedule did not run'
 
 
-@pytest.mark.parametrize('shape', [(32, 64, 65, 65, 128, 4, 2, 2), (24, 192, 16, 16, 192, 3, 1, 1), (32, 128, 33, 33, 256, 4, 2, 2)])
+@pytest.mark.parametrize('shape', [(32, 64, 65, 65, 128, 4, 2, 2), (24, 192, 16, 16, 192, 3, 1, 1), (32, 124, 33, 33, 256, 4, 2, 2)])
 def test_tail_split_general_form_vs_plain_schedule(hip, shape):
     """Option w43_tail_split = 2 (the default since the end of round 6): a plain conv GEMM launch whose last round of resident workgroups is ragged runs its last
     tiles as 2-4 workgroups of a fraction of the k range each; the last arriver re-reads all dumps and adds them in piece order.  At
     layer shapes of the step (PatchGAN scale-0 convs, an object-side 3x3 conv): forward and data gradient equal the plain schedule to
-    fp32 summation order, and five repeats are bit-identical (the combine order does not depend on who arrives last)."""
+    fp32 summation order, and five repeats are bit-identical (the combine order does not depend on who arrives last).  That the
+    forward launch took the split schedule is read from the ticket ring (sg_runtime_state): it drew counters in mode 2 and none in
+    mode 0.  (The third shape had 128 input channels until the ring was looked at: K = 2048 reaches split_kmin, the launch runs
+    split-K in both modes and the tail split never applied -- the test compared the plain schedule with itself; 124 channels keep
+    the 580 tiles and stay below split_kmin.)"""
     from scene_generation_amd import _hip
     N, C, H, W, Cout, KS, stride, pad = shape
     x, w, b = det((N, C, H, W), 331), det((Cout, C, KS, KS), 332, 0.05), det((Cout,), 333, 0.2)
@@ -339,7 +343,12 @@ def test_tail_split_general_form_vs_plain_schedule(hip, shape):
             reps = []
             for _ in range(5 if mode == 2 else 1):
                 xg, wg, bg = [t.to(DEV).requires_grad_() for t in (x, w, b)]
+                s0 = hip.runtime_state()
                 yg = hip.conv2d(xg, wg, bg, stride=stride, pad=pad)
+                s1 = hip.runtime_state()
+                drew = (s1['ring_laps'], s1['ring_at']) != (s0['ring_laps'], s0['ring_at'])
+                assert drew == (mode == 2), 'w43_tail_split = %d: the forward launch drew %s (ring %r -> %r)' % (
+                    mode, 'counters' if drew else 'no counters', s0, s1)
                 yg.backward(det(tuple(yg.shape), 334).to(DEV))
                 reps.append((yg.detach().clone(), xg.grad.clone(), wg.grad.clone()))
             for r in reps[1:]:
@@ -358,7 +367,8 @@ def test_parity_class_split_vs_plain_schedule(hip, kind, N, Cin, Cout, H):
     with few tiles the 4-tap class's tiles run as two half-k workgroups that meet through the tail-split ticket (igemm_core.h,
     ParityClasses::split).  At the step's shapes (and at the two-image shapes of the multi-rank bench case): against torch fp32, against
     the unsplit schedule to fp32 summation order, and five repeats bit-identical (the sum of the two halves does not depend on who
-    arrives last)."""
+    arrives last).  That the launch with the parity classes (the forward of 'up', the data gradient of 'down') took the split
+    schedule is read from the ticket ring (sg_runtime_state): it drew counters with par_split = 1 and none with par_split = 0."""
     from scene_generation_amd import _hip
     saved = _hip.get_option('par_split')
     if kind == 'up':
@@ -380,8 +390,16 @@ def test_parity_class_split_vs_plain_schedule(hip, kind, N, Cin, Cout, H):
             reps = []
             for _ in range(5 if mode == 1 else 1):
                 xg, wg, bg = [t.to(DEV).requires_grad_() for t in (x, w, b)]
+                gyg = gy.to(DEV)
+                s0 = hip.runtime_state()
                 yg = run(xg, wg, bg)
-                yg.backward(gy.to(DEV))
+                s1 = hip.runtime_state()
+                yg.backward(gyg)
+                s2 = hip.runtime_state()
+                a, c = (s0, s1) if kind == 'up' else (s1, s2)          # the launch that carries the parity classes
+                drew = (c['ring_laps'], c['ring_at']) != (a['ring_laps'], a['ring_at'])
+                assert drew == (mode == 1), 'par_split = %d: the parity-class launch drew %s (ring %r -> %r)' % (
+                    mode, 'counters' if drew else 'no counters', a, c)
                 reps.append((yg.detach().clone(), xg.grad.clone(), wg.grad.clone()))
             for r in reps[1:]:
                 assert all(torch.equal(a, c) for a, c in zip(r, reps[0]))
