@@ -1009,6 +1009,54 @@ int sg_isinf_row_terms(const float* probs, int n, int classes, int ldp, double* 
 size_t sg_isinf_subset_scores_ws_bytes(int S, int smax, int classes);
 int sg_isinf_subset_scores(const float* probs, int n, int classes, int ldp, const double* rs, const double* h, const int* idx,
                            const int* sizes, int S, int smax, double* out, void* ws, size_t ws_bytes, sgStream stream);
+/* ---- quasi-random inputs of the generator: scrambled Sobol points on the device (qmc.hip; scene_generation_amd/qmc.py) -----------------
+ * One image's randomness -- its mask-noise row, one appearance-bank pick per object, two attribute uniforms per object -- read off ONE
+ * point of a digitally shifted Sobol sequence of D = noise_dim + 3 * max_objects dimensions.  Everything below is integer arithmetic
+ * but the inverse normal CDF, every output element has one owner, there are no atomics: a call repeats bit for bit.  No call
+ * synchronises or allocates.  A bad argument returns one of the negative codes below (sg_last_error_string) and launches nothing:
+ *   SG_QMC_ERR_NULL  a null pointer        SG_QMC_ERR_DIMS  D (noise_dim, max_objects, rep, C) outside its range
+ *   SG_QMC_ERR_LD    a row stride below D  SG_QMC_ERR_RANGE first < 0 or first + n > 2^SG_QMC_MAXBIT
+ *   SG_QMC_ERR_COUNT a negative count, or one beyond the launch grid
+ * (counts are checked first, then the dimensions, the stride, the range and last the pointers).
+ *
+ * sg_sobol_points: out[i][d] int32, i < n, d < D, row stride ld >= D elements (columns D .. ld - 1 are not written) = the
+ * SG_QMC_MAXBIT-bit integer state of point number k = first + i in dimension d,
+ *   x(i, d) = shift[d] ^ XOR over the set bits b of g of dirs[d][b],   g = k ^ (k >> 1)
+ * -- the closed form of the Gray-code recurrence of torch.quasirandom.SobolEngine, whose ``sobolstate`` [D][30] and ``shift`` [D] are
+ * dirs and shift (int32, values below 2^30); x * 2^-30 is the point in [0, 1).  Point 0 is ``shift`` itself.  1 <= D <=
+ * SG_QMC_MAX_DIMS, first >= 0, n >= 0, first + n <= 2^30; n == 0 returns 0 without looking at the pointers.  A workgroup owns one
+ * point and 128 dimensions, so the walk over the bits of g is uniform across it.
+ *
+ * sg_qmc_unpack: the N points [N][ld] of a batch -> the three tables a forward consumes, one launch.  obj_to_img [O] int64 sorted
+ * ascending, seg_off [N + 1] int32 (sg_segment_offsets); object o of image n = obj_to_img[o] sits in slot j = o - seg_off[n] and owns
+ * the columns c = noise_dim + 3 j + {0, 1, 2}; ld >= noise_dim + 3 * max_objects, noise_dim >= 0, max_objects >= 0, not both 0.
+ *   noise [N][noise_dim] fp32 = (float)normcdfinv(((double)x + 0.5) * 2^-30): the centre of the cell, so every value is finite
+ *                               (x = 0 and x = 2^30 - 1 give -+6.1208...)
+ *   pick  [O] int32           = x(n, c + 0), the raw 30-bit integer (sg_bank_draw scales it)
+ *   u     [O][2] fp32         = (x >> 6) * 2^-24 of the columns c + 1, c + 2: exact in fp32 and below 1 (the contract of
+ *                               sg_sample_attributes' u)
+ * An object whose image is outside [0, N) or whose slot is outside [0, max_objects) gets pick = -1 and u = 0.
+ *
+ * sg_bank_draw: bank [R][rep] fp32, the rows of all classes back to back; class_off [C + 1] int64; objs [O] int64; pick [O] int32.
+ * With c = objs[o] and rows_c = class_off[c + 1] - class_off[c]:
+ *   idx = ((int64)pick[o] * rows_c) >> 30     (exact; idx < rows_c because pick < 2^30)
+ *   row_idx[o] = idx,  rows[o][:] = bank[class_off[c] + idx][:]
+ * An object with c outside [0, C), rows_c <= 0, pick outside [0, 2^30) or a source row outside [0, R) gets row_idx = -1 and a row
+ * of zeros; no address is formed from such an entry.  rep >= 1, C >= 1, R >= 0.  Rows are contiguous, so a load wider than 4 bytes
+ * is aligned in every row only if its width divides rep: the copy runs on the widest of 16 / 8 / 4 bytes that divides 4 * rep and
+ * both base addresses, which leaves no tail. */
+#define SG_QMC_MAXBIT 30
+#define SG_QMC_MAX_DIMS 21201
+#define SG_QMC_ERR_NULL (-3)
+#define SG_QMC_ERR_DIMS (-4)
+#define SG_QMC_ERR_LD (-5)
+#define SG_QMC_ERR_RANGE (-6)
+#define SG_QMC_ERR_COUNT (-7)
+int sg_sobol_points(const int32_t* dirs, const int32_t* shift, int32_t* out, int64_t first, int64_t n, int D, int ld, sgStream stream);
+int sg_qmc_unpack(const int32_t* points, int ld, const int64_t* obj_to_img, const int32_t* seg_off, float* noise, int32_t* pick,
+                  float* u, int N, int O, int noise_dim, int max_objects, sgStream stream);
+int sg_bank_draw(const float* bank, const int64_t* class_off, const int64_t* objs, const int32_t* pick, int32_t* row_idx,
+                 float* rows, int O, int C, int rep, int64_t R, sgStream stream);
 /* g_vecs[o, d] for d in [d_begin, D) (columns below d_begin are zero-filled) */
 int sg_masks_to_layout_bwd_vecs(const float* gout, const float* boxes, const void* masks, int masks_i64,
                                 const int64_t* obj_to_img, const int32_t* seg_off, float* g_vecs, int N, int O, int D,

@@ -67,7 +67,7 @@ class Model(nn.Module):
         self.layout_to_image = define_G(self.num_objs + rep_size, 3, ngf, n_downsample_global, n_blocks_global,
                                         'instance')
         # hooks that are not part of the reference surface
-        self.noise_override = None          # (1, mask_noise_dim) row used instead of torch.randn (parity tests)
+        self.noise_override = None          # (1, mask_noise_dim) row used instead of torch.randn (parity tests), or (N, mask_noise_dim): one row per image
         self.layout_objects_hint = 0        # objects/image the layout kernel provisions LDS for (0 = default 12)
         self.objs_host = None               # optional host copies of ``objs`` / ``obj_to_img`` (lists): skip the one
         self.obj_to_img_host = None         # D2H copy per forward that VectorPool and the sparse first conv need
@@ -103,7 +103,7 @@ class Model(nn.Module):
         with streams.fork(objs.device, 'front', enabled=side) as fk:
             with fk.branch(1, reads=(objs, triples, attributes)):
                 obj_vecs, pred_vecs = self.scene_graph_to_vectors(objs, triples, attributes)
-                box_vecs, mask_vecs = obj_vecs, self._mask_vecs(obj_vecs, O)
+                box_vecs, mask_vecs = obj_vecs, self._mask_vecs(obj_vecs, O, obj_to_img)
                 boxes_pred = self.box_net(box_vecs)
                 mask_scores = self.mask_net(mask_vecs.view(O, -1, 1, 1))
                 masks_pred = ops.activation(mask_scores.squeeze(1), ops.ACT_SIGMOID)
@@ -286,12 +286,19 @@ class Model(nn.Module):
     def create_components_vecs(self, imgs, boxes, obj_to_img, objs, obj_vecs, features, objs_host=None):
         """model.py:146-172 -- the reference's method, kept whole for callers of the reference surface; forward() runs its two
         halves separately (the first belongs to the object front, the second to the image path)."""
-        mask_vecs = self._mask_vecs(obj_vecs, objs.size(0))
+        mask_vecs = self._mask_vecs(obj_vecs, objs.size(0), obj_to_img)
         layout_vecs, wrong_layout_vecs = self._appearance_vecs(imgs, boxes, obj_to_img, objs, mask_vecs, features,
                                                                objs_host=objs_host)
         return obj_vecs, mask_vecs, layout_vecs, wrong_layout_vecs
 
-    def _mask_vecs(self, obj_vecs, O):
+    def _mask_vecs(self, obj_vecs, O, obj_to_img=None):
+        if self.noise_override is not None and self.noise_override.dim() == 2 and self.noise_override.size(0) != 1:
+            # one row per IMAGE (qmc.QuasiRandomInputs): object o takes the row of its image, a device gather
+            if obj_to_img is None:
+                raise ValueError('a noise_override of %d rows is one row per image: _mask_vecs needs obj_to_img'
+                                 % self.noise_override.size(0))
+            noise = self.noise_override.to(obj_vecs.device, obj_vecs.dtype).view(-1, self.mask_noise_dim)
+            return ops.concat_cols(obj_vecs, ops.embedding(noise.contiguous(), obj_to_img))     # (sg_embedding_fwd: a row gather)
         if self.noise_override is not None:
             noise = self.noise_override.to(obj_vecs.device, obj_vecs.dtype).view(1, self.mask_noise_dim)
         else:                                                # ONE noise row per batch (model.py:149-151)
@@ -302,6 +309,14 @@ class Model(nn.Module):
         if features is None:
             crops = crop_bbox_batch(imgs, boxes, obj_to_img, self.object_size)
             obj_repr = self.repr_net(self.image_encoder(crops))
+        elif torch.is_tensor(features):                      # every object's appearance row, already on the device (qmc.DeviceBank)
+            if features.dim() != 2 or tuple(features.shape) != (objs.size(0), self.rep_size):
+                raise ValueError('features as a tensor must be [%d, %d] (one row of rep_size per object), got %s'
+                                 % (objs.size(0), self.rep_size, tuple(features.shape)))
+            if not features.is_floating_point() or features.device != mask_vecs.device:
+                raise ValueError('features as a tensor must be a float tensor on %s, got %s on %s'
+                                 % (mask_vecs.device, features.dtype, features.device))
+            obj_repr = features.to(mask_vecs.dtype)          # replaces repr_net's output whole: nothing to compute, nothing to index
         else:                                                # only at inference time (model.py:158-163)
             obj_repr = self.repr_net(mask_vecs)
             rows = [i for i, f in enumerate(features) if f is not None]

@@ -4,7 +4,7 @@ PyTorch-ROCm is used here as plumbing only: device allocation (torch.empty), the
 Every forward / backward is one or a few hand-written gfx950 kernel launches through ctypes; there is no eager / CPU fallback --
 a CPU tensor raises.
 
-One namespace, seventeen modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
+One namespace, eighteen modules (the single 1 741-line ops.py of rounds 1-3, split by operator family in round 4):
   _core    ctypes call helpers, stream handle, workspace, parameter-gradient sinks (GradOut), path switches, layout hints,
            flat-buffer updates (Adam, fill, fold), profiler front end
   conv     Conv2d / ConvTranspose2d / sub-pixel up-conv / Linear (implicit GEMM, Winograd, head, skinny kernels)
@@ -29,6 +29,7 @@ One namespace, seventeen modules (the single 1 741-line ops.py of rounds 1-3, sp
   fidinf      FID-infinity's own operators: the two Gram matrices of the shifted fake rows (f64 matrix cores) and the per-subset terms
   attributes  size and location attributes from class statistics: the per-class histogram and the relation-constrained draw
   isinf       IS-infinity's own operators: the per-row sums and entropies of the softmax rows, the score of every subset of them
+  qmc         quasi-random inputs of the generator: Sobol points, their unpacking into noise / bank picks / uniforms, the bank draw
 Everything is re-exported here, so ``ops.conv2d``, ``ops.GradOut``, ``ops._call`` ... keep working.  The path switches
 (``ops.WINOGRAD``, ``ops.FACTORED_LAYOUT``, ``ops.UPCONV``, ``ops.HEADCONV``, ``ops.WINOGRAD24``, ``ops.COND_FOLD``) are WRITABLE through this
 namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator modules read (``_core.WINOGRAD``).
@@ -36,10 +37,10 @@ namespace: assigning ``ops.WINOGRAD = False`` updates the value the operator mod
 import sys
 import types
 
-from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid, lpips, featsets, imageprep, fidinf, attributes, isinf
+from . import _core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid, lpips, featsets, imageprep, fidinf, attributes, isinf, qmc
 
 _MODULES = (_core, graph, losses, layout, conv, nn, kmeans, scenegraph, classifier, inception, fid, lpips, featsets, imageprep, fidinf, attributes,
-            isinf)
+            isinf, qmc)
 _FLAGS = ('HEADCONV', 'WINOGRAD', 'WINOGRAD24', 'FACTORED_LAYOUT', 'UPCONV', 'COND_FOLD')
 
 for _m in _MODULES:

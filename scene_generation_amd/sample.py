@@ -4,6 +4,7 @@ scene_generation/data/utils.py it needs).
     python -m scene_generation_amd.sample --checkpoint CKPT.pt --output_dir OUT [--weights ema] [--scene_graphs FILE.json [--bank DIR]]
                                           [--layouts FILE.json] [--consistent_graphs 1] [--graph_metrics 1]
                                           [--sample_attributes 1 --attributes_file F.pickle [--attribute_size_rule geometric]]
+                                          [--quasi_random 1 [--qmc_seed S] [--qmc_max_objects J]]
 
 * ``Sampler``: one test-mode forward per collated batch (``sample_batch``, the flags of sample_images.py:203-221) or per list of
   scene graphs written by a person (``sample_json`` -> Model.forward_json), then the device-side ``imagenet_deprocess_batch``
@@ -36,6 +37,10 @@ scene_generation/data/utils.py it needs).
   different appearance draws.  ``sample_pair`` runs ``sample_batch`` and then a second forward of the same batch with fresh bank
   draws that feeds this scorer ONLY; read once by ``diversity_summary``; ``--diversity_backbone`` / ``--diversity_lin`` /
   ``--diversity_net`` on the command line.
+* ``quasi_random`` (a ``qmc.QuasiRandomInputs``, off by default; ``--quasi_random 1 [--qmc_seed S] [--qmc_max_objects J]``): the
+  k-th scored image takes its mask-noise row, its objects' bank rows and attribute uniforms from point k of a scrambled Sobol
+  sequence, generated and consumed on the device (three launches in front of the forward instead of the host loop over the bank);
+  the second forward of ``sample_pair`` draws from a stream of its own.  ``Sampler.last_draws`` keeps the last tables.
 * ``run_model`` / the command line: load a checkpoint (``--weights model | best | ema | ema_best``), sample, write PNG files
   (PIL, imported only when a file is written; ``.npy`` when PIL is absent).
 Not here: scene-graph drawing, the GUI server, the COCO loaders (``scene_generation.data`` stays the host
@@ -104,7 +109,12 @@ class Sampler(object):
 
     def __init__(self, model, features=None, colors=None, factored=True, graph_metrics=False, accuracy=None, inception=None,
                  fid=None, diversity=None, sets=None, attribute_stats=None, sample_attributes=False, attribute_seed=0,
-                 attribute_size_rule='reference'):
+                 attribute_size_rule='reference', quasi_random=None):
+        self.quasi_random = quasi_random     # qmc.QuasiRandomInputs: one Sobol point per scored image, or None (nothing new runs)
+        self._quasi_pair = None              # the stream of sample_pair's second, unscored forward (seed + 1), made on first use
+        self._device_bank = None             # qmc.DeviceBank of ``features``, packed on first use
+        self._pair_u = None                  # the scored forward's attribute uniforms, for the second forward of a pair
+        self.last_draws = None               # (noise, pick, u, row_idx) of the last quasi-random call (tests, debugging)
         self.sample_attributes = bool(sample_attributes)
         if self.sample_attributes:
             from .attributes import SIZE_RULES
@@ -129,11 +139,14 @@ class Sampler(object):
         self.iou = None                      # running (sum IoU, > 0.5, > 0.3, boxes) of sample_batch, on the device
 
     # -- the forward + what follows the network -------------------------------------------------------------------------------------
-    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs, score=None, scored=True):
-        """``scored=False`` (the second forward of ``sample_pair``): no scorer sees the network's output"""
+    def _forward(self, fn, objs_h, o2i_h, want_layout_rgb, want_layout, objs, score=None, scored=True, noise=None):
+        """``scored=False`` (the second forward of ``sample_pair``): no scorer sees the network's output.  ``noise`` [N, mask_noise_dim]
+        (quasi-random inputs): the model's noise_override for this forward only."""
         m = self.model
-        saved = (m.factored_test_layout, m.objs_host, m.obj_to_img_host)
+        saved = (m.factored_test_layout, m.objs_host, m.obj_to_img_host, m.noise_override)
         m.factored_test_layout, m.objs_host, m.obj_to_img_host = self.factored, objs_h, o2i_h
+        if noise is not None:
+            m.noise_override = noise
         try:
             with torch.no_grad():
                 imgs_pred, boxes_pred, masks_pred, _, layout, _ = fn()
@@ -159,19 +172,29 @@ class Sampler(object):
                 if want_layout:
                     ops.ensure_dense(layout)                # factored: the deferred dense kernel runs only here
         finally:
-            m.factored_test_layout, m.objs_host, m.obj_to_img_host = saved
+            m.factored_test_layout, m.objs_host, m.obj_to_img_host, m.noise_override = saved
         return SampleOut(images, boxes_pred, masks_pred, rgb, layout if want_layout else None, objs)
 
     def sample_batch(self, batch, use_gt_boxes=False, use_gt_masks=False, use_gt_textures=False, use_gt_attr=False,
                      want_layout_rgb=False, want_layout=False, _scored=True):
         """One collated batch (imgs, objs, boxes, masks, triples, obj_to_img, triple_to_img, attributes), the flags of
         sample_images.py:203-221.  Without ground-truth textures every object takes a random row of its class's bank, drawn with
-        ``random.randint`` in object order like the reference (``random.seed`` reproduces it).  (``_scored=False``, the second
+        ``random.randint`` in object order like the reference (``random.seed`` reproduces it); with ``quasi_random`` the rows, the
+        noise and the attribute uniforms come from the image's Sobol point instead, on the device.  (``_scored=False``, the second
         forward of ``sample_pair``: the same forward with no scorer fed and no counter touched.)"""
         imgs, objs, boxes, masks, triples, obj_to_img, triple_to_img, attributes = [t.to(self.device) for t in batch]
         objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()        # the call's one host synchronisation
         features = None
-        if not use_gt_textures:
+        noise = u = None
+        if self.quasi_random is not None:    # the image's noise row, bank picks and attribute uniforms from its Sobol point (qmc.py)
+            noise, pick, u = self._quasi_draw(obj_to_img, imgs.size(0), o2i_h, _scored)
+            row_idx = None
+            if not use_gt_textures:
+                features, row_idx = self._quasi_bank().draw(objs, pick, objs_host=objs_h)      # [O, rep_size], on the device
+            self.last_draws = (noise, pick, u, row_idx)
+            if _scored:
+                self._pair_u = u
+        elif not use_gt_textures:
             if self.features is None:
                 raise ValueError('No features file')                    # sample_images.py:174
             rows = []
@@ -183,9 +206,10 @@ class Sampler(object):
         if not use_gt_attr:
             attributes = torch.zeros_like(attributes)
         if self.sample_attributes and _scored:                          # blocks without a bit are drawn; the metrics score the result
-            attributes = given_attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, triple_to_img)
+            attributes = given_attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, triple_to_img, u=u)
         elif self.sample_attributes:                                    # the second forward of a pair: the first one's draw again
-            attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, triple_to_img, advance=-1)
+            attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, triple_to_img, advance=-1,
+                                               u=self._pair_u if u is not None else None)
         m = self.model
         score = None
         if _scored and self.accuracy is not None:        # sample_images.py:224-239: crops at the ground-truth boxes when they drive the layout
@@ -193,7 +217,8 @@ class Sampler(object):
                 self.accuracy.update(imgs_pred, boxes if use_gt_boxes else boxes_pred, obj_to_img, objs)
         out = self._forward(lambda: m(imgs, objs, triples, obj_to_img, boxes_gt=boxes, masks_gt=masks if use_gt_masks else None,
                                       attributes=attributes, test_mode=True, use_gt_box=use_gt_boxes, features=features),
-                            objs_h, o2i_h, want_layout_rgb, want_layout, objs, score, _scored)
+                            objs_h, o2i_h, want_layout_rgb, want_layout, objs, score, _scored,
+                            **({} if noise is None else {'noise': noise}))      # (off: the call is the one it always was)
         if not _scored:
             return out
         tot = iou_totals(out.boxes_pred, boxes, obj_to_img)
@@ -225,23 +250,51 @@ class Sampler(object):
             scene_graphs = [scene_graphs]
         objs, triples, obj_to_img, attributes, features = m.encode_scene_graphs(scene_graphs)
         objs_h, o2i_h = torch.stack((objs, obj_to_img)).tolist()
+        noise = u = None
+        if self.quasi_random is not None:    # noise and attribute columns; the bank rows are the graphs' own feature numbers, as ever
+            noise, pick, u = self._quasi_draw(obj_to_img, max(o2i_h) + 1, o2i_h, True)
+            self.last_draws = (noise, pick, u, None)
         if self.sample_attributes:
-            attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h)
+            attributes = self._fill_attributes(objs, triples, obj_to_img, attributes, o2i_h, u=u)
         out = self._forward(lambda: m(None, objs, triples, obj_to_img, attributes=attributes, test_mode=True, use_gt_box=False,
-                                      features=features), objs_h, o2i_h, want_layout_rgb, want_layout, objs)
+                                      features=features), objs_h, o2i_h, want_layout_rgb, want_layout, objs,
+                            **({} if noise is None else {'noise': noise}))
         self._graph_metrics(out, triples, attributes)
         return out
 
-    def _fill_attributes(self, objs, triples, obj_to_img, attributes, o2i_h, triple_to_img=None, advance=0):
+    def _fill_attributes(self, objs, triples, obj_to_img, attributes, o2i_h, triple_to_img=None, advance=0, u=None):
         """with ``sample_attributes``: one launch that draws the size / location blocks ``attributes`` leaves empty (given bits are
         kept) with the seed of this call, then moves the seed on; no host synchronisation (the host list is the call's own).
-        ``advance=-1``: the previous call's seed again, and the seed stays."""
+        ``advance=-1``: the previous call's seed again, and the seed stays.  ``u`` (quasi-random inputs): the device table of
+        uniforms to draw with, instead of the one made on the host from the seed."""
         from .attributes import sample_attributes
         seed = self.attribute_seed + advance
-        block, _, _ = sample_attributes(objs, triples, obj_to_img, self.attribute_stats, given=attributes, seed=seed,
+        block, _, _ = sample_attributes(objs, triples, obj_to_img, self.attribute_stats, given=attributes, seed=seed, u=u,
                                         triple_to_img=triple_to_img, obj_to_img_host=o2i_h, size_rule=self.attribute_size_rule)
         self.attribute_seed = seed + 1
         return block
+
+    def _quasi_draw(self, obj_to_img, N, o2i_h, scored):
+        """(noise, pick, u) of the next N points: of the scored stream, or -- the second forward of ``sample_pair`` -- of a second
+        stream with seed + 1, so that the scored one moves by one point per scored image whatever else is sampled"""
+        q = self.quasi_random
+        if not scored:
+            if self._quasi_pair is None:
+                from .qmc import QuasiRandomInputs
+                self._quasi_pair = QuasiRandomInputs(q.noise_dim, q.max_objects, seed=q.seed + 1, device=self.device)
+            q = self._quasi_pair
+        if q.noise_dim != self.model.mask_noise_dim:
+            raise ValueError('quasi_random draws noise rows of %d columns, the model\'s mask noise has %d'
+                             % (q.noise_dim, self.model.mask_noise_dim))
+        return q.draw(obj_to_img, ops.segment_offsets(obj_to_img, N), N, obj_to_img_host=o2i_h)
+
+    def _quasi_bank(self):
+        if self._device_bank is None:
+            if self.features is None:
+                raise ValueError('No features file')                    # sample_images.py:174
+            from .qmc import DeviceBank
+            self._device_bank = DeviceBank.from_dict(self.features, self.model.num_objs, self.device)
+        return self._device_bank
 
     def _graph_metrics(self, out, triples, attributes):
         """with ``graph_metrics``: four launches that add to the counters (centroids of the predicted masks, triple agreement, the
@@ -490,10 +543,15 @@ def run_model(args, checkpoint, output_dir, loader=None, device='cuda'):
         from .lpips import LPIPS, Diversity
         diversity = Diversity(LPIPS(getattr(args, 'diversity_net', 'alex'), backbone_weights=div_backbone, lin_weights=div_lin,
                                     device=device), batch_size=args.batch_size)
+    quasi = None
+    if getattr(args, 'quasi_random', False):
+        from .qmc import QuasiRandomInputs
+        quasi = QuasiRandomInputs(model.mask_noise_dim, max_objects=getattr(args, 'qmc_max_objects', 32),
+                                  seed=getattr(args, 'qmc_seed', 0), device=device)
     sampler = Sampler(model, features=features, factored=getattr(args, 'factored', True), graph_metrics=metrics, accuracy=meter,
                       inception=scorer, fid=fid, diversity=diversity, sets=sets, attribute_stats=stats, sample_attributes=want_attr,
                       attribute_seed=getattr(args, 'attribute_seed', 0),
-                      attribute_size_rule=getattr(args, 'attribute_size_rule', 'reference'))
+                      attribute_size_rule=getattr(args, 'attribute_size_rule', 'reference'), quasi_random=quasi)
     img_dir = _makedir(output_dir, 'images')
     gt_dir = _makedir(output_dir, 'images_gt', args.save_gt_imgs and not graphs and not layouts)
     layout_dir = _makedir(output_dir, 'layouts', args.save_layout)
@@ -616,6 +674,12 @@ def make_parser():
     p.add_argument('--attribute_size_rule', default='reference', choices=['reference', 'geometric'], help='how "inside" / '
                    '"surrounding" adjust a sampled size: as the reference does, or so that the surrounding object is the larger one')
     p.add_argument('--attribute_seed', default=0, type=int, help='seed of the first batch\'s attribute draws; batch k uses seed + k')
+    p.add_argument('--quasi_random', default=False, type=bool_flag, help='draw every image\'s mask noise, appearance-bank rows and '
+                   'attribute uniforms from one point of a scrambled Sobol sequence, on the device (python -m pydoc '
+                   'scene_generation_amd.qmc): the same --qmc_seed gives the same pictures')
+    p.add_argument('--qmc_seed', default=0, type=int, help='seed of the Sobol sequence\'s scrambling')
+    p.add_argument('--qmc_max_objects', default=32, type=int, help='objects per image a point holds draws for (three dimensions '
+                   'each); an image with more raises')
     p.add_argument('--accuracy_model_path', default=None, help='the object classifier (python -m scene_generation_amd.accuracy '
                    'train, or the reference\'s resnet101_172_classes.pth): prints the Accuracy line of sample_images.py')
     p.add_argument('--accuracy_model_name', default='resnet101', help='its architecture: resnet18 / 34 / 50 / 101 / 152')
