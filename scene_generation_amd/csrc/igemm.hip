@@ -973,21 +973,22 @@ using CfgDI64SF128 = TileCfg<64, 64, 2, 1, 2, 128, 1>;
 // the tile-major operands the forward and the adjoint data gradient built, K = the tiles)
 enum { WG_KK = 0, WG_KX = 1, WG_XX = 2 };
 template <int FORM, class CFG>
-int wino_gemm_cfg(const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, hipStream_t s) {
+int wino_gemm_cfg(const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, hipStream_t s, const LaunchMods& lm) {
   const EpRowMajorPlain ep{Cm, NB * cols};
   if constexpr (FORM == WG_KK)
-    return launch_cfg<CFG>(LoadKContig<CFG::BM, true, false>{A, K, M}, LoadKContig<CFG::BN, true, false>{B, K, NB * cols}, ep, M, NB * cols, K, 1, s);
+    return launch_cfg<CFG>(LoadKContig<CFG::BM, true, false>{A, K, M}, LoadKContig<CFG::BN, true, false>{B, K, NB * cols}, ep, M, NB * cols, K, 1, s, lm);
   else if constexpr (FORM == WG_KX)
-    return launch_cfg<CFG>(LoadKContig<CFG::BM, true, false>{A, K, M}, LoadXContigS<CFG::BN>{B, cols, cols}, ep, M, NB * cols, K, 1, s);
+    return launch_cfg<CFG>(LoadKContig<CFG::BM, true, false>{A, K, M}, LoadXContigS<CFG::BN>{B, cols, cols}, ep, M, NB * cols, K, 1, s, lm);
   else
-    return launch_cfg<CFG>(LoadXContigS<CFG::BM>{A, M, 0}, LoadXContigS<CFG::BN>{B, cols, cols}, ep, M, NB * cols, K, 1, s);
+    return launch_cfg<CFG>(LoadXContigS<CFG::BM>{A, M, 0}, LoadXContigS<CFG::BN>{B, cols, cols}, ep, M, NB * cols, K, 1, s, lm);
 }
 // THE GEMM launch of the Winograd code: the plan's (bm, bn, nsub, kfold, pipe) -> the TileCfg instantiation.  Only the
 // combinations wino_launch_plan can produce exist: 128-wide tiles for WG_KK / WG_XX, the chunked sum for WG_KK / WG_KX, the
 // wino_pipe == 1 loop for the 128x128 WG_KK GEMM.
-#define WG_RUN(CFG) wino_gemm_cfg<FORM, CFG>(A, B, Cm, M, cols, K, NB, s)
+#define WG_RUN(CFG) wino_gemm_cfg<FORM, CFG>(A, B, Cm, M, cols, K, NB, s, lm)
 template <int FORM>
-int wino_gemm_pick(const sgWinoPlan& g, const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, hipStream_t s) {
+int wino_gemm_pick(const sgWinoPlan& g, const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, hipStream_t s,
+                   const LaunchMods& lm) {
   const bool deep = g.nsub == 2;
   if constexpr (FORM != WG_KX) {
     // 128x128 tiles, 32-deep k-tiles, software-pipelined fragment reads, unconditional epilogue (the variants this replaced --
@@ -1008,13 +1009,11 @@ template <int FORM>
 void wino_bgemm(const sgWinoPlan& g, int kind, const float* A, const float* B, float* Cm, int M, int cols, int K, int NB, double flops,
                 hipStream_t s) {
   sgk::t_alg_bytes = 4.0 * NB * ((double)M * K + (double)cols * K + (double)M * cols);
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = cols; t_batch.nbatch = NB; t_batch.a_stride = M * K; t_batch.batch_major = 1;
-  if (FORM != WG_KK) t_batch.b_stride = K * cols;
-  {
-    SgProfScope prof(kind, s, flops, 0);
-    wino_gemm_pick<FORM>(g, A, B, Cm, M, cols, K, NB, s);
-  }
-  t_batch = BatchInfo{};
+  LaunchMods lm;
+  lm.batch.cols_per_batch = cols; lm.batch.nbatch = NB; lm.batch.a_stride = M * K; lm.batch.batch_major = 1;
+  if (FORM != WG_KK) lm.batch.b_stride = K * cols;
+  SgProfScope prof(kind, s, flops, 0);
+  wino_gemm_pick<FORM>(g, A, B, Cm, M, cols, K, NB, s, lm);
 }
 
 

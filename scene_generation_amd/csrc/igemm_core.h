@@ -76,7 +76,6 @@ inline bool skinny_shape(int M, int N) {
 
 namespace {
 using namespace sgk;
-thread_local unsigned t_variant_stride = 0;   // >0: tap t of the k-table reads from source copy t (set by kn1_run)
 
 // -DSG_TIMELINE (tools/probe/build_timeline.sh: a SEPARATE library, never the product build): wave 0 of every workgroup of an
 // igemm_kernel launch stamps s_memtime at five points -- entry, loaders initialised, first k-tile staged in LDS, main loop done,
@@ -1725,12 +1724,15 @@ inline int pick_tile(int M, int N) {
   return 1;
 }
 
-// thread-local launch modifiers (set by the sparse entry points around a regular dispatch)
-thread_local BatchInfo t_batch = {};
-thread_local int t_grid_z = 0;                // >0: explicit grid.z (per-image k-chunks, see BatchInfo::ksplit)
-thread_local int t_fixed_kchunk = 0;        // >0: grid.z = ceil(K / chunk) with exactly this chunk (one image per z)
-thread_local int t_xcd_z = 0;               // 1: pin the k-chunks of a plain split-K launch to XCDs (weight gradients)
-thread_local int t_min_z = 0;               // >0: at least this many k-chunks (trailing ones may be empty: zero slabs)
+// launch modifiers: how a caller shapes the grid of a launch_cfg launch (the sparse entry points and the weight-gradient plan build
+// one and hand it down; the default is a plain launch)
+struct LaunchMods {
+  BatchInfo batch = {};
+  int grid_z = 0;             // >0: explicit grid.z (per-image k-chunks, see BatchInfo::ksplit)
+  int fixed_kchunk = 0;       // >0: grid.z = ceil(K / chunk) with exactly this chunk (one image per z)
+  int xcd_z = 0;              // 1: pin the k-chunks of a plain split-K launch to XCDs (weight gradients)
+  int min_z = 0;              // >0: at least this many k-chunks (trailing ones may be empty: zero slabs)
+};
 
 // k-chunk, grid.z and XCD pinning of a split-K launch as functions of the launch modifiers above (launch_cfg launches exactly
 // this; nk_launch_plan reports it for the weight-gradient GEMMs).  bkt: the k-tile depth of the tile configuration
@@ -1745,7 +1747,7 @@ inline int splitk_grid_z(int K, int splits, int kchunk, int grid_z, int fixed_kc
   if (min_z > 0 && z < min_z && grid_z == 0) z = min_z;
   return z;
 }
-// xcd_mode: t_xcd_z.  plain split-K launches, and the per-image k-chunks (ksplit) of the factored stem's weight gradient
+// xcd_mode: LaunchMods::xcd_z.  plain split-K launches, and the per-image k-chunks (ksplit) of the factored stem's weight gradient
 // (grid.z = images x chunks: its column tiles re-read the same gy chunk from seven L2s -- 6.5x the algorithmic bytes in round 4)
 inline bool splitk_xcd(int xcd_mode, int grid_z, int fixed_kchunk, int ksplit, int cols_per_batch, int ncls, int z) {
   const bool plain_z = grid_z == 0 && fixed_kchunk == 0 && ksplit == 0;
@@ -1753,21 +1755,102 @@ inline bool splitk_xcd(int xcd_mode, int grid_z, int fixed_kchunk, int ksplit, i
   return xcd_mode && (plain_z || image_z) && cols_per_batch == 0 && ncls == 0 && z >= 8 && z % 8 == 0;
 }
 
+// The tail-split and parity-split schedule of a launch (launch_cfg, for the tile configurations and epilogues that take pieces):
+// may grow grid.x and fill bi.tail_* / bi.par.split, slot0, nslots, tile0.  BM .. TN: the tile configuration's constants; tiles:
+// grid.x of the unsplit launch; resident_wgs: workgroups of the instantiation a CU holds at once, asked for by the general form only
+inline void split_schedule(int BM, int BN, int BKT, int KFOLD, int TM, int TN, int M, int K, int splits, int tiles, BatchInfo& bi,
+                           dim3& grid, hipStream_t s, int n_cu, int (*resident_wgs)()) {
+  const int mode = sg_opt(SG_OPT_W43_TAIL_SPLIT);     // 0: off, 1: the F(4x4,3x3) half-round case only, 2: + the general form
+  const size_t PIECE_BYTES = (size_t)4 * TM * TN * 16 * 64 * sizeof(float);
+  const bool plain = grid.z == 1 && splits <= 1 && bi.kcnt == nullptr && bi.ksplit == 0 && bi.par.ncls == 0 && !bi.xcd_z;
+  const int kh = K / 2;
+  if (mode >= 1 && n_cu == 256 && plain && bi.batch_major && bi.cols_per_batch > 0 &&
+      tiles % 256 == 128 && tiles >= 384 && K % 2 == 0 && kh % BKT == 0 && kh >= 4 * BKT &&
+      (KFOLD == 0 || kh % KFOLD == 0) && M % BM == 0 && bi.cols_per_batch % BN == 0) {
+    // half a round of workgroups per CU left over (the 36 x 32 tiles of the F(4x4,3x3) GEMMs at the benchmark shape): the tiles
+    // of the half round as two half-k workgroups each, one next to the four whole tiles of every CU (see the kernel)
+    const int sx = 16, nsplit = 8 * sx;
+    float* slab = sg_tail_scratch(s, (size_t)nsplit * 2 * PIECE_BYTES);
+    int* cnt = slab ? sg_counter_alloc(s, nsplit, true) : nullptr;
+    if (slab && cnt) { bi.tail_sx = sx; bi.tail_slab = slab; bi.tail_cnt = cnt; grid.x = tiles + nsplit; }
+  } else if (sg_opt(SG_OPT_PAR_SPLIT) && n_cu > 0 && bi.par.ncls > 1 && grid.z == 1 && splits <= 1 && KFOLD == 0 && !bi.xcd_z &&
+             M % BM == 0 && (BM * BN <= 64 * 64 || sg_opt(SG_OPT_PAR_SPLIT) >= 2)) {
+    // (64x64 tiles only: on 128x128 tiles -- two resident workgroups per CU, 2.5 rounds -- the same split measured +10 %:
+    //  187 -> 206 us, profiles/r06_gemm_par_split.md)
+    // parity classes: split the heaviest class in two when it runs >= 4x the k range of the lightest and the launch is small
+    // enough for its tail to matter (at most ~2 rounds of resident workgroups)
+    int kmax = 0, kmin = 1 << 30;
+    for (int c = 0; c < bi.par.ncls; ++c) { kmax = bi.par.K[c] > kmax ? bi.par.K[c] : kmax; kmin = bi.par.K[c] < kmin ? bi.par.K[c] : kmin; }
+    const int rows = sg_cdiv(M, BM);
+    int nsl = 0, old0[5];
+    for (int c = 0; c <= bi.par.ncls; ++c) old0[c] = bi.par.tile0[c];
+    bool any = false;
+    for (int c = 0; c < bi.par.ncls; ++c) {
+      const int tc = old0[c + 1] - old0[c];
+      const bool sp2 = bi.par.K[c] == kmax && kmax >= 4 * kmin && (kmax / 2) % BKT == 0 && kmax / 2 >= sg_opt(SG_OPT_TAIL_KTMIN) * BKT;
+      bi.par.split[c] = sp2 ? 2 : 1;
+      bi.par.slot0[c] = nsl;
+      if (sp2) { nsl += tc; any = true; }
+    }
+    const long wgs = (long)rows * (old0[bi.par.ncls] + nsl);
+    if (any && wgs <= 2L * n_cu * 8 && (long)rows * nsl <= 4096) {
+      float* slab = sg_tail_scratch(s, (size_t)rows * nsl * 2 * PIECE_BYTES);
+      int* cnt = slab ? sg_counter_alloc(s, rows * nsl, true) : nullptr;
+      if (slab && cnt) {
+        bi.par.nslots = nsl;
+        bi.par.tile0[0] = 0;
+        for (int c = 0; c < bi.par.ncls; ++c) bi.par.tile0[c + 1] = bi.par.tile0[c] + (old0[c + 1] - old0[c]) * bi.par.split[c];
+        for (int c = bi.par.ncls + 1; c < 5; ++c) bi.par.tile0[c] = bi.par.tile0[bi.par.ncls];
+        bi.tail_slab = slab; bi.tail_cnt = cnt;
+        grid.x = rows * bi.par.tile0[bi.par.ncls];
+      } else any = false;
+    } else any = false;
+    if (!any) for (int c = 0; c < 4; ++c) { bi.par.split[c] = 1; bi.par.slot0[c] = 0; }
+  } else if (mode >= 2 && n_cu > 0 && plain && bi.cols_per_batch == 0 && KFOLD == 0 && resident_wgs() > 0) {
+    const int resident = resident_wgs();
+    const int smax = sg_opt(SG_OPT_TAIL_SMAX) < 2 ? 2 : (sg_opt(SG_OPT_TAIL_SMAX) > 8 ? 8 : sg_opt(SG_OPT_TAIL_SMAX));
+    const int kt = sg_cdiv(K, BKT), slots = n_cu * resident;
+    int n = 0, sp = 0, first = 0;
+    if (tiles <= slots) {                      // everything resident at once: r CUs carry one workgroup more than the others
+      const int r = tiles % n_cu;
+      if (r > 0 && tiles > n_cu) { n = r; sp = (n_cu + r / 2) / r; first = 1; }
+    } else {                                   // the last round holds R of `slots` workgroups
+      const int R = tiles % slots;
+      if (R > 0 && 4 * R < 3 * slots) { n = R; sp = slots / R; first = 0; }
+    }
+    if (sp > smax) sp = smax;
+    while (sp >= 2 && kt / sp < sg_opt(SG_OPT_TAIL_KTMIN)) --sp;      // pieces of at least this many k-tiles
+    if (first && sp >= 2) {                    // pieces first: n * sp must be a multiple of 8 (the whole tiles keep their XCDs)
+      int g = sp, h = 8;
+      while (h) { const int t = g % h; g = h; h = t; }
+      n -= n % (8 / g);
+    }
+    if (n > 0 && sp >= 2 && n <= 4096) {
+      float* slab = sg_tail_scratch(s, (size_t)n * sp * PIECE_BYTES);
+      int* cnt = slab ? sg_counter_alloc(s, n, true) : nullptr;
+      if (slab && cnt) {
+        bi.tail_n = n; bi.tail_s = sp; bi.tail_first = first; bi.tail_slab = slab; bi.tail_cnt = cnt;
+        grid.x = tiles + n * (sp - 1);
+      }
+    }
+  }
+}
+
 template <class CFG, class AL, class BL, class EP>
-int launch_cfg(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, int splits, hipStream_t s) {
+int launch_cfg(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, int splits, hipStream_t s, const LaunchMods& lm = {}) {
   int tiles = sg_cdiv(M, CFG::BM) * sg_cdiv(N, CFG::BN);
-  if (t_batch.cols_per_batch > 0) tiles = sg_cdiv(M, CFG::BM) * t_batch.nbatch * sg_cdiv(t_batch.cols_per_batch, CFG::BN);
-  if (t_batch.par.ncls > 0) tiles = sg_cdiv(M, CFG::BM) * t_batch.par.tile0[t_batch.par.ncls];
-  const int kchunk = splitk_chunk(K, splits, CFG::BKT, t_fixed_kchunk);
-  dim3 grid(tiles, 1, splitk_grid_z(K, splits, kchunk, t_grid_z, t_fixed_kchunk, t_min_z));
-  BatchInfo bi = t_batch;
+  if (lm.batch.cols_per_batch > 0) tiles = sg_cdiv(M, CFG::BM) * lm.batch.nbatch * sg_cdiv(lm.batch.cols_per_batch, CFG::BN);
+  if (lm.batch.par.ncls > 0) tiles = sg_cdiv(M, CFG::BM) * lm.batch.par.tile0[lm.batch.par.ncls];
+  const int kchunk = splitk_chunk(K, splits, CFG::BKT, lm.fixed_kchunk);
+  dim3 grid(tiles, 1, splitk_grid_z(K, splits, kchunk, lm.grid_z, lm.fixed_kchunk, lm.min_z));
+  BatchInfo bi = lm.batch;
   bi.prio = sg_opt(SG_OPT_WAVE_PRIO) ? 1 : 0;
   bi.par_chunk = 0;
   {
     const int g = sg_opt(SG_OPT_PAR_XCD_CHUNK);
     if (bi.par.ncls > 0 && g > 0 && (g & (g - 1)) == 0) bi.par_chunk = g;
   }
-  bi.xcd_z = splitk_xcd(t_xcd_z, t_grid_z, t_fixed_kchunk, bi.ksplit, bi.cols_per_batch, bi.par.ncls, (int)grid.z) ? 1 : 0;   // k-chunks pinned to XCDs
+  bi.xcd_z = splitk_xcd(lm.xcd_z, lm.grid_z, lm.fixed_kchunk, bi.ksplit, bi.cols_per_batch, bi.par.ncls, (int)grid.z) ? 1 : 0;   // k-chunks pinned to XCDs
   bi.tail_sx = 0; bi.tail_slab = nullptr; bi.tail_cnt = nullptr; bi.tail_n = 0; bi.tail_s = 0; bi.tail_first = 0;
   for (int c = 0; c < 4; ++c) { bi.par.split[c] = 1; bi.par.slot0[c] = 0; }
   bi.par.nslots = 0;
@@ -1782,80 +1865,7 @@ int launch_cfg(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, in
       }();
       return c;
     };
-    const int mode = sg_opt(SG_OPT_W43_TAIL_SPLIT);     // 0: off, 1: the F(4x4,3x3) half-round case only, 2: + the general form
-    constexpr size_t PIECE_BYTES = (size_t)4 * CFG::TM * CFG::TN * 16 * 64 * sizeof(float);
-    const bool plain = grid.z == 1 && splits <= 1 && bi.kcnt == nullptr && bi.ksplit == 0 && bi.par.ncls == 0 && !bi.xcd_z;
-    const int kh = K / 2;
-    if (mode >= 1 && n_cu == 256 && plain && bi.batch_major && bi.cols_per_batch > 0 &&
-        tiles % 256 == 128 && tiles >= 384 && K % 2 == 0 && kh % CFG::BKT == 0 && kh >= 4 * CFG::BKT &&
-        (CFG::KFOLD == 0 || kh % CFG::KFOLD == 0) && M % CFG::BM == 0 && bi.cols_per_batch % CFG::BN == 0) {
-      // half a round of workgroups per CU left over (the 36 x 32 tiles of the F(4x4,3x3) GEMMs at the benchmark shape): the tiles
-      // of the half round as two half-k workgroups each, one next to the four whole tiles of every CU (see the kernel)
-      const int sx = 16, nsplit = 8 * sx;
-      float* slab = sg_tail_scratch(s, (size_t)nsplit * 2 * PIECE_BYTES);
-      int* cnt = slab ? sg_counter_alloc(s, nsplit, true) : nullptr;
-      if (slab && cnt) { bi.tail_sx = sx; bi.tail_slab = slab; bi.tail_cnt = cnt; grid.x = tiles + nsplit; }
-    } else if (sg_opt(SG_OPT_PAR_SPLIT) && n_cu > 0 && bi.par.ncls > 1 && grid.z == 1 && splits <= 1 && CFG::KFOLD == 0 && !bi.xcd_z &&
-               M % CFG::BM == 0 && (CFG::BM * CFG::BN <= 64 * 64 || sg_opt(SG_OPT_PAR_SPLIT) >= 2)) {
-      // (64x64 tiles only: on 128x128 tiles -- two resident workgroups per CU, 2.5 rounds -- the same split measured +10 %:
-      //  187 -> 206 us, profiles/r06_gemm_par_split.md)
-      // parity classes: split the heaviest class in two when it runs >= 4x the k range of the lightest and the launch is small
-      // enough for its tail to matter (at most ~2 rounds of resident workgroups)
-      int kmax = 0, kmin = 1 << 30;
-      for (int c = 0; c < bi.par.ncls; ++c) { kmax = bi.par.K[c] > kmax ? bi.par.K[c] : kmax; kmin = bi.par.K[c] < kmin ? bi.par.K[c] : kmin; }
-      const int rows = sg_cdiv(M, CFG::BM);
-      int nsl = 0, old0[5];
-      for (int c = 0; c <= bi.par.ncls; ++c) old0[c] = bi.par.tile0[c];
-      bool any = false;
-      for (int c = 0; c < bi.par.ncls; ++c) {
-        const int tc = old0[c + 1] - old0[c];
-        const bool sp2 = bi.par.K[c] == kmax && kmax >= 4 * kmin && (kmax / 2) % CFG::BKT == 0 && kmax / 2 >= sg_opt(SG_OPT_TAIL_KTMIN) * CFG::BKT;
-        bi.par.split[c] = sp2 ? 2 : 1;
-        bi.par.slot0[c] = nsl;
-        if (sp2) { nsl += tc; any = true; }
-      }
-      const long wgs = (long)rows * (old0[bi.par.ncls] + nsl);
-      if (any && wgs <= 2L * n_cu * 8 && (long)rows * nsl <= 4096) {
-        float* slab = sg_tail_scratch(s, (size_t)rows * nsl * 2 * PIECE_BYTES);
-        int* cnt = slab ? sg_counter_alloc(s, rows * nsl, true) : nullptr;
-        if (slab && cnt) {
-          bi.par.nslots = nsl;
-          bi.par.tile0[0] = 0;
-          for (int c = 0; c < bi.par.ncls; ++c) bi.par.tile0[c + 1] = bi.par.tile0[c] + (old0[c + 1] - old0[c]) * bi.par.split[c];
-          for (int c = bi.par.ncls + 1; c < 5; ++c) bi.par.tile0[c] = bi.par.tile0[bi.par.ncls];
-          bi.tail_slab = slab; bi.tail_cnt = cnt;
-          grid.x = rows * bi.par.tile0[bi.par.ncls];
-        } else any = false;
-      } else any = false;
-      if (!any) for (int c = 0; c < 4; ++c) { bi.par.split[c] = 1; bi.par.slot0[c] = 0; }
-    } else if (mode >= 2 && n_cu > 0 && plain && bi.cols_per_batch == 0 && CFG::KFOLD == 0 && resident_wgs() > 0) {
-      const int resident = resident_wgs();
-      const int smax = sg_opt(SG_OPT_TAIL_SMAX) < 2 ? 2 : (sg_opt(SG_OPT_TAIL_SMAX) > 8 ? 8 : sg_opt(SG_OPT_TAIL_SMAX));
-      const int kt = sg_cdiv(K, CFG::BKT), slots = n_cu * resident;
-      int n = 0, sp = 0, first = 0;
-      if (tiles <= slots) {                      // everything resident at once: r CUs carry one workgroup more than the others
-        const int r = tiles % n_cu;
-        if (r > 0 && tiles > n_cu) { n = r; sp = (n_cu + r / 2) / r; first = 1; }
-      } else {                                   // the last round holds R of `slots` workgroups
-        const int R = tiles % slots;
-        if (R > 0 && 4 * R < 3 * slots) { n = R; sp = slots / R; first = 0; }
-      }
-      if (sp > smax) sp = smax;
-      while (sp >= 2 && kt / sp < sg_opt(SG_OPT_TAIL_KTMIN)) --sp;      // pieces of at least this many k-tiles
-      if (first && sp >= 2) {                    // pieces first: n * sp must be a multiple of 8 (the whole tiles keep their XCDs)
-        int g = sp, h = 8;
-        while (h) { const int t = g % h; g = h; h = t; }
-        n -= n % (8 / g);
-      }
-      if (n > 0 && sp >= 2 && n <= 4096) {
-        float* slab = sg_tail_scratch(s, (size_t)n * sp * PIECE_BYTES);
-        int* cnt = slab ? sg_counter_alloc(s, n, true) : nullptr;
-        if (slab && cnt) {
-          bi.tail_n = n; bi.tail_s = sp; bi.tail_first = first; bi.tail_slab = slab; bi.tail_cnt = cnt;
-          grid.x = tiles + n * (sp - 1);
-        }
-      }
-    }
+    split_schedule(CFG::BM, CFG::BN, CFG::BKT, CFG::KFOLD, CFG::TM, CFG::TN, M, K, splits, tiles, bi, grid, s, n_cu, resident_wgs);
   }
   AL al2 = al; BL bl2 = bl; EP ep2 = ep;
   host_prepare(al2); host_prepare(bl2); host_prepare(ep2);
@@ -1994,22 +2004,22 @@ inline bool fixed_taps_enabled() {
 // ---- conv-shaped GEMM: K = (c, taps), N = pixels -------------------------------------------------
 template <class CFG, int BM, int BN, int KS, int MODE>
 int launch_ab(const float* A, int K, int M, bool vec, const Gather& g, int Npix, const KEntry* ktab, const EpNCHW& ep,
-              int splits, bool nomask, hipStream_t s, const FixedTaps* fx = nullptr) {
+              int splits, bool nomask, hipStream_t s, const FixedTaps* fx = nullptr, const LaunchMods& lm = {}) {
   const bool two = g.C2 > 0;
   if (fx && vec && !two)          // whole channels per k-tile: taps fixed per thread, channel offset in an SGPR (LoadFixedKN)
-    return launch_cfg<CFG>(LoadKContig<BM, true>{A, K, M}, LoadFixedKN<BN, MODE>{g, Npix, KS, fx->lg, fx->tapcode}, ep, M, Npix, K, splits, s);
+    return launch_cfg<CFG>(LoadKContig<BM, true>{A, K, M}, LoadFixedKN<BN, MODE>{g, Npix, KS, fx->lg, fx->tapcode}, ep, M, Npix, K, splits, s, lm);
   if (MODE == 0 && two) {                                 // channel-concatenated sources only exist on the forward gather
     if (vec) {
-      if (nomask) return launch_cfg<CFG>(LoadKContig<BM, true, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, true, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s);
-      return launch_cfg<CFG>(LoadKContig<BM, true>{A, K, M}, LoadGatherKN<BN, KS, MODE, true>{g, Npix, ktab}, ep, M, Npix, K, splits, s);
+      if (nomask) return launch_cfg<CFG>(LoadKContig<BM, true, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, true, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s, lm);
+      return launch_cfg<CFG>(LoadKContig<BM, true>{A, K, M}, LoadGatherKN<BN, KS, MODE, true>{g, Npix, ktab}, ep, M, Npix, K, splits, s, lm);
     }
-    return launch_cfg<CFG>(LoadKContig<BM, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, true>{g, Npix, ktab}, ep, M, Npix, K, splits, s);
+    return launch_cfg<CFG>(LoadKContig<BM, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, true>{g, Npix, ktab}, ep, M, Npix, K, splits, s, lm);
   }
   if (vec) {
-    if (nomask) return launch_cfg<CFG>(LoadKContig<BM, true, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, false, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s);
-    return launch_cfg<CFG>(LoadKContig<BM, true>{A, K, M}, LoadGatherKN<BN, KS, MODE, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s);
+    if (nomask) return launch_cfg<CFG>(LoadKContig<BM, true, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, false, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s, lm);
+    return launch_cfg<CFG>(LoadKContig<BM, true>{A, K, M}, LoadGatherKN<BN, KS, MODE, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s, lm);
   }
-  return launch_cfg<CFG>(LoadKContig<BM, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s);
+  return launch_cfg<CFG>(LoadKContig<BM, false>{A, K, M}, LoadGatherKN<BN, KS, MODE, false>{g, Npix, ktab}, ep, M, Npix, K, splits, s, lm);
 }
 
 // split-K for conv-shaped GEMMs that would otherwise leave most CUs idle (few output tiles, long K): e.g. the
@@ -2091,15 +2101,15 @@ inline KnSparsePlan kn_sparse_plan(int KS2, int M, int L, int NB, int PHW, bool 
 
 template <int KS, int MODE>
 int run_kn(const float* A, int M, int K, const Gather& g, int NB, const float* bias, float* out, int Mtot, int act,
-           float slope, double flops, void* ktab_ws, size_t ws_avail, hipStream_t s) {
+           float slope, double flops, void* ktab_ws, size_t ws_avail, unsigned variant_stride, hipStream_t s) {
   const int Npix = NB * g.PH * g.PW;
-  const KnPlan pl = kn_plan(KS, MODE, M, K, Npix, Mtot == M, aligned16(A), g.C2 > 0, g.reflect != 0, t_variant_stride, ws_avail,
+  const KnPlan pl = kn_plan(KS, MODE, M, K, Npix, Mtot == M, aligned16(A), g.C2 > 0, g.reflect != 0, variant_stride, ws_avail,
                             g.PH * g.PW, aligned16(out), aligned16(ktab_ws));
   const bool vec = pl.vec, nomask = pl.nomask;
   const int tile = pl.tile, splits = pl.splits;
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(ktab_ws) + ktab_bytes(K));
   const int Kpad = sg_cdiv(K, 64) * 64 + 128;      // the k-loop prefetches entries up to two tiles past the end
-  const unsigned shw_ = (unsigned)(g.SH * g.SW), vstride = t_variant_stride;
+  const unsigned shw_ = (unsigned)(g.SH * g.SW), vstride = variant_stride;
   const KEntry* ktab = reinterpret_cast<const KEntry*>(cached_table(
       TabKey{0, K, Kpad, KS * KS, g.C1, g.C2, shw_, g.bcast2, nomask ? 1 : 0, vstride, 0, 0}, (size_t)Kpad * sizeof(KEntry), s,
       [&](void* dst) {
@@ -2135,12 +2145,12 @@ int run_kn(const float* A, int M, int K, const Gather& g, int NB, const float* b
 
 template <int MODE>
 int run_kn_ks(int KS, const float* A, int M, int K, const Gather& g, int NB, const float* bias, float* out, int Mtot,
-              int act, float slope, double flops, void* ktab_ws, size_t ws_avail, hipStream_t s) {
+              int act, float slope, double flops, void* ktab_ws, size_t ws_avail, unsigned variant_stride, hipStream_t s) {
   switch (KS) {
-    case 1: return run_kn<1, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
-    case 3: return run_kn<3, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
-    case 4: return run_kn<4, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
-    case 7: return run_kn<7, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
+    case 1: return run_kn<1, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, variant_stride, s);
+    case 3: return run_kn<3, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, variant_stride, s);
+    case 4: return run_kn<4, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, variant_stride, s);
+    case 7: return run_kn<7, MODE>(A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, variant_stride, s);
   }
   return -1;
 }
@@ -2246,8 +2256,8 @@ struct NkLaunch {
   int tile;            // 0: 128x128, 1: 64x64, 2: 32x128
   int S, kcs;
   int splits;          // what launch_cfg is handed
-  int zpad;            // t_min_z
-  size_t mn;           // floats of one slab
+  LaunchMods mods;     // ... and the modifiers it is handed: p.kchunk, p.grid_z and p.xcd are computed from these very fields
+  size_t mn;          // floats of one slab
   size_t rowsum_off;   // floats from the workspace to the row sums [grid_z][M] (p.rowsum_fused)
 };
 inline NkLaunch nk_launch_plan(const NkShape& h, bool sparse, int L, bool perimage, bool a16, bool want_gb, size_t ws_bytes,
@@ -2291,12 +2301,16 @@ inline NkLaunch nk_launch_plan(const NkShape& h, bool sparse, int L, bool perima
     // (the gather form reads the output gradient with 16-byte loads only on the 7x7 stem: one vector-memory instruction per thread
     // and k-tile instead of four next to the four gathered elements of B)
     p.a_vec = (n.tile != 2 && (padded || KS == 7) && vec_ok) ? 1 : 0;
-    p.kchunk = n.kcs; p.chunks = p.grid_z = NB * S;
-    // (image, chunk) slices pinned to XCDs when grid.z % 8 == 0
-    p.xcd = splitk_xcd(sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0, p.grid_z, 0, S, 0, 0, p.grid_z) ? 2 : 0;
+    n.splits = 1;
+    LaunchMods& lm = n.mods;
+    lm.batch.kimg = PQ; lm.batch.ksplit = S; lm.batch.kcs = n.kcs;
+    lm.grid_z = NB * S;
+    lm.xcd_z = sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0;      // (image, chunk) slices pinned to XCDs when grid.z % 8 == 0
+    p.kchunk = lm.batch.kcs;
+    p.chunks = p.grid_z = splitk_grid_z(Kpix, n.splits, Kpix, lm.grid_z, lm.fixed_kchunk, lm.min_z);
+    p.xcd = splitk_xcd(lm.xcd_z, lm.grid_z, lm.fixed_kchunk, lm.batch.ksplit, 0, 0, p.grid_z) ? 2 : 0;
     p.reduce = S > 1 ? SG_WR_GROUP : SG_WR_NONE;
     p.ws_needed = (int64_t)(padded ? pad_off + pbytes : (S > 1 ? slabs : 0));
-    n.splits = 1;
     return n;
   }
   if (sparse) pl.tap = true;
@@ -2313,10 +2327,13 @@ inline NkLaunch nk_launch_plan(const NkShape& h, bool sparse, int L, bool perima
   splits = sg_cdiv(Kpix, kchunk);
   // XCD-pinned k-chunks (igemm_kernel: xcd_z) need grid.z % 8 == 0: pad with empty chunks (kbeg >= Kpix: they store zero slabs)
   // when the workspace has room for them
+  LaunchMods& lm = n.mods;
   if (sg_opt(SG_OPT_WGRAD_XCD) && !sparse && splits >= 6) {
     const int z8 = (splits + 7) / 8 * 8;
-    if (ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)z8) { n.zpad = z8; splits = z8; }
+    if (ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)z8) { lm.min_z = z8; splits = z8; }
   }
+  lm.xcd_z = lm.min_z > 0 ? 1 : 0;
+  lm.fixed_kchunk = sparse ? PQ : 0;
   // bias gradient from the A loader's row sums: tap-major dense launches whose workspace has room for [splits][M] behind the slabs
   if (sg_opt(SG_OPT_WGRAD_ROWSUM) && want_gb && pl.tap && !sparse && M == h.Mtot &&
       ws_bytes >= (mn + (size_t)M) * sizeof(float) * (size_t)splits) {
@@ -2324,21 +2341,20 @@ inline NkLaunch nk_launch_plan(const NkShape& h, bool sparse, int L, bool perima
     n.rowsum_off = mn * (size_t)splits;
   }
   n.splits = splits;
-  const int fixed = sparse ? PQ : 0;
   p.form = pl.tap ? SG_WG_TAP : SG_WG_GATHER;
   p.bm = pl.tile == 0 ? 128 : (pl.tile == 1 ? 64 : 32); p.bn = pl.tile == 1 ? 64 : 128;
   p.cpad = pl.tap ? pl.cpad : 0;
   p.a_vec = (pl.tap && vec_ok) ? 1 : 0;                  // (the dense (channel, tap) form reads A with scalar loads)
   p.two = (pl.tap && h.C2 > 0) ? 1 : 0;
-  p.kchunk = splitk_chunk(Kpix, splits, BK * NSW, fixed);
-  p.chunks = (splits > 1 || fixed > 0) ? sg_cdiv(Kpix, p.kchunk) : 1;
-  p.grid_z = splitk_grid_z(Kpix, splits, p.kchunk, 0, fixed, n.zpad);
+  p.kchunk = splitk_chunk(Kpix, splits, BK * NSW, lm.fixed_kchunk);
+  p.chunks = (splits > 1 || lm.fixed_kchunk > 0) ? sg_cdiv(Kpix, p.kchunk) : 1;
+  p.grid_z = splitk_grid_z(Kpix, splits, p.kchunk, lm.grid_z, lm.fixed_kchunk, lm.min_z);
   // mask-free gather: reflection padding and whole 16-pixel k-tiles (split chunks are multiples of 16); one source only.  Never
   // with an empty XCD-padding chunk: its first k-tile is loaded like any other, and LoadTapNK<MASK = false> would read the
   // table's "no pixel" entry (-1) as an offset -- element 2^32 - 1 of the first channel plane
   p.nomask = (pl.tap && !p.two && h.reflect && (Kpix % (BK * NSW) == 0) && (!sparse || PQ % (BK * NSW) == 0) &&
               p.chunks == p.grid_z) ? 1 : 0;
-  p.xcd = splitk_xcd(n.zpad > 0 ? 1 : 0, 0, fixed, 0, 0, 0, p.grid_z) ? 1 : 0;
+  p.xcd = splitk_xcd(lm.xcd_z, lm.grid_z, lm.fixed_kchunk, lm.batch.ksplit, 0, 0, p.grid_z) ? 1 : 0;
   size_t need = 0;
   if (sparse) {
     p.reduce = perimage ? SG_WR_PERIMAGE : SG_WR_SPARSE;

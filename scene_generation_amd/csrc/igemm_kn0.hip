@@ -62,17 +62,17 @@ int run_kn_sparse(const float* W, int M, int K, const Gather& g, int NB, const f
   EpNCHW ep{out, bias, PHW, M, M, Npix, act, slope, 0, 0, 1, 0, 0, 0, 0};
   // flops actually issued: the padded compact K of every image (bench.py prices the dominant kernel with this)
   const double flops = 2.0 * M * (double)Kc * Npix;
-  t_batch = BatchInfo{}; t_batch.cols_per_batch = PHW; t_batch.nbatch = NB; t_batch.kcnt = kcnt; t_batch.a_stride = M * Kc; t_batch.b_stride = Kpad;
+  LaunchMods lm;
+  lm.batch.cols_per_batch = PHW; lm.batch.nbatch = NB; lm.batch.kcnt = kcnt; lm.batch.a_stride = M * Kc; lm.batch.b_stride = Kpad;
   {
     SgProfScope prof(sg_igemm_kind(0, KS, tile), s, flops, 0);
     switch (tile) {
-      case 0: launch_ab<typename CfgFor<KS>::C128, 128, 128, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s); break;
-      case 1: launch_ab<typename CfgFor<KS>::C64, 64, 64, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s); break;
-      case 3: launch_ab<typename CfgFor<KS>::C64W, 64, 128, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s); break;
-      default: launch_ab<typename CfgFor<KS>::C32, 32, 128, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s); break;
+      case 0: launch_ab<typename CfgFor<KS>::C128, 128, 128, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s, nullptr, lm); break;
+      case 1: launch_ab<typename CfgFor<KS>::C64, 64, 64, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s, nullptr, lm); break;
+      case 3: launch_ab<typename CfgFor<KS>::C64W, 64, 128, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s, nullptr, lm); break;
+      default: launch_ab<typename CfgFor<KS>::C32, 32, 128, KS, 0>(Wc, Kc, M, true, g, Npix, ktab, ep, 1, nomask, s, nullptr, lm); break;
     }
   }
-  t_batch = BatchInfo{};
   return 0;
 }
 
@@ -80,7 +80,7 @@ int run_kn_sparse(const float* W, int M, int K, const Gather& g, int NB, const f
 
 int sgk::kn0_run(int KS, const float* A, int M, int K, const Gather& g, int NB, const float* bias, float* out, int Mtot, int act,
                  float slope, double flops, void* ktab_ws, size_t ws_avail, hipStream_t s) {
-  return run_kn_ks<0>(KS, A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
+  return run_kn_ks<0>(KS, A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, 0, s);
 }
 int sgk::kn_sparse_run(int KS, const float* W, int M, int K, const Gather& g, int NB, const float* bias, float* out, int act,
                        float slope, const Sparse& sp, void* ws, hipStream_t s) {

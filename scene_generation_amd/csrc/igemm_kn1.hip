@@ -130,20 +130,19 @@ int run_kn_parity(const float* W, int Rdim, int B, int m0, int M, const Gather& 
   const EpNCHW ep{out, bias, par.PH[0] * par.PW[0], Mtot, M, par.Npix[0], act, slope, 0, par.PW[0], 2, par.ph0[0], par.pw0[0],
                   g.PW, g.PH * g.PW};
   const KEntry* kt0 = reinterpret_cast<const KEntry*>(par.ktab[0]);
-  t_batch = BatchInfo{};
-  t_batch.par = par;
+  LaunchMods lm;
+  lm.batch.par = par;
   const FixedTaps fixed{par.lg[0], par.tapcode[0]};
   const FixedTaps* fx = pl.fixed ? &fixed : nullptr;
   {
     SgProfScope prof(sg_igemm_kind(1, KS, tile), s, flops_issued, 0);
     switch (tile) {
-      case 0: launch_ab<typename CfgFor<KS>::C128, 128, 128, KS, 1>(wbase, par.K[0], M, true, gs, par.Npix[0], kt0, ep, 1, false, s, fx); break;
-      case 1: launch_ab<typename CfgFor<KS>::C64, 64, 64, KS, 1>(wbase, par.K[0], M, vec, gs, par.Npix[0], kt0, ep, 1, false, s, fx); break;
-      case 3: launch_ab<typename CfgFor<KS>::C64W, 64, 128, KS, 1>(wbase, par.K[0], M, vec, gs, par.Npix[0], kt0, ep, 1, false, s, fx); break;
-      default: launch_ab<typename CfgFor<KS>::C32, 32, 128, KS, 1>(wbase, par.K[0], M, vec, gs, par.Npix[0], kt0, ep, 1, false, s, fx); break;
+      case 0: launch_ab<typename CfgFor<KS>::C128, 128, 128, KS, 1>(wbase, par.K[0], M, true, gs, par.Npix[0], kt0, ep, 1, false, s, fx, lm); break;
+      case 1: launch_ab<typename CfgFor<KS>::C64, 64, 64, KS, 1>(wbase, par.K[0], M, vec, gs, par.Npix[0], kt0, ep, 1, false, s, fx, lm); break;
+      case 3: launch_ab<typename CfgFor<KS>::C64W, 64, 128, KS, 1>(wbase, par.K[0], M, vec, gs, par.Npix[0], kt0, ep, 1, false, s, fx, lm); break;
+      default: launch_ab<typename CfgFor<KS>::C32, 32, 128, KS, 1>(wbase, par.K[0], M, vec, gs, par.Npix[0], kt0, ep, 1, false, s, fx, lm); break;
     }
   }
-  t_batch = BatchInfo{};
   return 0;
 }
 int run_kn_parity_ks(int KS, const float* W, int Rdim, int B, int m0, int M, const Gather& g, int NB, const float* bias,
@@ -160,10 +159,7 @@ int run_kn_parity_ks(int KS, const float* W, int Rdim, int B, int m0, int M, con
 
 int sgk::kn1_run(int KS, const float* A, int M, int K, const Gather& g, int NB, const float* bias, float* out, int Mtot, int act,
                  float slope, double flops, void* ktab_ws, size_t ws_avail, unsigned variant_stride, hipStream_t s) {
-  t_variant_stride = variant_stride;
-  const int rc = run_kn_ks<1>(KS, A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, s);
-  t_variant_stride = 0;
-  return rc;
+  return run_kn_ks<1>(KS, A, M, K, g, NB, bias, out, Mtot, act, slope, flops, ktab_ws, ws_avail, variant_stride, s);
 }
 int sgk::kn_parity_run(int KS, const float* W, int Rdim, int B, int m0, int M, const Gather& g, int NB, const float* bias,
                        float* out, int Mtot, int act, float slope, double flops, void* ws, size_t ws_bytes, hipStream_t s) {

@@ -86,45 +86,46 @@ __global__ void reflect_pad_planes_kernel(const float* __restrict__ x, const int
 }
 // the per-image weight gradient of the factored 7x7 stem over padded planes: launch_nk_general's three forms with LoadPaddedNK
 void launch_nk_padded(int tile, bool vecA, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep,
-                      int Kpix, hipStream_t s, const Sparse& sp, const float* pp) {
+                      int Kpix, hipStream_t s, const Sparse& sp, const float* pp, const LaunchMods& lm) {
   float* const rowsum = nullptr;
   const FastDiv dPQ((unsigned)PQ), dPW((unsigned)g.PW);
   const int PWp = g.SW + 2 * g.pad, PP = (g.SH + 2 * g.pad) * PWp;
   const unsigned bytes = (unsigned)((size_t)(Kpix / PQ) * sp.L * PP * sizeof(float));
 #define SG_PAD_B(BNv) LoadPaddedNK<BNv, 7, NSW>{pp, bytes, PQ, g.PW, PWp, PP, sp.L, sp.cnt, dPQ, dPW}
   if (tile == 2)
-    launch_cfg<CfgW32>(LoadPixK<32>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(128), ep, M, Ncols, Kpix, 1, s);
+    launch_cfg<CfgW32>(LoadPixK<32>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(128), ep, M, Ncols, Kpix, 1, s, lm);
   else if (vecA)
-    launch_cfg<CfgW64>(LoadPixKVec<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s);
+    launch_cfg<CfgW64>(LoadPixKVec<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s, lm);
   else
-    launch_cfg<CfgW64>(LoadPixK<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s);
+    launch_cfg<CfgW64>(LoadPixK<64>{A, M, Mtot, PQ, dPQ, rowsum}, SG_PAD_B(64), ep, M, Ncols, Kpix, 1, s, lm);
 #undef SG_PAD_B
 }
 // general (c, tap)-ordered loader: only for few-channel inputs (RGB crops / images)
 template <int KS>
 void launch_nk_general(int tile, bool vecA, const float* A, int M, int Mtot, int PQ, const Gather& g, int Ncols, const EpRowMajor& ep,
-                       int Kpix, int splits, hipStream_t s, const Sparse* sp = nullptr, int zdiv = 1) {
+                       int Kpix, int splits, hipStream_t s, const LaunchMods& lm, const Sparse* sp = nullptr, int zdiv = 1) {
   float* const rowsum = nullptr;
   const FastDiv dPQ((unsigned)PQ);
   const int* sl = sp ? sp->list : nullptr; const int* sc = sp ? sp->cnt : nullptr; const int L = sp ? sp->L : 0;
   if (tile == 2)
     launch_cfg<CfgW32>(LoadPixK<32>{A, M, Mtot, PQ, dPQ, rowsum}, LoadGatherNK<128, KS, false, true, NSW>{g, Ncols, sl, sc, L, zdiv}, ep,
-                       M, Ncols, Kpix, splits, s);
+                       M, Ncols, Kpix, splits, s, lm);
   else if (KS == 7 && vecA)
     // (nk_launch_plan: vecA only with KS == 7, per-image lists, PQ % 4 == 0, A 16-byte aligned)
     // the per-image weight gradient of the factored 7x7 stem (64 x 9*49 x 16 384 per image: the slowest GEMM launch of the step,
     // 45 TFLOP/s): the output gradient is read with 16-byte loads -- one vector-memory instruction per thread and k-tile instead of
     // four next to the four gathered elements of B (same-box A/B, two pairs: 31.24 vs 31.31 ms/step, +0.2 %)
     launch_cfg<CfgW64>(LoadPixKVec<64>{A, M, Mtot, PQ, dPQ, rowsum}, LoadGatherNK<64, KS, false, true, NSW>{g, Ncols, sl, sc, L, zdiv}, ep,
-                       M, Ncols, Kpix, splits, s);
+                       M, Ncols, Kpix, splits, s, lm);
   else
     launch_cfg<CfgW64>(LoadPixK<64>{A, M, Mtot, PQ, dPQ, rowsum}, LoadGatherNK<64, KS, false, true, NSW>{g, Ncols, sl, sc, L, zdiv}, ep,
-                       M, Ncols, Kpix, splits, s);
+                       M, Ncols, Kpix, splits, s, lm);
 }
 
 template <class CFG, int BMv, int BNv>
 void launch_nk_tap(const float* A, int M, int Mtot, int PQ, bool vecA, const Gather& g, int KS, int Ccols, int cpad,
-                   const Sparse* sp, bool nomask, const EpWgrad& ep, int Kpix, int splits, hipStream_t s, float* rowsum) {
+                   const Sparse* sp, bool nomask, const EpWgrad& ep, int Kpix, int splits, hipStream_t s, float* rowsum,
+                   const LaunchMods& lm) {
   const FastDiv dPQ((unsigned)PQ), dPW((unsigned)g.PW);
   const int* sl = sp ? sp->list : nullptr; const int* sc = sp ? sp->cnt : nullptr; const int L = sp ? sp->L : 0;
   const int Nv = KS * KS * cpad;
@@ -132,14 +133,14 @@ void launch_nk_tap(const float* A, int M, int Mtot, int PQ, bool vecA, const Gat
 #define SG_TAP_B(TWOv, MASKv) LoadTapNK<BNv, TWOv, MASKv, CFG::NSUB>{g, KS, Ccols, cpad, sl, sc, L, dPQ, dPW}
   if (vecA) {
     const LoadPixKVec<BMv> al{A, M, Mtot, PQ, dPQ, rowsum};
-    if (two) launch_cfg<CFG>(al, SG_TAP_B(true, true), ep, M, Nv, Kpix, splits, s);
-    else if (nomask) launch_cfg<CFG>(al, SG_TAP_B(false, false), ep, M, Nv, Kpix, splits, s);
-    else launch_cfg<CFG>(al, SG_TAP_B(false, true), ep, M, Nv, Kpix, splits, s);
+    if (two) launch_cfg<CFG>(al, SG_TAP_B(true, true), ep, M, Nv, Kpix, splits, s, lm);
+    else if (nomask) launch_cfg<CFG>(al, SG_TAP_B(false, false), ep, M, Nv, Kpix, splits, s, lm);
+    else launch_cfg<CFG>(al, SG_TAP_B(false, true), ep, M, Nv, Kpix, splits, s, lm);
   } else {
     const LoadPixK<BMv> al{A, M, Mtot, PQ, dPQ, rowsum};
-    if (two) launch_cfg<CFG>(al, SG_TAP_B(true, true), ep, M, Nv, Kpix, splits, s);
-    else if (nomask) launch_cfg<CFG>(al, SG_TAP_B(false, false), ep, M, Nv, Kpix, splits, s);
-    else launch_cfg<CFG>(al, SG_TAP_B(false, true), ep, M, Nv, Kpix, splits, s);
+    if (two) launch_cfg<CFG>(al, SG_TAP_B(true, true), ep, M, Nv, Kpix, splits, s, lm);
+    else if (nomask) launch_cfg<CFG>(al, SG_TAP_B(false, false), ep, M, Nv, Kpix, splits, s, lm);
+    else launch_cfg<CFG>(al, SG_TAP_B(false, true), ep, M, Nv, Kpix, splits, s, lm);
   }
 #undef SG_TAP_B
 }
@@ -167,28 +168,22 @@ int run_nk_ks(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, 
     const size_t mnc = nl.mn;
     float* dstp = S > 1 ? reinterpret_cast<float*>(ws) : sp->gwimg;
     const EpRowMajor ep{dstp, nullptr, M, Ncols, Ncols, SG_ACT_NONE, 0.f, mnc};
-    t_batch = BatchInfo{}; t_batch.kimg = PQ; t_batch.ksplit = S; t_batch.kcs = nl.kcs;
-    t_grid_z = NB * S;
-    t_xcd_z = sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0;      // (image, chunk) slices pinned to XCDs when grid.z % 8 == 0 (launch_cfg)
     if (pl.form == SG_WG_PADDED) {                   // the listed planes reflect-padded once, behind the slabs (nk_launch_plan)
       float* pp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + sp->pad_off);
       const int PWp = g.SW + 2 * g.pad, PP = (g.SH + 2 * g.pad) * PWp;
       hipLaunchKernelGGL(reflect_pad_planes_kernel, dim3(sg_cdiv(PP, 256), Ccols, NB), dim3(256), 0, s, g.src1, sp->list, sp->cnt, pp,
                          g.C1, Ccols, g.SH, g.SW, g.pad, PWp, PP, FastDiv((unsigned)PWp));
       SgProfScope prof(sg_igemm_kind(2, KS, tile), s, 2.0 * M * (double)Ncols * Kpix, 0);
-      launch_nk_padded(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, s, *sp, pp);
+      launch_nk_padded(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, s, *sp, pp, nl.mods);
     } else {
       SgProfScope prof(sg_igemm_kind(2, KS, tile), s, 2.0 * M * (double)Ncols * Kpix, 0);
       switch (KS) {
-        case 1: launch_nk_general<1>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
-        case 3: launch_nk_general<3>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
-        case 4: launch_nk_general<4>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
-        case 7: launch_nk_general<7>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, sp, S); break;
+        case 1: launch_nk_general<1>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, nl.mods, sp, S); break;
+        case 3: launch_nk_general<3>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, nl.mods, sp, S); break;
+        case 4: launch_nk_general<4>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, nl.mods, sp, S); break;
+        case 7: launch_nk_general<7>(tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, 1, s, nl.mods, sp, S); break;
       }
     }
-    t_batch = BatchInfo{};
-    t_grid_z = 0;
-    t_xcd_z = 0;
     if (pl.reduce == SG_WR_GROUP)
       hipLaunchKernelGGL(slab_group_reduce_kernel, dim3(sg_cdiv(mnc * NB, 256)), dim3(256), 0, s, (const float*)ws, sp->gwimg,
                          mnc, S, NB);
@@ -198,9 +193,7 @@ int run_nk_ks(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, 
   const int splits = nl.splits;
   const size_t mn = nl.mn;
   float* const rowsum = pl.rowsum_fused ? reinterpret_cast<float*>(ws) + nl.rowsum_off : nullptr;
-  if (sp) { t_fixed_kchunk = PQ; flops = 2.0 * M * (double)Ncols * Kpix; }
-  t_xcd_z = nl.zpad > 0 ? 1 : 0;
-  t_min_z = nl.zpad;
+  if (sp) flops = 2.0 * M * (double)Ncols * Kpix;
   float* dst = (splits > 1 || sp || tap) ? reinterpret_cast<float*>(ws) : out;
   {
     SgProfScope prof(sg_igemm_kind(2, KS, nl.tile), s, flops, 0);
@@ -209,23 +202,20 @@ int run_nk_ks(int KS, const float* A, int M, int Mtot, const Gather& g, int NB, 
       // (nomask is passed as planned for one source; launch_nk_tap ignores it for two)
       const bool nomask = pl.nomask != 0;
       switch (nl.tile) {
-        case 0: launch_nk_tap<CfgW128, 128, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
-        case 1: launch_nk_tap<CfgW64, 64, 64>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
-        default: launch_nk_tap<CfgW32, 32, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum); break;
+        case 0: launch_nk_tap<CfgW128, 128, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum, nl.mods); break;
+        case 1: launch_nk_tap<CfgW64, 64, 64>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum, nl.mods); break;
+        default: launch_nk_tap<CfgW32, 32, 128>(A, M, Mtot, PQ, vecA, g, KS, Ccols, pl.cpad, sp, nomask, ep, Kpix, splits, s, rowsum, nl.mods); break;
       }
     } else {
       const EpRowMajor ep{dst, nullptr, M, Ncols, Ncols, SG_ACT_NONE, 0.f, mn};
       switch (KS) {
-        case 1: launch_nk_general<1>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        case 3: launch_nk_general<3>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        case 4: launch_nk_general<4>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
-        case 7: launch_nk_general<7>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s); break;
+        case 1: launch_nk_general<1>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s, nl.mods); break;
+        case 3: launch_nk_general<3>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s, nl.mods); break;
+        case 4: launch_nk_general<4>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s, nl.mods); break;
+        case 7: launch_nk_general<7>(nl.tile, vecA, A, M, Mtot, PQ, g, Ncols, ep, Kpix, splits, s, nl.mods); break;
       }
     }
   }
-  t_fixed_kchunk = 0;
-  t_xcd_z = 0;
-  t_min_z = 0;
   const size_t nout = (size_t)M * C * KS2;
   switch (pl.reduce) {
     case SG_WR_PERIMAGE: {

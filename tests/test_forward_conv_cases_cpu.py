@@ -352,6 +352,11 @@ def test_restated_constants_match_the_sources():
     assert 'pick_tile(' not in body and 'sg_opt(' not in body
     body = core[core.index('int run_kn(const float* A'):core.index('int run_kn_ks(')]
     assert 'pl.reduce == SG_FR_VEC' in body and 'aligned16(slabs)' not in body and 'sg_opt(' not in body and body.count('kn_plan(') == 1
+    # launch modifiers are an argument (LaunchMods, variant_stride): the thread-locals that carried them are gone from every source
+    gone = re.compile(r'\b(t_batch|t_grid_z|t_fixed_kchunk|t_xcd_z|t_min_z|t_variant_stride)\b')
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith(('.h', '.hip', '.sh')):
+            assert not gone.search(_src(name)), name
     assert ig.count('check_fwd_args(') == 5          # its definition, the three entry points, the query
     text = open(os.path.join(ROOT, 'include', 'sg2im_hip.h')).read()
     vals = dict((k, int(v)) for k, v in re.findall(r'(SG_F[WR]_\w+)\s*=\s*(\d+)', text))

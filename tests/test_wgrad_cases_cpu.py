@@ -323,7 +323,7 @@ def test_restated_constants_match_the_sources():
     assert 'constexpr size_t PAD_MAX_BYTES = (size_t)1 << 30;' in core and WG.PAD_MAX_BYTES == 1 << 30
     # ONE function holds the decisions: the launcher and the query call it, nobody restates it
     assert core.count('nk_launch_plan(') == 1 and nk.count('nk_launch_plan(') == 1 and ig.count('nk_launch_plan(') == 1
-    assert 'sg_opt(' not in nk[nk.index('int run_nk_ks('):].replace('t_xcd_z = sg_opt(SG_OPT_WGRAD_XCD) ? 2 : 0;', '')
+    assert 'sg_opt(' not in nk[nk.index('int run_nk_ks('):]
     assert 'CfgW64W' not in core + nk                               # the 64x128 tap tile nk_plan could never pick is gone
     body = core[core.index('inline NkPlan nk_plan('):core.index('// THE launch plan of a weight-gradient GEMM')]
     assert 'p.tile = M <= 32 ? 2 : 1;' in body and 'p.tile = 0;' in body and body.count('p.tile = ') == 2      # never tile 3

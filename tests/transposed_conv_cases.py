@@ -16,8 +16,8 @@ gamma from dense_pointwise_cases, n = the number of terms of THAT output (the re
 run on absolute values.  c per entry point, from the code:
   C_GATHER = 8   sg_convT2d_fwd, sg_conv2d_dgrad, sg_conv2d_dgrad_folded, sg_convT2d_dgrad (conv-shaped GEMM launches): the partial
                  sums of one output meet in at most 8 pieces = 7 adds -- split-K slabs (igemm_core.h kn_splits: ``if (sp > 8) sp = 8``;
-                 the table forces at most 8), or the two halves of a parity split (launch_cfg: ``bi.par.split[c] = sp2 ? 2 : 1``), or
-                 tail-split pieces (launch_cfg: ``smax = ... > 8 ? 8``); the three exclude each other (``splits <= 1`` in both
+                 the table forces at most 8), or the two halves of a parity split (split_schedule: ``bi.par.split[c] = sp2 ? 2 : 1``), or
+                 tail-split pieces (split_schedule: ``smax = ... > 8 ? 8``); the three exclude each other (``splits <= 1`` in both
                  conditions) -- plus the bias add of the epilogue.
   c_wgrad(Kpix)  sg_convT2d_wgrad: the k range N*H*W is cut into chunks that are multiples of 64 (igemm_nk.hip: ``kchunk = ...
                  sg_cdiv(sg_cdiv(Kpix, splits), 64) * 64``), so at most ceil(Kpix / 64) slabs meet; the bias gradient is a plain sum of
