@@ -6,7 +6,7 @@ import copy
 import numpy as np
 import torch
 
-from scene_generation_amd.synthetic import fill_deterministic, make_sampling_vocab
+from scene_generation_amd.synthetic import fill_deterministic, make_batch, make_sampling_vocab, make_vocab
 
 C, P, A, REP = 12, 4, 35, 32
 BANK_SEED = 97
@@ -107,3 +107,48 @@ def iou_inputs():
     gt = torch.cat([a, a + 0.1 + 0.4 * torch.rand(O, 2, generator=g)], 1)
     pred = (gt + 0.12 * torch.randn(O, 4, generator=g)).clamp(0, 1)
     return pred, gt, o2i
+
+
+def _images(n, seed, size=75):
+    """images that differ in tint and gradient (pure noise lands every image on nearly the same feature row)"""
+    g = torch.Generator().manual_seed(seed)
+    noise = torch.rand(n, 3, size, size, generator=g) * 2 - 1
+    tint = torch.rand(n, 3, 1, 1, generator=g) * 2 - 1
+    ramp = torch.linspace(-1, 1, size).view(1, 1, 1, size) * (torch.rand(n, 3, 1, 1, generator=g) * 2 - 1)
+    return (0.5 * tint + 0.3 * ramp + 0.2 * noise).clamp(-1, 1)
+
+
+def inference_model(cls):
+    C, P, A = 12, 4, 35
+    m = cls(make_vocab(C, P, A), image_size=(32, 32), gconv_hidden_dim=64, gconv_num_layers=3, mask_size=8,
+            mlp_normalization='none', appearance_normalization='batch', activation='leakyrelu-0.2',
+            n_downsample_global=2, use_attributes=True, pool_size=2)
+    fill_deterministic(m)
+    with torch.no_grad():       # same override as tools/make_golden.py (non-degenerate predicted boxes)
+        m.box_net[2].weight.mul_(0.05)
+        m.box_net[2].bias.copy_(torch.tensor([0.1, 0.15, 0.6, 0.7]))
+    m.eval()
+    batch = make_batch(N=3, min_objs=2, max_objs=4, size=32, mask_size=8, num_objs=C, num_preds=P, num_attributes=A,
+                       seed=321)
+    return m, batch
+
+
+def inference_cases(batch, g):
+    imgs, objs, boxes, masks, triples, o2i, _, attributes = batch
+    O_ = objs.size(0)
+    from tools_det import det
+    feats = [det((32,), 70 + i).abs() if i % 2 == 0 else None for i in range(O_)]
+    return [('gtbox_gtmask', dict(boxes_gt=boxes, masks_gt=masks, use_gt_box=True)),
+            ('predbox_predmask', dict(boxes_gt=boxes, masks_gt=None, use_gt_box=False)),
+            ('features', dict(boxes_gt=boxes, masks_gt=masks, use_gt_box=True, features=feats))]
+
+
+def sampling_model(cls, dev):
+    """small_model() on the device, with a fixed mask noise"""
+    m = small_model(cls, make_sampling_vocab(C, 7, A)).to(dev)
+    m.noise_override = torch.linspace(-1, 1, 64).view(1, -1)
+    return m
+
+
+def sampling_batch(seed=321):
+    return make_batch(N=3, min_objs=2, max_objs=4, size=32, mask_size=8, num_objs=C, num_preds=7, num_attributes=35, seed=seed)

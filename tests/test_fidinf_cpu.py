@@ -8,12 +8,10 @@ import pytest
 import torch
 
 import fidinf_ref as R
+from fidinf_ref import REL, _Net
 from scene_generation_amd import _hip, featsets, fid, fidinf, ops, sample
 
 NEW = ('sg_fidinf_grams_ws_bytes', 'sg_fidinf_grams', 'sg_fidinf_subset_terms_ws_bytes', 'sg_fidinf_subset_terms')
-# The two float64 formulations of tests/fidinf_ref.py (D x D symmetric form, Gram form) disagree by at most 1.95e-14 relative on the
-# 30 subsets below (profiles/fidinf_test_margins.md); the forms under test are held to 8 x that.
-REL = 8 * 1.95e-14
 
 
 # ---- host logic -----------------------------------------------------------------------------------------------------------------------
@@ -100,14 +98,6 @@ def test_extrapolation_beats_the_full_set_value(seed):
 
 
 # ---- the tap protocol -----------------------------------------------------------------------------------------------------------------
-class _Net(torch.nn.Module):
-    """stands in for an InceptionV3 where only ``fc.in_features`` is read"""
-
-    def __init__(self, dim=8):
-        super().__init__()
-        self.fc = torch.nn.Linear(dim, 2)
-
-
 class _Log(object):
     """a ``then`` that records every call"""
 

@@ -4,7 +4,6 @@ reports the plan it claims under each of its option sets (the library's host-onl
 device); the union of the rows' plan classes is a literal list; the Python restatement of the plan equals the query over a grid;
 the query rejects bad arguments and the descs whose reflection would read outside the plane; the restated constants are the ones in
 the sources."""
-import contextlib
 import ctypes
 import itertools
 import os
@@ -16,20 +15,13 @@ import torch
 import torch.nn.functional as F
 
 import forward_conv_cases as FC
+from gpu_harness import options
 from scene_generation_amd import _hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'scene_generation_amd', 'csrc')
 RTOL = 1e-12
 SHAPES = list(dict((c['shape_key'], c) for c in FC.CASES).values())
-
-
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(FC.option(k, v))
-        yield
 
 
 def case_plan(lib, case, opts, **over):

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 import accuracy_ref as R
 import sampling_helpers as SH
+from gpu_harness import Margins, N, margins_fixture
 from conftest import skip_random_init
 from scene_generation_amd import accuracy as A
 from scene_generation_amd import ops, sample
@@ -29,19 +30,9 @@ DEV = 'cuda:0'
 FACTOR = 16.0
 FACTORS = {'fold': 8.0, 'sgd_steps': 8.0}                     # families whose factor is halved (worst observed ratio under 1/8 of 16: profiles/accuracy_test_margins.md)
 FLOOR = 2.0 ** -24
-MARGINS = {}
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump_yardstick('accuracy_margins.json', FACTORS, FACTOR))
 CLS_KINDS = ('maxpool3s2', 'add_relu', 'bn_fold', 'sgd', 'classify_stats')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    """when the module's tests are done: the worst ratio per family that was checked -> accuracy_margins.json in the suite's output
-    directory (a record, not a check; a partial run writes the families it ran)"""
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('accuracy_margins.json', {k: {'ratio_of_fp32_yardstick': v[0], 'bound': FACTORS.get(k, FACTOR), 'case': v[1]}
-                                        for k, v in MARGINS.items()})
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -57,10 +48,6 @@ def T(a, dtype=None):
     return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
-def N(t):
-    return t.detach().cpu().numpy()
-
-
 def offset_copy(a, off=1):
     """a device copy of ``a`` that starts ``off`` elements into its allocation (4 bytes past a 16-byte boundary for fp32) and is
     followed by one guard element -> (view, whole buffer, guard value)"""
@@ -70,21 +57,9 @@ def offset_copy(a, off=1):
     return buf[off:off + a.size].view(a.shape), buf, guard
 
 
-def rel_err(a, ref64):
-    scale = float(ref64.abs().max())
-    return float((a.detach().double().cpu() - ref64).abs().max()) / (scale if scale > 0 else 1.0)
-
-
 def check(family, name, got, ref64, ref32):
     """|got - ref64| <= factor * max(|ref32 - ref64|, 2^-24 max|ref64|), in max norm over the tensor; factor = the family's"""
-    factor = FACTORS.get(family, FACTOR)
-    assert tuple(got.shape) == tuple(ref64.shape), (name, tuple(got.shape), tuple(ref64.shape))
-    e, yard = rel_err(got, ref64), max(rel_err(ref32, ref64), FLOOR)
-    ratio = e / yard
-    if ratio > MARGINS.get(family, (0.0, ''))[0]:
-        MARGINS[family] = (ratio, name)
-    print('%-10s %-44s err %.3e  fp32 yardstick %.3e  ratio %.3f' % (family, name, e, yard, ratio))
-    assert ratio <= factor, '%s: error %.3e is %.1f x the fp32 yardstick %.3e (bound %g x)' % (name, e, ratio, yard, factor)
+    MARGINS.yardstick(family, name, got, ref64, ref32, FACTORS, FACTOR, FLOOR)
 
 
 # =====================================================================================================================================
@@ -639,7 +614,7 @@ def test_accuracy_meter_against_the_reference_loop(classifier):
 def test_accuracy_cli_train_and_score(tmp_path, capsys):
     """both subcommands of python -m scene_generation_amd.accuracy on a resnet18 at 56 x 56: the synthetic loaders, the FusedSGD +
     StepLR wiring, the save name, a file load_model reads back, and the score path through sample.build_model"""
-    from test_gpu_ema import _batch, _run, _trainer
+    from trainer_helpers import _batch, _run, _trainer
     path = A.main(['train', '--model_name', 'resnet18', '--epochs', '2', '--batch_size', '2', '--input_shape', '56', '--image_size', '32',
                    '--n_class', '12', '--synthetic_batches', '2', '--save_loc', str(tmp_path)])
     out = capsys.readouterr()
@@ -691,7 +666,7 @@ def test_sampler_with_meter_keeps_one_host_read(classifier, monkeypatch):
 
 
 def test_sample_cli_prints_accuracy(classifier, tmp_path, capsys):
-    from test_gpu_ema import _batch, _run, _trainer
+    from trainer_helpers import _batch, _run, _trainer
     tr, ck, args = _trainer(tmp_path / 'train')
     _run(tr, _batch(), range(1))
     path = tr.save_checkpoint(ck, 1, args, 0)

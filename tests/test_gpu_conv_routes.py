@@ -9,7 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_parity import close, det
+from gpu_harness import close
+from tools_det import det
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'

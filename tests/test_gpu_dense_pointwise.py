@@ -7,120 +7,20 @@ Everything goes through the C ABI (ctypes), so gradients, null pointers and offs
 passes through ops.linear for the autograd wiring.  Sums are held to |got - ref64| <= gamma(n) sum|terms| element by element
 (n roundings, u = 2^-24); copies, selections and single products to bit-equality with their fp32 expectation.  The worst error /
 bound ratio of every family is written to dense_pointwise_margins.json next to the suite's other calibration records."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import dense_pointwise_cases as DP
-import test_gpu_parity as P
-from test_gpu_parity import close
+from gpu_harness import GUARD, Margins, call, margins_fixture, options, outbuf, place, ptr, same, stream, take
+from gpu_harness import L, _release_operands  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-GUARD = 12345.0
-_MARGINS = {}
-_KEEP = []          # operands placed by the running test: a launch is asynchronous, its inputs must outlive the expression
+MARGINS = Margins()
+within, close_noted = MARGINS.within, MARGINS.close_noted
+_margins = margins_fixture(lambda: MARGINS.dump('dense_pointwise_margins.json'))      # the worst error / bound ratio per family
 ENTRIES = (DP.LINEAR_FWD, DP.LINEAR_BWD_DATA, DP.LINEAR_BWD_WEIGHT)
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()      # fails loudly if the extension is missing
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _margins():
-    """after the module: the worst observed error / bound ratio per family -> dense_pointwise_margins.json"""
-    yield
-    P._dump('dense_pointwise_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in _MARGINS.items()})
-
-
-@pytest.fixture(autouse=True)
-def _release_operands():
-    yield
-    del _KEEP[:]
-
-
-def _note(family, ratio, name):
-    if family not in _MARGINS or ratio > _MARGINS[family][0]:
-        _MARGINS[family] = (float(ratio), name)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def place(a, off=0):
-    """the fp32 array on the device, ``off`` floats into a buffer of its own (the view keeps the buffer alive)"""
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    base = torch.empty(a.size + 8, dtype=torch.float32, device=DEV)
-    assert base.data_ptr() % 16 == 0
-    v = base[off:off + max(a.size, 1)]        # (never empty: an empty tensor has no address)
-    v[:a.size].copy_(torch.from_numpy(a).reshape(-1))
-    _KEEP.append(v)
-    return v
-
-
-def outbuf(n, off=0):
-    """n floats to be written plus a guard value behind them"""
-    base = torch.full((n + off + 1,), GUARD, dtype=torch.float32, device=DEV)
-    return base[off:off + n + 1]
-
-
-def take(o, shape):
-    """the result as a numpy array; the guard must be untouched"""
-    h = o.cpu().numpy()
-    assert h[-1] == GUARD, 'the kernel wrote behind its output'
-    return h[:-1].reshape(shape).copy()
-
-
-def call(L, name, *args):
-    rc = getattr(L, name)(*args)
-    assert rc == 0, '%s returned %d: %s' % (name, rc, L.sg_last_error_string().decode())
-
-
-def within(family, got, ref, bound, name):
-    """|got - ref| <= bound element by element (bound 0: equality)"""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), ref.shape)
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    if got.size == 0:
-        return
-    assert np.isfinite(got).all(), '%s: non-finite values' % name
-    err = np.abs(got - ref)
-    ratio = np.where(bound > 0, err / np.maximum(bound, 1e-300), np.where(err > 0, np.inf, 0.0))
-    worst = float(ratio.max())
-    print('%s %s: worst error / bound %.3f' % (family, name, worst))
-    _note(family, worst, name)
-    i = int(ratio.argmax())
-    assert worst <= 1.0, '%s: error %.3e exceeds the rounding bound %.3e (element %d, %.2f of the bound)' % (
-        name, err.reshape(-1)[i], bound.reshape(-1)[i], i, worst)
-
-
-def same(got, want, name):
-    got, want = np.asarray(got), np.asarray(want, dtype=np.float32)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert torch.equal(torch.from_numpy(np.ascontiguousarray(got)), torch.from_numpy(np.ascontiguousarray(want))), (
-        '%s: %d of %d elements differ from the fp32 expectation' % (name, int((got != want).sum()), got.size))
-
-
-def close_noted(family, a, b, tol, name):
-    a, b = torch.from_numpy(np.asarray(a, dtype=np.float64)), torch.from_numpy(np.asarray(b, dtype=np.float64))
-    ratio = float((a - b).abs().max()) / (tol * max(1.0, float(b.abs().max()))) if a.numel() else 0.0
-    print('%s %s: max error / bound %.3f' % (family, name, ratio))
-    n0 = len(P._CLOSE_LOG)
-    try:
-        close(a, b, tol, name)
-    finally:
-        _note(family, max([ratio] + [r[0] for r in P._CLOSE_LOG[n0:]]), name)
 
 
 # =============================================================================================
@@ -160,7 +60,7 @@ def test_dense_case(L, case):
     results = {}
     for kname, skinny in DP.KERNELS:
         for nsub in DP.NSUB_VALUES:
-            with DP.option('linear_skinny', skinny), DP.option('linear_nsub', nsub):
+            with options({'linear_skinny': skinny, 'linear_nsub': nsub}):
                 for e in ENTRIES:
                     name = '%s %s %s nsub%d' % (case['name'], DP.ENTRY_NAMES[e], kname, nsub)
                     plan = actual_plan(L, e, xd, wd, gd, rows, in_f, out_f)
@@ -205,7 +105,7 @@ def test_dense_onehot_probe(L, k):
             want, xd, wd, bd, gd = x, place(x), None, None, eyed
         for kname, skinny in DP.KERNELS:
             for nsub in DP.NSUB_VALUES:
-                with DP.option('linear_skinny', skinny), DP.option('linear_nsub', nsub):
+                with options({'linear_skinny': skinny, 'linear_nsub': nsub}):
                     got, gb = run_entry(L, e, xd, wd, bd, gd, rows, in_f, out_f, DP.ACT_NONE, 0.0, True)
                     same(got, want, 'one-hot K=%d %s %s nsub%d' % (k, DP.ENTRY_NAMES[e], kname, nsub))
                     if gb is not None:

@@ -16,6 +16,8 @@ import torch
 
 import featsets_ref as R
 import sampling_helpers as SH
+from gpu_harness import Margins, N, _guarded, _guards_ok, _place, margins_fixture
+from sampling_helpers import _images
 from scene_generation_amd import featsets as FS
 from scene_generation_amd import fid as FID
 from scene_generation_amd import inception as I
@@ -25,47 +27,8 @@ from scene_generation_amd.synthetic import make_batch, make_sampling_vocab
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-GUARD = -777.0
-IGUARD = -777
-MARGINS = {}
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('featsets_margins.json', MARGINS)
-
-
-def _margin(name, share, case):
-    if share > MARGINS.get(name, {'share_of_bound': -1.0})['share_of_bound']:
-        MARGINS[name] = {'share_of_bound': float(share), 'case': case}
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def _place(x, extra=0, off=0):
-    """a device copy of x [rows, D] with row stride D + extra that starts ``off`` elements into its allocation"""
-    rows, D = x.shape
-    buf = torch.full((off + rows * (D + extra) + 1,), float('nan'), dtype=torch.float32, device=DEV)
-    view = buf[off:off + rows * (D + extra)].view(rows, D + extra)[:, :D]
-    view.copy_(torch.from_numpy(x))
-    return view
-
-
-def _guarded(shape, dtype):
-    n = int(np.prod(shape))
-    g = GUARD if dtype == torch.float64 else IGUARD
-    buf = torch.full((n + 2,), g, dtype=dtype, device=DEV)
-    return buf, buf[1:1 + n].view(shape)
-
-
-def _guards_ok(buf):
-    g = GUARD if buf.dtype == torch.float64 else IGUARD
-    return buf[0].item() == g and buf[-1].item() == g
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump('featsets_margins.json', 'share_of_bound', empty=False))
 
 
 def poly_sums(x, y, ix, iy, gamma, coef0, degree, extra=0, off=0):
@@ -216,13 +179,13 @@ def test_poly_sums_and_kid_within_the_bound(shape, float_sets):
     got = poly_sums(x, y, ix, iy, 1.0 / D, 1.0, 3)
     share = float((np.abs(got - want) / bound).max())
     print('poly sums %s: worst share of the bound %.4f' % (shape, share))
-    _margin('poly_sums', share, '%d_%d_%d' % shape)
+    MARGINS.note('poly_sums', share, '%d_%d_%d' % shape)
     assert (np.abs(got - want) <= bound).all()
     per = lambda sums: sums[:, 0] / (s * (s - 1.0)) + sums[:, 1] / (s * (s - 1.0)) - 2.0 * sums[:, 2] / (s * s)
     kb = R.kid_bound(bound, s)
     kshare = float((np.abs(per(got) - per(want)) / kb).max())
     print('kid %s: per-subset values %s, worst share of the propagated bound %.4f' % (shape, per(got), kshare))
-    _margin('kid', kshare, '%d_%d_%d' % shape)
+    MARGINS.note('kid', kshare, '%d_%d_%d' % shape)
     assert (np.abs(per(got) - per(want)) <= kb).all()
     mean, std = FS.kid_from_sums(got, s)
     rmean, rstd = R.kid_from_sums(want, s)
@@ -241,12 +204,12 @@ def test_manifold_within_the_bound(shape, float_sets):
     rb = bxx.max(1)                                 # the k-th smallest moves by no more than the largest error of its row
     share = float((np.abs(got_r2 - want_r2) / rb).max())
     print('radii %s: worst share of the bound %.4f' % (shape, share))
-    _margin('knn_radius', share, '%d_%d_%d' % shape)
+    MARGINS.note('knn_radius', share, '%d_%d_%d' % shape)
     assert (np.abs(got_r2 - want_r2) <= rb).all()
     got_c, got_m = manifold_counts(x, got_r2, y)
     mshare = float((np.abs(got_m - dxy.min(1)) / bxy.max(1)).max())
     print('nearest query %s: worst share of the bound %.4f' % (shape, mshare))
-    _margin('mind2', mshare, '%d_%d_%d' % shape)
+    MARGINS.note('mind2', mshare, '%d_%d_%d' % shape)
     assert (np.abs(got_m - dxy.min(1)) <= bxy.max(1)).all()
     gap = np.abs(dxy - want_r2[:, None])
     band = gap <= 2.0 * (bxy + rb[:, None])         # pairs the rounding may decide either way, the radius's own error counted
@@ -305,14 +268,6 @@ def test_feature_bank_merge_equals_one_bank(tmp_path):
     one.save(path)
     assert torch.equal(FS.FeatureBank.load(path, DEV).rows(), rows)
     assert torch.equal(ops.feat_knn_radius(a.rows(), 3), ops.feat_knn_radius(rows, 3))
-
-
-def _images(n, seed, size=75):
-    g = torch.Generator().manual_seed(seed)
-    noise = torch.rand(n, 3, size, size, generator=g) * 2 - 1
-    tint = torch.rand(n, 3, 1, 1, generator=g) * 2 - 1
-    ramp = torch.linspace(-1, 1, size).view(1, 1, 1, size) * (torch.rand(n, 3, 1, 1, generator=g) * 2 - 1)
-    return (0.5 * tint + 0.3 * ramp + 0.2 * noise).clamp(-1, 1)
 
 
 @pytest.fixture(scope='module')
@@ -490,7 +445,7 @@ def test_command_lines(tmp_path, capsys):
 
 def test_sample_cli_prints_the_three_lines(tmp_path, capsys):
     import random
-    from test_gpu_ema import _batch as ema_batch, _run, _trainer
+    from trainer_helpers import _batch as ema_batch, _run, _trainer
     tr, ck, args = _trainer(tmp_path / 'train')
     _run(tr, ema_batch(), range(1))
     path = tr.save_checkpoint(ck, 1, args, 0)

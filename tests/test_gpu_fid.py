@@ -21,6 +21,8 @@ import torch
 import fid_ref as FR
 import inception_ref as R
 import sampling_helpers as SH
+from gpu_harness import METRIC_GUARD, Margins, N, _place, margins_fixture
+from sampling_helpers import _images
 from conftest import skip_random_init
 from scene_generation_amd import fid as FID
 from scene_generation_amd import inception as I
@@ -36,20 +38,9 @@ FACTORS = {'fid_net': 8.0, 'plain_net': 8.0}
 FLOOR = 2.0 ** -24
 E2E_FACTOR, E2E_FLOOR = 64.0, 2.0 ** -50
 U = 2.0 ** -53
-GUARD = -777.0
-MARGINS = {}
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('fid_margins.json', MARGINS)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
+GUARD = METRIC_GUARD
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump_yardstick('fid_margins.json', FACTORS, FACTOR))
 
 
 # =====================================================================================================================================
@@ -59,16 +50,6 @@ def N(t):
 SHAPES = [((1,), 16, 0, 0), ((3,), 16, 0, 0), ((4,), 48, 0, 0), ((5,), 100, 0, 1), ((37,), 100, 3, 0), ((64,), 2048, 0, 0),
           ((32, 32, 32, 32, 2), 2048, 0, 0)]
 IDS = ['%s_x%d%s%s' % ('+'.join(map(str, s[0])), s[1], '_ldx%d' % (s[1] + s[2]) if s[2] else '', '_off4B' if s[3] else '') for s in SHAPES]
-
-
-def _place(x, extra, off):
-    """a device copy of x [rows, D] with row stride D + extra that starts ``off`` elements into its allocation -> the strided view"""
-    rows, D = x.shape
-    buf = torch.full((off + rows * (D + extra) + 1,), float('nan'), dtype=torch.float32, device=DEV)
-    view = buf[off:off + rows * (D + extra)].view(rows, D + extra)[:, :D]
-    view.copy_(torch.from_numpy(x))
-    assert view.data_ptr() % 16 == 4 * off % 16 and (rows < 2 or view.stride(0) == D + extra)
-    return view
 
 
 def _accumulate(chunks, D, extra=0, off=0):
@@ -223,19 +204,8 @@ def test_branch_pools_bit_exact(HW):
 # =====================================================================================================================================
 # 6. the FID form of the network
 # =====================================================================================================================================
-def _rel_err(a, ref64):
-    scale = float(ref64.abs().max())
-    return float((a.detach().double().cpu() - ref64).abs().max()) / (scale if scale > 0 else 1.0)
-
-
 def _check(family, name, got, ref64, ref32):
-    factor = FACTORS.get(family, FACTOR)
-    e, yard = _rel_err(got, ref64), max(_rel_err(ref32, ref64), FLOOR)
-    ratio = e / yard
-    if ratio > MARGINS.get(family, {'ratio_of_fp32_yardstick': 0.0})['ratio_of_fp32_yardstick']:
-        MARGINS[family] = {'ratio_of_fp32_yardstick': ratio, 'bound': factor, 'case': name}
-    print('%-8s %-32s err %.3e  fp32 yardstick %.3e  ratio %.3f' % (family, name, e, yard, ratio))
-    assert ratio <= factor, '%s: error %.3e is %.1f x the fp32 yardstick %.3e (bound %g x)' % (name, e, ratio, yard, factor)
+    MARGINS.yardstick(family, name, got, ref64, ref32, FACTORS, FACTOR, FLOOR)
 
 
 @pytest.fixture(scope='module')
@@ -291,15 +261,6 @@ def test_fid_form_features_and_logits(fid_pair):
 # =====================================================================================================================================
 # 7-9. the object, end to end and in its callers
 # =====================================================================================================================================
-def _images(n, seed, size=75):
-    """images that differ in tint and gradient (pure noise lands every image on nearly the same feature row)"""
-    g = torch.Generator().manual_seed(seed)
-    noise = torch.rand(n, 3, size, size, generator=g) * 2 - 1
-    tint = torch.rand(n, 3, 1, 1, generator=g) * 2 - 1
-    ramp = torch.linspace(-1, 1, size).view(1, 1, 1, size) * (torch.rand(n, 3, 1, 1, generator=g) * 2 - 1)
-    return (0.5 * tint + 0.3 * ramp + 0.2 * noise).clamp(-1, 1)
-
-
 @pytest.fixture(scope='module')
 def fid_net():
     """the seeded random FID-form network ``FrechetInceptionDistance(weights=None)`` builds"""
@@ -327,8 +288,8 @@ def test_end_to_end_against_the_nuclear_norm(fid_net, capsys):
     host = FID.frechet_distance(*FR.stats(feats[0]), *FR.stats(feats[1]))
     yard = max(abs(host - want), E2E_FLOOR * scale)
     ratio = abs(got - want) / yard
-    MARGINS['fid_e2e'] = {'ratio_of_yardstick': ratio, 'bound': E2E_FACTOR, 'fid': got, 'nuclear': want, 'host_symmetric': host,
-                          'trace_scale': scale}
+    MARGINS.extra['fid_e2e'] = {'ratio_of_yardstick': ratio, 'bound': E2E_FACTOR, 'fid': got, 'nuclear': want, 'host_symmetric': host,
+                                'trace_scale': scale}
     print('fid_e2e  got %.17g  nuclear %.17g  host symmetric form %.17g  scale %.6g  ratio %.3f' % (got, want, host, scale, ratio))
     assert want > 1e-6 * scale                                    # two sets that differ
     assert ratio <= E2E_FACTOR, (got, want, host, scale)

@@ -15,53 +15,20 @@ import pytest
 import torch
 
 import fidinf_ref as R
+from fidinf_ref import REL, _Net
+from gpu_harness import METRIC_GUARD, Margins, N, _guarded, _guards_ok, _place, margins_fixture
+from sampling_helpers import _images
 from scene_generation_amd import featsets as FS
 from scene_generation_amd import fid as FID
 from scene_generation_amd import fidinf as FI
 from scene_generation_amd import inception as I
 from scene_generation_amd import ops, sample
-from test_fidinf_cpu import REL, _Net
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-GUARD = -777.0
-MARGINS = {}
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('fidinf_margins.json', MARGINS)
-
-
-def _margin(name, share, case):
-    if share > MARGINS.get(name, {'share_of_bound': -1.0})['share_of_bound']:
-        MARGINS[name] = {'share_of_bound': float(share), 'case': case}
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def _place(x, extra=0, off=0):
-    """a device copy of x [rows, D] with row stride D + extra that starts ``off`` elements into its allocation"""
-    rows, D = x.shape
-    buf = torch.full((off + rows * (D + extra) + 1,), float('nan'), dtype=torch.float32, device=DEV)
-    view = buf[off:off + rows * (D + extra)].view(rows, D + extra)[:, :D]
-    view.copy_(torch.from_numpy(x))
-    return view
-
-
-def _guarded(shape, fill=GUARD):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2,), fill, dtype=torch.float64, device=DEV)
-    return buf, buf[1:1 + n].view(shape)
-
-
-def _guards_ok(buf):
-    return buf[0].item() == GUARD and buf[-1].item() == GUARD
+GUARD = METRIC_GUARD
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump('fidinf_margins.json', 'share_of_bound', empty=False))
 
 
 def _dev64(a):
@@ -101,8 +68,8 @@ def test_grams_within_the_derived_bound(n, D, extra, off):
     assert np.isfinite(P).all() and np.isfinite(G).all() and not (P == GUARD).any() and not (G == GUARD).any()
     sp, sg = float((np.abs(P - Pr) / bP).max()), float((np.abs(G - Gr) / bG).max())
     print('grams n=%d D=%d: worst share of the bound P %.4f G %.4f' % (n, D, sp, sg))
-    _margin('grams_P', sp, '%d_%d' % (n, D))
-    _margin('grams_G', sg, '%d_%d' % (n, D))
+    MARGINS.note('grams_P', sp, '%d_%d' % (n, D))
+    MARGINS.note('grams_G', sg, '%d_%d' % (n, D))
     assert (np.abs(P - Pr) <= bP).all() and (np.abs(G - Gr) <= bG).all()
     assert np.array_equal(P, P.T) and np.array_equal(G, G.T)                        # bit for bit
     P2, G2 = grams(x, mu, sigma, extra, off)
@@ -160,13 +127,13 @@ def test_subset_terms_on_ragged_subsets():
     Mh, sh = N(M), N(sums)
     share = float((np.abs(sh - want_sums) / bsums).max())
     print('subset sums: worst share of the bound %.4f' % share)
-    _margin('subset_sums', share, '37')
+    MARGINS.note('subset_sums', share, '37')
     assert (np.abs(sh - want_sums) <= bsums).all()
     for q, s in enumerate(sizes):
         block = Mh[q, :s, :s]
         mshare = float((np.abs(block - want_M[q]) / bM[q]).max())
         print('M block of %d rows: worst share of the bound %.4f' % (s, mshare))
-        _margin('subset_M', mshare, str(int(s)))
+        MARGINS.note('subset_M', mshare, str(int(s)))
         assert (np.abs(block - want_M[q]) <= bM[q]).all()
         assert np.array_equal(block, block.T)                                       # bit for bit
         outside = np.ones((37, 37), bool)
@@ -223,9 +190,9 @@ def test_fid_infinity_against_the_restatement_and_the_dxd_route(case64):
     dxd = FID.frechet_distance(c['mu'], c['sigma'], mu2, sigma2)
     rel_dxd = abs(res['fid'] - dxd) / abs(dxd)
     print('FID_N: the Gram route %.12f, FeatureMoments + frechet_distance %.12f, %.3g relative' % (res['fid'], dxd, rel_dxd))
-    _margin('fid_infinity_fids', float(rel.max() / REL), '64_400')
-    _margin('fid_infinity_intercept', float(rel_inf / REL), '64_400')
-    _margin('fid_n_against_dxd', float(rel_dxd / REL), '64_400')
+    MARGINS.note('fid_infinity_fids', float(rel.max() / REL), '64_400')
+    MARGINS.note('fid_infinity_intercept', float(rel_inf / REL), '64_400')
+    MARGINS.note('fid_n_against_dxd', float(rel_dxd / REL), '64_400')
     assert (rel <= REL).all() and rel_inf <= REL and rel_dxd <= REL
     assert FI.fid_infinity(rows, c['mu'], c['sigma']) == res                        # the same bits
     other = FI.fid_infinity(rows, c['mu'], c['sigma'], seed=1)
@@ -294,14 +261,6 @@ def test_shared_forward_fixed_and_open_real_side(case64):
 # =====================================================================================================================================
 # 4. the command lines
 # =====================================================================================================================================
-def _images(n, seed, size=75):
-    g = torch.Generator().manual_seed(seed)
-    noise = torch.rand(n, 3, size, size, generator=g) * 2 - 1
-    tint = torch.rand(n, 3, 1, 1, generator=g) * 2 - 1
-    ramp = torch.linspace(-1, 1, size).view(1, 1, 1, size) * (torch.rand(n, 3, 1, 1, generator=g) * 2 - 1)
-    return (0.5 * tint + 0.3 * ramp + 0.2 * noise).clamp(-1, 1)
-
-
 def test_command_line(tmp_path, capsys):
     Image = pytest.importorskip('PIL.Image')
     for name, seed, n in (('real', 5, 8), ('fake', 6, 6)):
@@ -336,7 +295,7 @@ def test_command_line(tmp_path, capsys):
 
 def test_sample_cli_prints_the_line_after_fid(tmp_path, capsys):
     import random
-    from test_gpu_ema import _batch as ema_batch, _run, _trainer
+    from trainer_helpers import _batch as ema_batch, _run, _trainer
     tr, ck, args = _trainer(tmp_path / 'train')
     _run(tr, ema_batch(), range(1))
     path = tr.save_checkpoint(ck, 1, args, 0)

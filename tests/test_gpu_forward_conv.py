@@ -8,7 +8,6 @@ the library reports for THIS call (same options, the actual addresses of w, y an
 one the row claims and the one forward_conv_cases.py restates; every element within its own bound of float64 (gamma(K + 1 + c), c
 from the reported plan); a second call bit-identical.  The worst error / bound ratio per plan goes to forward_conv_margins.json
 (profiles/forward_conv_test_margins.md holds a run's)."""
-import contextlib
 import ctypes
 
 import numpy as np
@@ -16,47 +15,15 @@ import pytest
 import torch
 
 import forward_conv_cases as FC
-import test_gpu_parity as P
-import test_gpu_dense_pointwise as G
-from test_gpu_dense_pointwise import place, outbuf, take, within, same, call, ptr, stream, GUARD
-from test_gpu_transposed_conv import twice
+from gpu_harness import (GUARD, Margins, Workspace, _KEEP, call, margins_fixture, opt_tag, options, outbuf, place, place_fenced, ptr, same,
+                         same_bits, stream, take, twice)
+from gpu_harness import L, _release_operands  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-_MARGINS = {}
-GUARD_WORDS = 256
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()      # fails loudly if the extension is missing
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _margins():
-    """after the module: the worst observed error / bound ratio per plan -> forward_conv_margins.json"""
-    yield
-    P._dump('forward_conv_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in sorted(_MARGINS.items())})
-
-
-@pytest.fixture(autouse=True)
-def _release_operands():
-    yield
-    del G._KEEP[:]
-
-
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(FC.option(k, v))
-        yield
-
-
-def opt_tag(o):
-    return ' '.join('%s=%d' % kv for kv in sorted(o.items()))
+MARGINS = Margins()
+within = MARGINS.within
+_margins = margins_fixture(lambda: MARGINS.dump('forward_conv_margins.json'))      # the worst error / bound ratio per plan
 
 
 def family(case, plan):
@@ -64,34 +31,6 @@ def family(case, plan):
     ld = 'fixed' if plan['loader'] == FC.FW_FIXED else ('nomask' if plan['nomask'] else 'table')
     red = ('', ' reduce=vec', ' reduce=scalar')[plan['reduce']]
     return '%s %dx%d %s %s%s k%d%s' % (case['entry'], plan['bm'], plan['bn'], 'vecA' if plan['a_vec'] else 'scalarA', ld, src, case['KS'], red)
-
-
-def held(fam, got, ref, bound, name):
-    """within(), with the worst ratio noted for this module's margins file"""
-    err = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
-    b = np.broadcast_to(np.asarray(bound, dtype=np.float64), err.shape)
-    ratio = np.where(b > 0, err / np.maximum(b, 1e-300), np.where(err > 0, np.inf, 0.0))
-    worst = float(np.nan_to_num(ratio, nan=np.inf).max()) if ratio.size else 0.0
-    if fam not in _MARGINS or worst > _MARGINS[fam][0]:
-        _MARGINS[fam] = (worst, name)
-    within(fam, got, ref, bound, name)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
-
-
-def same_bits(a, b, name):
-    assert np.array_equal(bits(a), bits(b)), '%s: %d of %d elements differ' % (name, int((bits(a) != bits(b)).sum()), a.size)
-
-
-def place_fenced(a):
-    """place(), four floats into its buffer, with NaN in the four floats before and the four behind: a gather that is off by a few
-    elements at either end of an input reads a NaN -- which no zero weight hides -- and stays inside the buffer"""
-    v = place(a, 4)
-    v._base[:4] = float('nan')
-    v._base[4 + a.size:] = float('nan')
-    return v
 
 
 def run(L, case, inp, w_off=None, y_off=None, ws_off=None, ws_bytes=None, entry=None, expect_refusal=False):
@@ -106,33 +45,30 @@ def run(L, case, inp, w_off=None, y_off=None, ws_off=None, ws_bytes=None, entry=
     N, M = case['N'], case['Cout']
     n = N * M * case['OH'] * case['OW']
     o = outbuf(n, y_off)
-    words = (ws_bytes + 3) // 4
-    wsb = torch.full((words + GUARD_WORDS + 4,), GUARD, dtype=torch.float32, device=DEV)
-    assert wsb.data_ptr() % 16 == 0 and (o.data_ptr() - 4 * y_off) % 16 == 0
-    ws = wsb[ws_off:]
-    ws[:words] = float('nan')
-    plan = FC.fwd_plan(L, d, FC.ENTRY_OF[entry], case['L'], wd.data_ptr() % 16, o.data_ptr() % 16, ws.data_ptr() % 16, ws_bytes)
+    assert (o.data_ptr() - 4 * y_off) % 16 == 0
+    ws = Workspace(ws_bytes, ws_off)
+    plan = FC.fwd_plan(L, d, FC.ENTRY_OF[entry], case['L'], wd.data_ptr() % 16, o.data_ptr() % 16, ws.buf.data_ptr() % 16, ws_bytes)
     args = [ctypes.byref(d), ptr(x1d), ptr(x2d), ptr(wd), ptr(bd)]
     if entry != 'dense':
         ld, cd = torch.from_numpy(inp['lists']).to(DEV), torch.from_numpy(inp['cnt']).to(DEV)
-        G._KEEP.extend([ld, cd])
+        _KEEP.extend([ld, cd])
         args += [ptr(ld), ptr(cd), case['L']]
-    args += [ptr(o), case['act'], case['slope'], ptr(ws), ws_bytes, stream()]
+    args += [ptr(o), case['act'], case['slope'], ptr(ws.buf), ws_bytes, stream()]
     if expect_refusal:
         rc = getattr(L, FC.ENTRY_FN[entry])(*args)
         torch.cuda.synchronize()
-        return dict(plan=plan, rc=rc, error=L.sg_last_error_string().decode(), out=o.cpu().numpy(), ws=wsb.cpu().numpy())
+        return dict(plan=plan, rc=rc, error=L.sg_last_error_string().decode(), out=o.cpu().numpy(), ws=ws.host())
     assert plan is not None, L.sg_last_error_string().decode()
     assert 0 <= plan['ws_needed'] <= ws_bytes, (plan, ws_bytes)
     call(L, FC.ENTRY_FN[entry], *args)
     torch.cuda.synchronize()
-    assert bool((ws[words:words + GUARD_WORDS].cpu() == GUARD).all()), 'the launch wrote behind the workspace bytes it was given'
+    ws.intact(case['name'])
     return dict(plan=plan, ws_bytes=ws_bytes, y=take(o, (N, M, case['OH'], case['OW'])))
 
 
 def check(case, r, name):
     ref = FC.case_refs(case)
-    held(family(case, r['plan']), r['y'], ref['y'], FC.y_bound(case, r['plan']), name)
+    within(family(case, r['plan']), r['y'], ref['y'], FC.y_bound(case, r['plan']), name)
     if case['entry'] != 'dense':              # an image that lists nothing: act(bias), exactly
         inp = FC.case_inputs(case)
         b = np.zeros(case['Cout'], dtype=np.float32) if inp['b'] is None else inp['b']
@@ -238,7 +174,7 @@ def test_sparse_equals_dense_on_zero_filled_input_and_perimage_on_gathered_weigh
                         z['x2'][b, c - C1] = 0
         dn = run(L, case, z, entry='dense')
         both = FC.y_bound(case, sp['plan']) + FC.y_bound(case, dn['plan'])
-        held('sparse against dense', sp['y'], dn['y'], both, case['name'])
+        within('sparse against dense', sp['y'], dn['y'], both, case['name'])
         # the per-image entry with the weights gathered through the lists: the same compact rows, bit for bit
         pi = run(L, case, dict(inp, wimg=FC.gather_wimg(inp['w'], inp['lists'], inp['cnt'])), entry='perimage')
     assert pi['plan'] == sp['plan']

@@ -4,9 +4,9 @@ tests/test_graph_layout_cases_cpu.py shows that the cases reach the branches and
 
 Sums in a fixed order are held to two things: bit-equality with a sequential fp32 sum in the documented order (the kernels'
 "same adds, same order" contract) and the rounding bound gamma(n - 1) sum|x_i| against float64.  Layout and crop outputs also
-carry the rounding of the sample coordinate and use close() of test_gpu_parity.py with the project's tolerances
+carry the rounding of the sample coordinate and use close() of tests/gpu_harness.py with the project's tolerances
 (graph_layout_cases.LAYOUT_TOL / CROP_TOL).  The worst error / bound ratio of every family is written to
-graph_layout_margins.json next to the suite's other calibration records (test_gpu_parity._dump)."""
+graph_layout_margins.json next to the suite's other calibration records."""
 import functools
 
 import numpy as np
@@ -15,74 +15,19 @@ import torch
 
 import graph_layout_cases as GL
 import norm_cases as NC
-import test_gpu_parity as P
-from test_gpu_parity import close
+from gpu_harness import Margins, margins_fixture, same
+from gpu_harness import hip  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-_MARGINS = {}
-
-
-@pytest.fixture(scope='module')
-def hip():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import ops, _hip
-    _hip.lib()      # fails loudly if the extension is missing
-    return ops
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _margins():
-    """after the module: the worst observed error / bound ratio per family -> graph_layout_margins.json (test_gpu_parity._dump)"""
-    yield
-    P._dump('graph_layout_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in _MARGINS.items()})
-
-
-def _note(family, ratio, name):
-    if family not in _MARGINS or ratio > _MARGINS[family][0]:
-        _MARGINS[family] = (float(ratio), name)
+MARGINS = Margins()
+within, close_noted = MARGINS.within, MARGINS.close_noted
+_margins = margins_fixture(lambda: MARGINS.dump('graph_layout_margins.json'))      # the worst error / bound ratio per family
 
 
 def dev(a, grad=False):
     t = (GL.t32(a) if isinstance(a, np.ndarray) else a).to(DEV)
     return t.requires_grad_() if grad else t
-
-
-def within(family, got, ref, bound, name):
-    """|got - ref| <= bound element by element (bound 0: equality)"""
-    got = got.detach().double().cpu()
-    ref = (torch.from_numpy(np.asarray(ref)) if not isinstance(ref, torch.Tensor) else ref.detach()).double()
-    bound = (torch.from_numpy(np.asarray(bound)) if not isinstance(bound, torch.Tensor) else bound).double().expand_as(ref)
-    assert got.shape == ref.shape, (name, tuple(got.shape), tuple(ref.shape))
-    if got.numel() == 0:
-        return
-    assert torch.isfinite(got).all(), '%s: non-finite values' % name
-    err = (got - ref).abs()
-    ratio = torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, float('inf')),
-                                                                               torch.zeros_like(err)))
-    worst = float(ratio.max())
-    print('%s %s: worst error / bound %.3f' % (family, name, worst))
-    _note(family, worst, name)
-    i = int(ratio.argmax())
-    assert worst <= 1.0, '%s: error %.3e exceeds the rounding bound %.3e (element %d, %.2f of the bound)' % (
-        name, float(err.view(-1)[i]), float(bound.reshape(-1)[i]), i, worst)
-
-
-def close_noted(family, a, b, tol, name):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    n0 = len(P._CLOSE_LOG)
-    ratio = 0.0
-    if a.numel() and a.shape == b.shape:
-        ratio = float((a - b).abs().max()) / (tol * max(1.0, float(b.abs().max())))
-    print('%s %s: max error / bound %.3f' % (family, name, ratio))
-    try:
-        close(a, b, tol, name)
-    finally:
-        _note(family, max([ratio] + [r[0] for r in P._CLOSE_LOG[n0:]]), name)
-
-
-def same(a, b):
-    return torch.equal(a.detach().cpu(), (GL.t32(b) if isinstance(b, np.ndarray) else b.detach().cpu()))
 
 
 # =============================================================================================

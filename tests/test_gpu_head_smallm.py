@@ -16,80 +16,16 @@ import torch
 
 import forward_conv_cases as FC
 import head_smallm_cases as HS
-import test_gpu_dense_pointwise as G
-import test_gpu_parity as P
 import transposed_conv_cases as T
 import wgrad_cases as WG
-from test_gpu_dense_pointwise import outbuf, take, within, same, call, ptr, stream, GUARD
-from test_gpu_forward_conv import place_fenced
-from test_gpu_transposed_conv import twice, dref
+from gpu_harness import Margins, Workspace, _KEEP, call, dref, margins_fixture, outbuf, place_fenced, ptr, same, stream, taken, twice
+from gpu_harness import L, _release_operands  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-_MARGINS = {}
-GUARD_WORDS = 256
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()      # fails loudly if the extension is missing
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _margins():
-    """after the module: the worst observed error / bound ratio per plan -> head_smallm_margins.json"""
-    yield
-    P._dump('head_smallm_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in sorted(_MARGINS.items())})
-
-
-@pytest.fixture(autouse=True)
-def _release_operands():
-    yield
-    del G._KEEP[:]
-
-
-def held(fam, got, ref, bound, name):
-    """within(), with the worst ratio noted for this module's margins file"""
-    err = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
-    b = np.broadcast_to(np.asarray(bound, dtype=np.float64), err.shape)
-    ratio = np.where(b > 0, err / np.maximum(b, 1e-300), np.where(err > 0, np.inf, 0.0))
-    worst = float(np.nan_to_num(ratio, nan=np.inf).max()) if ratio.size else 0.0
-    if fam not in _MARGINS or worst > _MARGINS[fam][0]:
-        _MARGINS[fam] = (worst, name)
-    within(fam, got, ref, bound, name)
-
-
-def fenced(a, off=0):
-    """place_fenced(), ``off`` floats further from the 16-byte boundary (NaN in the four floats before and the four behind)"""
-    if off == 0:
-        return place_fenced(a)
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    base = torch.full((a.size + 8 + off,), float('nan'), dtype=torch.float32, device=DEV)
-    assert base.data_ptr() % 16 == 0
-    v = base[4 + off:4 + off + a.size]
-    v.copy_(torch.from_numpy(a).reshape(-1))
-    G._KEEP.append(v)
-    return v
-
-
-def taken(o, shape, name):
-    y = take(o, shape)
-    assert not (y == GUARD).any(), '%s: %d result elements were never written' % (name, int((y == GUARD).sum()))
-    return y
-
-
-class Workspace:
-    """the bytes the query asked for, NaN, and guard words behind them"""
-
-    def __init__(self, nbytes):
-        self.n, self.words = nbytes, (nbytes + 3) // 4
-        self.buf = torch.full((self.words + GUARD_WORDS,), GUARD, dtype=torch.float32, device=DEV)
-        self.buf[:self.words] = float('nan')
-
-    def intact(self, name):
-        assert bool((self.buf[self.words:].cpu() == GUARD).all()), '%s: the launch wrote behind the workspace bytes the query asked for' % name
+MARGINS = Margins()
+within = MARGINS.within
+_margins = margins_fixture(lambda: MARGINS.dump('head_smallm_margins.json'))      # the worst error / bound ratio per plan
 
 
 def family(case, entry, plan):
@@ -104,7 +40,7 @@ def family(case, entry, plan):
 def operands(case, inp, x_off=None):
     """the row's inputs on the device, fenced: x (at the row's offset), w, gy, bias or None"""
     x_off = case['x_off'] if x_off is None else x_off
-    return dict(x=fenced(inp['x'], x_off), w=fenced(inp['w']), gy=fenced(inp['gy']), b=None if inp.get('b') is None else fenced(inp['b']))
+    return dict(x=place_fenced(inp['x'], x_off), w=place_fenced(inp['w']), gy=place_fenced(inp['gy']), b=None if inp.get('b') is None else place_fenced(inp['b']))
 
 
 def run_entry(L, case, entry, dev, y_off=None):
@@ -198,9 +134,9 @@ def test_case(L, case):
             assert plan[k] == v, '%s: plan field %s is %s, the table claims %s (%s)' % (name, k, plan[k], v, plan)
         assert plan == HS.case_py_plan(case, entry), name
         bound = own_bound(case, entry, plan)
-        held(family(case, entry, plan), got, ref[REF_KEY[entry]], bound, name)
+        within(family(case, entry, plan), got, ref[REF_KEY[entry]], bound, name)
         other, obound = generic_entry(L, case, entry, aligned)
-        held('against the generic %s' % entry, got, other, bound + obound, name + ' against the generic entry point')
+        within('against the generic %s' % entry, got, other, bound + obound, name + ' against the generic entry point')
 
 
 STREAM_ROWS = [c for c in HS.HEAD_CASES if HS.case_py_plan(c, 'fwd')['kind'] == HS.HEAD_STREAM]
@@ -215,7 +151,7 @@ def test_stream_rows_run_staged_when_an_address_is_off(L, case):
         name = '%s [x + %d, y + %d floats]' % (case['name'], x_off, y_off)
         got, plan = run_entry(L, case, 'fwd', operands(case, inp, x_off=x_off), y_off=y_off)
         assert plan['kind'] == HS.HEAD_STAGED and plan == HS.case_py_plan(case, 'fwd', 4 * x_off, 4 * y_off), (name, plan)
-        held(family(case, 'fwd', plan), got, ref['y'], HS.y_bound(case, plan), name)
+        within(family(case, 'fwd', plan), got, ref['y'], HS.y_bound(case, plan), name)
 
 
 # =============================================================================================
@@ -239,13 +175,13 @@ def test_onehot_probes_are_exact(L, case):
         same(y, HS.place_fwd(case, inp['x'], sel), name + ' y')
         if case['family'] == 'head':
             same(run_entry(L, case, 'dgrad', dev)[0], HS.place_dgrad(case, inp['gy'], *sel[0]), name + ' gx')
-        del G._KEEP[:]
+        del _KEEP[:]
     for site in HS.probe_sites(case):
         g1 = np.zeros_like(inp['gy'])
         g1[site[0], site[1], site[2][0], site[2][1]] = 1.0
         gw, _ = run_entry(L, case, 'wgrad', operands(case, dict(inp, gy=g1)))
         same(gw, HS.place_wgrad(case, inp['x'], site), '%s one-hot gy at %s' % (case['name'], site))
-        del G._KEEP[:]
+        del _KEEP[:]
 
 
 # =============================================================================================
@@ -274,16 +210,16 @@ def test_operator_takes_the_special_route_and_the_generic_one_with_the_switch_of
                 n = int(L.sg_conv2d_ws_bytes(dref(d), 0))
                 plan = FC.fwd_plan(L, d, FC.FW_CONV, 0, 0, 0, 0, n)
                 bound = HS._act_bound(case, HS.gamma(plan['K'] + 1 + FC.joins(case, plan)) * ref['y_sabs'], ref['y'])
-                held('operator, generic route', y.detach().cpu().numpy(), ref['y'], bound, name + ' y (HEADCONV off)')
+                within('operator, generic route', y.detach().cpu().numpy(), ref['y'], bound, name + ' y (HEADCONV off)')
                 continue
             plan = HS.case_py_plan(case, 'fwd', 0, 0)
-            held('operator, ' + family(case, 'fwd', plan), y.detach().cpu().numpy(), ref['y'], HS.y_bound(case, plan), name + ' y')
+            within('operator, ' + family(case, 'fwd', plan), y.detach().cpu().numpy(), ref['y'], HS.y_bound(case, plan), name + ' y')
             if case['act'] == HS.ACT_NONE:
                 y.backward(torch.from_numpy(inp['gy']).to(DEV))
                 gplan = HS.case_py_plan(case, 'wgrad', 0, 0)
-                held('operator, ' + family(case, 'wgrad', gplan), w.grad.cpu().numpy(), ref['gw'], HS.gw_bound(case, gplan), name + ' gw')
+                within('operator, ' + family(case, 'wgrad', gplan), w.grad.cpu().numpy(), ref['gw'], HS.gw_bound(case, gplan), name + ' gw')
                 if case['family'] == 'head':
-                    held('operator, ' + family(case, 'dgrad', HS.case_py_plan(case, 'dgrad', 0, 0)), x.grad.cpu().numpy(), ref['gx'], HS.gx_bound(case), name + ' gx')
+                    within('operator, ' + family(case, 'dgrad', HS.case_py_plan(case, 'dgrad', 0, 0)), x.grad.cpu().numpy(), ref['gx'], HS.gx_bound(case), name + ' gx')
     finally:
         ops.HEADCONV = saved
 
@@ -306,7 +242,7 @@ def test_smallm_backward_copies_a_gradient_that_starts_mid_vector(L):
         y.backward(gy)
         grads.append(w.grad.cpu().numpy())
     assert np.array_equal(grads[0], grads[1])
-    held('operator, smallm wgrad MO=3', grads[1], HS.case_refs(case)['gw'], HS.gw_bound(case, None), case['name'] + ' gw from a misaligned gy')
+    within('operator, smallm wgrad MO=3', grads[1], HS.case_refs(case)['gw'], HS.gw_bound(case, None), case['name'] + ' gw from a misaligned gy')
 
 
 def test_table_reaches_every_plan_class(L):

@@ -17,11 +17,11 @@ import torch.nn.functional as F
 
 import inception_ref as R
 import sampling_helpers as SH
+from gpu_harness import Margins, N, margins_fixture
 from conftest import skip_random_init
 from scene_generation_amd import inception as I
 from scene_generation_amd import ops, sample
 from scene_generation_amd.model import Model
-from scene_generation_amd.synthetic import make_batch, make_sampling_vocab
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -29,25 +29,13 @@ FACTOR = 16.0
 # families whose worst observed ratio is under 2 (profiles/inception_test_margins.md): their factor is halved to 8; score_e2e keeps 16
 FACTORS = {k: 8.0 for k in ('rect_conv', 'avgpool', 'resize', 'softmax', 'net')}
 FLOOR = 2.0 ** -24
-MARGINS = {}
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump_yardstick('inception_margins.json', FACTORS, FACTOR))
 SCORE_RTOL = 1e-9
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('inception_margins.json', {k: {'ratio_of_fp32_yardstick': v[0], 'bound': FACTORS.get(k, FACTOR), 'case': v[1]}
-                                         for k, v in MARGINS.items()})
 
 
 def T(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 def offset_copy(a, off=1):
@@ -59,21 +47,9 @@ def offset_copy(a, off=1):
     return buf[off:off + a.size].view(a.shape), buf, guard
 
 
-def rel_err(a, ref64):
-    scale = float(ref64.abs().max())
-    return float((a.detach().double().cpu() - ref64).abs().max()) / (scale if scale > 0 else 1.0)
-
-
 def check(family, name, got, ref64, ref32):
     """|got - ref64| <= factor * max(|ref32 - ref64|, 2^-24 max|ref64|), in max norm over the tensor; factor = the family's"""
-    factor = FACTORS.get(family, FACTOR)
-    assert tuple(got.shape) == tuple(ref64.shape), (name, tuple(got.shape), tuple(ref64.shape))
-    e, yard = rel_err(got, ref64), max(rel_err(ref32, ref64), FLOOR)
-    ratio = e / yard
-    if ratio > MARGINS.get(family, (0.0, ''))[0]:
-        MARGINS[family] = (ratio, name)
-    print('%-10s %-44s err %.3e  fp32 yardstick %.3e  ratio %.3f' % (family, name, e, yard, ratio))
-    assert ratio <= factor, '%s: error %.3e is %.1f x the fp32 yardstick %.3e (bound %g x)' % (name, e, ratio, yard, factor)
+    MARGINS.yardstick(family, name, got, ref64, ref32, FACTORS, FACTOR, FLOOR)
 
 
 # =====================================================================================================================================
@@ -420,8 +396,7 @@ def test_inception_score_object_end_to_end(pair, capsys):
         scale = abs(want[torch.float64][0])
         e, yard = abs(got - s64) / scale, max(abs(s32 - s64) / scale, FLOOR)
         ratio = e / yard
-        if ratio > MARGINS.get('score_e2e', (0.0, ''))[0]:
-            MARGINS['score_e2e'] = (ratio, name)
+        MARGINS.note('score_e2e', ratio, name)
         print('score_e2e  %-6s got %.9g  fp64 %.9g  fp32 %.9g  ratio %.3f' % (name, got, s64, s32, ratio))
         assert ratio <= FACTORS.get('score_e2e', FACTOR), (name, got, s64, s32)
 
@@ -470,13 +445,10 @@ def test_scorer_warns_grows_cleans_and_repeats(scorer, capsys):
 # 5. wiring: check_model and the Sampler
 # =====================================================================================================================================
 def _sampling_model():
-    m = SH.small_model(Model, make_sampling_vocab(SH.C, 7, SH.A)).to(DEV)
-    m.noise_override = torch.linspace(-1, 1, 64).view(1, -1)
-    return m
+    return SH.sampling_model(Model, DEV)
 
 
-def _batch(seed=321):
-    return make_batch(N=3, min_objs=2, max_objs=4, size=32, mask_size=8, num_objs=SH.C, num_preds=7, num_attributes=35, seed=seed)
+_batch = SH.sampling_batch
 
 
 def test_check_model_with_the_scorer():
@@ -525,7 +497,7 @@ def test_sample_cli_prints_the_inception_line(tmp_path, capsys):
     """``sample --inception_weights PATH``: the scorer is built from a saved state_dict, the result gains ``inception`` and exactly one
     ``Inception MEAN STD`` line is printed; with the flag absent every other output is what it was"""
     import random
-    from test_gpu_ema import _batch as ema_batch, _run, _trainer
+    from trainer_helpers import _batch as ema_batch, _run, _trainer
     tr, ck, args = _trainer(tmp_path / 'train')
     _run(tr, ema_batch(), range(1))
     path = tr.save_checkpoint(ck, 1, args, 0)

@@ -19,31 +19,20 @@ import pytest
 import torch
 
 import isinf_ref as R
+from fidinf_ref import _Net
+from gpu_harness import Margins, N, _guarded, _guards_ok, _place, margins_fixture
+from sampling_helpers import _images
 from scene_generation_amd import _hip
 from scene_generation_amd import inception as I
 from scene_generation_amd import isinf as II
 from scene_generation_amd import ops, sample
-from test_fidinf_cpu import _Net
-from test_gpu_fidinf import N, _guarded, _guards_ok, _images, _place
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 POISON = -777.0
 RPW = _hip.CONST['SG_ISINF_ROWS_PER_WG']
-MARGINS = {}
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('isinf_margins.json', MARGINS)
-
-
-def _margin(name, share, case):
-    if share > MARGINS.get(name, {'share_of_bound': -1.0})['share_of_bound']:
-        MARGINS[name] = {'share_of_bound': float(share), 'case': case}
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump('isinf_margins.json', 'share_of_bound', empty=False))
 
 
 def _share(err, bound):
@@ -73,17 +62,17 @@ def test_row_terms_within_the_derived_bound(C, extra, off):
     p = _rows(n, C, 100 + C)
     want_s, want_h = R.row_terms(p)
     bs, bh = R.row_bounds(want_s, want_h, C)
-    sbuf, rs = _guarded((n,))
-    hbuf, h = _guarded((n,))
+    sbuf, rs = _guarded((n,), fill=POISON)
+    hbuf, h = _guarded((n,), fill=POISON)
     view = _place(p, extra, off)
     got = ops.isinf_row_terms(view, rs=rs, h=h)
-    assert got[0] is rs and got[1] is h and _guards_ok(sbuf) and _guards_ok(hbuf)
+    assert got[0] is rs and got[1] is h and _guards_ok(sbuf, POISON) and _guards_ok(hbuf, POISON)
     s, hh = N(rs), N(h)
     assert np.isfinite(s).all() and np.isfinite(hh).all() and s[n // 2] == 0.0 and hh[n // 2] == 0.0      # the all-zero row: exact zeros
     share_s, share_h = _share(np.abs(s - want_s), bs), _share(np.abs(hh - want_h), bh)
     print('row terms C=%d extra=%d off=%d: worst share of the bound s %.4f h %.4f' % (C, extra, off, share_s, share_h))
-    _margin('row_sums', share_s, '%d_%d_%d' % (C, extra, off))
-    _margin('row_entropies', share_h, '%d_%d_%d' % (C, extra, off))
+    MARGINS.note('row_sums', share_s, '%d_%d_%d' % (C, extra, off))
+    MARGINS.note('row_entropies', share_h, '%d_%d_%d' % (C, extra, off))
     assert share_s <= 1.0 and share_h <= 1.0
     rs2, h2 = ops.isinf_row_terms(view)
     assert np.array_equal(N(rs2), s) and np.array_equal(N(h2), hh)                   # the same call, the same bits
@@ -128,8 +117,8 @@ def test_subset_scores_on_ragged_subsets(C, extra, off):
         bl, bs = R.log_score_bound(*parts[q], C), R.score_bound(want[q, 1], *parts[q], C)
         sl, ss = abs(out[q, 0] - want[q, 0]) / bl, abs(out[q, 1] - want[q, 1]) / bs
         print('subset of %d rows, C=%d: log score %.15g (%.4f of the bound %.3g), score %.4f of its bound' % (s, C, out[q, 0], sl, bl, ss))
-        _margin('subset_log_score', sl, '%d_%d_%d_%d' % (C, extra, off, s))
-        _margin('subset_score', ss, '%d_%d_%d_%d' % (C, extra, off, s))
+        MARGINS.note('subset_log_score', sl, '%d_%d_%d_%d' % (C, extra, off, s))
+        MARGINS.note('subset_score', ss, '%d_%d_%d_%d' % (C, extra, off, s))
         assert sl <= 1.0 and ss <= 1.0
     again = ops.isinf_subset_scores(view, rs, h, idx, sizes)
     assert np.array_equal(N(again), out)                                            # the same call, the same bits
@@ -276,7 +265,7 @@ def test_rows_accessor_and_the_full_set_against_the_existing_score(scored):
     bound = R.score_bound(existing, H, T, n, 1000)
     share = abs(res['is'] - existing) / bound
     print('IS of all 300 rows: the subset kernels %.15g, sg_inception_score %.15g, %.4f of the bound %.3g' % (res['is'], existing, share, bound))
-    _margin('full_set_against_inception_score', share, '300_1000')
+    MARGINS.note('full_set_against_inception_score', share, '300_1000')
     assert share <= 1.0
     assert res['is'] > 5.0                           # a peaked, varied set of rows: the test can tell a score from 1
 
@@ -312,9 +301,9 @@ def test_is_infinity_against_the_restated_pipeline(scored, points, repeats):
     s_log = abs(np.log(res['is_inf_log']) - np.log(want['is_inf_log'])) / (b_log + 8 * R.U * np.abs(coef).sum() * np.log(max(want['scores'])))
     print('is_infinity points=%d repeats=%d: subsets within %.4f of their bounds, IS_inf %.12g (%.4f of its bound), IS_inf_log %.12g (%.4f)'
           % (points, repeats, share, res['is_inf'], s_inf, res['is_inf_log'], s_log))
-    _margin('is_infinity_subsets', share, '%d_%d' % (points, repeats))
-    _margin('is_infinity_intercept', s_inf, '%d_%d' % (points, repeats))
-    _margin('is_infinity_log_intercept', s_log, '%d_%d' % (points, repeats))
+    MARGINS.note('is_infinity_subsets', share, '%d_%d' % (points, repeats))
+    MARGINS.note('is_infinity_intercept', s_inf, '%d_%d' % (points, repeats))
+    MARGINS.note('is_infinity_log_intercept', s_log, '%d_%d' % (points, repeats))
     assert share <= 1.0 and s_inf <= 1.0 and s_log <= 1.0
     assert II.is_infinity(scorer.rows(), num_points=points, repeats=repeats) == res  # the same bits
     if repeats == 3:
@@ -336,8 +325,9 @@ def test_one_host_read(scored, monkeypatch):
 
 def test_isinfinity_after_check_model():
     from scene_generation_amd.evaluate import check_model
-    from test_gpu_inception import _batch, _sampling_model
-    m = _sampling_model().eval()
+    from scene_generation_amd.model import Model
+    from sampling_helpers import sampling_batch as _batch, sampling_model
+    m = sampling_model(Model, DEV).eval()
     sc = I.InceptionScore(batch_size=4, resize=True, weights=None, device=DEV)
     cfg = type('A', (), {'num_val_samples': 6})()
     loader = [_batch(1), _batch(2), _batch(3)]
@@ -385,7 +375,7 @@ def test_command_lines_and_the_probs_round_trip(tmp_path, capsys):
 
 def test_sample_cli_prints_the_line_after_the_inception_line(tmp_path, capsys):
     import random
-    from test_gpu_ema import _batch as ema_batch, _run, _trainer
+    from trainer_helpers import _batch as ema_batch, _run, _trainer
     tr, ck, args = _trainer(tmp_path / 'train')
     _run(tr, ema_batch(), range(1))
     path = tr.save_checkpoint(ck, 1, args, 0)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import kmeans_ref as KR
+from gpu_harness import _dump
 from scene_generation_amd import bank, ops, sample
 from scene_generation_amd.model import Model
 from scene_generation_amd.synthetic import fill_deterministic, make_batch, make_sampling_vocab, make_vocab
@@ -562,6 +563,5 @@ def test_bank_build_launch_profile():
 
 def test_write_parity_record():
     """the largest observed errors of the tests above -> kmeans_parity.json in the suite's output directory (a record, not a check)"""
-    from test_gpu_parity import _dump
     assert PARITY
     _dump('kmeans_parity.json', PARITY)

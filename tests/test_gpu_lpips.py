@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 import lpips_ref as LR
 import sampling_helpers as SH
+from gpu_harness import Margins, margins_fixture
 from conftest import skip_random_init
 from scene_generation_amd import inception as I
 from scene_generation_amd import lpips as LP
@@ -32,17 +33,9 @@ FACTOR = 16.0
 # families whose worst observed ratio is under 2 (profiles/lpips_test_margins.md): their factor is halved to 8
 FACTORS = {k: 8.0 for k in ('wide_conv', 'layer', 'alex_taps', 'lpips_alex', 'lpips_vgg', 'diversity_e2e')}
 FLOOR = 2.0 ** -24
-MARGINS = {}
+MARGINS = Margins()
+_write_margins = margins_fixture(lambda: MARGINS.dump_yardstick('lpips_margins.json', FACTORS, FACTOR))
 SENTINEL = -12345.0
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('lpips_margins.json', {k: {'ratio_of_fp32_yardstick': v[0], 'bound': FACTORS.get(k, FACTOR), 'case': v[1]}
-                                     for k, v in MARGINS.items()})
 
 
 def offset_copy(t, off=1):
@@ -56,18 +49,7 @@ def offset_copy(t, off=1):
 
 def check(family, name, got, ref64, ref32):
     """|got - ref64| <= factor * max(|ref32 - ref64|, 2^-24 max|ref64|), in max norm over the tensor; factor = the family's"""
-    factor = FACTORS.get(family, FACTOR)
-    got, ref64, ref32 = [torch.as_tensor(t).detach().double().cpu() for t in (got, ref64, ref32)]
-    assert tuple(got.shape) == tuple(ref64.shape), (name, tuple(got.shape), tuple(ref64.shape))
-    assert bool(torch.isfinite(got).all()), name
-    scale = float(ref64.abs().max()) or 1.0
-    e = float((got - ref64).abs().max()) / scale
-    yard = max(float((ref32 - ref64).abs().max()) / scale, FLOOR)
-    ratio = e / yard
-    if ratio > MARGINS.get(family, (-1.0, ''))[0]:
-        MARGINS[family] = (ratio, name)
-    print('%-10s %-44s err %.3e  fp32 yardstick %.3e  ratio %.3f' % (family, name, e, yard, ratio))
-    assert ratio <= factor, '%s: error %.3e is %.1f x the fp32 yardstick %.3e (bound %g x)' % (name, e, ratio, yard, factor)
+    MARGINS.yardstick(family, name, got, ref64, ref32, FACTORS, FACTOR, FLOOR)
 
 
 # =====================================================================================================================================
@@ -424,8 +406,7 @@ def test_sample_pair_end_to_end():
         s64, s32 = want[torch.float64][k], want[torch.float32][k]
         e, yard = abs(got[name] - s64) / scale, max(abs(s32 - s64) / scale, FLOOR)
         ratio = e / yard
-        if ratio > MARGINS.get('diversity_e2e', (-1.0, ''))[0]:
-            MARGINS['diversity_e2e'] = (ratio, name)
+        MARGINS.note('diversity_e2e', ratio, name)
         print('diversity_e2e %-5s got %.12g  fp64 %.12g  fp32 %.12g  ratio %.3f' % (name, got[name], s64, s32, ratio))
         assert ratio <= FACTORS.get('diversity_e2e', FACTOR), (name, got[name], s64, s32)
     with pytest.raises(ValueError, match='nothing is random'):

@@ -1,6 +1,6 @@
 """Every InstanceNorm / BatchNorm / channel-sum launch plan and every scalar-loss, multi-loss and cross-entropy path against a
 float64 reference of the same operation (the shape tables are tests/norm_cases.py; tests/test_norm_dispatch_cpu.py shows they
-reach every plan the dispatch can choose).  Tolerances follow close() of test_gpu_parity.py and are no looser than its
+reach every plan the dispatch can choose).  Tolerances follow close() of gpu_harness.py and are no looser than its
 test_instance_norm / test_batch_norm: y 2e-5, gradients 1e-4."""
 import ctypes
 
@@ -11,19 +11,12 @@ import torch.nn.functional as F
 
 import norm_cases as NC
 from oracle import sg_oracle as O
-from test_gpu_parity import close
+from gpu_harness import close
+from gpu_harness import hip  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 SLOPE = 0.2
-
-
-@pytest.fixture(scope='module')
-def hip():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import ops, _hip
-    _hip.lib()
-    return ops
 
 
 def _gen(seed):

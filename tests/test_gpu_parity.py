@@ -15,52 +15,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from oracle import sg_oracle as O
-from scene_generation_amd.synthetic import fill_deterministic, make_batch, make_vocab, batch_to, _hash_uniform
+from scene_generation_amd.synthetic import fill_deterministic, make_batch, make_vocab, batch_to
 from scene_generation_amd.args import parser
+from gpu_harness import _CLOSE_LOG, _dump, close
+from gpu_harness import hip  # noqa: F401  (fixture)
+from tools_det import det
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-
-
-def det(shape, salt, scale=1.0, shift=0.0):
-    n = int(np.prod(shape))
-    return _hash_uniform(n, salt).view(*shape) * 2 * scale + shift
-
-
-_CLOSE_LOG = []
-
-
-def close(a, b, tol=1e-5, name=''):
-    """max|a-b| <= tol * max(1, max|b|)   AND   (an absolute bound scaled by the largest entry lets a
-    small-magnitude channel be 100 % wrong) relative-L2 bounds per tensor and per channel:
-        ||a - b||_2 <= 20 tol ||b||_2 + 0.25 tol max(1, max|b|) sqrt(n)
-    i.e. the rms error of the tensor / of every channel (dim 1 of an (N,C,H,W) map, last dim of a matrix) must be 20 tol
-    of that channel's own rms, plus an absolute rms floor four times tighter than the max-error bound (a channel that is the
-    result of cancellation cannot be accurate relative to itself).  Calibration: the tightest margins of a full GPU run are
-    written to gpurun_out/close_margins.json (r4: worst 0.39 of the bound, a 4-element bias gradient; everything else < 0.15)."""
-    a = a.detach().double().cpu()
-    b = (torch.from_numpy(np.asarray(b)) if not isinstance(b, torch.Tensor) else b.detach()).double().cpu()
-    assert a.shape == b.shape, (name, tuple(a.shape), tuple(b.shape))
-    if a.numel() == 0:
-        return
-    assert torch.isfinite(a).all(), '%s: non-finite values' % name
-    err = (a - b).abs().max().item()
-    scale = max(1.0, b.abs().max().item())
-    assert err <= tol * scale, '%s: max err %.3e (scale %.3e, tol %.1e)' % (name, err, scale, tol)
-    d = a - b
-    groups = [('tensor', d.reshape(1, -1), b.reshape(1, -1))]
-    if a.dim() == 4 and a.size(1) > 1:
-        groups.append(('channel', d.transpose(0, 1).reshape(a.size(1), -1), b.transpose(0, 1).reshape(a.size(1), -1)))
-    elif a.dim() == 2 and a.size(1) > 1 and a.size(0) > 1:
-        groups.append(('column', d.t(), b.t()))
-    for kind, dd, bb in groups:
-        en, bn, n = dd.norm(dim=1), bb.norm(dim=1), dd.size(1)
-        lim = 20 * tol * bn + 0.25 * tol * scale * (n ** 0.5)
-        ratio = float((en / lim).max())
-        _CLOSE_LOG.append((ratio, kind, name, tol))
-        i = int((en / lim).argmax())
-        assert ratio <= 1.0, '%s: %s %d relative-L2 error %.3e of |b| %.3e exceeds the bound %.3e (tol %.1e)' % (
-            name, kind, i, float(en[i]), float(bn[i]), float(lim[i]), tol)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -69,14 +31,6 @@ def _close_margins():
     yield
     worst = sorted(_CLOSE_LOG, key=lambda t: -t[0])[:40]
     _dump('close_margins.json', [{'ratio_of_bound': r, 'kind': k, 'name': n, 'tol': t} for r, k, n, t in worst])
-
-
-@pytest.fixture(scope='module')
-def hip():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import ops, _hip
-    _hip.lib()      # fails loudly if the extension is missing
-    return ops
 
 
 # ------------------------------------------------------------------------------------------
@@ -917,7 +871,7 @@ def test_masks_to_layout_test_mode_vs_oracle_config2_shape(hip):
 
 def test_model_inference_forward_golden(hip, golden):
     """Model.forward(test_mode=True[, features]) in eval mode == the reference (model.py:111-117,158-163)."""
-    from test_oracle_golden import inference_model, inference_cases
+    from sampling_helpers import inference_model, inference_cases
     from scene_generation_amd.model import Model
     from scene_generation_amd.synthetic import batch_to
     g = golden('model_test_mode')
@@ -1906,18 +1860,6 @@ def _step_metrics(tr, ref, out, out_ref, snaps):
         big = bn > 1e-3 * fbn
         m['worst_tensor_rel_' + n] = float((dn[big] / bn[big]).max()) if bool(big.any()) else 0.0
     return m
-
-
-def _dump(name, obj):
-    import json
-    import os
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
-    try:
-        os.makedirs(d, exist_ok=True)
-        with open(os.path.join(d, name), 'w') as f:
-            json.dump(obj, f, indent=1, sort_keys=True)
-    except OSError:
-        pass
 
 
 def _assert_step_metrics(m, tag, out_tol, loss_tol, cos_min=0.9995, worst_tol=3e-2):

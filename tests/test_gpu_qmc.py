@@ -20,6 +20,7 @@ import torch
 
 import qmc_ref as R
 import sampling_helpers as SH
+from gpu_harness import _dump, _guarded, margins_fixture
 from scene_generation_amd import _hip, attributes, ops, qmc, sample, scenegraph
 from scene_generation_amd.model import Model
 from scene_generation_amd.synthetic import batch_to, make_batch, make_sampling_vocab
@@ -29,16 +30,9 @@ DEV = 'cuda:0'
 POISON = -777
 G = 16                                      # guard words on each side
 MARGINS = {}
+_write_margins = margins_fixture(lambda: MARGINS and _dump('qmc_margins.json', MARGINS))
 _TABLES = {}
 E = {k: _hip.CONST['SG_QMC_ERR_' + k] for k in ('NULL', 'DIMS', 'LD', 'RANGE', 'COUNT')}
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _write_margins():
-    yield
-    if MARGINS:
-        from test_gpu_parity import _dump
-        _dump('qmc_margins.json', MARGINS)
 
 
 def T(a, dtype=None):
@@ -53,13 +47,6 @@ def _tables(D, scramble, seed=5):
         dirs, shift = R.tables(D, scramble, seed)
         _TABLES[key] = (dirs, shift, T(dirs, torch.int32), T(shift, torch.int32))
     return _TABLES[key]
-
-
-def _guarded(shape, dtype, fill=POISON):
-    """(whole buffer, the view of ``shape`` in its middle): G guard words on each side"""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * G,), fill, dtype=dtype, device=DEV)
-    return buf, buf[G:G + n].view(*shape)
 
 
 def _raw(name, **a):
@@ -79,7 +66,7 @@ def test_sobol_points_equal_the_restatement(D, scramble):
         for first in (0, 1, 2 ** 20 - 3, 2 ** 30 - n):
             want = R.points(dirs, shift, first, n)
             for ld in (D, D + 3):
-                buf, out = _guarded((n, ld), torch.int32)
+                buf, out = _guarded((n, ld), torch.int32, POISON, G)
                 assert _raw('sg_sobol_points', dirs=ddirs.data_ptr(), shift=dshift.data_ptr(), out=out.data_ptr(), first=first, n=n, D=D,
                             ld=ld) == 0
                 expect = np.full((n, ld), POISON, np.int64)
@@ -95,7 +82,7 @@ def test_sobol_points_equal_the_restatement(D, scramble):
 def test_sobol_points_negative_codes_write_nothing():
     D = 3
     _, _, ddirs, dshift = _tables(D, True)
-    buf, out = _guarded((4, D), torch.int32)
+    buf, out = _guarded((4, D), torch.int32, POISON, G)
     good = dict(dirs=ddirs.data_ptr(), shift=dshift.data_ptr(), out=out.data_ptr(), first=0, n=4, D=D, ld=D)
     seen = set()
     for kw, code in ((dict(dirs=None), 'NULL'), (dict(shift=None), 'NULL'), (dict(out=None), 'NULL'), (dict(D=0), 'DIMS'),
@@ -219,9 +206,9 @@ def test_unpack_object_limit_and_bad_arguments():
     assert p2[2].item() == -1 and p2[0].item() == wp[0]
     # every negative code, the outputs still poisoned
     dp = T(pts, torch.int32)
-    nb, nz = _guarded((2, noise_dim), torch.float32)
-    pb, pk = _guarded((6,), torch.int32)
-    ub, uu = _guarded((6, 2), torch.float32)
+    nb, nz = _guarded((2, noise_dim), torch.float32, POISON, G)
+    pb, pk = _guarded((6,), torch.int32, POISON, G)
+    ub, uu = _guarded((6, 2), torch.float32, POISON, G)
     good = dict(points=dp.data_ptr(), ld=q.dimension, obj_to_img=o2i.data_ptr(), seg_off=seg.data_ptr(), noise=nz.data_ptr(),
                 pick=pk.data_ptr(), u=uu.data_ptr(), N=2, O=6, noise_dim=noise_dim, max_objects=J)
     for kw, code in ((dict(points=None), 'NULL'), (dict(obj_to_img=None), 'NULL'), (dict(seg_off=None), 'NULL'), (dict(noise=None), 'NULL'),
@@ -268,7 +255,7 @@ def test_bank_draw_equals_the_restatement(rep, off):
     dobjs, dpick = T(np.array(objs, np.int64)), T(np.array(pick, np.int32))
     rbuf = torch.full((O * rep + 2 * G + off,), float(POISON), dtype=torch.float32, device=DEV)
     rows = rbuf[G + off:G + off + O * rep].view(O, rep)
-    ibuf, idx = _guarded((O,), torch.int32)
+    ibuf, idx = _guarded((O,), torch.int32, POISON, G)
     assert _raw('sg_bank_draw', bank=bank.data_ptr(), class_off=b.class_off.data_ptr(), objs=dobjs.data_ptr(), pick=dpick.data_ptr(),
                 row_idx=idx.data_ptr(), rows=rows.data_ptr(), O=O, C=5, rep=rep, R=104) == 0
     assert np.array_equal(idx.cpu().numpy(), want_idx) and torch.equal(rows.cpu(), torch.from_numpy(want_rows))
@@ -293,8 +280,8 @@ def test_bank_draw_equals_the_restatement(rep, off):
 def test_bank_draw_negative_codes_and_bad_arguments():
     b = qmc.DeviceBank.from_dict({0: np.ones((2, 4)), 1: np.ones((3, 4))}, 2, DEV)
     objs, pick = T(np.array([0, 1, 1], np.int64)), T(np.array([1, 2, 3], np.int32))
-    rbuf, rows = _guarded((3, 4), torch.float32)
-    ibuf, idx = _guarded((3,), torch.int32)
+    rbuf, rows = _guarded((3, 4), torch.float32, POISON, G)
+    ibuf, idx = _guarded((3,), torch.int32, POISON, G)
     good = dict(bank=b.bank.data_ptr(), class_off=b.class_off.data_ptr(), objs=objs.data_ptr(), pick=pick.data_ptr(), row_idx=idx.data_ptr(),
                 rows=rows.data_ptr(), O=3, C=2, rep=4, R=5)
     for kw, code in ((dict(bank=None), 'NULL'), (dict(class_off=None), 'NULL'), (dict(objs=None), 'NULL'), (dict(pick=None), 'NULL'),

@@ -14,7 +14,8 @@ import sampling_helpers as SH
 from scene_generation_amd import ops, sample
 from scene_generation_amd.model import Model
 from scene_generation_amd.synthetic import batch_to, fill_deterministic, make_batch, make_vocab
-from test_gpu_parity import close, det
+from gpu_harness import _dump, close
+from tools_det import det
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -179,7 +180,7 @@ def test_forward_json_golden(golden):
 
 
 def test_factored_test_mode_forward_golden(golden):
-    from test_oracle_golden import inference_model, inference_cases
+    from sampling_helpers import inference_model, inference_cases
     g = golden('model_test_mode')
     m, batch = inference_model(Model)
     m = m.to(DEV)
@@ -239,7 +240,6 @@ def test_factored_vs_dense_full_size():
 
 def test_write_parity_record():
     """the observed deviations of the tests above -> sample_parity.json in the suite's output directory (a record, not a check)"""
-    from test_gpu_parity import _dump
     assert PARITY
     _dump('sample_parity.json', PARITY)
 
@@ -326,7 +326,7 @@ def test_sampler_layout_kernel_launched(factored):
 
 
 def test_ema_weights_from_checkpoint_and_files(tmp_path):
-    from test_gpu_ema import _batch, _run, _trainer
+    from trainer_helpers import _batch, _run, _trainer
     tr, ck, args = _trainer(tmp_path / 'train', ema_decay=0.5)
     _run(tr, _batch(), range(3))
     path = tr.save_checkpoint(ck, 3, args, 0)

@@ -19,7 +19,8 @@ import torch
 import torch.nn.functional as F
 
 import norm_cases as NC
-from test_gpu_parity import close
+from gpu_harness import close
+from gpu_harness import hip  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -28,14 +29,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARITY_SHAPE = ('up', 2, 512, 256, 8)                # the smallest case of test_parity_class_split_vs_plain_schedule
 GENERAL_SHAPE = (24, 192, 16, 16, 192, 3, 1, 1)      # of test_tail_split_general_form_vs_plain_schedule: the smallest that splits
 F43_SHAPE = (32, 1024, 8)                            # N, C, H: 36 * t % 256 == 128 needs t = 32 tiles, i.e. 32 planes of 8 x 8
-
-
-@pytest.fixture(scope='module')
-def hip():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import ops, _hip
-    _hip.lib()
-    return ops
 
 
 def rnd(shape, seed, scale=1.0):

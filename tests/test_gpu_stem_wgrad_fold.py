@@ -19,17 +19,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_harness import L  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 GUARD = 12345.0
 U = 2.0 ** -24
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()
 
 
 def _stream():

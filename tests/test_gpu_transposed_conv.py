@@ -8,82 +8,24 @@ Everything goes through the C ABI (ctypes): channel windows, null bias, null gb 
 Each case asserts the plan the library reports for it (sg_conv2d_tgather_plan), runs every entry twice (bit-equal) and holds the
 result to |got - ref64| <= gamma(n + c) sum|a||b| element by element; one-hot probes -- the index logic -- and the weight fold are
 held to bit equality.  The worst error / bound ratio of every family goes to transposed_conv_margins.json."""
-import contextlib
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-import test_gpu_dense_pointwise as G
-import test_gpu_parity as P
 import transposed_conv_cases as T
-from test_gpu_dense_pointwise import place, outbuf, take, within, same, call, ptr, stream
+from gpu_harness import GUARD, Margins, call, dref, margins_fixture, opt_tag, options, outbuf, place, ptr, same, scratch, stream, take, twice
+from gpu_harness import L, _release_operands  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-_MARGINS = {}
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()      # fails loudly if the extension is missing
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _margins():
-    """after the module: the worst observed error / bound ratio per family -> transposed_conv_margins.json"""
-    yield
-    P._dump('transposed_conv_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in _MARGINS.items()})
-
-
-@pytest.fixture(autouse=True)
-def _release_operands():
-    yield
-    del G._KEEP[:]
-
-
-def held(family, got, ref, bound, name):
-    """within(), with the worst ratio noted for this module's margins file"""
-    err = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
-    b = np.broadcast_to(np.asarray(bound, dtype=np.float64), err.shape)
-    ratio = np.where(b > 0, err / np.maximum(b, 1e-300), np.where(err > 0, np.inf, 0.0))
-    worst = float(ratio.max()) if ratio.size else 0.0
-    if family not in _MARGINS or worst > _MARGINS[family][0]:
-        _MARGINS[family] = (worst, name)
-    within(family, got, ref, bound, name)
-
-
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(T.option(k, v))
-        yield
-
-
-def opt_tag(o):
-    return ' '.join('%s=%d' % kv for kv in sorted(o.items()))
-
-
-def dref(d):
-    return ctypes.byref(d)
-
-
-def workspace(nbytes, off=0):
-    """nbytes of scratch starting ``off`` floats behind a 16-byte boundary"""
-    base = torch.empty(nbytes // 4 + 8 + off, dtype=torch.float32, device=DEV)
-    assert base.data_ptr() % 16 == 0
-    v = base[off:]
-    G._KEEP.append(v)
-    return v
+MARGINS = Margins()
+within = MARGINS.within
+_margins = margins_fixture(lambda: MARGINS.dump('transposed_conv_margins.json'))      # the worst error / bound ratio per family
 
 
 def conv_ws(L, d, kind, off=0):
     n = int(L.sg_conv2d_ws_bytes(dref(d), kind))
-    return workspace(n, off), n
+    return scratch(n, off), n
 
 
 # ---- the entry points, one C-ABI call each ---------------------------------------------------------------------------
@@ -141,7 +83,7 @@ def conv_dgrad(L, d, gd, wd, c0, c1, off=0):
 def dgrad_folded(L, d, gd, wd, c0, c1, off=0):
     n = int(L.sg_conv2d_dgrad_folded_ws_bytes(dref(d)))
     assert n > 0 and L.sg_conv2d_dgrad_folded_supported(dref(d)) == 1
-    ws = workspace(n, off)
+    ws = scratch(n, off)
     o = outbuf(d.N * (c1 - c0) * d.H * d.W)
     call(L, 'sg_conv2d_dgrad_folded', dref(d), ptr(gd), ptr(wd), ptr(o), c0, c1, ptr(ws), n, stream())
     return take(o, (d.N, c1 - c0, d.H, d.W)), ws
@@ -153,14 +95,6 @@ def assert_plan(L, case, d, entry, c0, c1, ws, name):
     got = T.tgather_plan(L, d, entry, c0, c1, ws.data_ptr() % 16)
     for k, v in want.items():
         assert got[k] == v, '%s: plan field %s is %s, the table claims %s (%s)' % (name, k, got[k], v, got)
-
-
-def twice(fn, name):
-    a, b = fn(), fn()
-    for x, y in zip(a, b):
-        if isinstance(x, np.ndarray):
-            assert np.array_equal(x, y), '%s: a second run differs' % name
-    return a
 
 
 # =============================================================================================
@@ -178,13 +112,13 @@ def test_convT_case(L, case):
             name = '%s [%s]' % (case['name'], opt_tag(o))
             y, ws = twice(lambda: convT_fwd(L, d, xd, wd, bd, case['ws_off']), name + ' fwd')
             assert_plan(L, case, d, entry, c0, c1, ws, name)
-            held('convT_fwd_%s' % ('parity' if d.stride == 2 and d.KS >= 3 else 'plain'), y, ref['y'], ref['y_bound'], name + ' y')
+            within('convT_fwd_%s' % ('parity' if d.stride == 2 and d.KS >= 3 else 'plain'), y, ref['y'], ref['y_bound'], name + ' y')
             gx, = twice(lambda: (convT_dgrad(L, d, gd, wd),), name + ' dgrad')
-            held('convT_dgrad', gx, ref['gx'], ref['gx_bound'], name + ' gx')
+            within('convT_dgrad', gx, ref['gx'], ref['gx_bound'], name + ' gx')
             gw, gb = twice(lambda: convT_wgrad(L, d, gd, xd, case['bias']), name + ' wgrad')
-            held('convT_wgrad', gw, ref['gw'], ref['gw_bound'], name + ' gw')
+            within('convT_wgrad', gw, ref['gw'], ref['gw_bound'], name + ' gw')
             if gb is not None:
-                held('convT_bias_grad', gb, ref['gb'], ref['gb_bound'], name + ' gb')
+                within('convT_bias_grad', gb, ref['gb'], ref['gb_bound'], name + ' gb')
 
 
 @pytest.mark.parametrize('case', T.DGRAD_CASES, ids=lambda c: c['name'])
@@ -198,9 +132,9 @@ def test_conv_dgrad_case(L, case):
             name = '%s [%s]' % (case['name'], opt_tag(o))
             g, gx, ws = twice(lambda: conv_dgrad(L, d, gd, wd, c0, c1, case['ws_off']), name)
             assert_plan(L, case, d, entry, c0, c1, ws, name)
-            held('conv_dgrad_%s' % ('parity' if d.stride == 2 and d.KS >= 3 else 'plain'), g, ref['g'], ref['g_bound'], name + ' g')
+            within('conv_dgrad_%s' % ('parity' if d.stride == 2 and d.KS >= 3 else 'plain'), g, ref['g'], ref['g_bound'], name + ' g')
             if gx is not None:
-                held('conv_dgrad_pad_upsample_bwd', gx, ref['gx'], ref['gx_bound'], name + ' gx')
+                within('conv_dgrad_pad_upsample_bwd', gx, ref['gx'], ref['gx_bound'], name + ' gx')
 
 
 @pytest.mark.parametrize('case', T.FOLDED_CASES, ids=lambda c: c['name'])
@@ -214,7 +148,7 @@ def test_dgrad_folded_case(L, case):
             name = '%s [%s]' % (case['name'], opt_tag(o))
             gx, ws = twice(lambda: dgrad_folded(L, d, gd, wd, c0, c1, case['ws_off']), name)
             assert_plan(L, case, d, entry, c0, c1, ws, name)
-            held('dgrad_folded', gx, ref, bound, name)
+            within('dgrad_folded', gx, ref, bound, name)
 
 
 @pytest.mark.parametrize('cin,cout', T.SUBPIXEL_FOLD_CHANNELS)
@@ -247,17 +181,17 @@ def test_subpixel_case(L, case):
             name = '%s [%s]' % (case['name'], opt_tag(o))
             y, ws = twice(lambda: convT_fwd(L, d, xd, wtd, bd), name + ' fwd')
             assert_plan(L, case, d, entry, c0, c1, ws, name)
-            held('subpixel_fwd', y, ref['y'], ref['y_bound'], name + ' y')
-            held('subpixel_dgrad', convT_dgrad(L, d, gd, wtd), ref['gx'], ref['gx_bound'], name + ' gx')
+            within('subpixel_fwd', y, ref['y'], ref['y_bound'], name + ' y')
+            within('subpixel_dgrad', convT_dgrad(L, d, gd, wtd), ref['gx'], ref['gx_bound'], name + ' gx')
             ws2, n = conv_ws(L, d, 2)
             gwt, ob = outbuf(d.C1 * d.Cout * 16), (outbuf(d.Cout) if case['bias'] else None)
             call(L, 'sg_convT2d_wgrad', dref(d), ptr(gd), ptr(xd), ptr(gwt), ptr(ob), ptr(ws2), n, stream())
             take(gwt, (d.C1, d.Cout, 4, 4))
             gw = outbuf(d.Cout * d.C1 * 9)
             call(L, 'sg_upconv3_unfold_wgrad', ptr(gwt[:-1]), ptr(gw), d.Cout, d.C1, stream())
-            held('subpixel_wgrad', take(gw, (d.Cout, d.C1, 3, 3)), ref['gw'], ref['gw_bound'], name + ' gw')
+            within('subpixel_wgrad', take(gw, (d.Cout, d.C1, 3, 3)), ref['gw'], ref['gw_bound'], name + ' gw')
             if ob is not None:
-                held('convT_bias_grad', take(ob, (d.Cout,)), ref['gb'], ref['gb_bound'], name + ' gb')
+                within('convT_bias_grad', take(ob, (d.Cout,)), ref['gb'], ref['gb_bound'], name + ' gb')
 
 
 # =============================================================================================
@@ -332,7 +266,7 @@ def test_dgrad_folded_onehot_probe(L, case):
         ref, bound = T.folded_refs(case, dict(gy=g1, w=inp['w']))
         single = cnt <= 1
         same(np.where(single, got, 0), np.where(single, ref, 0).astype(np.float32), name + ' (single taps)')
-        held('dgrad_folded_onehot_sums', np.where(single, 0, got), np.where(single, 0, ref), np.where(single, 0, bound), name + ' (reflected sums)')
+        within('dgrad_folded_onehot_sums', np.where(single, 0, got), np.where(single, 0, ref), np.where(single, 0, bound), name + ' (reflected sums)')
 
 
 # =============================================================================================
@@ -365,17 +299,17 @@ def test_conv_transpose2d_autograd_wiring(L, name):
                 m.weight.copy_(w)
             y = m(x.requires_grad_())
             r0, b0 = T._with_bound(lambda x_, w_: T.convT_fwd(x_, w_, None, s, p, op), T.C_GATHER, (inp['x'], inp['w']))
-            held('convT_autograd', y.detach().cpu().numpy(), r0, b0, name + ' layer without bias')
+            within('convT_autograd', y.detach().cpu().numpy(), r0, b0, name + ' layer without bias')
             y.backward(gy)
-            held('convT_autograd', x.grad.cpu().numpy(), ref['gx'], ref['gx_bound'], name + ' layer gx')
-            held('convT_autograd', m.weight.grad.cpu().numpy(), ref['gw'], ref['gw_bound'], name + ' layer gw')
+            within('convT_autograd', x.grad.cpu().numpy(), ref['gx'], ref['gx_bound'], name + ' layer gx')
+            within('convT_autograd', m.weight.grad.cpu().numpy(), ref['gw'], ref['gw_bound'], name + ' layer gw')
             continue
         y = ops.conv_transpose2d(x, w, b, stride=s, pad=p, out_pad=op)
-        held('convT_autograd', y.detach().cpu().numpy(), ref['y'], ref['y_bound'], '%s y (%s)' % (name, want))
+        within('convT_autograd', y.detach().cpu().numpy(), ref['y'], ref['y_bound'], '%s y (%s)' % (name, want))
         y.backward(gy)
         for k, t, key in (('x', x, 'gx'), ('w', w, 'gw'), ('b', b, 'gb')):
             if k in want:
-                held('convT_autograd', t.grad.cpu().numpy(), ref[key], ref[key + '_bound'], '%s %s (%s)' % (name, key, want))
+                within('convT_autograd', t.grad.cpu().numpy(), ref[key], ref[key + '_bound'], '%s %s (%s)' % (name, key, want))
             else:
                 assert t.grad is None, (name, want, k)
 
@@ -387,7 +321,7 @@ def test_convT_entries_reject_what_the_forward_rejects(L):
     x, w, gy = place(np.zeros((N, C, H, W))), place(np.zeros((C, Co, 3, 3))), place(np.zeros((N, Co, H, W)))
     for kw in (dict(C2=2), dict(ups=2), dict(reflect=True)):
         d = T.make_desc(N, C, H, W, Co, 3, 1, 1, kw.get('reflect', False), kw.get('ups', 1), H, W, 0, C2=kw.get('C2', 0))
-        ws = workspace(1 << 20)
+        ws = scratch(1 << 20)
         o = outbuf(4096)
         for fn, args in (('sg_convT2d_fwd', (ptr(x), ptr(w), None, ptr(o), ptr(ws), 1 << 20, stream())),
                          ('sg_convT2d_dgrad', (ptr(gy), ptr(w), ptr(o), ptr(ws), 1 << 20, stream())),
@@ -396,4 +330,4 @@ def test_convT_entries_reject_what_the_forward_rejects(L):
             assert rc != 0, '%s accepted %s' % (fn, kw)
             assert L.sg_last_error_string().decode() == '%s: unsupported desc' % fn
         take(o, (4096,))
-        assert (o[:-1] == G.GUARD).all(), 'a rejected call wrote its output'
+        assert (o[:-1] == GUARD).all(), 'a rejected call wrote its output'

@@ -8,50 +8,20 @@ words behind them; the plan the library reports for THIS call (same options, sam
 claims and the one wgrad_cases.py restates; every element within its own bound of float64 (wgrad_cases: gamma(n + c), c from the
 reported plan); guards intact; a second call bit-identical.  The worst error / bound ratio per plan goes to wgrad_margins.json
 (profiles/wgrad_test_margins.md holds a run's)."""
-import contextlib
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 import wgrad_cases as WG
-import test_gpu_parity as P
-import test_gpu_dense_pointwise as G
-from test_gpu_dense_pointwise import place, outbuf, take, within, call, ptr, stream, GUARD
+from gpu_harness import Margins, Workspace, _KEEP, call, margins_fixture, options, outbuf, place, ptr, same_bits, stream, take
+from gpu_harness import L, _release_operands  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-_MARGINS = {}
-GUARD_WORDS = 256       # more than a tile's rows: a store one tile past the last row of the workspace still lands on a guard word
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()      # fails loudly if the extension is missing
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _margins():
-    """after the module: the worst observed error / bound ratio per plan -> wgrad_margins.json"""
-    yield
-    P._dump('wgrad_margins.json', {k: {'ratio_of_bound': v[0], 'case': v[1]} for k, v in sorted(_MARGINS.items())})
-
-
-@pytest.fixture(autouse=True)
-def _release_operands():
-    yield
-    del G._KEEP[:]
-
-
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(WG.option(k, v))
-        yield
+MARGINS = Margins()
+within = MARGINS.within
+_margins = margins_fixture(lambda: MARGINS.dump('wgrad_margins.json'))      # the worst error / bound ratio per plan
 
 
 FORMS = {WG.WG_TAP: 'tap', WG.WG_GATHER: 'gather', WG.WG_PADDED: 'padded'}
@@ -62,21 +32,6 @@ def family(case, plan):
     return '%s %s %dx%d %s%s%s reduce=%s xcd=%d' % (case['kind'], FORMS[plan['form']], plan['bm'], plan['bn'], 'vecA' if plan['a_vec'] else 'scalarA',
                                                     ' two' if plan['two'] else '', ' nomask' if plan['nomask'] else '', REDUCES[plan['reduce']],
                                                     plan['xcd'])
-
-
-def held(fam, got, ref, bound, name):
-    """within(), with the worst ratio noted for this module's margins file"""
-    err = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
-    b = np.broadcast_to(np.asarray(bound, dtype=np.float64), err.shape)
-    ratio = np.where(b > 0, err / np.maximum(b, 1e-300), np.where(err > 0, np.inf, 0.0))
-    worst = float(np.nan_to_num(ratio, nan=np.inf).max()) if ratio.size else 0.0
-    if fam not in _MARGINS or worst > _MARGINS[fam][0]:
-        _MARGINS[fam] = (worst, name)
-    within(fam, got, ref, bound, name)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
 
 
 def run(L, case, a_off=None):
@@ -91,11 +46,8 @@ def run(L, case, a_off=None):
     plan = q(ws_bytes)
     assert plan is not None, L.sg_last_error_string().decode()
     assert 0 <= plan['ws_needed'] <= ws_bytes, (plan, ws_bytes)
-    words = (ws_bytes + 3) // 4
-    ws = torch.full((words + GUARD_WORDS,), GUARD, dtype=torch.float32, device=DEV)
-    assert ws.data_ptr() % 16 == 0
-    ws[:words] = float('nan')
-    wsp = ptr(ws) if ws_bytes else None
+    ws = Workspace(ws_bytes)
+    wsp = ptr(ws.buf) if ws_bytes else None
     M, C, KS, N = case['Cout'], case['C1'] + case['C2'], case['KS'], case['N']
     ob = outbuf(M) if case['gb'] else None
     if case['kind'] == 'dense':
@@ -103,7 +55,7 @@ def run(L, case, a_off=None):
         call(L, 'sg_conv2d_wgrad', ctypes.byref(d), ptr(gyd), ptr(x1d), ptr(x2d), ptr(o), ptr(ob), wsp, ws_bytes, stream())
     else:
         ld, cd = torch.from_numpy(inp['lists']).to(DEV), torch.from_numpy(inp['cnt']).to(DEV)
-        G._KEEP.extend([ld, cd])
+        _KEEP.extend([ld, cd])
         if case['kind'] == 'sparse':
             o, shape = outbuf(M * C * KS * KS), (M, C, KS, KS)
             call(L, 'sg_conv2d_wgrad_sparse', ctypes.byref(d), ptr(gyd), ptr(x1d), ptr(x2d), ptr(ld), ptr(cd), case['L'], ptr(o), ptr(ob),
@@ -113,16 +65,16 @@ def run(L, case, a_off=None):
             call(L, 'sg_conv2d_wgrad_perimage', ctypes.byref(d), ptr(gyd), ptr(x1d), ptr(x2d), ptr(ld), ptr(cd), case['L'], ptr(o), wsp,
                  ws_bytes, stream())
     torch.cuda.synchronize()
-    assert bool((ws[words:].cpu() == GUARD).all()), 'the launch wrote behind the workspace bytes it was given'
+    ws.intact(case['name'])
     return dict(plan=plan, ws_bytes=ws_bytes, gw=take(o, shape), gb=take(ob, (M,)) if case['gb'] else None)
 
 
 def check(case, r, name):
     ref = WG.case_refs(case)
     fam = family(case, r['plan'])
-    held(fam, r['gw'], ref['gw'], WG.gw_bound(case, r['plan']), name + ' gw')
+    within(fam, r['gw'], ref['gw'], WG.gw_bound(case, r['plan']), name + ' gw')
     if r['gb'] is not None:
-        held('bias gradient: %s' % ('row sums %dx%d %s' % (r['plan']['bm'], r['plan']['bn'], 'vecA' if r['plan']['a_vec'] else 'scalarA')
+        within('bias gradient: %s' % ('row sums %dx%d %s' % (r['plan']['bm'], r['plan']['bn'], 'vecA' if r['plan']['a_vec'] else 'scalarA')
                                     if r['plan']['rowsum_fused'] else 'sg_channel_sum'), r['gb'], ref['gb'], ref['gb_bound'], name + ' gb')
     if case['kind'] == 'sparse':          # a channel nobody lists: exactly zero
         assert not r['gw'][:, case['C1'] + case['C2'] - 1].any()
@@ -130,10 +82,6 @@ def check(case, r, name):
         cnt = WG.case_inputs(case)['cnt']
         for b in range(case['N']):
             assert not r['gw'][b, :, int(cnt[b]):].any(), 'columns beyond the image\'s channel list must be zero'
-
-
-def same_bits(a, b, name):
-    assert np.array_equal(bits(a), bits(b)), '%s: %d of %d elements differ' % (name, int((bits(a) != bits(b)).sum()), a.size)
 
 
 @pytest.mark.parametrize('case', WG.CASES, ids=lambda c: c['name'])

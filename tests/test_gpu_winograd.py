@@ -8,32 +8,21 @@ placed and the saved operands as passed), runs every entry twice (bit-equal), wi
 accepts, and holds each result to the hard bound per element and to the rms line (rms error <= 2 x the float32 restatement's).
 One-hot probes carry the index logic: the hard bound with n = 1, which is exact equality wherever the form's tiles do not reach.
 The worst ratios of every family go to winograd_margins.json."""
-import contextlib
-import ctypes
 import time
 
 import numpy as np
 import pytest
 import torch
 
-import test_gpu_dense_pointwise as G
-import test_gpu_parity as P
 import winograd_cases as WC
-from test_gpu_dense_pointwise import place, outbuf, take, within, same, call, ptr, stream  # noqa: F401
-from test_gpu_parity import close
+from gpu_harness import GUARD, Workspace, _dump, call, close, dref, opt_tag, options, outbuf, place, ptr, scratch, stream, take, twice
+from gpu_harness import L, _release_operands  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 EPS = 1e-5
 _MARGINS = {}
 _T0 = [0.0]
-
-
-@pytest.fixture(scope='module')
-def L():
-    assert torch.cuda.is_available(), 'gpu tests need a device'
-    from scene_generation_amd import _hip
-    return _hip.lib()      # fails loudly if the extension is missing
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -43,13 +32,7 @@ def _margins():
     yield
     out = {k: {'ratio_of_hard_bound': v[0], 'hard_case': v[1], 'rms_over_baseline': v[2], 'rms_case': v[3]} for k, v in _MARGINS.items()}
     out['_module_seconds'] = time.time() - _T0[0]
-    P._dump('winograd_margins.json', out)
-
-
-@pytest.fixture(autouse=True)
-def _release_operands():
-    yield
-    del G._KEEP[:]
+    _dump('winograd_margins.json', out)
 
 
 def noter(family):
@@ -63,31 +46,8 @@ def noter(family):
     return note
 
 
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(WC.option(k, v))
-        yield
-
-
-def opt_tag(o):
-    return ' '.join('%s=%d' % kv for kv in sorted(o.items())) or 'defaults'
-
-
 def option_sets(case):
     return [dict(case['opts'])] + [dict(case['opts'], **o) for (n, o, _) in WC.OPTION_TOGGLES if n == case['name']]
-
-
-def dref(d):
-    return ctypes.byref(d)
-
-
-def workspace(nbytes):
-    base = torch.empty(nbytes // 4 + 8, dtype=torch.float32, device=DEV)
-    assert base.data_ptr() % 16 == 0
-    G._KEEP.append(base)
-    return base
 
 
 def align_of(**ops):
@@ -108,14 +68,6 @@ def assert_plan(L, case, d, entry, opts, align, saved, name):
     return got
 
 
-def twice(fn, name):
-    a, b = fn(), fn()
-    for x, y in zip(a, b):
-        if isinstance(x, np.ndarray):
-            assert np.array_equal(x, y), '%s: a second run differs' % name
-    return a
-
-
 def saved_sizes(d, plan):
     xi = 36 if plan['form'] == WC.WF_F43 else 16
     return xi * d.C1 * d.Cout, xi * plan['P'] * d.C1, xi * plan['P'] * d.Cout
@@ -125,7 +77,7 @@ def saved_sizes(d, plan):
 def wino_ws(L, d, f24=False):
     n = int((L.sg_conv2d_wino24_ws_bytes if f24 else L.sg_conv2d_wino_ws_bytes)(dref(d)))
     assert n > 0
-    return workspace(n), n
+    return scratch(n), n
 
 
 def run_fwd(L, d, xd, wd, bd, sizes=None, saved=0):
@@ -137,7 +89,7 @@ def run_fwd(L, d, xd, wd, bd, sizes=None, saved=0):
     call(L, 'sg_conv2d_wino_fwd', dref(d), ptr(xd), ptr(wd), ptr(bd), ptr(o), 0, 0.0, ptr(ut), ptr(v), ptr(ws), n, stream())
     for s in (ut, v):
         if s is not None:
-            assert float(s[-1]) == G.GUARD, 'a saved operand was written behind its size'
+            assert float(s[-1]) == GUARD, 'a saved operand was written behind its size'
     return take(o, (d.N, d.Cout, d.OH, d.OW)), ut, v
 
 
@@ -147,7 +99,7 @@ def run_dgrad(L, d, gd, wd, sizes=None, ut=None, keep_ytp=False):
     o = outbuf(d.N * d.C1 * d.H * d.W)
     call(L, 'sg_conv2d_wino_dgrad', dref(d), ptr(gd), ptr(wd), ptr(o), ptr(ut), ptr(ytp), ptr(ws), n, stream())
     if ytp is not None:
-        assert float(ytp[-1]) == G.GUARD, 'ytp_save was written behind its size'
+        assert float(ytp[-1]) == GUARD, 'ytp_save was written behind its size'
     return take(o, (d.N, d.C1, d.H, d.W)), ytp
 
 
@@ -195,7 +147,7 @@ def test_winograd_case(L, case):
     yref, ybound = with_bias(r, inp['b'])
     for opts in option_sets(case):
         with options(opts):
-            tag = '%s [%s]' % (case['name'], opt_tag(opts))
+            tag = '%s [%s]' % (case['name'], opt_tag(opts, 'defaults'))
             if f24:
                 for entry, what, a, b, bias, key in ((WC.WINO24_FWD, 'fwd', xd, wd, bd, 'y'), (WC.WINO24_DGRAD, 'dgrad', gd, wd, None, 'gx'),
                                                      (WC.WINO24_WGRAD, 'wgrad', gd, xd, None, 'gw')):
@@ -442,16 +394,13 @@ def test_fused_backward_bias_partials_stay_inside_the_workspace(L):
     rstd = (1.0 / np.sqrt(y64.var(axis=(2, 3)) + EPS)).astype(np.float32)
     nbytes = int(L.sg_conv2d_wino_ws_bytes(dref(d)))
     assert nbytes > 0 and nbytes % 4 == 0
-    guards = 1024
-    ws = torch.empty(nbytes // 4 + guards, dtype=torch.float32, device=DEV)
-    assert ws.data_ptr() % 16 == 0
-    ws[nbytes // 4:].fill_(G.GUARD)
+    ws = Workspace(nbytes, guards=1024, nan=False)
     god, yd, md, rd, wd = place(gout), place(ypre), place(mean), place(rstd), place(np.zeros(C * C * 9, dtype=np.float32))
     gconv_d, gb_d = outbuf(N * C * H * W), outbuf(C)
     call(L, 'sg_conv2d_wino_dgrad_instnorm', dref(d), ptr(god), ptr(yd), ptr(md), ptr(rd), act, slope, ptr(wd), ptr(gconv_d), None,
-         ptr(gb_d), None, None, ptr(ws), nbytes, stream())
+         ptr(gb_d), None, None, ptr(ws.buf), nbytes, stream())
     gconv, gb = take(gconv_d, (N, C, H, W)), take(gb_d, (C,))
-    assert bool((ws[nbytes // 4:] == G.GUARD).all()), 'the fused data gradient wrote behind its workspace'
+    ws.intact('the fused data gradient')
     # the norm's gradient in float64 of the operands as passed (mean / rstd rounded to fp32); units at the activation kink left out
     r64 = rstd.astype(np.float64)[:, :, None, None]
     z = (y64 - mean.astype(np.float64)[:, :, None, None]) * r64
@@ -480,7 +429,7 @@ def _rejected(L, fn, args, outs, message):
     assert message in msg, (fn, msg)
     torch.cuda.synchronize()
     for o in outs:
-        assert bool((o == G.GUARD).all()), '%s wrote to an output it rejected' % fn
+        assert bool((o == GUARD).all()), '%s wrote to an output it rejected' % fn
 
 
 def test_rejected_arguments(L):
@@ -520,7 +469,7 @@ def test_rejected_arguments(L):
     gw = outbuf(d.Cout * d.C1 * 16 + 1)
     _rejected(L, 'sg_conv2d_wino24_wgrad', (dref(d), ptr(place(inp['gy'])), ptr(x0), ptr(gw[1:]), ptr(ws), n, s), (gw,), '16-byte aligned')
     # unsupported descs: 192 channels, a tile count that is no multiple of 128, F(2x2,4x4) under w24_pmin tiles
-    big = workspace(1 << 24)
+    big = scratch(1 << 24)
     for dd, fn in ((WC.make_desc(8, 192, 8, 8, 192, 3, 1, 1, True, 1, 8, 8), 'sg_conv2d_wino_fwd'),
                    (WC.make_desc(4, 128, 8, 8, 128, 3, 1, 1, True, 1, 8, 8), 'sg_conv2d_wino_fwd'),
                    (WC.make_desc(2, 128, 12, 12, 128, 4, 1, 1, False, 1, 11, 11), 'sg_conv2d_wino24_fwd')):

@@ -12,7 +12,7 @@ import torch
 
 import graph_layout_cases as GL
 from oracle import sg_oracle as O
-from test_gpu_parity import close
+from gpu_harness import close
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'scene_generation_amd', 'csrc')

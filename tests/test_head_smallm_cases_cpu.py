@@ -16,16 +16,13 @@ import torch
 import torch.nn.functional as F
 
 import head_smallm_cases as HS
+from gpu_harness import dref
 from scene_generation_amd import _hip, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'scene_generation_amd', 'csrc', 'smallm.hip')
 RTOL = 1e-12
 SHAPES = list(dict((c['shape_key'], c) for c in HS.CASES).values())
-
-
-def dref(d):
-    return ctypes.byref(d)
 
 
 def err(lib):

@@ -7,19 +7,12 @@ import pytest
 import torch
 
 from oracle import sg_oracle as O
+from gpu_harness import close
+from sampling_helpers import inference_cases, inference_model
 from scene_generation_amd.synthetic import fill_deterministic, make_batch, make_vocab
 from scene_generation_amd.args import parser
 
 T = torch.from_numpy
-
-
-def close(a, b, tol=1e-5, name=''):
-    a = a.detach().double() if isinstance(a, torch.Tensor) else torch.tensor(a).double()
-    b = T(np.asarray(b)).double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    err = (a - b).abs().max().item() if a.numel() else 0.0
-    scale = max(1.0, b.abs().max().item() if b.numel() else 1.0)
-    assert err <= tol * scale, '%s: max err %.3e (scale %.3e)' % (name, err, scale)
 
 
 @pytest.mark.parametrize('case', ['small', 'small_sum', 'full', 'dense', 'one'])
@@ -395,31 +388,6 @@ def test_masks_to_layout_test_mode_vs_reference(golden, case):
     out = O.masks_to_layout(T(g['vecs']), T(g['boxes']), T(g['masks']), T(g['obj_to_img']), int(g['H']), int(g['W']),
                             pooling=pooling, test_mode=True)
     close(out, g['out'], 1e-5, 'test-mode layout')
-
-
-def inference_model(cls):
-    C, P, A = 12, 4, 35
-    m = cls(make_vocab(C, P, A), image_size=(32, 32), gconv_hidden_dim=64, gconv_num_layers=3, mask_size=8,
-            mlp_normalization='none', appearance_normalization='batch', activation='leakyrelu-0.2',
-            n_downsample_global=2, use_attributes=True, pool_size=2)
-    fill_deterministic(m)
-    with torch.no_grad():       # same override as tools/make_golden.py (non-degenerate predicted boxes)
-        m.box_net[2].weight.mul_(0.05)
-        m.box_net[2].bias.copy_(torch.tensor([0.1, 0.15, 0.6, 0.7]))
-    m.eval()
-    batch = make_batch(N=3, min_objs=2, max_objs=4, size=32, mask_size=8, num_objs=C, num_preds=P, num_attributes=A,
-                       seed=321)
-    return m, batch
-
-
-def inference_cases(batch, g):
-    imgs, objs, boxes, masks, triples, o2i, _, attributes = batch
-    O_ = objs.size(0)
-    from tools_det import det
-    feats = [det((32,), 70 + i).abs() if i % 2 == 0 else None for i in range(O_)]
-    return [('gtbox_gtmask', dict(boxes_gt=boxes, masks_gt=masks, use_gt_box=True)),
-            ('predbox_predmask', dict(boxes_gt=boxes, masks_gt=None, use_gt_box=False)),
-            ('features', dict(boxes_gt=boxes, masks_gt=masks, use_gt_box=True, features=feats))]
 
 
 def test_model_inference_forward_vs_reference(golden):

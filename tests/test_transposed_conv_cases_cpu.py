@@ -3,7 +3,6 @@ formulation (torch double, autograd for the gradients), every forward / adjoint 
 placements equal the restatements, the parity-class geometry restated in Python is what sg_conv2d_tgather_plan reports over a grid
 of descriptors, the table -- as tests/test_gpu_transposed_conv.py runs it -- reaches every plan class that grid can produce, and the
 restated constants are the ones in the sources."""
-import contextlib
 import functools
 import os
 import re
@@ -14,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import transposed_conv_cases as T
+from gpu_harness import options
 from scene_generation_amd import _hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,14 +30,6 @@ def agree(got, want, name):
     assert got.shape == want.shape, (name, got.shape, want.shape)
     scale = max(1.0, float(np.abs(want).max())) if want.size else 1.0
     assert float(np.abs(got - want).max()) <= RTOL * scale, name
-
-
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(T.option(k, v))
-        yield
 
 
 def in64(case):

@@ -3,7 +3,6 @@ over the explicitly padded, upsampled and concatenated input; one-hot probes in 
 (the library's host-only query sg_conv2d_wgrad_plan, which loads without a device); the table as a whole reaches every value of
 every plan field; the Python restatement of the plan equals the query over a grid of shapes; the query rejects bad arguments; and
 the restated constants are the ones in the sources."""
-import contextlib
 import ctypes
 import itertools
 import os
@@ -16,20 +15,13 @@ import torch.nn.functional as F
 
 import wgrad_cases as WG
 import transposed_conv_cases as T
+from gpu_harness import options
 from scene_generation_amd import _hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'scene_generation_amd', 'csrc')
 RTOL = 1e-12
 SHAPES = list(dict((c['shape_key'], c) for c in WG.CASES).values())
-
-
-@contextlib.contextmanager
-def options(d):
-    with contextlib.ExitStack() as st:
-        for k, v in d.items():
-            st.enter_context(WG.option(k, v))
-        yield
 
 
 def agree(got, want, name):

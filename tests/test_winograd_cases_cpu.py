@@ -2,7 +2,6 @@
 direct convolution, the pairs are adjoint, the float32 restatement meets its own hard bound and gives a usable rms baseline, mutants
 of it are caught, and -- through the library's host-only query sg_conv2d_wino_plan -- the case table reaches every value of every
 plan field and every case's expected plan holds under each of its option sets."""
-import contextlib
 import ctypes
 import os
 import re
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 import winograd_cases as WC
+from gpu_harness import options
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = lambda c: c['name']
@@ -20,14 +20,6 @@ IDS = lambda c: c['name']
 def lib():
     from scene_generation_amd import _hip
     return _hip.lib()
-
-
-@contextlib.contextmanager
-def options(opts):
-    with contextlib.ExitStack() as st:
-        for k, v in opts.items():
-            st.enter_context(WC.option(k, v))
-        yield
 
 
 def option_sets(case):
