@@ -12,11 +12,8 @@
 Every figure: warmed up, then the median of ``--blocks`` blocks of at least ``--seconds`` each, with their spread.  One JSON line
 per figure, appended to profiles/accuracy_bench.jsonl (or --out)."""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -24,43 +21,10 @@ import torch  # noqa: E402
 
 from scene_generation_amd import accuracy, layers, ops  # noqa: E402
 from scene_generation_amd.optim import FusedSGD  # noqa: E402
+from tools.benchkit import emit, measure, profiled, require_device  # noqa: E402
 
 HBM_PEAK_GBS, MFMA_F32_TFLOPS = 8000.0, 157.3
 DEV = 'cuda:0'
-
-
-def timed_block(fn, min_seconds, device_events):
-    reps = 1
-    while True:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        host_ms = (time.perf_counter() - t0) * 1e3
-        ms = e0.elapsed_time(e1) if device_events else host_ms
-        if host_ms >= min_seconds * 1e3:
-            return ms / reps
-        reps = max(reps + 1, int(reps * min_seconds * 1.2e3 / max(host_ms, 1e-3)))
-
-
-def measure(fn, args, device_events=False):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    blocks = [timed_block(fn, args.seconds, device_events) for _ in range(args.blocks)]
-    med = statistics.median(blocks)
-    return {'ms': med, 'spread': (max(blocks) - min(blocks)) / med, 'blocks_ms': blocks}
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def forward_flops(model, x):
@@ -91,13 +55,7 @@ def forward_flops(model, x):
 
 def kinds_of(fn):
     """the library's time per kernel kind in one profiled call (events around every launch: the sum exceeds the unprofiled time)"""
-    ops.prof_enable(True)
-    try:
-        ops.prof_reset()
-        fn()
-        prof = ops.prof_read()
-    finally:
-        ops.prof_enable(False)
+    prof, _ = profiled(fn)
     return {k: {'launches': v['launches'], 'ms': round(v['ms'], 4), 'TFLOPs': round(v['flops'] / v['ms'] / 1e9, 2) if v['ms'] else 0.0}
             for k, v in prof.items() if v['launches']}
 
@@ -122,7 +80,7 @@ def bench_network(args):
         accuracy.ResNet.fold_batchnorm = fold
         try:
             rec = dict(base, bench='eval_forward_folded' if fold else 'eval_forward_unfolded', flops=flops, clock='device events')
-            rec.update(measure(fwd, args, device_events=True))
+            rec.update(measure(fwd, args.seconds, args.blocks, warmup=2, device_events=True))
             rec['TFLOPs'] = flops / rec['ms'] / 1e9
             rec['share_of_f32_mfma_peak'] = rec['TFLOPs'] / MFMA_F32_TFLOPS
             rec['ms_per_crop'] = rec['ms'] / B
@@ -138,7 +96,7 @@ def bench_network(args):
             with torch.no_grad():
                 return model(xo)
         rec = dict(base, bench='eval_forward_folded', chunk=other, flops=flops * other // B, clock='device events')
-        rec.update(measure(fwd_other, args, device_events=True))
+        rec.update(measure(fwd_other, args.seconds, args.blocks, warmup=2, device_events=True))
         rec['TFLOPs'] = rec['flops'] / rec['ms'] / 1e9
         rec['share_of_f32_mfma_peak'] = rec['TFLOPs'] / MFMA_F32_TFLOPS
         rec['ms_per_crop'] = rec['ms'] / other
@@ -171,7 +129,7 @@ def bench_network(args):
 
     for name, fn in (('score_meter', score_meter), ('score_item_loop', score_reference)):
         rec = dict(base, bench=name, objects=O, clock='host, ends in a synchronise')
-        rec.update(measure(fn, args))
+        rec.update(measure(fn, args.seconds, args.blocks, warmup=2))
         emit(args.out, rec)
 
     # one training step under the freeze rule
@@ -185,7 +143,7 @@ def bench_network(args):
 
     rec = dict(base, bench='train_step_freeze_rule', clock='device events', trainable=int(opt.fp.numel),
                frozen_stages=model.frozen_stages())
-    rec.update(measure(step, args, device_events=True))
+    rec.update(measure(step, args.seconds, args.blocks, warmup=2, device_events=True))
     emit(args.out, rec)
 
 
@@ -212,7 +170,7 @@ def bench_kernels(args):
     figures.append(('classify_stats', lambda: ops.classify_stats(logits, target, 0, acc), 4 * logits.numel() + 8 * 1024))
     for name, fn, nbytes in figures:
         rec = {'bench': 'kernel_' + name, 'bytes': nbytes, 'clock': 'device events'}
-        rec.update(measure(fn, args, device_events=True))
+        rec.update(measure(fn, args.seconds, args.blocks, warmup=2, device_events=True))
         rec['GBs'] = nbytes / rec['ms'] / 1e6
         rec['share_of_hbm_peak'] = rec['GBs'] / HBM_PEAK_GBS
         emit(args.out, rec)
@@ -231,9 +189,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=1.0)
     ap.add_argument('--skip', default='', help='comma list of: network, kernels')
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_accuracy.py measures on cuda:0; there is no fallback')
-    torch.cuda.set_device(0)
+    require_device()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if 'kernels' not in args.skip:
         bench_kernels(args)

@@ -14,7 +14,6 @@
 Every time: warmed up, then the median of ``--blocks`` blocks of at least ``--seconds`` each, with their spread, clocks as found.
 One JSON line per figure, appended to profiles/attributes_bench.jsonl (or --out)."""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -28,44 +27,9 @@ import torch  # noqa: E402
 from scene_generation_amd import attributes, ops, sample, scenegraph  # noqa: E402
 from scene_generation_amd.model import Model  # noqa: E402
 from scene_generation_amd.synthetic import CONFIGS, batch_to, fill_deterministic, make_batch, make_config_batch, make_vocab  # noqa: E402
+from tools.benchkit import emit, measure, require_device, timed_block  # noqa: E402
 
 DEV = 'cuda:0'
-
-
-def timed_block(fn, min_seconds, device_events):
-    """-> ms per call of back-to-back calls for >= min_seconds: between two device events, or on the host clock around a final
-    synchronise"""
-    reps = 1
-    while True:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        host_ms = (time.perf_counter() - t0) * 1e3
-        ms = e0.elapsed_time(e1) if device_events else host_ms
-        if host_ms >= min_seconds * 1e3:
-            return ms / reps
-        reps = max(reps + 1, int(reps * min_seconds * 1.2e3 / max(host_ms, 1e-3)))
-
-
-def measure(fn, args, device_events=False):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    blocks = [timed_block(fn, args.seconds, device_events) for _ in range(args.blocks)]
-    med = statistics.median(blocks)
-    return {'ms': med, 'spread': (max(blocks) - min(blocks)) / med, 'blocks_ms': blocks}
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def bench_call(name, args):
@@ -88,10 +52,10 @@ def bench_call(name, args):
 
     base = {'config': name, 'N': cfg['N'], 'O': O, 'T': T, 'triples_per_image': T / cfg['N']}
     rec = dict(base, bench='sample_attributes', clock='host, ends in a synchronise')
-    rec.update(measure(call, args))
+    rec.update(measure(call, args.seconds, args.blocks))
     emit(args.out, rec)
     rec = dict(base, bench='sg_sample_attributes', clock='device events')
-    rec.update(measure(launch, args, device_events=True))
+    rec.update(measure(launch, args.seconds, args.blocks, device_events=True))
     emit(args.out, rec)
     counts = stats.counts.cpu().numpy()
     np_in = [t.numpy() for t in (host.objs, host.obj_to_img, host.triples, host.triple_to_img)]
@@ -127,7 +91,7 @@ def bench_sampler(args):
     blocks = {'on': [], 'off': []}
     for _ in range(args.blocks):
         for mode in ('on', 'off'):
-            blocks[mode].append(timed_block(lambda: samplers[mode].sample_batch(batch, **flags), args.seconds, True))
+            blocks[mode].append(timed_block(lambda: samplers[mode].sample_batch(batch, **flags), args.seconds)[1])
     for mode in ('on', 'off'):
         med = statistics.median(blocks[mode])
         emit(args.out, {'bench': 'sample_batch', 'N': N, 'size': S, 'sample_attributes': mode, 'ms_per_batch': med,
@@ -150,9 +114,7 @@ def main():
     ap.add_argument('--configs', default='c2,c5')
     ap.add_argument('--only', default='', choices=['', 'calls', 'sampler'])
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_attributes.py measures on cuda:0; there is no fallback')
-    torch.cuda.set_device(0)
+    require_device()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     emit(args.out, {'bench': 'run', 'time': time.strftime('%Y-%m-%d %H:%M:%S'), 'device': torch.cuda.get_device_name(0),
                     'seconds': args.seconds, 'blocks': args.blocks})

@@ -14,7 +14,6 @@ about 10 % of P, the last ten classes below 100 rows), D = 32, K = 100 / 10 / 1;
 
 One JSON line per figure, appended to profiles/bank_bench.jsonl (or --out)."""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -26,6 +25,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from scene_generation_amd import bank, ops  # noqa: E402
+from tools.benchkit import device_block, emit, host_ms, require_device  # noqa: E402
 
 HBM_PEAK_GBS, FP32_VALU_TFLOPS = 8000.0, 157.3
 DEV = 'cuda:0'
@@ -53,33 +53,6 @@ def make_bank(P, C, D, seed=0):
     return x, off, sizes
 
 
-def timed_block(fn, min_seconds):
-    """-> ms per call: back-to-back calls between two device events until >= min_seconds of device time"""
-    calls, reps, total = 0, 1, 0.0
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    while total < min_seconds * 1e3:
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1)
-        if calls == 0 and ms < min_seconds * 1e3:
-            reps = max(1, int(reps * min_seconds * 1.1e3 / max(ms, 1e-3)))
-            if reps > 1:
-                continue
-        total += ms
-        calls += reps
-    return total / calls
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
-
-
 def bench_kernels(a, x, off, K):
     P, D = x.shape
     plan = ops.kmeans_plan(off)
@@ -101,7 +74,7 @@ def bench_kernels(a, x, off, K):
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
-        blocks = [timed_block(fn, a.seconds) for _ in range(a.blocks)]
+        blocks = [device_block(lambda i: fn(), a.seconds)[0] for _ in range(a.blocks)]
         med = statistics.median(blocks)
         gbs, tf = nbytes / (med * 1e-3) / 1e9, flops / (med * 1e-3) / 1e12
         t_mem, t_alu = nbytes / (HBM_PEAK_GBS * 1e9), flops / (FP32_VALU_TFLOPS * 1e12)
@@ -112,20 +85,12 @@ def bench_kernels(a, x, off, K):
                      'least_us': round(max(t_mem, t_alu) * 1e6, 2), 'frac_of_bound': round(max(t_mem, t_alu) * 1e3 / med, 4)})
 
 
-def timed_host(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
 def bench_build(a, x, off):
     bank.cluster_bank(x, off, (100, 10, 1))                                  # warm-up of every shape
     runs, report = [], None
     for _ in range(a.blocks):
         rep = []
-        ms, _ = timed_host(lambda: bank.cluster_bank(x, off, (100, 10, 1), order='none', report=rep))
+        ms, _ = host_ms(lambda: bank.cluster_bank(x, off, (100, 10, 1), order='none', report=rep), sync=True)
         runs.append(ms)
         report = rep
     emit(a.out, {'figure': 'build', 'P': x.size(0), 'D': x.size(1), 'ms': round(statistics.median(runs), 2),
@@ -135,7 +100,7 @@ def bench_build(a, x, off):
     times = {s: [] for s in strides}
     for _ in range(a.blocks):                                                 # alternating in one process
         for s in strides:
-            ms, res = timed_host(lambda: bank.kmeans_segmented(x, off, 100, host_stride=s))
+            ms, res = host_ms(lambda: bank.kmeans_segmented(x, off, 100, host_stride=s), sync=True)
             times[s].append(ms)
     for s in strides:
         emit(a.out, {'figure': 'host_stride', 'stride': s, 'K': 100, 'ms': round(statistics.median(times[s]), 2),
@@ -169,7 +134,7 @@ def main():
     p.add_argument('--blocks', type=int, default=5)
     p.add_argument('--sklearn', type=int, default=1)
     a = p.parse_args()
-    torch.cuda.set_device(0)
+    require_device()
     prop = torch.cuda.get_device_properties(0)
     emit(a.out, {'figure': 'run', 'time': time.strftime('%Y-%m-%d %H:%M:%S'), 'device': prop.name, 'CUs': prop.multi_processor_count,
                  'clock_rate_khz': getattr(prop, 'clock_rate', None), 'memory_clock_rate_khz': getattr(prop, 'memory_clock_rate', None),

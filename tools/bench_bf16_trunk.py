@@ -3,7 +3,6 @@
 at the trunk shapes of BASELINE configs[1] (N 32, 8x8) and the per-GPU shape of configs[3] (N 8, 16x16).  HIP events on the
 launch stream, median of 7 runs of 20 back-to-back calls after warm-up.  One JSON line per (shape, path, direction).
 Usage: python tools/bench_bf16_trunk.py"""
-import json
 import os
 import statistics
 import sys
@@ -13,29 +12,14 @@ import torch
 
 from scene_generation_amd import ops
 from scene_generation_amd.ops._core import _call, _conv_desc, _p, _q, _stream, workspace
+from tools.benchkit import emit, event_runs, require_device
 
 PEAK_BF16 = 2.5e15
 SHAPES = [('configs[1]', 32, 1024, 8, 8), ('configs[3]', 8, 1024, 16, 16)]
 
 
-def timeit(fn, n=20, reps=7):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / n * 1e3)
-    return statistics.median(ts), min(ts)
-
-
 def main():
-    torch.cuda.set_device(0)
+    require_device()
     dev = torch.device('cuda:0')
     for name, N, C, H, W in SHAPES:
         g = torch.Generator(device=dev).manual_seed(0)
@@ -69,11 +53,12 @@ def main():
             }
         for path, fns in paths.items():
             for direction, fn in fns.items():
-                med, best = timeit(fn)
-                print(json.dumps({'shape': name, 'N': N, 'C': C, 'H': H, 'W': W, 'path': path, 'dir': direction,
+                us = [ms * 1e3 for ms in event_runs(fn, 20, 7, 3)]
+                med, best = statistics.median(us), min(us)
+                emit(None, {'shape': name, 'N': N, 'C': C, 'H': H, 'W': W, 'path': path, 'dir': direction,
                                   'us_median': round(med, 1), 'us_min': round(best, 1),
                                   'direct_tflops': round(flop / (med * 1e-6) / 1e12, 1),
-                                  'frac_bf16_peak': round(flop / (med * 1e-6) / PEAK_BF16, 3)}), flush=True)
+                                  'frac_bf16_peak': round(flop / (med * 1e-6) / PEAK_BF16, 3)})
 
 
 if __name__ == '__main__':

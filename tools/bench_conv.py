@@ -1,8 +1,9 @@
 """Micro-benchmark of the implicit-GEMM conv kernels on the shapes of BASELINE config 2 (HIP events, GPU box)."""
-import os, sys, time
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from scene_generation_amd import ops
+from tools.benchkit import event_runs, require_device
 
 DEV = 'cuda'
 SHAPES = [
@@ -25,19 +26,12 @@ for spec in filter(None, os.environ.get('SG_BENCH_SHAPES', '').split(';')):
     SHAPES.append((f[0], int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[5]), int(f[6]), int(f[7]), f[8] == '1', int(f[9])))
 
 
-def timeit(fn, n=int(os.environ.get('SG_BENCH_ITERS', '10')), reps=3):
-    """best of ``reps`` runs of ``n`` back-to-back calls (HIP events on the launch stream)"""
-    fn(); fn(); torch.cuda.synchronize()
-    best = float('inf')
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / n)
-    return best
+def best(fn, n=int(os.environ.get('SG_BENCH_ITERS', '10'))):
+    """ms per call: the best of 3 runs of ``n`` back-to-back calls (HIP events on the launch stream), 2 warm-ups"""
+    return min(event_runs(fn, n, 3, 2))
 
+
+require_device()
 
 for name, N, Cin, H, Cout, KS, st, pad, refl, ups in SHAPES:
     if len(sys.argv) > 1 and not any(a in name for a in sys.argv[1:]):
@@ -48,7 +42,7 @@ for name, N, Cin, H, Cout, KS, st, pad, refl, ups in SHAPES:
     y = ops.conv2d(x, w, b, stride=st, pad=pad, reflect=refl, upsample=ups)
     gy = torch.randn_like(y)
     flops = 2.0 * y.numel() * Cin * KS * KS
-    t_f = timeit(lambda: ops.conv2d(x, w, b, stride=st, pad=pad, reflect=refl, upsample=ups))
+    t_f = best(lambda: ops.conv2d(x, w, b, stride=st, pad=pad, reflect=refl, upsample=ups))
     xw = x.detach().requires_grad_(False)
 
     def bwd_data():
@@ -56,9 +50,9 @@ for name, N, Cin, H, Cout, KS, st, pad, refl, ups in SHAPES:
         yy = ops.conv2d(xx, w.detach(), b, stride=st, pad=pad, reflect=refl, upsample=ups)
         return xx, yy
     xx, yy = bwd_data()
-    t_d = timeit(lambda: torch.autograd.grad(yy, xx, gy, retain_graph=True))
+    t_d = best(lambda: torch.autograd.grad(yy, xx, gy, retain_graph=True))
     ww = w.detach().requires_grad_(True)
     y2 = ops.conv2d(x.detach(), ww, b, stride=st, pad=pad, reflect=refl, upsample=ups)
-    t_w = timeit(lambda: torch.autograd.grad(y2, ww, gy, retain_graph=True))
+    t_w = best(lambda: torch.autograd.grad(y2, ww, gy, retain_graph=True))
     print('%-20s out %-18s GF %7.1f | fwd %7.3f ms %6.1f TF | dgrad %7.3f ms %6.1f TF | wgrad %7.3f ms %6.1f TF' % (
         name, tuple(y.shape), flops / 1e9, t_f, flops / t_f / 1e9, t_d, flops / t_d / 1e9, t_w, flops / t_w / 1e9), flush=True)

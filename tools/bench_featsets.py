@@ -26,7 +26,7 @@ import torch  # noqa: E402
 
 from scene_generation_amd import featsets as FS  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
-from tools.bench_fid import emit, measure  # noqa: E402
+from tools.benchkit import emit, host_ms, measure, require_device  # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -68,12 +68,6 @@ def numpy_manifold_counts(a, r2, b):
     return (d <= r2[:, None]).sum(0), d.min(1)
 
 
-def host_ms(fn):
-    t0 = time.perf_counter()
-    fn()
-    return (time.perf_counter() - t0) * 1e3
-
-
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--dim', type=int, default=2048)
@@ -87,8 +81,7 @@ def main(argv=None):
     p.add_argument('--fid_bench', default=os.path.join(ROOT, 'profiles', 'fid_bench.jsonl'))
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'featsets_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     D, k = args.dim, args.k
     ips, ref_gflops = fid_bench_figures(args.fid_bench)
     base = {'device': torch.cuda.get_device_name(0), 'dim': D, 'host_threads': torch.get_num_threads(), 'numpy': np.__version__,
@@ -107,20 +100,20 @@ def main(argv=None):
         hx, hy = x.cpu().numpy().astype(np.float64), y.cpu().numpy().astype(np.float64)
         s = min(args.subset_size, n)
         ix, iy = FS.draw_subsets(0, args.subsets, s, n, n)
-        r = measure(lambda: ops.feat_poly_sums(x, y, ix, iy, 1.0 / D, 1.0, 3), args)
+        r = measure(lambda: ops.feat_poly_sums(x, y, ix, iy, 1.0 / D, 1.0, 3), args.seconds, args.blocks, clocks=True)
         q = min(args.numpy_subsets, args.subsets)
-        np_ms = host_ms(lambda: numpy_poly_sums(hx, hy, ix[:q], iy[:q], 1.0 / D, 1.0)) * args.subsets / q
+        np_ms = host_ms(lambda: numpy_poly_sums(hx, hy, ix[:q], iy[:q], 1.0 / D, 1.0))[0] * args.subsets / q
         emit(args.out, dict(base, figure='poly_sums', n=n, m=n, subsets=args.subsets, subset_size=s, numpy_subsets_timed=q,
                             **derived(r['ms'], 2.0 * D * args.subsets * (s * (s + 1.0) + s * s), 2 * n, np_ms), **r))
 
-        r = measure(lambda: ops.feat_knn_radius(x, k), args)
-        np_ms = host_ms(lambda: numpy_knn_radius(hx, k))
+        r = measure(lambda: ops.feat_knn_radius(x, k), args.seconds, args.blocks, clocks=True)
+        np_ms = host_ms(lambda: numpy_knn_radius(hx, k))[0]
         emit(args.out, dict(base, figure='knn_radius', n=n, k=k, **derived(r['ms'], 2.0 * D * n * n, n, np_ms), **r))
 
         r2 = ops.feat_knn_radius(x, k)
         hr2 = r2.cpu().numpy()
-        r = measure(lambda: ops.feat_manifold_counts(x, r2, y), args)
-        np_ms = host_ms(lambda: numpy_manifold_counts(hx, hr2, hy))
+        r = measure(lambda: ops.feat_manifold_counts(x, r2, y), args.seconds, args.blocks, clocks=True)
+        np_ms = host_ms(lambda: numpy_manifold_counts(hx, hr2, hy))[0]
         emit(args.out, dict(base, figure='manifold_counts', n=n, m=n, k=k, **derived(r['ms'], 2.0 * D * n * n, 2 * n, np_ms), **r))
 
     # the whole of compute() at the validation pass's size, as a user meets it (host clock, the read-back included)

@@ -13,8 +13,6 @@ device synchronise, with the spread, and next to it the same launches between tw
 driver reports are read before and after (sysfs, read only; null where the host does not show them).  Nothing is asserted.  One JSON
 line per figure, appended to profiles/fid_bench.jsonl (or --out).  Random weights (the arithmetic does not depend on them)."""
 import argparse
-import glob
-import json
 import os
 import statistics
 import sys
@@ -28,64 +26,9 @@ import torch  # noqa: E402
 from scene_generation_amd import fid as FID  # noqa: E402
 from scene_generation_amd import inception as I  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
+from tools.benchkit import clocks, emit, measure, require_device  # noqa: E402
 
 DEV = 'cuda:0'
-
-
-def clocks():
-    """{'sclk_mhz', 'mclk_mhz'} of the first card that reports an active level, else nulls"""
-    out = {'sclk_mhz': None, 'mclk_mhz': None}
-    for key, name in (('sclk_mhz', 'pp_dpm_sclk'), ('mclk_mhz', 'pp_dpm_mclk')):
-        for path in sorted(glob.glob('/sys/class/drm/card*/device/' + name)):
-            try:
-                active = [l for l in open(path).read().splitlines() if l.strip().endswith('*')]
-            except OSError:
-                continue
-            if active:
-                out[key] = int(''.join(c for c in active[0].split(':')[1] if c.isdigit()))
-                break
-    return out
-
-
-def timed_block(fn, min_seconds):
-    reps = 1
-    while True:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) * 1e3
-        if ms >= min_seconds * 1e3:
-            return ms / reps, reps
-        reps = max(reps + 1, int(reps * min_seconds * 1.2e3 / max(ms, 1e-3)))
-
-
-def measure(fn, args):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    before = clocks()
-    blocks, reps = [], 1
-    for _ in range(args.blocks):
-        ms, reps = timed_block(fn, args.seconds)
-        blocks.append(ms)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    med = statistics.median(blocks)
-    return {'ms': med, 'spread': (max(blocks) - min(blocks)) / med, 'blocks_ms': blocks, 'device_events_ms': e0.elapsed_time(e1) / reps,
-            'launches_per_block': reps, 'clocks_before': before, 'clocks_after': clocks()}
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def main(argv=None):
@@ -97,8 +40,7 @@ def main(argv=None):
     p.add_argument('--rows', type=int, default=256, help='rows per side of the distance that is timed')
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'fid_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     D = args.dim
     base = {'device': torch.cuda.get_device_name(0), 'batch': args.batch, 'dim': D}
 
@@ -106,7 +48,7 @@ def main(argv=None):
     mom = FID.FeatureMoments(D, DEV)
     x = torch.relu(torch.randn(args.batch, D, device=DEV, generator=g))
     tri_bytes = 16.0 * (D * (D + 1) / 2)                            # the upper triangle read and written, 8 bytes each way
-    r = measure(lambda: ops.fid_moments_update(x, mom.sum, mom.outer), args)
+    r = measure(lambda: ops.fid_moments_update(x, mom.sum, mom.outer), args.seconds, args.blocks, clocks=True)
     update_ms = r['ms']
     emit(args.out, dict(base, figure='moments_update', rows=args.batch, alg_bytes=tri_bytes + 4.0 * args.batch * D,
                         alg_gbytes_per_s=(tri_bytes + 4.0 * args.batch * D) / (r['ms'] * 1e-3) / 1e9,
@@ -120,7 +62,8 @@ def main(argv=None):
             m.update(torch.relu(torch.randn(min(args.batch, args.rows - a), D, device=DEV, generator=g) * (1.0 + 0.1 * k) + 0.1 * k))
         sides.append(m)
     flat = torch.empty(D + D * D, dtype=torch.float64, device=DEV)
-    r = measure(lambda: ops.fid_moments_finalize(sides[0].sum, sides[0].outer, sides[0].count, out=flat), args)
+    r = measure(lambda: ops.fid_moments_finalize(sides[0].sum, sides[0].outer, sides[0].count, out=flat), args.seconds, args.blocks,
+                clocks=True)
     emit(args.out, dict(base, figure='moments_finalize', n=sides[0].count, alg_bytes=12.0 * D * D,
                         alg_gbytes_per_s=12.0 * D * D / (r['ms'] * 1e-3) / 1e9, **r))
 
@@ -152,7 +95,7 @@ def main(argv=None):
         torch.manual_seed(0)
         net = I.InceptionV3(num_classes=I.FID_CLASSES, aux_logits=False, fid_variant=True).to(DEV)
     imgs = torch.rand(args.batch, 3, 299, 299, device=DEV) * 2 - 1
-    r = measure(lambda: net.features(imgs), args)
+    r = measure(lambda: net.features(imgs), args.seconds, args.blocks, clocks=True)
     emit(args.out, dict(base, figure='features_forward_299', images_per_s=args.batch / (r['ms'] * 1e-3),
                         update_share_of_forward=update_ms / r['ms'], **r))
 

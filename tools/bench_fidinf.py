@@ -28,7 +28,7 @@ import torch  # noqa: E402
 from scene_generation_amd import fid as FID  # noqa: E402
 from scene_generation_amd import fidinf as FI  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
-from tools.bench_fid import emit, measure  # noqa: E402
+from tools.benchkit import emit, measure, require_device  # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -56,8 +56,7 @@ def main(argv=None):
     p.add_argument('--blocks', type=int, default=5)
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'fidinf_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     N, D = args.rows, args.dim
     g = torch.Generator(device=DEV).manual_seed(1)
     real = FID.FeatureMoments(D, DEV)
@@ -83,10 +82,11 @@ def main(argv=None):
 
     dmu, dsigma = torch.from_numpy(mu.copy()).to(DEV), torch.from_numpy(sigma.copy()).to(DEV)
     P, G = ops.fidinf_grams(rows, dmu, dsigma)
-    rg = measure(lambda: ops.fidinf_grams(rows, dmu, dsigma, P=P, G=G), args)
+    rg = measure(lambda: ops.fidinf_grams(rows, dmu, dsigma, P=P, G=G), args.seconds, args.blocks, clocks=True)
     didx, dsz = idx, sizes
     M, sums = ops.fidinf_subset_terms(P, G, didx, dsz)
-    rt = measure(lambda: ops.fidinf_subset_terms(P, G, didx, dsz, M=M, sums=sums), args)        # (the table upload included)
+    rt = measure(lambda: ops.fidinf_subset_terms(P, G, didx, dsz, M=M, sums=sums), args.seconds, args.blocks,
+                 clocks=True)                                       # (the table upload included)
     flops = 2.0 * N * D * D + 2.0 * 2.0 * N * N * D             # Y, then P and G over the full square
     nt, ntd = (N + 63) // 64, (D + 63) // 64
     done = 2.0 * 64 * 64 * D * (nt * ntd + 2 * (nt * (nt + 1) // 2))      # what the kernels execute: whole tiles, the upper pairs only

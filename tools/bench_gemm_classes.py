@@ -64,6 +64,7 @@ def parse():
 def run_cases(a, tag=''):
     import torch
     from scene_generation_amd import ops
+    from tools.benchkit import profiled
     dev = 'cuda'
     only = set(filter(None, a.only.split(',')))
     passes = a.passes.split(',')
@@ -90,16 +91,14 @@ def run_cases(a, tag=''):
                'wgrad': lambda: torch.autograd.grad(yw, w, gy, retain_graph=True)}
         for p in passes:
             fn = fns[p]
+
+            def iterate():
+                for _ in range(a.iters):
+                    fn()
             with torch.no_grad() if p == 'fwd' else torch.enable_grad():
                 fn(); fn()
                 torch.cuda.synchronize()
-                ops.prof_reset()
-                ops.prof_enable(True)
-                for _ in range(a.iters):
-                    fn()
-                torch.cuda.synchronize()
-                ops.prof_enable(False)
-            prof = {k: v for k, v in ops.prof_read().items() if v['launches']}
+                prof = {k: v for k, v in profiled(iterate)[0].items() if v['launches']}
             tot = sum(v['ms'] for v in prof.values()) / a.iters
             for k, v in sorted(prof.items(), key=lambda kv: -kv[1]['ms']):
                 us = 1e3 * v['ms'] / v['launches']
@@ -113,6 +112,7 @@ def run_cases(a, tag=''):
 def run_bgemm(a, tag=''):
     import torch
     from scene_generation_amd import _hip
+    from tools.benchkit import event_runs
     L = _hip.lib()
     rows = []
     st = torch.cuda.current_stream().cuda_stream
@@ -126,15 +126,7 @@ def run_bgemm(a, tag=''):
         C = torch.empty(M, nb * cols, device='cuda')
         for tile in (2, 3):
             fn = lambda: _hip.check(L.sg_batched_gemm_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), nb, M, cols, K, tile, st), 'bgemm')
-            fn(); fn(); torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            best = 1e9
-            for _ in range(3):
-                e0.record()
-                for _ in range(a.iters):
-                    fn()
-                e1.record(); torch.cuda.synchronize()
-                best = min(best, e0.elapsed_time(e1) / a.iters)
+            best = min(event_runs(fn, a.iters, 3, 2))
             fl = 2.0 * nb * M * cols * K
             rows.append((tag, name, 'tile%d' % tile, '%d workgroups' % ((M // 64) * (cols // 64) * nb), 1, 1e3 * best,
                          fl / (best * 1e-3) / 1e12, 0.0, 1e3 * best))
@@ -170,9 +162,9 @@ def main():
             print('+', ' '.join(cmd), flush=True)
             subprocess.call(cmd, cwd='/tmp', env=dict(os.environ, TMPDIR='/tmp'))
         return
-    import torch
     from scene_generation_amd import _hip
-    torch.cuda.set_device(0)
+    from tools.benchkit import require_device
+    require_device()
     for o in a.opt:
         k, v = o.split('=')
         _hip.set_option(k, int(v))

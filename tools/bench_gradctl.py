@@ -4,7 +4,6 @@ configs[1] (tools/bench_ema.py's buffer).  HIP events on the launch stream, 7 ru
 each line carries the median, the fastest and the slowest run: their spread is the allowance the comparison gets.  The last line
 states the two comparisons.  One JSON line each.
 Usage: python tools/bench_gradctl.py"""
-import json
 import os
 import statistics
 import sys
@@ -13,27 +12,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from scene_generation_amd import ops
-from tools.bench_ema import generator_flat_numel
-
-
-def timeit(fn, n=10, reps=7):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / n * 1e3)
-    return statistics.median(ts), min(ts), max(ts)
+from tools.benchkit import emit, event_runs, generator_flat_numel, require_device
 
 
 def main():
-    torch.cuda.set_device(0)
+    require_device()
     dev = torch.device('cuda:0')
     params, n = generator_flat_numel()
     g = torch.Generator(device=dev).manual_seed(0)
@@ -54,20 +37,21 @@ def main():
     }
     res = {}
     for name, (bpp, fn) in kernels.items():
-        med, best, worst = timeit(fn)
+        us = [ms * 1e3 for ms in event_runs(fn, 10, 7, 3)]
+        med, best, worst = statistics.median(us), min(us), max(us)
         res[name] = r = {'kernel': name, 'params': params, 'flat_numel': n, 'bytes_per_param': bpp, 'us_median': round(med, 1),
                          'us_min': round(best, 1), 'us_max': round(worst, 1),
                          'tb_per_s': round(bpp * n / (med * 1e-6) / 1e12, 3),
                          'tb_per_s_spread': [round(bpp * n / (worst * 1e-6) / 1e12, 3), round(bpp * n / (best * 1e-6) / 1e12, 3)]}
-        print(json.dumps(r), flush=True)
+        emit(None, r)
     adam = [res['sg_adam_step'], res['sg_adam_step (again)']]
     lo = min(a['tb_per_s_spread'][0] for a in adam)
     slowest = max(a['us_max'] for a in adam)
-    print(json.dumps({
+    emit(None, {
         'yardstick': 'sg_adam_step in this run', 'adam_tb_per_s': [a['tb_per_s'] for a in adam], 'adam_tb_per_s_slowest_run': lo,
         'grad_norm_tb_per_s': res['sg_grad_norm']['tb_per_s'], 'grad_norm_reaches_adam_rate': res['sg_grad_norm']['tb_per_s'] >= lo,
         'adam_ctl_us_median': res['sg_adam_step_ctl']['us_median'], 'adam_us_slowest_run': slowest,
-        'adam_ctl_inside_adam_spread': res['sg_adam_step_ctl']['us_median'] <= slowest}), flush=True)
+        'adam_ctl_inside_adam_spread': res['sg_adam_step_ctl']['us_median'] <= slowest})
 
 
 if __name__ == '__main__':

@@ -29,7 +29,7 @@ import torch  # noqa: E402
 from scene_generation_amd import fid as FID  # noqa: E402
 from scene_generation_amd import imageprep as IP  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
-from tools.bench_fid import emit, measure  # noqa: E402
+from tools.benchkit import emit, measure, require_device  # noqa: E402
 
 DEV = 'cuda:0'
 COPY_RATE = 6.29e12                 # bytes / s: the copy rate measured on the MI355X
@@ -83,12 +83,12 @@ def bench_resize(args, base):
             by['all'] = sum(by.values())
             launch(ops.PIL_ALL)
             for name, phases in (('coef', ops.PIL_COEF), ('horizontal', ops.PIL_HORIZONTAL), ('vertical', ops.PIL_VERTICAL), ('all', ops.PIL_ALL)):
-                r = measure(lambda: launch(phases), args)
+                r = measure(lambda: launch(phases), args.seconds, args.blocks, clocks=True)
                 rate = by[name] / (r['device_events_ms'] * 1e-3)
                 emit(args.out, dict(base, figure='resize_launch', launch=name, batch=n, source=[H, W], target=list(size), filter=filt,
                                     bytes=by[name], bytes_per_s=rate, share_of_copy_rate=rate / COPY_RATE,
                                     hbm_floor_us=by[name] / COPY_RATE * 1e6, **r))
-            r = measure(lambda: ops.pil_resize(dev, desc, size, filt, out=y), args)
+            r = measure(lambda: ops.pil_resize(dev, desc, size, filt, out=y), args.seconds, args.blocks, clocks=True)
             emit(args.out, dict(base, figure='resize_call', batch=n, source=[H, W], target=list(size), filter=filt, bytes=by['all'], **r))
             # (b) the host alternative, one thread
             from PIL import Image
@@ -193,8 +193,7 @@ def main(argv=None):
     p.add_argument('--skip', nargs='*', default=[], choices=['resize', 'feed'])
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'imageprep_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     import PIL
     base = {'device': torch.cuda.get_device_name(0), 'host_threads': torch.get_num_threads(), 'pillow': PIL.__version__}
     if 'resize' not in args.skip:

@@ -14,11 +14,9 @@
 Every timed figure: warmed up, then the median of ``--blocks`` blocks of at least ``--seconds`` each, with their spread.  One JSON
 line per figure, appended to profiles/inception_bench.jsonl (or --out).  Random weights (the arithmetic does not depend on them)."""
 import argparse
-import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,39 +24,10 @@ import torch  # noqa: E402
 
 from scene_generation_amd import inception as I  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
+from tools.benchkit import emit, measure, profiled, require_device, timed_block  # noqa: E402
 
 MFMA_F32_TFLOPS = 157.3
 DEV = 'cuda:0'
-
-
-def timed_block(fn, min_seconds):
-    reps = 1
-    while True:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) * 1e3
-        if ms >= min_seconds * 1e3:
-            return ms / reps
-        reps = max(reps + 1, int(reps * min_seconds * 1.2e3 / max(ms, 1e-3)))
-
-
-def measure(fn, args):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    blocks = [timed_block(fn, args.seconds) for _ in range(args.blocks)]
-    med = statistics.median(blocks)
-    return {'ms': med, 'spread': (max(blocks) - min(blocks)) / med, 'blocks_ms': blocks}
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def unit_flops(u):
@@ -81,8 +50,7 @@ def main(argv=None):
     p.add_argument('--num_val_samples', type=int, default=64)
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'inception_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     base = {'device': torch.cuda.get_device_name(0), 'batch': args.batch, 'size': args.size}
 
     scorer = I.InceptionScore(batch_size=args.batch, resize=True, weights=None, device=DEV)
@@ -101,25 +69,25 @@ def main(argv=None):
     def feed():
         scorer.clean()
         scorer(imgs)
-    r = measure(feed, args)
+    r = measure(feed, args.seconds, args.blocks, warmup=2)
     tf = flops / (r['ms'] * 1e-3) / 1e12
     emit(args.out, dict(base, figure='score', images_per_s=args.batch / (r['ms'] * 1e-3), gflop_per_image=flops / args.batch / 1e9,
                         tflops_whole_forward=tf, share_of_f32_mfma_peak_whole_forward=tf / MFMA_F32_TFLOPS, **r))
     x299 = ops.resize_bilinear(imgs, (299, 299))
-    r = measure(lambda: net(x299), args)
+    r = measure(lambda: net(x299), args.seconds, args.blocks, warmup=2)
     tf = flops / (r['ms'] * 1e-3) / 1e12
     emit(args.out, dict(base, figure='network_forward_299', images_per_s=args.batch / (r['ms'] * 1e-3), tflops_whole_forward=tf,
                         share_of_f32_mfma_peak_whole_forward=tf / MFMA_F32_TFLOPS, **r))
     probs = scorer.probs
     n = min(probs.size(0), 4 * args.batch)
     probs[:n] = torch.softmax(torch.randn(n, probs.size(1), device=DEV), 1)
-    r = measure(lambda: ops.inception_score(probs, n, 5), args)
+    r = measure(lambda: ops.inception_score(probs, n, 5), args.seconds, args.blocks, warmup=2)
     emit(args.out, dict(base, figure='inception_score_kernel', rows=n, splits=5, **r))
 
     # ---- per geometry class: one conv unit at a time between the library's event timers ---------------------------------------------
     classes = {}
-    ops.prof_enable(True)
-    try:
+
+    def per_class_then_one_pass():
         for u in units:
             g = torch.Generator(device=DEV).manual_seed(1)
             x = torch.randn(u['N'], u['C'], u['H'], u['W'], device=DEV, generator=g)
@@ -145,13 +113,11 @@ def main(argv=None):
             c['lo'] += min(rounds)
             c['hi'] += max(rounds)
             c['flops'] += unit_flops(u)
-        # the other kinds over one whole pass
+        # the other kinds over one whole pass: what is read when this returns
         ops.prof_reset()
         scorer.clean()
         scorer(imgs)
-        prof = ops.prof_read()
-    finally:
-        ops.prof_enable(False)
+    prof, _ = profiled(per_class_then_one_pass)
     total_ms = sum(c['ms'] for c in classes.values())
     for name, c in sorted(classes.items()):
         tf = c['flops'] / (c['ms'] * 1e-3) / 1e12
@@ -185,7 +151,7 @@ def main(argv=None):
     blocks = {'with': [], 'without': []}
     for _ in range(args.blocks):                                    # the two variants alternate, block by block
         for name, fn in variants.items():
-            blocks[name].append(timed_block(fn, args.seconds))
+            blocks[name].append(timed_block(fn, args.seconds)[0])
     med = {k: statistics.median(v) for k, v in blocks.items()}
     emit(args.out, dict(base, figure='check_model', num_val_samples=nb * args.batch, with_scorer_ms=med['with'],
                         without_scorer_ms=med['without'], with_scorer_blocks_ms=blocks['with'], without_scorer_blocks_ms=blocks['without'],

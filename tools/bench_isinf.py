@@ -17,7 +17,6 @@ import argparse
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,7 +26,7 @@ import torch  # noqa: E402
 from scene_generation_amd import _hip  # noqa: E402
 from scene_generation_amd import isinf as II  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
-from tools.bench_fid import emit, measure  # noqa: E402
+from tools.benchkit import emit, host_ms, measure, require_device  # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -51,15 +50,10 @@ def torch_route(probs, didx, sizes):
 
 
 def wall(fn, runs):
-    fn()                                             # warm-up: the workspace, the allocator
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        res = fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return res, times
+    """-> (the last result, host ms of each of ``runs`` calls, a synchronise included), after one warm-up: the workspace, the allocator"""
+    fn()
+    timed = [host_ms(fn, sync=True) for _ in range(runs)]
+    return timed[-1][1], [ms for ms, _ in timed]
 
 
 def main(argv=None):
@@ -72,8 +66,7 @@ def main(argv=None):
     p.add_argument('--blocks', type=int, default=5)
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'isinf_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     C = args.classes
     for n in args.rows:
         g = torch.Generator(device=DEV).manual_seed(1)
@@ -87,10 +80,11 @@ def main(argv=None):
         out = torch.empty(S, 2, dtype=torch.float64, device=DEV)
         nbytes = int(_hip.lib().sg_isinf_subset_scores_ws_bytes(S, smax, C))
         ws = ops.workspace(nbytes, probs.device)
-        rr = measure(lambda: ops.isinf_row_terms(probs, rs=rs, h=h), args)
+        rr = measure(lambda: ops.isinf_row_terms(probs, rs=rs, h=h), args.seconds, args.blocks, clocks=True)
         rk = measure(lambda: ops._call('sg_isinf_subset_scores', ops._p(probs), n, C, probs.stride(0), ops._pd(rs), ops._pd(h), ops._p(didx),
-                                       ops._p(dsz), S, smax, ops._pd(out), ops._p(ws), nbytes, ops._stream()), args)
-        rw = measure(lambda: ops.isinf_subset_scores(probs, rs, h, idx, sizes, out=out), args)
+                                       ops._p(dsz), S, smax, ops._pd(out), ops._p(ws), nbytes, ops._stream()),
+                     args.seconds, args.blocks, clocks=True)
+        rw = measure(lambda: ops.isinf_subset_scores(probs, rs, h, idx, sizes, out=out), args.seconds, args.blocks, clocks=True)
         mine = out.cpu().numpy()
 
         long_idx = didx.long()

@@ -6,6 +6,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from scene_generation_amd import ops, _hip
+from tools.benchkit import event_runs, require_device
 
 DEV = 'cuda'
 SHAPES = [('c2 net1.0', 224, 454, 512), ('c2 net1.1', 224, 512, 1152), ('c2 net2.0', 208, 512, 512), ('c2 net2.1', 208, 512, 128),
@@ -13,17 +14,8 @@ SHAPES = [('c2 net1.0', 224, 454, 512), ('c2 net1.1', 224, 512, 1152), ('c2 net2
           ('c5 net2.1', 1056, 512, 128), ('c4 net1.1', 140, 512, 1152), ('objD fc', 208, 1024, 172)]
 
 
-def timeit(fn, n=20, reps=3):
-    fn(); fn(); torch.cuda.synchronize()
-    best = float('inf')
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / n)
-    return best
+def best(fn):
+    return min(event_runs(fn, 20, 3, 2))
 
 
 def run(name, rows, inf, outf):
@@ -39,9 +31,9 @@ def run(name, rows, inf, outf):
     res = []
     for kernel, thr in (('tiled', 0), ('skinny', 1 << 30)):
         _hip.set_option('linear_skinny', thr)
-        tf = timeit(lambda: ops._call('sg_linear_fwd', x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), rows, inf, outf, 1, 0.0, s))
-        td = timeit(lambda: ops._call('sg_linear_bwd_data', gy.data_ptr(), w.data_ptr(), gx.data_ptr(), rows, inf, outf, s))
-        tw = timeit(lambda: ops._call('sg_linear_bwd_weight', gy.data_ptr(), x.data_ptr(), gw.data_ptr(), None, rows, inf, outf, s))
+        tf = best(lambda: ops._call('sg_linear_fwd', x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), rows, inf, outf, 1, 0.0, s))
+        td = best(lambda: ops._call('sg_linear_bwd_data', gy.data_ptr(), w.data_ptr(), gx.data_ptr(), rows, inf, outf, s))
+        tw = best(lambda: ops._call('sg_linear_bwd_weight', gy.data_ptr(), x.data_ptr(), gw.data_ptr(), None, rows, inf, outf, s))
         res.append((kernel, tf, td, tw))
     _hip.set_option('linear_skinny', 2048)
     for kernel, tf, td, tw in res:
@@ -49,5 +41,6 @@ def run(name, rows, inf, outf):
             name, rows, inf, outf, kernel, 1e3 * tf, fl / tf / 1e9, 1e3 * td, fl / td / 1e9, 1e3 * tw, fl / tw / 1e9), flush=True)
 
 
+require_device()
 for sh in SHAPES:
     run(*sh)

@@ -14,7 +14,6 @@ synchronise, with the spread, and next to it the same launches between two devic
 reports are read before and after (sysfs, read only; null where the host does not show them).  Nothing is asserted.  One JSON line
 per figure, appended to profiles/lpips_bench.jsonl (or --out).  Random weights (the arithmetic does not depend on them)."""
 import argparse
-import json
 import os
 import random
 import sys
@@ -25,20 +24,13 @@ import torch  # noqa: E402
 
 from scene_generation_amd import lpips as LP  # noqa: E402
 from scene_generation_amd import ops  # noqa: E402
-from tools.bench_fid import measure  # noqa: E402
+from tools.benchkit import emit, measure, require_device  # noqa: E402
 
 DEV = 'cuda:0'
 MFMA_F32_TFLOPS = 157.3
 HBM_TBYTES_PER_S = 8.0
 # (C, side of the tap) at 128 x 128
 TAPS = {'alex': ((64, 31), (192, 15), (384, 7), (256, 7), (256, 7)), 'vgg': ((64, 128), (128, 64), (256, 32), (512, 16), (512, 8))}
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def torch_layer(f0, f1, w, eps=1e-10):
@@ -58,8 +50,7 @@ def main(argv=None):
     p.add_argument('--skip_sampler', type=int, default=0)
     p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lpips_bench.jsonl'))
     args = p.parse_args(argv)
-    assert torch.cuda.is_available(), 'the benchmark needs cuda:0: nothing is measured without a device'
-    torch.cuda.set_device(0)
+    require_device()
     P, S = args.pairs, args.size
     base = {'device': torch.cuda.get_device_name(0), 'pairs': P, 'size': S}
     g = torch.Generator(device=DEV).manual_seed(1)
@@ -69,7 +60,7 @@ def main(argv=None):
     w = torch.randn(64, 3, 11, 11, device=DEV, generator=g) * 0.05
     b = torch.randn(64, device=DEV, generator=g) * 0.05
     y = ops.conv2d_wide(x, w, b, stride=4, pad=(2, 2), act=ops.ACT_RELU)
-    r = measure(lambda: ops.conv2d_wide(x, w, b, stride=4, pad=(2, 2), act=ops.ACT_RELU, out=y), args)
+    r = measure(lambda: ops.conv2d_wide(x, w, b, stride=4, pad=(2, 2), act=ops.ACT_RELU, out=y), args.seconds, args.blocks, clocks=True)
     flops = 2.0 * 64 * 363 * 2 * P * y.size(2) * y.size(3)
     tf = flops / (r['ms'] * 1e-3) / 1e12
     emit(args.out, dict(base, figure='wide_conv_alex_stem', images=2 * P, out_side=y.size(2), flops=flops, tflops=tf,
@@ -84,8 +75,8 @@ def main(argv=None):
             wk = torch.rand(C, device=DEV, generator=g)
             out = torch.empty(P, dtype=torch.float64, device=DEV)
             f0, f1 = f[:P], f[P:]
-            r = measure(lambda: ops.lpips_layer(f0, f1, wk, out=out), args)
-            rt = measure(lambda: torch_layer(f0, f1, wk), args)
+            r = measure(lambda: ops.lpips_layer(f0, f1, wk, out=out), args.seconds, args.blocks, clocks=True)
+            rt = measure(lambda: torch_layer(f0, f1, wk), args.seconds, args.blocks, clocks=True)
             nbytes = 8.0 * P * C * side * side
             gbs = nbytes / (r['ms'] * 1e-3) / 1e9
             dev = float((out.float() - torch_layer(f0, f1, wk)).abs().max() / out.abs().max())
@@ -102,7 +93,7 @@ def main(argv=None):
         m = models[net] = LP.LPIPS(net, device=DEV)
         for k, C in enumerate(m.net.channels):
             setattr(m, 'lin%d' % k, torch.rand(C, device=DEV, generator=g))
-        r = measure(lambda: m(x0, x1), args)
+        r = measure(lambda: m(x0, x1), args.seconds, args.blocks, clocks=True)
         emit(args.out, dict(base, figure='lpips_call', net=net, pairs_per_s=P / (r['ms'] * 1e-3), **r))
 
     # what sample_pair adds to a sampling batch
@@ -122,8 +113,8 @@ def main(argv=None):
         plain = sample.Sampler(model, features=bank)
         paired = sample.Sampler(model, features=bank, diversity=LP.Diversity(models['alex'], batch_size=P))
         random.seed(0)
-        rb = measure(lambda: plain.sample_batch(batch), args)
-        rp = measure(lambda: paired.sample_pair(batch), args)
+        rb = measure(lambda: plain.sample_batch(batch), args.seconds, args.blocks, clocks=True)
+        rp = measure(lambda: paired.sample_pair(batch), args.seconds, args.blocks, clocks=True)
         emit(args.out, dict(base, figure='sample_pair', net='alex', sample_batch_ms=rb['ms'], sample_batch_spread=rb['spread'],
                             added_ms=rp['ms'] - rb['ms'], added_share_of_sample_batch=(rp['ms'] - rb['ms']) / rb['ms'], **rp))
 

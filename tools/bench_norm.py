@@ -8,25 +8,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from scene_generation_amd import ops, _hip
 from scene_generation_amd.ops import _core
+from tools.benchkit import event_runs, require_device
 
-torch.cuda.set_device(0)
+require_device()
 SHAPES = [(32, 64, 128, 128), (32, 128, 64, 64), (32, 256, 32, 32), (32, 512, 16, 16), (64, 128, 32, 32), (64, 256, 16, 16),
           (64, 512, 17, 17), (32, 128, 32, 32), (64, 128, 16, 16), (64, 256, 8, 8), (64, 512, 9, 9), (256, 64, 8, 8), (256, 128, 4, 4)]
 R = 30
-
-
-def bench(fn, nbytes):
-    for _ in range(3):
-        fn(0)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(R):
-        fn(i)
-    e1.record()
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / R
-    return us, nbytes / us * 1e-3
 
 
 print('| shape | pass | scalar us | GB/s | vec us | GB/s | speed-up |\n|---|---|---|---|---|---|---|')
@@ -50,7 +37,8 @@ for N, C, H, W in SHAPES:
         res = []
         for opt in (1, 2):
             _hip.set_option('instnorm_reg', opt)
-            res.append(bench(fn, nb))
+            us = event_runs(fn, R, 1, 3, indexed=True)[0] * 1e3
+            res.append((us, nb / us * 1e-3))
         print('| %dx%dx%dx%d | %s | %.1f | %.0f | %.1f | %.0f | %.2f |' % (N, C, H, W, name, res[0][0], res[0][1], res[1][0], res[1][1],
                                                                           res[0][0] / res[1][0]))
     del xs, gs, ys

@@ -12,9 +12,7 @@
 Every time: warmed up, then the median of ``--blocks`` blocks of at least ``--seconds`` each, with their spread, clocks as found.
 One JSON line per figure, appended to profiles/qmc_bench.jsonl (or --out)."""
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -27,48 +25,10 @@ import torch  # noqa: E402
 from scene_generation_amd import ops, qmc, sample  # noqa: E402
 from scene_generation_amd.model import Model  # noqa: E402
 from scene_generation_amd.synthetic import batch_to, fill_deterministic, make_batch, make_vocab  # noqa: E402
+from tools.benchkit import emit, measure, require_device, summary, timed_block  # noqa: E402
 
 DEV = 'cuda:0'
 N, C, ROWS, REP, NOISE, SLOTS = 32, 172, 100, 32, 64, 32
-
-
-def timed_block(fn, min_seconds, device_events):
-    """-> ms per call of back-to-back calls for >= min_seconds: between two device events, or on the host clock around a final
-    synchronise"""
-    reps = 1
-    while True:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        host_ms = (time.perf_counter() - t0) * 1e3
-        ms = e0.elapsed_time(e1) if device_events else host_ms
-        if host_ms >= min_seconds * 1e3:
-            return ms / reps
-        reps = max(reps + 1, int(reps * min_seconds * 1.2e3 / max(host_ms, 1e-3)))
-
-
-def summary(blocks):
-    med = statistics.median(blocks)
-    return {'ms': med, 'spread': (max(blocks) - min(blocks)) / med, 'blocks_ms': blocks}
-
-
-def measure(fn, args, device_events=False):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    return summary([timed_block(fn, args.seconds, device_events) for _ in range(args.blocks)])
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def make_bank(seed=0):
@@ -99,7 +59,7 @@ def bench_calls(args, batch):
                      ('sg_qmc_unpack', lambda: ops.sg_qmc_unpack(points, b.obj_to_img, seg, NOISE, SLOTS)),
                      ('sg_bank_draw', lambda: ops.sg_bank_draw(bank.bank, bank.class_off, b.objs, pick))):
         rec = dict(base, bench=name, clock='device events')
-        rec.update(measure(fn, args, device_events=True))
+        rec.update(measure(fn, args.seconds, args.blocks, device_events=True))
         emit(args.out, rec)
 
     def three():
@@ -108,7 +68,7 @@ def bench_calls(args, batch):
         return bank.draw(b.objs, p, objs_host=objs_h)
 
     rec = dict(base, bench='draw_and_bank_draw', clock='host, ends in a synchronise')
-    rec.update(measure(three, args))
+    rec.update(measure(three, args.seconds, args.blocks))
     emit(args.out, rec)
 
 
@@ -159,7 +119,7 @@ def bench_front(args, batch):
             blocks = {'off': [], 'on': []}
             for _ in range(args.blocks):                      # alternating, so that a drift of the clocks hits both alike
                 for mode in ('off', 'on'):
-                    blocks[mode].append(timed_block(make(mode), args.seconds, events))
+                    blocks[mode].append(timed_block(make(mode), args.seconds)[1 if events else 0])
         finally:
             if hook is not None:
                 del m.forward
@@ -178,9 +138,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=0.5)
     ap.add_argument('--only', default='', choices=['', 'calls', 'front'])
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_qmc.py measures on cuda:0; there is no fallback')
-    torch.cuda.set_device(0)
+    require_device()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     emit(args.out, {'bench': 'run', 'time': time.strftime('%Y-%m-%d %H:%M:%S'), 'device': torch.cuda.get_device_name(0),
                     'seconds': args.seconds, 'blocks': args.blocks})

@@ -11,7 +11,6 @@
 
 One JSON line per figure, appended to profiles/sample_bench.jsonl (or --out)."""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -25,6 +24,7 @@ import torch  # noqa: E402
 from scene_generation_amd import ops, sample  # noqa: E402
 from scene_generation_amd.model import Model  # noqa: E402
 from scene_generation_amd.synthetic import batch_to, fill_deterministic, make_batch, make_vocab  # noqa: E402
+from tools.benchkit import device_block, emit, require_device  # noqa: E402
 
 HBM_PEAK_GBS, HBM_COPY_GBS = 8000.0, 6290.0
 DEV = 'cuda:0'
@@ -50,34 +50,6 @@ def layout_rgb_bytes(N, H, W):
     return N * H * W * (2 * 8.0 + 12.0)
 
 
-def timed_block(fn, min_seconds):
-    """-> (ms per call, calls): back-to-back calls between two device events until >= min_seconds of device time"""
-    calls, reps = 0, 1
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    total = 0.0
-    while total < min_seconds * 1e3:
-        e0.record()
-        for i in range(reps):
-            fn(calls + i)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1)
-        if calls == 0 and ms < min_seconds * 1e3:                # size one block to cover the whole second
-            reps = max(1, int(reps * min_seconds * 1.1e3 / max(ms, 1e-3)))
-            if reps > 1:
-                continue
-        total += ms
-        calls += reps
-    return total / calls, calls
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
-
-
 def bench_sampler(a):
     from conftest import skip_random_init
     shapes = [(1, 128, 8), (8, 128, 8), (32, 128, 8), (8, 256, 16)]
@@ -98,8 +70,7 @@ def bench_sampler(a):
         blocks = {'on': [], 'off': []}
         for _ in range(a.blocks):
             for mode in ('on', 'off'):
-                ms, calls = timed_block(lambda i: samplers[mode].sample_batch(batch, **flags), a.seconds)
-                blocks[mode].append(ms)
+                blocks[mode].append(device_block(lambda i: samplers[mode].sample_batch(batch, **flags), a.seconds)[0])
         for mode in ('on', 'off'):
             med = statistics.median(blocks[mode])
             emit(a.out, {'figure': 'sample_batch', 'N': N, 'size': S, 'max_objs': max_objs, 'factored': mode, 'ms_per_batch': round(med, 4),
@@ -147,7 +118,7 @@ def bench_kernels(a):
                 for i in range(3):
                     fn(i)
                 torch.cuda.synchronize()
-                blocks = [timed_block(fn, a.kernel_seconds)[0] for _ in range(a.blocks)]
+                blocks = [device_block(fn, a.kernel_seconds)[0] for _ in range(a.blocks)]
                 med = statistics.median(blocks)
                 gbs = nbytes / (med * 1e-3) / 1e9
                 emit(a.out, {'figure': 'kernel', 'kernel': name, 'N': N, 'size': S, 'J': J, 'O': O_, 'us': round(med * 1e3, 2),
@@ -164,7 +135,7 @@ def main():
     p.add_argument('--blocks', type=int, default=5)
     p.add_argument('--only', default='', choices=['', 'sampler', 'kernels'])
     a = p.parse_args()
-    torch.cuda.set_device(0)
+    require_device()
     emit(a.out, {'figure': 'run', 'time': time.strftime('%Y-%m-%d %H:%M:%S'), 'device': torch.cuda.get_device_name(0),
                  'seconds': a.seconds, 'kernel_seconds': a.kernel_seconds, 'blocks': a.blocks})
     if a.only in ('', 'kernels'):

@@ -13,11 +13,8 @@
 Every figure: warmed up, then the median of ``--blocks`` blocks of at least ``--seconds`` each, with their spread.  One JSON line
 per figure, appended to profiles/scenegraph_bench.jsonl (or --out)."""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,59 +22,16 @@ import torch  # noqa: E402
 
 from scene_generation_amd import ops, scenegraph  # noqa: E402
 from scene_generation_amd.synthetic import CONFIGS, batch_to, make_config_batch  # noqa: E402
+from tools.benchkit import emit, measure, profiled, require_device  # noqa: E402
 
 HBM_PEAK_GBS, VALU_LANE_TOPS, OPS_PER_ELEMENT = 8000.0, 78.6, 12.0
 DEV = 'cuda:0'
 
 
-def timed_block(fn, min_seconds, device_events):
-    """-> ms per call of back-to-back calls for >= min_seconds: between two device events, or on the host clock around a final
-    synchronise"""
-    reps = 1
-    while True:
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        host_ms = (time.perf_counter() - t0) * 1e3
-        ms = e0.elapsed_time(e1) if device_events else host_ms
-        if host_ms >= min_seconds * 1e3:
-            return ms / reps
-        reps = max(reps + 1, int(reps * min_seconds * 1.2e3 / max(host_ms, 1e-3)))
-
-
-def measure(fn, args, device_events=False):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    blocks = [timed_block(fn, args.seconds, device_events) for _ in range(args.blocks)]
-    med = statistics.median(blocks)
-    return {'ms': med, 'spread': (max(blocks) - min(blocks)) / med, 'blocks_ms': blocks}
-
-
 def launches_of(fn):
     """(kernel launches of the library by kind, C-ABI calls) of one call"""
-    ops.prof_enable(True)
-    try:
-        ops.prof_reset()
-        c0 = ops.CALLS[0]
-        fn()
-        calls = ops.CALLS[0] - c0
-        prof = ops.prof_read()
-    finally:
-        ops.prof_enable(False)
+    prof, calls = profiled(fn)
     return {k: v['launches'] for k, v in prof.items() if v['launches']}, calls
-
-
-def emit(out, rec):
-    line = json.dumps(rec, sort_keys=True)
-    print(line, flush=True)
-    with open(out, 'a') as f:
-        f.write(line + '\n')
 
 
 def bench_batch(name, args):
@@ -104,7 +58,7 @@ def bench_batch(name, args):
         launches, calls = launches_of(fn)
         rec = {'bench': what, 'config': name, 'N': cfg['N'], 'O': O, 'T': int(triples.size(0)), 'M': int(b.masks.size(1)),
                'pairs_per_obj': r, 'launches': launches, 'abi_calls': calls, 'clock': 'host, ends in a synchronise'}
-        rec.update(measure(fn, args))
+        rec.update(measure(fn, args.seconds, args.blocks))
         emit(args.out, rec)
 
 
@@ -116,7 +70,7 @@ def bench_dataset_pass(args):
     boxes = torch.cat([xy, xy + 0.1 + 0.4 * torch.rand(O, 2, device=DEV, generator=g)], 1).contiguous()
     nbytes = O * (M * M * 8 + 16 + 8 + 4)
     rec = {'bench': 'object_centers', 'O': O, 'M': M, 'dtype': 'int64', 'bytes': nbytes, 'clock': 'device events'}
-    rec.update(measure(lambda: ops.sg_object_centers(boxes, masks), args, device_events=True))
+    rec.update(measure(lambda: ops.sg_object_centers(boxes, masks), args.seconds, args.blocks, device_events=True))
     t_mem, t_alu = nbytes / (HBM_PEAK_GBS * 1e9) * 1e3, O * M * M * OPS_PER_ELEMENT / (VALU_LANE_TOPS * 1e12) * 1e3
     rec.update({'GBs': nbytes / rec['ms'] / 1e6, 'share_of_hbm_peak': t_mem / rec['ms'], 'least_ms_memory': t_mem,
                 'least_ms_valu': t_alu, 'bound': 'memory' if t_mem >= t_alu else 'integer VALU',
@@ -132,9 +86,7 @@ def main():
     ap.add_argument('--objects', type=int, default=100000, help='masks of the dataset-sized pass')
     ap.add_argument('--configs', default='c2,c5')
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_scenegraph.py measures on cuda:0; there is no fallback')
-    torch.cuda.set_device(0)
+    require_device()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for name in [c for c in args.configs.split(',') if c]:
         bench_batch(name, args)

@@ -12,22 +12,10 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from scene_generation_amd import _hip
+from tools.benchkit import event_runs, require_device
 
 DEV = 'cuda'
 PEAK = 157.3
-
-
-def timeit(fn, n=20, reps=3):
-    fn(); fn(); torch.cuda.synchronize()
-    best = float('inf')
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / n)
-    return best
 
 
 def run(name, nb, M, cols, K, tiles=(0, 1, 2, 3)):
@@ -49,13 +37,13 @@ def run(name, nb, M, cols, K, tiles=(0, 1, 2, 3)):
         torch.cuda.synchronize()
         got = c.view(M, nb, cols).permute(1, 0, 2).double()
         err = float((got - want).abs().max() / want.abs().max())
-        ms = timeit(fn)
+        ms = min(event_runs(fn, 20, 3, 2))
         print('%-34s tile %dx%-3d%s  %4d workgroups  %7.1f us  %6.1f TFLOP/s (%.2f of peak)  rel.err %.1e' % (
             name, bm, bn, tag, (M // bm) * (cols // bn) * nb, 1e3 * ms, flops / (ms * 1e-3) / 1e12, flops / (ms * 1e-3) / 1e12 / PEAK, err))
 
 
 if __name__ == '__main__':
-    torch.cuda.set_device(0)
+    require_device()
     run('F(2x2,3x3) fwd/dgrad 16x1024x512', 16, 1024, 512, 1024)
     run('F(4x4,3x3) fwd/dgrad 36x1024x128', 36, 1024, 128, 1024)
     run('F(4x4,3x3) wgrad 36x1024x1024,K128', 36, 1024, 1024, 128)
