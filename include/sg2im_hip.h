@@ -839,7 +839,7 @@ int sg_maxpool3s1_fwd(const float* x, float* y, int NC, int H, int W, sgStream s
 int sg_fid_moments_update(const float* x, int rows, int D, int ldx, double* sum, double* outer, sgStream stream);
 int sg_fid_moments_finalize(const double* sum, const double* outer, long long n, int D, double* mu, double* sigma, sgStream stream);
 /* ---- the diversity score: LPIPS on AlexNet / VGG-16 (lpips.hip; scene_generation_amd/lpips.py) ------------------------------------------
- * Forward only.  No wrapper synchronises or allocates (the wide convolution keeps its k-split table in the plan cache like every
+ * Forward, and the data gradient of the distance for LPIPS as a loss.  No wrapper synchronises or allocates (the wide convolution keeps its k-split table in the plan cache like every
  * gather); no float atomics: the same calls give bit-identical results.  Base pointers of fp32 operands may be unaligned.  A bad
  * argument returns a negative code (sg_last_error_string) and launches nothing.
  *
@@ -866,6 +866,21 @@ int sg_lpips_input(const void* x, int x_uint8, int x_nhwc, int N, int HW, float*
 size_t sg_lpips_layer_ws_bytes(int P, int C, int HW);
 int sg_lpips_layer(const float* f0, const float* f1, const float* w, int P, int C, int HW, float eps, double* out, int accumulate,
                    void* ws, size_t ws_bytes, sgStream stream);
+/* The gradient of one tap with respect to f0 (LPIPS as a training loss; f1 is the detached target).  gout fp64 [P] on the device,
+ * 8-byte aligned, = dL / d out[p]; gf0 fp32 [P, C, HW], every element written exactly once (overwritten).  With n0, s0 = n0 + eps, t_c
+ * as above:
+ *   g_c = 2 w[c] t_c (float)(gout[p] / HW),   dot = sum_c g_c f0_c,   gf0_k = g_k / s0 - (f0_k / s0) * ((dot / s0) / n0)
+ * in fp32, ordered so that no intermediate leaves the fp32 range while n0 is a normal float.  t_c is the forward's, by the same code:
+ * f0 == f1 bit for bit gives gf0 == +0 everywhere.  A pixel with n0 == 0 gets the finite g_k / s0 (the second term is defined as 0
+ * there; eps > 0 assumed), where autograd of the formula gives NaN from the derivative of sqrt at 0: every tap is a ReLU output, a
+ * pixel of all zeros has every pre-activation <= 0, and the ReLU backward drops the value (torch's by selection, sg_act_bwd by the
+ * factor 0: the value has to be finite).  Two reads and one write of
+ * the feature map, no workspace, no atomics, fixed-order sums: bit-identical from run to run.  P == 0 returns 0 and launches
+ * nothing. */
+int sg_lpips_layer_bwd(const float* f0, const float* f1, const float* w, const double* gout, int P, int C, int HW, float eps,
+                       float* gf0, sgStream stream);
+/* The backward of sg_lpips_input for fp32 [N, 3, HW] pictures: gx[n, c, i] = gy[n, c, i] / scale[c], one correctly rounded division. */
+int sg_lpips_input_bwd(const float* gy, int N, int HW, float* gx, sgStream stream);
 /* ---- statistics of all pairs of feature rows (featsets.hip; scene_generation_amd/featsets.py) --------------------------------------------
  * The Kernel Inception Distance's kernel sums and the k-NN manifold estimate (improved precision / recall, density / coverage).  Feature
  * rows are fp32 [rows, D] with a row stride >= D elements (any 4-byte aligned base).  Every dot product is formed in fp64 from the

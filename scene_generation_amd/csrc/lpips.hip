@@ -6,8 +6,10 @@
 //   sg_lpips_input          the scaling layer: (x - shift[c]) / scale[c] from fp32 in [-1, 1] or from uint8
 //   sg_lpips_layer          one tap of the distance: channel-normalise both feature maps, weighted squared difference summed over the
 //                           channels (fp32), spatial mean in fp64 -- one pass over the features
+//   sg_lpips_layer_bwd      the gradient of a tap with respect to f0 (LPIPS as a training loss), in the forward kernel's shape
+//   sg_lpips_input_bwd      the scaling layer's backward: gy / scale[c]
 //
-// Forward only.  No float atomics and no sum whose order depends on the launch: every result is bit-identical from run to run.
+// The convolution is forward only (the loss runs on VGG-16, whose layers have their own backward).  No float atomics and no sum whose order depends on the launch: every result is bit-identical from run to run.
 #include "igemm_core.h"
 #include "rect_gather.h"
 #include <math.h>
@@ -150,6 +152,101 @@ __global__ void __launch_bounds__(64) lpips_finish_kernel(const double* __restri
   if (threadIdx.x == 0) out[p] = lpips_store(dred[0] / (double)HW, out + p, accumulate);
 }
 
+// ---- the gradient of one tap with respect to f0 (the perceptual loss: scene_generation_amd/lpips.py LPIPSLoss) ---------------------------
+// The forward kernel's shape: the same (channel group, pixel) threads, the same registers, the same pass 1 and the same t_c, so
+// f0 == f1 bit for bit gives t_c = 0 and a gradient of exactly +0.  Three phases, two LDS reductions in ascending g per pixel:
+//   phase 1: q0, q1 -> n = sqrt(q), s = n + eps per side                                            (reduction 1)
+//   phase 2: g_c = 2 w_c t_c * (float)(gout[p] / HW), kept in the registers f1 occupied; dot = sum_c g_c f0_c     (reduction 2)
+//   phase 3: gf0_k = g_k / s0 - (f0_k / s0) * ((dot / s0) / n0): every factor stays in the fp32 range while n0 is a normal float
+//            (|dot| <= |g| n0, so (dot / s0) / n0 <= |g| / s0; the denominator n0 * s0^2 ~ 1e-35 of the textbook form is never formed)
+// A pixel with n0 == 0 gets the finite g_k / s0 (second term 0), where autograd of the formula gives NaN (the derivative of sqrt at
+// 0): every tap is a ReLU output, so a pixel whose channels are all 0 has every pre-activation <= 0 and the ReLU backward drops
+// whatever arrives there -- torch's by selection, this library's act_bwd by the factor 0, which needs the value finite.  Every element of gf0 is written exactly once (no atomics, no
+// workspace): two reads and one write of the feature map, bit-identical from run to run.
+template <int TP, int RC>
+__global__ void __launch_bounds__(TPB) lpips_layer_bwd_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
+                                                             const float* __restrict__ w, const double* __restrict__ gout, int C,
+                                                             int HW, int ntiles, float eps, float* __restrict__ gf0) {
+  constexpr int G = TPB / TP;
+  __shared__ float red[2][G][TP];
+  const int px = threadIdx.x % TP, g = threadIdx.x / TP;
+  const int p = blockIdx.x / ntiles, tile = blockIdx.x - p * ntiles;
+  const int pix = tile * TP + px;
+  const bool inside = pix < HW;
+  const size_t base = (size_t)p * C * HW + (inside ? pix : 0);
+  const float* a = f0 + base;
+  const float* b = f1 + base;
+  float* o = gf0 + base;
+  const float gs = (float)(gout[p] / (double)HW);
+  float r0[RC], r1[RC];
+  float q0 = 0.f, q1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < RC; ++i) {
+    const int c = g + i * G;
+    const bool ok = inside && c < C;
+    r0[i] = ok ? a[(size_t)c * HW] : 0.f;
+    r1[i] = ok ? b[(size_t)c * HW] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < RC; ++i) { q0 = fmaf(r0[i], r0[i], q0); q1 = fmaf(r1[i], r1[i], q1); }
+  if (inside)
+    for (int c = g + RC * G; c < C; c += G) {
+      const float u = a[(size_t)c * HW], v = b[(size_t)c * HW];
+      q0 = fmaf(u, u, q0); q1 = fmaf(v, v, q1);
+    }
+  red[0][g][px] = q0; red[1][g][px] = q1;
+  __syncthreads();
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+  for (int j = 0; j < G; ++j) { s0 += red[0][j][px]; s1 += red[1][j][px]; }
+  const float n0 = __fsqrt_rn(s0);
+  const float d0 = __fadd_rn(n0, eps), d1 = __fadd_rn(__fsqrt_rn(s1), eps);
+  float dot = 0.f;
+#pragma unroll
+  for (int i = 0; i < RC; ++i) {
+    const int c = g + i * G;
+    const float t = __fsub_rn(__fdiv_rn(r0[i], d0), __fdiv_rn(r1[i], d1));      // the forward's t: a channel past C holds 0 on both sides
+    const float wc = (w && c < C) ? w[c] : 1.f;
+    r1[i] = __fmul_rn(__fmul_rn(__fmul_rn(2.f, wc), t), gs);
+    dot = fmaf(r1[i], r0[i], dot);
+  }
+  if (inside)
+    for (int c = g + RC * G; c < C; c += G) {
+      const float u = a[(size_t)c * HW];
+      const float t = __fsub_rn(__fdiv_rn(u, d0), __fdiv_rn(b[(size_t)c * HW], d1));
+      dot = fmaf(__fmul_rn(__fmul_rn(__fmul_rn(2.f, w ? w[c] : 1.f), t), gs), u, dot);
+    }
+  __syncthreads();
+  red[0][g][px] = dot;
+  __syncthreads();
+  float ds = 0.f;
+#pragma unroll
+  for (int j = 0; j < G; ++j) ds += red[0][j][px];
+  const float k = n0 > 0.f ? __fdiv_rn(__fdiv_rn(ds, d0), n0) : 0.f;
+  if (!inside) return;
+#pragma unroll
+  for (int i = 0; i < RC; ++i) {
+    const int c = g + i * G;
+    // (+ 0: a gradient of -0 -- t = 0 under a negative gout -- leaves as +0)
+    if (c < C) o[(size_t)c * HW] = __fadd_rn(__fsub_rn(__fdiv_rn(r1[i], d0), __fmul_rn(__fdiv_rn(r0[i], d0), k)), 0.f);
+  }
+  for (int c = g + RC * G; c < C; c += G) {
+    const float u = a[(size_t)c * HW];
+    const float t = __fsub_rn(__fdiv_rn(u, d0), __fdiv_rn(b[(size_t)c * HW], d1));
+    const float gc = __fmul_rn(__fmul_rn(__fmul_rn(2.f, w ? w[c] : 1.f), t), gs);
+    o[(size_t)c * HW] = __fadd_rn(__fsub_rn(__fdiv_rn(gc, d0), __fmul_rn(__fdiv_rn(u, d0), k)), 0.f);
+  }
+}
+
+// the scaling layer's backward: gx = gy / scale[c], one rounding like the forward's division
+__global__ void __launch_bounds__(TPB) lpips_input_bwd_kernel(const float* __restrict__ gy, float* __restrict__ gx, unsigned total,
+                                                             FastDiv fhw) {
+  const unsigned i = blockIdx.x * TPB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned c = fhw.div(i) % 3u;
+  gx[i] = __fdiv_rn(gy[i], c == 0 ? .458f : (c == 1 ? .448f : .450f));
+}
+
 // the launch of a tap: 64-pixel tiles (a wave reads 256 contiguous bytes per channel) while a thread's C / 4 channels fit its 32
 // registers per side and the launch still gives every compute unit a workgroup; 16-pixel tiles otherwise (C / 16 channels per thread: up to 512 in registers)
 struct LayerPlan { int tp, rc, ntiles; };
@@ -243,5 +340,37 @@ extern "C" int sg_lpips_layer(const float* f0, const float* f1, const float* w, 
     hipLaunchKernelGGL(lpips_finish_kernel, dim3(P), dim3(64), 0, s, (const double*)part, pl.ntiles, HW, out, accumulate);
     SG_LAUNCH_CHECK("sg_lpips_layer (tile sum)");
   }
+  return 0;
+}
+
+extern "C" int sg_lpips_layer_bwd(const float* f0, const float* f1, const float* w, const double* gout, int P, int C, int HW, float eps,
+                                  float* gf0, sgStream stream) {
+  SG_ARG_CHECK(layer_sizes_ok(P, C, HW), "sg_lpips_layer_bwd: bad sizes (P=%d C=%d HW=%d; P * C * HW below 2^31)", P, C, HW);
+  SG_ARG_CHECK(eps >= 0.f, "sg_lpips_layer_bwd: eps must not be negative");
+  if (P == 0) return 0;
+  SG_ARG_CHECK(f0 && f1 && gout && gf0, "sg_lpips_layer_bwd: null operand");
+  SG_ARG_CHECK((reinterpret_cast<uintptr_t>(gout) & 7) == 0, "sg_lpips_layer_bwd: gout must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const LayerPlan pl = layer_plan(P, C, HW);                     // the forward's plan: the same tiles and registers
+  const dim3 grid((unsigned)P * (unsigned)pl.ntiles);
+  SgProfScope prof(SG_K_LPIPS_LAYER, s, 0.0, 12.0 * (double)P * C * HW);
+#define SG_LPIPS_LAUNCH(TP, RC)                                                                                                 \
+  hipLaunchKernelGGL((lpips_layer_bwd_kernel<TP, RC>), grid, dim3(TPB), 0, s, f0, f1, w, gout, C, HW, pl.ntiles, eps, gf0)
+  if (pl.tp == 64) { if (pl.rc == 16) SG_LPIPS_LAUNCH(64, 16); else SG_LPIPS_LAUNCH(64, 32); }
+  else { if (pl.rc == 16) SG_LPIPS_LAUNCH(16, 16); else SG_LPIPS_LAUNCH(16, 32); }
+#undef SG_LPIPS_LAUNCH
+  SG_LAUNCH_CHECK("sg_lpips_layer_bwd");
+  return 0;
+}
+
+extern "C" int sg_lpips_input_bwd(const float* gy, int N, int HW, float* gx, sgStream stream) {
+  SG_ARG_CHECK(N >= 0 && HW >= 1 && (double)N * 3.0 * HW < 2147483647.0, "sg_lpips_input_bwd: bad sizes (N=%d HW=%d)", N, HW);
+  if (N == 0) return 0;
+  SG_ARG_CHECK(gy && gx, "sg_lpips_input_bwd: null operand");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned total = (unsigned)N * 3u * (unsigned)HW;
+  SgProfScope prof(SG_K_LPIPS_INPUT, s, 0.0, 8.0 * (double)total);
+  hipLaunchKernelGGL(lpips_input_bwd_kernel, dim3(sg_cdiv(total, TPB)), dim3(TPB), 0, s, gy, gx, total, FastDiv((unsigned)HW));
+  SG_LAUNCH_CHECK("sg_lpips_input_bwd");
   return 0;
 }

@@ -4,16 +4,19 @@ graph with different appearance draws -- the "Diversity" column of the reference
     python -m scene_generation_amd.lpips --net alex --backbone W --lin L --dir0 A --dir1 B   -> Diversity MEAN STD
                                          [--image_size H,W [--resize_filter bilinear|bicubic]]
 
-* ``AlexFeatures`` / ``Vgg16Features``: the two backbones, inference only, parameters under torchvision's names
+* ``AlexFeatures`` / ``Vgg16Features``: the two backbones, frozen (``forward`` is inference only), parameters under torchvision's names
   (``features.<i>.weight|bias``), five taps each.  AlexNet's 11 x 11 stride-4 stem is ``ops.conv2d_wide``, its other convs
   ``ops.conv2d_rect``, its pools ``ops.maxpool3s2v``; VGG-16 runs the conv + ReLU and 2 x 2 pool launches ``losses.Vgg19`` runs.
 * ``LPIPS``: the scaling layer (``ops.lpips_input``), ONE forward of the 2P pictures of P pairs, five ``ops.lpips_layer`` launches
   that add the taps into a float64 [P] device tensor.  No host synchronisation.
+* ``LPIPSLoss``: the same distance on VGG-16 as a training objective (``Trainer(lpips_loss=...)`` / SG_LPIPS_LOSS): the backbone run
+  with the caller's grad mode (``Vgg16Features.taps``), the target half under ``no_grad``, ``ops.lpips_layer_bwd`` per tap backward.
 * ``Diversity``: the scorer ``Sampler(diversity=...)`` drives -- distances gathered in a device buffer, read once by ``compute()``.
 * Published numbers come from the package's pretrained backbone and its learned "lin" weights.  Nothing is ever downloaded: both are
   local files.  Without lin weights the unweighted baseline runs, with a loud warning.
 """
 import argparse
+import os
 import re
 import sys
 
@@ -24,7 +27,7 @@ from . import ops
 from .evalkit import find_images, grow_rows, state_dict_of, stored_size_chunks
 from .imageprep import ImageDirFeeder, add_arguments
 
-__all__ = ['AlexFeatures', 'Vgg16Features', 'LPIPS', 'Diversity', 'load_lin_weights', 'backbone_state_dict', 'pair_files', 'main']
+__all__ = ['AlexFeatures', 'Vgg16Features', 'LPIPS', 'LPIPSLoss', 'lpips_loss_from_env', 'check_lpips_loss', 'Diversity', 'load_lin_weights', 'backbone_state_dict', 'pair_files', 'main']
 
 # (torchvision ``features`` index, cin, cout, kernel, stride, pad, 3 x 3 stride-2 max-pool in front)
 _ALEX_CONVS = ((0, 3, 64, 11, 4, 2, False), (3, 64, 192, 5, 1, 2, True), (6, 192, 384, 3, 1, 1, True), (8, 384, 256, 3, 1, 1, False),
@@ -134,15 +137,43 @@ class Vgg16Features(_Backbone):
         self._he_init(seed)
 
     def forward(self, x):
-        taps = []
         with torch.no_grad():
-            for lo, hi in _VGG16_SLICES:
-                x = self.features(x, start=lo, end=hi)
-                taps.append(x)
+            return self.taps(x)
+
+    def taps(self, x):
+        """the five taps under the CALLER's grad mode: the parameters are frozen, so a backward through them is data gradients only
+        (what ``LPIPSLoss`` differentiates; ``forward`` is this under ``no_grad``)"""
+        taps = []
+        for lo, hi in _VGG16_SLICES:
+            x = self.features(x, start=lo, end=hi)
+            taps.append(x)
         return taps
 
 
 # ---- the distance -----------------------------------------------------------------------------------------------------------------------
+def _load_weights(module, who, net, backbone_weights, lin_weights):
+    """what ``LPIPS`` and ``LPIPSLoss`` share: ``module.net`` loaded from ``backbone_weights`` (or from ``lin_weights`` when that is a
+    whole LPIPS module's state_dict), the five lin vectors registered as buffers ``lin<k>`` (None: the unweighted form), and the loud
+    warnings for whatever is missing"""
+    lin_sd = state_dict_of(lin_weights) if lin_weights is not None else None
+    if backbone_weights is None and lin_sd is not None and backbone_state_dict(lin_sd) is not None:
+        backbone_weights = lin_sd
+    if backbone_weights is not None:
+        module.net.load_backbone(backbone_weights)
+    else:
+        print('WARNING: %s(%s) is built WITHOUT pretrained backbone weights: a seeded random initialisation. Its distances '
+              'are MEANINGLESS as LPIPS; pass the path of a torchvision %s state_dict.'
+              % (who, net, 'alexnet' if net == 'alex' else 'vgg16'), file=sys.stderr)
+    if lin_sd is not None:
+        lins = load_lin_weights(lin_sd, module.net.channels)
+    else:
+        print('WARNING: %s(%s) runs WITHOUT lin weights (lin_weights=None): the unweighted baseline, every channel weight 1. '
+              'ITS NUMBERS DO NOT COMPARE WITH PUBLISHED LPIPS / DIVERSITY VALUES.' % (who, net), file=sys.stderr)
+        lins = [None] * 5
+    for k, w in enumerate(lins):
+        module.register_buffer('lin%d' % k, w)
+
+
 class LPIPS(nn.Module):
     """``forward(x0, x1)`` -> float64 [P] on the device: the LPIPS distance of each pair of pictures [P, 3, H, W], float32 in [-1, 1]
     or uint8 (``channels_last=True``: [P, H, W, 3]).
@@ -158,23 +189,7 @@ class LPIPS(nn.Module):
             raise ValueError("LPIPS: net must be 'alex' or 'vgg', got %r (the SqueezeNet variant is not built)" % (net,))
         self.net_name = net
         self.net = AlexFeatures() if net == 'alex' else Vgg16Features()
-        lin_sd = state_dict_of(lin_weights) if lin_weights is not None else None
-        if backbone_weights is None and lin_sd is not None and backbone_state_dict(lin_sd) is not None:
-            backbone_weights = lin_sd
-        if backbone_weights is not None:
-            self.net.load_backbone(backbone_weights)
-        else:
-            print('WARNING: LPIPS(%s) is built WITHOUT pretrained backbone weights: a seeded random initialisation. Its distances '
-                  'are MEANINGLESS as LPIPS; pass the path of a torchvision %s state_dict.'
-                  % (net, 'alexnet' if net == 'alex' else 'vgg16'), file=sys.stderr)
-        if lin_sd is not None:
-            lins = load_lin_weights(lin_sd, self.net.channels)
-        else:
-            print('WARNING: LPIPS(%s) runs WITHOUT lin weights (lin_weights=None): the unweighted baseline, every channel weight 1. '
-                  'ITS NUMBERS DO NOT COMPARE WITH PUBLISHED LPIPS / DIVERSITY VALUES.' % net, file=sys.stderr)
-            lins = [None] * 5
-        for k, w in enumerate(lins):
-            self.register_buffer('lin%d' % k, w)
+        _load_weights(self, 'LPIPS', net, backbone_weights, lin_weights)
         self.to(device)
         self.eval()
 
@@ -195,6 +210,101 @@ class LPIPS(nn.Module):
 
     def lin_device(self):
         return next(self.net.parameters()).device
+
+
+class LPIPSLoss(nn.Module):
+    """LPIPS-VGG as a training objective: ``forward(x, y)`` -> a float32 scalar, the mean over the batch of LPIPS(x, y), with a
+    gradient for ``x`` only.  ``y`` (the target) is detached and its taps are taken under ``no_grad`` in a second pass of the frozen
+    backbone, as ``losses.VGGLoss`` does: no data gradient is spent on the target half.  The distance is ``ops.LpipsDistanceFn``: the
+    five ``ops.lpips_layer`` launches of ``LPIPS`` forward, one ``ops.lpips_layer_bwd`` launch per tap backward.  Runs eagerly.
+
+    ``input``: 'imagenet' -- pictures normalised with the ImageNet mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225), what a
+    ``Trainer`` holds; they feed the backbone directly, because the scaling layer of LPIPS on [-1, 1] pictures IS that normalisation
+    (shift = 2 mean - 1, scale = 2 std, to within 3e-8).  The two routes differ by the float32 rounding of the input: a picture that
+    went through [-1, 1] and ``ops.lpips_input`` is not bit for bit the one normalised from [0, 1].  'unit' -- pictures in [-1, 1],
+    through ``ops.lpips_input`` and its backward.
+
+    Weights and warnings as for ``LPIPS``.  VGG-16 only: the AlexNet form would need a data gradient of the 11 x 11 stride-4 stem.
+    A pixel of a tap whose channels are all zero gets a finite gradient from the distance, which the ReLU in front of the tap then
+    drops (sg_lpips_layer_bwd in the header)."""
+
+    def __init__(self, backbone_weights=None, lin_weights=None, input='imagenet', net='vgg', device='cuda'):
+        super().__init__()
+        if net != 'vgg':
+            raise ValueError("LPIPSLoss: net must be 'vgg', got %r (no other backbone has a data gradient here)" % (net,))
+        if input not in ('imagenet', 'unit'):
+            raise ValueError("LPIPSLoss: input must be 'imagenet' or 'unit', got %r" % (input,))
+        self.net_name, self.input = net, input
+        self.net = Vgg16Features()
+        _load_weights(self, 'LPIPSLoss', net, backbone_weights, lin_weights)
+        self.to(device)
+        self.eval()
+
+    def lin(self, k):
+        return getattr(self, 'lin%d' % k)
+
+    def forward(self, x, y):
+        if x.shape != y.shape or x.dim() != 4 or x.size(1) != 3 or x.dtype != torch.float32 or y.dtype != torch.float32:
+            raise ValueError('LPIPSLoss: two float32 picture batches [N, 3, H, W] of one shape, got %s %s and %s %s'
+                             % (x.dtype, tuple(x.shape), y.dtype, tuple(y.shape)))
+        y = y.detach()
+        if self.input == 'unit':
+            x, y = ops.LpipsInputFn.apply(x), ops.lpips_input(y)
+        fx = self.net.taps(x)
+        with torch.no_grad():            # the target and a frozen network: nothing to record
+            fy = self.net.taps(y)
+        d = ops.LpipsDistanceFn.apply(ops.LPIPS_EPS, *fx, *fy, *[self.lin(k) for k in range(5)])
+        return d.mean().float()
+
+
+_LOSS_KEYS = ('weight', 'backbone', 'lin')
+
+
+def check_lpips_loss(value, what='lpips_loss'):
+    """-> {'weight': float > 0, 'backbone': path or None, 'lin': path or None}: the ``Trainer``'s LPIPS term.  ``value``: a number
+    (the weight), a dict over those keys, or the spelling of SG_LPIPS_LOSS: ``'1.0'`` or ``'weight=1.0,backbone=PATH,lin=PATH'``
+    (``weight`` is required, the paths are optional).  Anything else raises ValueError naming ``what``."""
+    if isinstance(value, str):
+        parts = [s.strip() for s in value.split(',')]
+        if len(parts) == 1 and '=' not in parts[0]:
+            value = parts[0]
+        else:
+            d = {}
+            for s in parts:
+                name, eq, v = s.partition('=')
+                if not eq or name.strip() in d or not v.strip():
+                    raise ValueError('%s: expected a float or weight=float[,backbone=PATH][,lin=PATH], got %r' % (what, value))
+                d[name.strip()] = v.strip()
+            value = d
+    if not isinstance(value, dict):
+        value = {'weight': value}
+    for name in value:
+        if name not in _LOSS_KEYS:
+            raise ValueError('%s: unknown key %r (expected %s)' % (what, name, ', '.join(_LOSS_KEYS)))
+    if 'weight' not in value:
+        raise ValueError('%s: no weight' % what)
+    try:
+        w = float(value['weight'])
+    except (TypeError, ValueError):
+        raise ValueError('%s: expected a positive finite weight, got %r' % (what, value['weight']))
+    if isinstance(value['weight'], bool) or not 0.0 < w < float('inf'):      # (also rejects nan)
+        raise ValueError('%s: expected a positive finite weight, got %r' % (what, value['weight']))
+    out = {'weight': w}
+    for name in ('backbone', 'lin'):
+        v = value.get(name)
+        if v is not None and not isinstance(v, (str, dict)):
+            raise ValueError('%s: %s must be a path (or a state_dict), got %r' % (what, name, type(v).__name__))
+        out[name] = v
+    return out
+
+
+def lpips_loss_from_env(environ=None):
+    """SG_LPIPS_LOSS: the LPIPS term of a Trainer built without ``lpips_loss``.  Unset or empty: None (no term); ``1.0``: the weight;
+    ``weight=1.0,backbone=PATH,lin=PATH``: the weight and the weight files; anything else raises ValueError (check_lpips_loss)."""
+    v = (os.environ if environ is None else environ).get('SG_LPIPS_LOSS', '')
+    if v.strip() == '':
+        return None
+    return check_lpips_loss(v, 'SG_LPIPS_LOSS=%r' % v)
 
 
 class Diversity(object):

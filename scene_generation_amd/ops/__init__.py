@@ -21,7 +21,7 @@ One namespace, eighteen modules (the single 1 741-line ops.py of rounds 1-3, spl
   fid         the Frechet Inception Distance's own operators: the float64 moment update (f64 matrix cores) and its finalize, the two
               branch pools of the FID form of the network
   lpips       the diversity score's own operators: the wide (up to 11 x 11, stride <= 4) convolution, the scaling layer of LPIPS, one tap
-              of its distance
+              of its distance; for LPIPS as a loss the tap's gradient, the scaling layer's backward and the autograd functions
   featsets    statistics of all pairs of feature rows on the f64 matrix cores: the KID kernel sums, the k-NN manifold radii and the
               membership pass of precision / recall and density / coverage
   imageprep   Pillow's uint8 resize (bilinear / bicubic), bit for bit, over a ragged batch of packed RGB images, the loader's

@@ -1,6 +1,7 @@
 """The diversity score's own operators (csrc/lpips.hip): the wide forward convolution (kernels up to 11 x 11, stride up to 4: AlexNet's
-stem), the scaling layer of LPIPS and one tap of its distance.  Forward only (inference); no wrapper synchronises.  (Part of
-scene_generation_amd.ops: see ops/__init__.py.)"""
+stem), the scaling layer of LPIPS and one tap of its distance -- and, for LPIPS as a training loss, the tap's gradient with respect to
+the prediction's features, the scaling layer's backward and the autograd functions around them.  The convolution is forward only; no
+wrapper synchronises.  (Part of scene_generation_amd.ops: see ops/__init__.py.)"""
 import torch
 
 from ._core import ACT_NONE, _L, _call, _dev, _f32, _p, _stream, workspace
@@ -69,3 +70,84 @@ def lpips_layer(f0, f1, w=None, out=None, accumulate=False, eps=LPIPS_EPS):
     ws = workspace(nbytes, f0.device) if nbytes else None
     _call('sg_lpips_layer', _p(f0), _p(f1), _p(w), P, C, HW, float(eps), _pd(out), 1 if accumulate else 0, _p(ws), nbytes, _stream())
     return out
+
+
+def lpips_layer_bwd(f0, f1, w, gout, eps=LPIPS_EPS):
+    """the gradient of ``lpips_layer(f0, f1, w)`` with respect to ``f0``: ``gout`` float64 [P] on the device (dL / d out, never read
+    by the host) -> ``gf0`` float32 of f0's shape, every element written once.  ``f1`` is the target and gets no gradient.  A pixel
+    of ``f0`` whose channels are all zero gets the finite ``g / (0 + eps)`` where autograd of the formula gives NaN (see
+    sg_lpips_layer_bwd in the header: the ReLU in front of a tap drops that value)."""
+    _dev(f0, 'features')
+    _dev(f1, 'features')
+    _dev(gout, 'distance gradient')
+    if f0.dtype != torch.float32 or f1.dtype != torch.float32:
+        raise TypeError('lpips_layer_bwd: features must be float32, got %s and %s' % (f0.dtype, f1.dtype))
+    if f0.dim() < 2 or f0.shape != f1.shape or f0.device != f1.device:
+        raise ValueError('lpips_layer_bwd: two feature maps [P, C, ...] of one shape and device, got %s and %s'
+                         % (tuple(f0.shape), tuple(f1.shape)))
+    f0 = f0 if f0.is_contiguous() else f0.contiguous()
+    f1 = f1 if f1.is_contiguous() else f1.contiguous()
+    P, C = f0.size(0), f0.size(1)
+    HW = 1
+    for n in f0.shape[2:]:
+        HW *= int(n)
+    if w is not None:
+        w = _f32(w, 'lin weights').reshape(-1)
+        if w.numel() != C:
+            raise ValueError('lpips_layer_bwd: %d lin weights for %d channels' % (w.numel(), C))
+    if gout.dtype != torch.float64 or gout.dim() != 1 or gout.numel() != P or gout.device != f0.device:
+        raise ValueError('lpips_layer_bwd: gout must be a float64 tensor [%d] on the features\' device, got %s %s'
+                         % (P, gout.dtype, tuple(gout.shape)))
+    gout = gout if gout.is_contiguous() else gout.contiguous()
+    gf0 = torch.empty_like(f0)
+    _call('sg_lpips_layer_bwd', _p(f0), _p(f1), _p(w), _pd(gout), P, C, HW, float(eps), _p(gf0), _stream())
+    return gf0
+
+
+def lpips_input_bwd(gy):
+    """the backward of ``lpips_input`` on float32 [N, 3, H, W] pictures: ``gy / scale[c]`` -> float32 [N, 3, H, W]"""
+    gy = _f32(gy, 'lpips_input_bwd: the gradient')
+    if gy.dim() != 4 or gy.size(1) != 3:
+        raise ValueError('lpips_input_bwd: gradient [N, 3, H, W], got %s' % (tuple(gy.shape),))
+    gx = torch.empty_like(gy)
+    _call('sg_lpips_input_bwd', _p(gy), gy.size(0), gy.size(2) * gy.size(3), _p(gx), _stream())
+    return gx
+
+
+class LpipsInputFn(torch.autograd.Function):
+    """``lpips_input`` of float32 [N, 3, H, W] pictures in [-1, 1] with its backward"""
+
+    @staticmethod
+    def forward(ctx, x):
+        return lpips_input(x)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return lpips_input_bwd(gy)
+
+
+class LpipsDistanceFn(torch.autograd.Function):
+    """``apply(eps, *taps_x, *taps_y, *lins)``: the five taps of the prediction, the five of the target, the five lin weight vectors
+    (None: ones) -> the float64 [P] distances, by the five ``lpips_layer`` launches of ``LPIPS.forward`` (the same bits).  The
+    backward is one ``lpips_layer_bwd`` launch per tap on the incoming float64 [P] gradient; targets and weights get None."""
+
+    @staticmethod
+    def forward(ctx, eps, *tensors):
+        n = len(tensors) // 3
+        assert len(tensors) == 3 * n and n > 0
+        fx, fy, lins = tensors[:n], tensors[n:2 * n], tensors[2 * n:]
+        out = torch.empty(fx[0].size(0), dtype=torch.float64, device=fx[0].device)
+        for k in range(n):
+            lpips_layer(fx[k], fy[k], lins[k], out=out, accumulate=k > 0, eps=eps)
+        ctx.eps, ctx.n = eps, n
+        ctx.lins = lins                                  # frozen buffers, or None: not tensors autograd tracks
+        ctx.save_for_backward(*fx, *fy)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        n, saved = ctx.n, ctx.saved_tensors
+        gout = gout.contiguous()
+        grads = [lpips_layer_bwd(saved[k], saved[n + k], ctx.lins[k], gout, ctx.eps) if ctx.needs_input_grad[1 + k] else None
+                 for k in range(n)]
+        return (None,) + tuple(grads) + (None,) * (2 * n)

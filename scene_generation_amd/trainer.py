@@ -16,6 +16,8 @@ Same attributes and step functions as the reference Trainer; differences in HOW 
     ``ema_model()`` for sampling, extra checkpoint keys next to the reference's
   * optional gradient control (``grad_clip`` / ``grad_norms``, SG_GRAD_CLIP / SG_GRAD_NORMS, default off): global-norm clipping and
     a skip-on-non-finite guard decided on the device, norms in ``write_losses``
+  * optional LPIPS-VGG term of the generator's loss (``lpips_loss`` / SG_LPIPS_LOSS, default off): ``g_lpips`` next to ``g_vgg``, a
+    frozen VGG-16 with its own tap-distance backward kernel
 TensorBoard / image logging of the reference (trainer.py:342-397) is glue outside the hot path: ``write_losses``
 prints; checkpoints keep the reference schema (trainer.py:136-203, train.py:132-162).
 """
@@ -27,6 +29,7 @@ import torch
 from . import ops
 from .discriminators import AcCropDiscriminator, define_mask_D, define_D
 from .losses import get_gan_losses, GANLoss, VGGLoss
+from .lpips import LPIPSLoss, check_lpips_loss, lpips_loss_from_env
 from .model import Model
 from . import optim, streams
 from .optim import FusedAdam
@@ -88,7 +91,7 @@ def _frozen(*modules):
 
 class Trainer:
     def __init__(self, args, vocab, checkpoint=None, device=None, distributed=False, model_extra=None, trunk_precision=None,
-                 ema_decay=None, ema_start=0, grad_clip=None, grad_norms=None):
+                 ema_decay=None, ema_start=0, grad_clip=None, grad_norms=None, lpips_loss=None):
         self.vocab = vocab
         self.args = args
         respect_cpu_quota()          # host threads <= the container's CPU quota: an OpenMP burst must not freeze the launch thread
@@ -113,6 +116,10 @@ class Trainer:
         # non-finite guard on all of them, without clipping.  A run-time choice like the EMA: no flag is added
         self._grad_clip = (optim.grad_clip_from_env() if grad_clip is None else optim.check_grad_clip(grad_clip)) or {}
         self._grad_norms = optim.grad_norms_from_env() if grad_norms is None else bool(grad_norms)
+        # LPIPS-VGG as a term of the generator's loss (lpips.LPIPSLoss): None = SG_LPIPS_LOSS (unset: off), False = off.  A weight,
+        # a dict {'weight', 'backbone', 'lin'} or the variable's spelling.  A run-time choice like the EMA: no flag is added
+        self._lpips_loss = (lpips_loss_from_env() if lpips_loss is None else
+                            (None if lpips_loss is False else check_lpips_loss(lpips_loss)))
         self.init_generator(args, checkpoint)
         self.init_image_discriminator(args, checkpoint)
         self.init_obj_discriminator(args, checkpoint)
@@ -224,6 +231,12 @@ class Trainer:
                       '<torchvision vgg19 state_dict> for real training or --vgg_features_weight 0 to drop the term.'
                       % args.vgg_features_weight, file=sys.stderr)
             self.criterionVGG = VGGLoss(weights=vgg_weights).to(self.device)
+        # the frozen VGG-16 of the LPIPS term: no parameter of it joins an optimiser, nothing of it is exchanged between ranks
+        self.criterionLPIPS = None
+        cfg = getattr(self, '_lpips_loss', None)
+        if cfg is not None:
+            self.criterionLPIPS = LPIPSLoss(backbone_weights=cfg['backbone'], lin_weights=cfg['lin'], input='imagenet',
+                                            device=self.device)
         self.criterionGAN = GANLoss(use_lsgan=not args.no_lsgan)
         self.optimizer = self._adam(self.model, args.learning_rate)
 
@@ -431,6 +444,8 @@ class Trainer:
 
             if self.criterionVGG is not None:            # trainer.py:218-221
                 L.add_loss(self.criterionVGG(imgs_pred, imgs), 'g_vgg', args.vgg_features_weight)
+            if self.criterionLPIPS is not None:          # opt-in (lpips_loss= / SG_LPIPS_LOSS), independent of g_vgg
+                L.add_loss(self.criterionLPIPS(imgs_pred, imgs), 'g_lpips', self._lpips_loss['weight'])
 
             fo = streams.fork(imgs_pred.device, 'objD').__enter__()      # joined below, before the total is formed
             with fo.branch(1, reads=(imgs_pred, objs, boxes, obj_to_img)):
